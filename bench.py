@@ -11,6 +11,13 @@ Hamming match of every frame against its successor in the batch (+ TH_LOW / 0.6
 ratio filter) -> gather of the fixed-size result records on rank 0 (N>1 only).
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: set-up, the W warm-up steps, the K timed steps and the line
+(`metric`, `value` = frames/s of the K steps, `unit`, `higher_is_better`, `dtype`, `ms_per_step`).  `--dump-outputs DIR`
+writes the last timed step's results (rank 0's shard) as DIR/<name>.npy, float32.  `--full` adds everything else the
+bench measures or checks, after the same timed region: the per-kernel split and roofline, the clock-conditioned
+region, the oracle check (`verified`), the PCIe / one-frame legs, the FEM, matcher-loop, BoW and stereo legs and the
+CPU baseline; the `--no-*` options below prune those legs of a `--full` run.
+
 `roofline`: dominant kernel's algorithmic bytes / its mean launch time, timed
 with HIP events on the launch stream inside the timed region (the events of the
 kernel's own start and end: hipExtLaunchKernelGGL inside the library).  `cpu_baseline`:
@@ -92,6 +99,39 @@ def verify_against_oracle(frames, kps, desc, counts, best, second, idx, match12,
                 and np.array_equal(match12[f, :n], rm) and int(nmatch[f]) == rn):
             return False, f"pair ({f}, {g}): match result differs"
     return True, None
+
+
+def dump_outputs(dirname, ctx, pack, lay, dev):
+    """--dump-outputs: the results of the step context `ctx` ran last, as its caller receives them, to dirname/<name>.npy in float32
+    (every value is an integer below 2^24 or a float32 already, so the conversion is exact).  Only each frame's first counts[f]
+    rows are results (the rest of the fixed-capacity buffers is never written), so the per-frame rows are concatenated in
+    frame order and `keypoint_counts` splits them again.  At most 64 x 2,024 rows: 22 MB in all."""
+    import torch
+    from orb_slam2_e_amd.extractor import KP_DTYPE
+    u = ctx.user
+    rec = torch.empty(lay.rec_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.stream(u.tstream):
+        pack(ctx, rec)
+    torch.cuda.synchronize()
+    R = lay.unpack(rec.cpu().numpy())
+    best, second, idx = (t.cpu().numpy() for t in (u.best, u.second, u.idx))
+    counts = R["counts"].astype(np.int64)
+    rows = lambda a: np.concatenate([a[f, :n] for f, n in enumerate(counts)])
+    kps = rows(R["kps"])
+    out = {
+        "keypoints": np.stack([kps[name].astype(np.float32) for name in KP_DTYPE.names], axis=1),   # x y size angle response octave class_id
+        "descriptors": rows(R["desc"]).astype(np.float32),                                          # 32 bytes per keypoint
+        "keypoint_counts": counts.astype(np.float32),
+        "match_best_dist": rows(best).astype(np.float32),      # frame f's keypoints against frame f+1 mod 64
+        "match_second_dist": rows(second).astype(np.float32),
+        "match_best_idx": rows(idx).astype(np.float32),
+        "match12": rows(R["match12"]).astype(np.float32),     # accepted match (TH_LOW, ratio) or -1
+        "match_count": R["nmatch"].astype(np.float32),
+    }
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def fem_bench(rank, world, dist, torch, dev, cdev, nmesh=256, iters=200, csr_out=None):
@@ -716,7 +756,15 @@ def main():
     ap.add_argument("--no-pin", action="store_true", help="N > 1: leave the ranks' CPU placement to the scheduler")
     ap.add_argument("--no-gather-sweep", action="store_true", help="N > 1: skip the short timed regions at other --gather-every values")
     ap.add_argument("--launch-timeout", type=float, default=None, help="--gpus N > 1 started without a launcher: seconds the N ranks may run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other measurement and check (roofline, conditioned region, oracle "
+                         "check, host-I/O, FEM / matcher-loop / BoW / stereo legs, CPU baseline); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (rank 0's 64 frames: keypoints, descriptors, counts, match results) "
+                         "as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
 
     # N > 1 and not yet a rank of a launcher: this process becomes the parent of N ranks (fresh child processes running this same
     # command line with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) and relays rank 0's line.  Nothing above or in
@@ -847,23 +895,30 @@ def main():
         kern["k_match_sets_mfma"] = (mm.value, ml.value)
         return kern
 
-    # untimed pass with events around every kernel: the per-kernel split and the dominant kernel
+    # untimed pass, one context, one step at a time: every run has it in front of the W warm-ups (a plain run as well -- the
+    # clocks the K timed steps start from depend on it); --full puts events around every kernel: the per-kernel split and the
+    # dominant kernel
     KINDS = [n for n in KERNEL_KINDS]
-    for c in ctxs:
-        L.orbx_profile_enable(c.ex._h, -1)
-    L.orbm_profile_enable(1)
+    dom = None
+    if args.full:
+        for c in ctxs:
+            L.orbx_profile_enable(c.ex._h, -1)
+        L.orbm_profile_enable(1)
     nprof = 3
     for k in range(nprof):      # one context, one step at a time: no overlap in the per-kernel split
         step(0)
         torch.cuda.synchronize()
     sync()
-    kern_all = read_profiles()
-    split_ms = {k: v[0] / nprof for k, v in kern_all.items()}
-    # a start/stop event pair inflates each measured launch by ~10-20 us (rocprof traces in profiles/); rank the
-    # kinds by time net of 15 us per launch so that a multi-launch chain is not picked for its event overhead
-    dom = max(split_ms, key=lambda k: split_ms[k] - 0.015 * kern_all[k][1] / nprof)
-    # timed region: events around the dominant kernel only (each event costs dispatch-gap time)
+    if args.full:
+        kern_all = read_profiles()
+        split_ms = {k: v[0] / nprof for k, v in kern_all.items()}
+        # a start/stop event pair inflates each measured launch by ~10-20 us (rocprof traces in profiles/); rank the
+        # kinds by time net of 15 us per launch so that a multi-launch chain is not picked for its event overhead
+        dom = max(split_ms, key=lambda k: split_ms[k] - 0.015 * kern_all[k][1] / nprof)
+    # timed region of a --full run: events around the dominant kernel only (each event costs dispatch-gap time); a plain run has none
     def enable_dominant():      # (re-)arming also clears the accumulated times
+        if dom is None:
+            return
         for c in ctxs:
             L.orbx_profile_enable(c.ex._h, (1 << KINDS.index(dom)) if dom in KINDS else 0)
         L.orbm_profile_enable(1 if dom == "k_match_sets_mfma" else 0)
@@ -880,39 +935,49 @@ def main():
         step(k)
     sync()
     dt = max_over_ranks(time.perf_counter() - t0, world, cdev)
-    kern = read_profiles()          # the dominant kernel's launch times of THIS region (HIP events on the launch stream)
-    # Beside it, reported and never `value`: the same K steps after clock conditioning.  The passes above leave the card nearly
-    # idle, and from there it takes tens of milliseconds of load to reach the clocks it then sustains -- a 20-step region is
-    # 5-6 ms.  Measured on one box, 20 timed steps: 0.280-0.289 ms per step after W = 2 or 10 warm-up steps alone, 0.261-0.269 ms
-    # after 200 more.  So PRECONDITION_STEPS (~80 ms) of the same pipelined steps, W warm-ups again, and K timed steps:
-    # `ms_per_step_conditioned` (rounds 3-4 reported THIS figure as `value`; the driver's --warmup could not see the preamble).
-    for k in range(PRECONDITION_STEPS):
-        step(k)
-    sync()
-    for k in range(args.warmup):
-        step(k)
-    sync()
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        step(k)
-    sync()
-    dt_cond = max_over_ranks(time.perf_counter() - t0, world, cdev)
+    if args.full:
+        kern = read_profiles()      # the dominant kernel's launch times of THIS region (HIP events on the launch stream)
 
-    # N > 1: the same steps at other gather cadences, short regions after the headline one (a single multi-GPU run then tunes
-    # --gather-every; the headline keeps the value it was started with)
+    # what the last timed step computed, read before anything else runs on its context
+    last = pipe.ctxs[(args.steps - 1) % len(pipe.ctxs)]
+    L.orbx_copy_results_dev(last.user.ex._h, None, None, C.c_void_p(counts_t.data_ptr()), C.c_void_p(last.user.stream))
+    torch.cuda.synchronize()
+    counts, nmatch = counts_t, last.user.nmatch.clone()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, pack, lay, dev)
+
+    # --full, beside the headline and never `value`: the same K steps after clock conditioning.  The passes above leave the card
+    # nearly idle, and from there it takes tens of milliseconds of load to reach the clocks it then sustains -- a 20-step region
+    # is 5-6 ms.  Measured on one box, 20 timed steps: 0.280-0.289 ms per step after W = 2 or 10 warm-up steps alone, 0.261-0.269
+    # ms after 200 more.  So PRECONDITION_STEPS (~80 ms) of the same pipelined steps, W warm-ups again, and K timed steps:
+    # `ms_per_step_conditioned` (rounds 3-4 reported THIS figure as `value`; the driver's --warmup could not see the preamble).
+    if args.full:
+        for k in range(PRECONDITION_STEPS):
+            step(k)
+        sync()
+        for k in range(args.warmup):
+            step(k)
+        sync()
+        t0 = time.perf_counter()
+        for k in range(args.steps):
+            step(k)
+        sync()
+        dt_cond = max_over_ranks(time.perf_counter() - t0, world, cdev)
+
+    # N > 1, --full: the same steps at other gather cadences, short regions after the headline one (a single multi-GPU run then
+    # tunes --gather-every; the headline keeps the value it was started with)
     sweep = None
-    if world > 1 and pipe.do_gather and not args.no_gather_sweep:
+    if args.full and world > 1 and pipe.do_gather and not args.no_gather_sweep:
         from orb_slam2_e_amd.shard import gather_sweep
         sweep = gather_sweep(pipe, sync, world, cdev, values=tuple(sorted({1, 4, 16, GE})))
     for c in ctxs:
         L.orbx_profile_enable(c.ex._h, 0)
     L.orbm_profile_enable(0)
-    ex, nmatch, stream = ctxs[0].ex, ctxs[0].nmatch, ctxs[0].stream
 
-    # ---- the checker (outside the timed region): one more step on context 0, its results against the CPU oracle on
+    # ---- the checker (--full, outside the timed region): one more step on context 0, its results against the CPU oracle on
     # every rank; for N > 1 rank 0 also compares the records it received with the senders' own bytes (checksums)
     verified, verify_note = None, None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         import hashlib
         captured["want"] = args.steps
         pipe.on_receive = on_receive
@@ -943,7 +1008,7 @@ def main():
         verified, verify_note = bool(ok), why
 
     host_io = None
-    if not args.no_host_io and rank == 0:
+    if args.full and not args.no_host_io and rank == 0:
         # PCIe-inclusive rate: 64 host frames in, every frame's keypoints / descriptors / counts out.  (a) the plain
         # synchronous calls on pageable memory; (b) what a batch front-end does: pinned buffers, the upload, the kernels
         # and the download of a batch queued on one stream per context, contexts rotating.
@@ -1016,7 +1081,7 @@ def main():
 
     fem = None
     fem_csr = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"orbx_bench_fem_csr_{os.getpid()}.npz")
-    if not args.no_fem:
+    if args.full and not args.no_fem:
         fem = fem_bench(rank, world, dist, torch, dev, cdev, nmesh=args.fem_meshes, csr_out=fem_csr)
         if rank == 0:
             fem["compute1_per_frame"] = fem_compute1_bench()
@@ -1025,22 +1090,13 @@ def main():
     if rank == 0:
         total_frames = world * BATCH * args.steps
         value = total_frames / dt
-        launches_per_step = max(kern[dom][1] // max(args.steps, 1), 1)
-        avg_launch_ms = kern[dom][0] / max(kern[dom][1], 1)
-        alg = ALG_BYTES[dom] * BATCH / launches_per_step  # algorithmic bytes per launch
-        achieved = alg / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
-        L.orbx_copy_results_dev(ex._h, None, None, C.c_void_p(counts_t.data_ptr()), C.c_void_p(stream))
-        torch.cuda.synchronize()
-        counts = counts_t
         out = {
             "metric": "frames/s ORB extract+match (640x480, 2000 feat)",
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "ms_per_step_unconditioned": dt / args.steps * 1e3,     # = ms_per_step: the K steps directly behind the W warm-ups
-            "ms_per_step_conditioned": dt_cond / args.steps * 1e3,  # the same K steps after PRECONDITION_STEPS more untimed ones (never `value`)
-            "value_conditioned": total_frames / dt_cond,
             "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "verified": verified,
+            "verified": verified,           # the oracle check runs in a --full run only (None: not checked)
+            "full": bool(args.full),
             "config": {"workload": (f"{world}xMI355X: {world * BATCH}-frame batch sharded {BATCH}/GPU, " if world > 1 else
                                     f"1xMI355X: batch of {BATCH} ") + "synthetic 640x480 frames, ORB extract (2000 feat, 8 levels) "
                                    "+ 2000x2000 brute-force Hamming match per frame" +
@@ -1050,7 +1106,6 @@ def main():
                                  "rectangles and discs + per-frame noise; frame i is matched against frame i+1 mod 64",
                        "frames_per_gpu": BATCH, "global_batch": world * BATCH, "pipeline_contexts": len(ctxs),
                        "preconditioning_steps": 0,                    # in front of the region `value` is timed on: none since round 5
-                       "preconditioning_steps_of_ms_per_step_conditioned": PRECONDITION_STEPS,
                        "allpairs_kernel": "k_match_sets (popcount)" if args.match_kernel == "popcount" else "k_match_sets_mfma_shared (FP4 matrix cores, train tiles shared through LDS)",
                        "parallelism": (f"frames sharded {BATCH}/rank, results gathered on rank 0 ({GE} steps per "
                                         f"{'gloo' if rehearse else 'RCCL'} gather)") if world > 1 else "single GPU",
@@ -1058,49 +1113,60 @@ def main():
                        "rank0_cpu_affinity": affinity,
                        "mean_keypoints_per_frame": float(counts.float().mean().item()),
                        "mean_matches_per_frame": float(nmatch.float().mean().item())},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                         "avg_launch_ms": avg_launch_ms, "alg_bytes_per_launch": alg},
-            "pipeline_hbm_frac": value / world * FRAME_BYTES / 1e9 / HBM_PEAK_GBS,
-            "kernel_ms_per_step_untimed_pass": split_ms,
         }
         if verified is not None:
             out["verified_what"] = ("one step's keypoints (float bits), descriptors, best/second/arg-best, accepted matches and match counts "
                                     "of all frames of every rank == CPU oracle, outside the timed region" +
                                     ("; gathered records == the senders' bytes (sha256)" if world > 1 and pipe.do_gather else "") +
                                     (f"; FAILED: {verify_note}" if not verified else ""))
-        # the all-pairs matcher is the one contraction on the path: 2 x 256 FP4 multiply-adds per descriptor pair
-        nk = counts.double().clamp(max=cap).cpu()
-        pair_flops = 512.0 * float((nk[qa.cpu().long()] * nk[qb.cpu().long()]).sum())
-        mm_ms = split_ms.get("k_match_sets_mfma", 0.0)
-        if mm_ms > 0 and args.match_kernel != "popcount":
-            out["matcher_mfma"] = {"kernel": "k_match_sets_mfma_shared", "bound": "mfma", "achieved": pair_flops / (mm_ms * 1e-3) / 1e12,
-                                   "peak": MFMA_FP4_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": pair_flops / (mm_ms * 1e-3) / 1e12 / MFMA_FP4_PEAK_TFLOPS,
-                                   "flops_per_launch": pair_flops, "launch_ms_untimed_pass": mm_ms,
-                                   "note": "FP4 MFMA computes the selection keys; one key per MFMA result enters the running pair, the winner's group is finished with popcounts; bounded by matrix time + LDS round trips at two waves per SIMD"}
-        if dom == "k_match_sets_mfma" and args.match_kernel != "popcount":
-            tf = pair_flops / (avg_launch_ms * 1e-3) / 1e12
-            out["roofline"].update({"bound": "mfma", "achieved": tf, "peak": MFMA_FP4_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                    "frac": tf / MFMA_FP4_PEAK_TFLOPS, "flops_per_launch": pair_flops})
-        tr = load_traffic()   # HBM bytes per launch from the committed PMC passes (FETCH_SIZE x2 + WRITE_SIZE)
-        if dom in tr:
-            out["roofline"]["traffic"] = tr[dom]["hbm_bytes_per_launch"]
-            out["roofline"]["traffic_source"] = tr[dom]["source"]
-            if tr[dom].get("valu_wave_insts_per_launch"):
-                # the kernels that dominate this path are bound by integer VALU issue, not by HBM:
-                # the same launch time priced against the instruction count of the committed PMC pass
-                ginst = tr[dom]["valu_wave_insts_per_launch"] / (avg_launch_ms * 1e-3) / 1e9
-                out["roofline"]["valu"] = {"achieved": ginst, "peak": VALU_PEAK_GINST, "unit": "G wave64-instr/s",
-                                           "frac": ginst / VALU_PEAK_GINST,
-                                           "wave_insts_per_launch": tr[dom]["valu_wave_insts_per_launch"]}
-        # avg_launch_ms is the kernel's launch-to-end time IN the pipelined run, where it shares the chip with the other two
-        # contexts' kernels; the same two fractions for the kernel running by itself (the untimed one-context pass; its event
-        # pair adds ~3 us to the time, so these are lower bounds)
-        alone_ms = split_ms.get(dom, 0.0) / max(1, kern_all[dom][1] // nprof) if dom in kern_all else 0.0
-        if alone_ms > 0 and out["roofline"]["bound"] == "hbm":
-            out["roofline"]["alone"] = {"launch_ms": alone_ms, "frac": alg / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-            if dom in tr and tr[dom].get("valu_wave_insts_per_launch"):
-                out["roofline"]["alone"]["valu_frac"] = tr[dom]["valu_wave_insts_per_launch"] / (alone_ms * 1e-3) / 1e9 / VALU_PEAK_GINST
+        if args.full:
+            launches_per_step = max(kern[dom][1] // max(args.steps, 1), 1)
+            avg_launch_ms = kern[dom][0] / max(kern[dom][1], 1)
+            alg = ALG_BYTES[dom] * BATCH / launches_per_step  # algorithmic bytes per launch
+            achieved = alg / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
+            out.update({
+                "ms_per_step_unconditioned": dt / args.steps * 1e3,     # = ms_per_step: the K steps directly behind the W warm-ups
+                "ms_per_step_conditioned": dt_cond / args.steps * 1e3,  # the same K steps after PRECONDITION_STEPS more untimed ones (never `value`)
+                "value_conditioned": total_frames / dt_cond,
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                             "avg_launch_ms": avg_launch_ms, "alg_bytes_per_launch": alg},
+                "pipeline_hbm_frac": value / world * FRAME_BYTES / 1e9 / HBM_PEAK_GBS,
+                "kernel_ms_per_step_untimed_pass": split_ms,
+            })
+            out["config"]["preconditioning_steps_of_ms_per_step_conditioned"] = PRECONDITION_STEPS
+            # the all-pairs matcher is the one contraction on the path: 2 x 256 FP4 multiply-adds per descriptor pair
+            nk = counts.double().clamp(max=cap).cpu()
+            pair_flops = 512.0 * float((nk[qa.cpu().long()] * nk[qb.cpu().long()]).sum())
+            mm_ms = split_ms.get("k_match_sets_mfma", 0.0)
+            if mm_ms > 0 and args.match_kernel != "popcount":
+                out["matcher_mfma"] = {"kernel": "k_match_sets_mfma_shared", "bound": "mfma", "achieved": pair_flops / (mm_ms * 1e-3) / 1e12,
+                                       "peak": MFMA_FP4_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": pair_flops / (mm_ms * 1e-3) / 1e12 / MFMA_FP4_PEAK_TFLOPS,
+                                       "flops_per_launch": pair_flops, "launch_ms_untimed_pass": mm_ms,
+                                       "note": "FP4 MFMA computes the selection keys; one key per MFMA result enters the running pair, the winner's group is finished with popcounts; bounded by matrix time + LDS round trips at two waves per SIMD"}
+            if dom == "k_match_sets_mfma" and args.match_kernel != "popcount":
+                tf = pair_flops / (avg_launch_ms * 1e-3) / 1e12
+                out["roofline"].update({"bound": "mfma", "achieved": tf, "peak": MFMA_FP4_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                        "frac": tf / MFMA_FP4_PEAK_TFLOPS, "flops_per_launch": pair_flops})
+            tr = load_traffic()   # HBM bytes per launch from the committed PMC passes (FETCH_SIZE x2 + WRITE_SIZE)
+            if dom in tr:
+                out["roofline"]["traffic"] = tr[dom]["hbm_bytes_per_launch"]
+                out["roofline"]["traffic_source"] = tr[dom]["source"]
+                if tr[dom].get("valu_wave_insts_per_launch"):
+                    # the kernels that dominate this path are bound by integer VALU issue, not by HBM:
+                    # the same launch time priced against the instruction count of the committed PMC pass
+                    ginst = tr[dom]["valu_wave_insts_per_launch"] / (avg_launch_ms * 1e-3) / 1e9
+                    out["roofline"]["valu"] = {"achieved": ginst, "peak": VALU_PEAK_GINST, "unit": "G wave64-instr/s",
+                                               "frac": ginst / VALU_PEAK_GINST,
+                                               "wave_insts_per_launch": tr[dom]["valu_wave_insts_per_launch"]}
+            # avg_launch_ms is the kernel's launch-to-end time IN the pipelined run, where it shares the chip with the other two
+            # contexts' kernels; the same two fractions for the kernel running by itself (the untimed one-context pass; its event
+            # pair adds ~3 us to the time, so these are lower bounds)
+            alone_ms = split_ms.get(dom, 0.0) / max(1, kern_all[dom][1] // nprof) if dom in kern_all else 0.0
+            if alone_ms > 0 and out["roofline"]["bound"] == "hbm":
+                out["roofline"]["alone"] = {"launch_ms": alone_ms, "frac": alg / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+                if dom in tr and tr[dom].get("valu_wave_insts_per_launch"):
+                    out["roofline"]["alone"]["valu_frac"] = tr[dom]["valu_wave_insts_per_launch"] / (alone_ms * 1e-3) / 1e9 / VALU_PEAK_GINST
         if sweep is not None:
             out["gather_sweep"] = {"ms_per_step_by_gather_every": sweep, "gather_every_of_value": GE,
                                    "note": "24-step regions after the headline one, same steps, MAX over ranks"}
@@ -1110,13 +1176,13 @@ def main():
             out["fem"] = fem
             if verified is not None and "verified" in fem:
                 out["verified"] = bool(verified and fem["verified"])
-        if not args.no_fem:
+        if args.full and not args.no_fem:
             out["matcher_loops"] = matcher_loops_bench()
             out["bow_transform"] = bow_bench(torch, dev)
             out["stereo"] = stereo_bench()
             if out["verified"] is not None:
                 out["verified"] = bool(out["verified"] and out["stereo"]["batch"]["verified"] and out["bow_transform"]["verified"])
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # (N > 1: rank 0 times the extract + match leg alone -- the others wait at the closing barrier; the FEM / stereo / loop
             # baselines belong to the N = 1 line)
             legs = ["extract"] + ([] if (args.no_fem or world > 1) else ["fem", "stereo", "loops", "bow"])

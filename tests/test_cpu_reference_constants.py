@@ -1,20 +1,15 @@
 """The DATA the hot path shares with the reference -- the rBRIEF pattern, patch / border sizes, matcher thresholds, the FEM call's material
-and penalty constants, the Levenberg hook's weights and the outlier thresholds -- read as text from the reference's sources where they lie
-and compared with what the oracle and the product carry.  Dev container only (the reference mount does not travel): skipped elsewhere.
+and penalty constants, the Levenberg hook's weights and the outlier thresholds -- as read out of the reference's sources by
+tools/make_reference_facts.py into tests/golden/reference_facts.json, compared with what the oracle and the product carry.
 This pins tables and constants, not algorithms: the oracle's arithmetic stays "parity unpinned" (DESIGN 5)."""
 import inspect
 import os
 import re
 
-import pytest
+from reference_facts import ints_digest, load
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="reference mount not present")
-
-
-def _ref(path):
-    return open(os.path.join(REF, path), errors="replace").read()
+REF = load()
 
 
 def _ours(path):
@@ -30,20 +25,12 @@ def _ints(text):
 
 
 def test_rbrief_pattern_is_the_references_table():
-    src = _ref("src/ORBextractor.cc")
-    body = src[src.index("bit_pattern_31_[256*4]"):]
-    ref = _ints(body[body.index("{") + 1: body.index("};")])
-    assert len(ref) == 1024
+    ref = REF["rbrief_pattern"]
+    assert ref["count"] == 1024
     prod = _ints(_ours("orb_slam2_e_amd/csrc/orb_pattern.inc"))
-    assert prod == ref
+    assert len(prod) == ref["count"] and ints_digest(prod) == ref["sha256"]
     o = _ours("oracle/orb_pattern_data.h")
-    assert _ints(o[o.index("{") + 1: o.index("};")]) == ref
-
-
-def _const(text, name):
-    m = re.search(r"\b" + name + r"\s*=\s*([-0-9.eE]+)", _nocomment(text))
-    assert m, name
-    return float(m.group(1))
+    assert _ints(o[o.index("{") + 1: o.index("};")]) == prod
 
 
 def _define(text, name):
@@ -53,17 +40,16 @@ def _define(text, name):
 
 
 def test_extractor_sizes():
-    ref, orc = _ref("src/ORBextractor.cc"), _ours("oracle/orb_oracle.c")
+    ref, orc = REF["extractor_sizes"], _ours("oracle/orb_oracle.c")
     for name in ("PATCH_SIZE", "HALF_PATCH_SIZE", "EDGE_THRESHOLD"):
-        assert _const(ref, name) == _define(orc, name), name
+        assert ref[name] == _define(orc, name), name
     m = re.search(r"constexpr int EDGE\s*=\s*(\d+)", _ours("orb_slam2_e_amd/csrc/orbx_internal.h"))
-    assert m and float(m.group(1)) == _const(ref, "EDGE_THRESHOLD")
+    assert m and float(m.group(1)) == ref["EDGE_THRESHOLD"]
 
 
 def test_matcher_thresholds_are_this_forks():
     """This fork lowers upstream's 100 / 50 to 95 / 45 (ORBmatcher.cc:37-38)."""
-    ref = _ref("src/ORBmatcher.cc")
-    th_high, th_low, histo = (_const(ref, "ORBmatcher::" + n) for n in ("TH_HIGH", "TH_LOW", "HISTO_LENGTH"))
+    th_high, th_low, histo = (REF["matcher"][n] for n in ("TH_HIGH", "TH_LOW", "HISTO_LENGTH"))
     assert (th_high, th_low, histo) == (95, 45, 30)
     orc = _ours("oracle/match_oracle.c")
     assert _define(orc, "HISTO_LENGTH") == histo
@@ -77,10 +63,8 @@ def test_matcher_thresholds_are_this_forks():
 
 def test_fem_call_constants():
     """Optimizer.cc:480 builds FEA2(id, E, nu, h, fg, nElType, debug); FEA2.cc:105-107 imposes the encastre with Klarge."""
-    m = re.search(r"FEA2\s+fea2\(\s*pFrame->mnId\s*,\s*([-0-9.eE]+)\s*,\s*([-0-9.eE]+)\s*,\s*([-0-9.eE]+)\s*,\s*([-0-9.eE]+)\s*,", _nocomment(_ref("src/Optimizer.cc")))
-    assert m
-    E, nu, h, fg = (float(v) for v in m.groups())
-    klarge = {float(v) for v in re.findall(r"ImposeDirichletEncastre_K\(\s*nMode\s*,\s*\w+\s*,\s*([-0-9.eE]+)\s*\)", _nocomment(_ref("Thirdparty/g2o/g2o/FEA/src/FEA2.cc")))}
+    E, nu, h, fg = (REF["fem_call"][k] for k in ("E", "nu", "h", "fg"))
+    klarge = set(REF["fem_call"]["Klarge"])
     assert len(klarge) == 1
     from orb_slam2_e_amd.fem import FEA2
     import oracle
@@ -97,21 +81,18 @@ def test_fem_call_constants():
 def test_levenberg_hook_and_outlier_constants():
     """optimization_algorithm_levenberg.cpp: the hook's weights (w_rE 1, w_sE 5, first trial 1 / 2), ten trials after a failure, the
     good-step scales; Optimizer.cc: four rounds of ten iterations, chi2 5.991 for every round."""
-    lev = _nocomment(_ref("Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp"))
+    lev = REF["levenberg"]
     orc = _nocomment(_ours("oracle/pose_nr_oracle.c"))
-    for pat in (r"w_rE\s*=\s*([0-9.]+)", r"w_sE\s*=\s*([0-9.]+)"):
-        assert sorted(float(v) for v in re.findall(pat, lev)) == sorted(float(v) for v in re.findall(pat, orc)), pat
-    assert float(re.search(r"_maxTrialsAfterFailure\s*=[^;]*?(\d+)\s*\)?\s*;", lev).group(1)) == float(re.search(r"_maxTrialsAfterFailure\s*=\s*(\d+)", orc).group(1)) == 10
-    opt = _nocomment(_ref("src/Optimizer.cc"))
-    fn = opt[opt.index("Optimizer::PoseOptimizationNR"):]
-    fn = fn[:fn.index("\nint Optimizer::", 10)] if "\nint Optimizer::" in fn[10:] else fn
-    its = re.search(r"its\[4\]\s*=\s*\{([^}]*)\}", fn)
-    assert its and _ints(its.group(1)) == _ints(re.search(r"its\[4\]\s*=\s*\{([^}]*)\}", orc).group(1)) == [10, 10, 10, 10]
-    chi = re.search(r"chi2\[4\]\s*=\s*\{([^}]*)\}", fn)
-    assert chi and {float(v) for v in re.findall(r"[0-9.]+", chi.group(1))} == {5.991}
+    for name in ("w_rE", "w_sE"):
+        pat = name + r"\s*=\s*([0-9.]+)"
+        assert lev[name] == sorted(float(v) for v in re.findall(pat, orc)), pat
+    assert lev["max_trials_after_failure"] == float(re.search(r"_maxTrialsAfterFailure\s*=\s*(\d+)", orc).group(1)) == 10
+    fn = REF["pose_optimization_nr"]
+    assert fn["its"] == _ints(re.search(r"its\[4\]\s*=\s*\{([^}]*)\}", orc).group(1)) == [10, 10, 10, 10]
+    assert fn["chi2"] is not None and set(fn["chi2"]) == {5.991}
     g2o = _ours("oracle/mini_g2o.h")
     assert {float(v) for v in re.findall(r"> (5\.\d+)\)|<= (5\.\d+)\)", g2o) for v in v if v} == {5.991}
-    assert "sqrt(5.991)" in g2o and re.search(r"sqrt\(5\.991\)", fn)
+    assert "sqrt(5.991)" in g2o and fn["uses_sqrt_5_991"]
 
 
 def test_the_forks_own_extractor_settings():
@@ -119,17 +100,10 @@ def test_the_forks_own_extractor_settings():
     6 levels, FAST 24 / 7 -- is the one tests/test_gpu_extract.py and bench.py's `fork_settings` leg run; prisms (nElType 2) and the dead
     inverse path (bUseInverse 0) are what the FEM tests assume."""
     import collections
-    import glob
-    tuples, eltype, inverse = collections.Counter(), collections.Counter(), collections.Counter()
-    for f in glob.glob(os.path.join(REF, "roslaunch", "*.yaml")) + glob.glob(os.path.join(REF, "Examples", "*", "*.yaml")):
-        t = open(f, errors="replace").read()
-        g = {k: re.search(r"^ORBextractor\." + k + r":\s*([0-9.]+)", t, re.M) for k in ("nFeatures", "scaleFactor", "nLevels", "iniThFAST", "minThFAST")}
-        if all(g.values()):
-            tuples[tuple(float(v.group(1)) for v in g.values())] += 1
-        m = re.search(r"^RelocParam\.nElType:\s*(\d+)", t, re.M)
-        if m: eltype[int(m.group(1))] += 1
-        m = re.search(r"^RelocParam\.bUseInverse:\s*(\d+)", t, re.M)
-        if m: inverse[int(m.group(1))] += 1
+    lf = REF["launch_files"]
+    tuples = collections.Counter({tuple(k): n for k, n in lf["extractor_tuples"]})
+    eltype = collections.Counter({k: n for k, n in lf["nElType"]})
+    inverse = collections.Counter({k: n for k, n in lf["bUseInverse"]})
     assert tuples.most_common(1)[0][0] == (1200.0, 1.1, 6.0, 24.0, 7.0) and tuples.most_common(1)[0][1] >= 10
     assert eltype.most_common(1)[0][0] == 2 and set(inverse) == {0}
     src = _ours("tests/test_gpu_extract.py") + _ours("bench.py")

@@ -1,7 +1,9 @@
 """Regenerates integration/reference.patch: the handful of edits to the reference tree that the shells in integration/ need
 (build list, one member per class, the constructors that make / share the resident frame, guards around the methods the shells
 redefine).  Reads /root/reference (this container only), edits copies in a scratch directory and writes `diff -U1` of the result --
-the patch holds the changed lines and one line of context, nothing else of the reference."""
+the patch holds the changed lines and one line of context, nothing else of the reference.
+tests/golden/reference_facts.json records this file's sha256 and what it writes: after any edit here, re-run
+tools/make_reference_facts.py as well (tests/test_cpu_integration_shells.py fails until then)."""
 import os
 import re
 import shutil
