@@ -31,7 +31,7 @@ enum {
 };
 
 const char *orbx_last_error(void);
-/* ABI version of this header (major*100+minor). */
+/* ABI version of this header (major*100+minor).  136 (additions only): the pose-only optimisation (orbm_pose_*). */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -533,6 +533,49 @@ int orbm_search_by_sim3(const orbm_frame *kf1, const orbm_frame *kf2, const orbm
                         const float *R12, const float *t12, const orbm_points *points1, const orbm_points *points2, float th, int th_high,
                         int32_t *vnMatch1, int32_t *vnMatch2, int32_t *match12, int *nfound, orbm_window_query *q12_out,
                         orbm_window_query *q21_out);
+
+/* ------------------------------------------------------------------ pose-only optimisation
+ * Optimizer::PoseOptimization(Frame *pFrame)   src/Optimizer.cc:264-476, the g2o graph it builds and the Levenberg loop g2o runs on
+ * it (one VertexSE3Expmap, an EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose with a Huber kernel per keypoint that
+ * holds a map point, 4 rounds x 10 iterations, inlier / outlier classification between rounds) in ONE launch per call, one
+ * workgroup per problem.  The frame is passed flat, by keypoint index i < n (at most 8,192):
+ *   kps_un[i]      mvKeysUn[i] (pt, octave)           uright[i]   mvuRight[i] (< 0: monocular edge; NULL: every edge monocular)
+ *   has_mp[i]      mvpMapPoints[i] != NULL            mp_pos[i][3]  mvpMapPoints[i]->GetWorldPos()
+ *   Tcw_in         mTcw (4 x 4 row-major floats)      Tcw_out     what SetPose receives (= Tcw_in with fewer than 3 map points)
+ *   outlier[i]     mvbOutlier[i], written only where has_mp[i]
+ *   *ngood         the return value, nInitialCorrespondences - nBad
+ * Results are the same bits from run to run and whether a problem runs alone or in a batch. */
+typedef struct orbm_pose_camera {
+    float fx, fy, cx, cy, bf;           /* Frame::fx, fy, cx, cy, mbf */
+    int32_t nlevels;                    /* mvInvLevelSigma2.size(), 1..32 */
+    const float *inv_level_sigma2;      /* Frame::mvInvLevelSigma2 (host memory) */
+} orbm_pose_camera;
+/* Optional out-struct (test aid): what the rounds did, and the estimate in double before Converter::toCvMat. */
+typedef struct orbm_pose_stats {
+    int32_t rounds;                     /* rounds run: 4, 1 with fewer than 10 edges, 0 with fewer than 3 */
+    int32_t iterations[4];              /* SparseOptimizer::optimize iterations (Levenberg solve() calls) per round */
+    int32_t trials[4];                  /* damped-system solves (Levenberg trials) per round */
+    int32_t ninitial;                   /* nInitialCorrespondences */
+    double chi2;                        /* currentChi after the last iteration of the last round (0 if it had none) */
+    double q[4];                        /* final estimate: rotation x y z w ... */
+    double t[3];                        /* ... and translation */
+} orbm_pose_stats;
+/* Single call, host arrays. */
+int orbm_pose_optimization(const orbx_keypoint *kps_un, const float *uright, int n, const uint8_t *has_mp, const float *mp_pos,
+                           const orbm_pose_camera *cam, const float *Tcw_in, float *Tcw_out, uint8_t *outlier, int *ngood,
+                           orbm_pose_stats *stats);
+/* Single call on a resident frame: mvKeysUn and mvuRight are the frame handle's (orbm_frame_create / _from_extractor, in HBM), so
+ * per call only has_mp[n] and mp_pos[n][3] travel, by keypoint index.  Same results as orbm_pose_optimization, bit for bit. */
+int orbm_frame_pose_optimization(const orbm_frame *frame, const uint8_t *has_mp, const float *mp_pos, const orbm_pose_camera *cam,
+                                 const float *Tcw_in, float *Tcw_out, uint8_t *outlier, int *ngood, orbm_pose_stats *stats);
+/* B problems in one launch (the relocalisation candidates of Tracking::Relocalization): problem p owns keypoints
+ * kp_off[p] .. kp_off[p + 1] - 1 of kps_un / uright / has_mp / mp_pos / outlier (kp_off[0] = 0), Tcw_in[p][16], Tcw_out[p][16],
+ * ngood[p], stats[p] (or NULL); one camera.  is_device = 0: host arrays, synchronous.  is_device = 1: every array (kp_off
+ * included) is in device memory and the call only enqueues the launch on `stream` (NULL: the null stream); a problem with more
+ * than 8,192 keypoints then gets ngood[p] = ORBX_ERR_UNSUPPORTED and no other output. */
+int orbm_pose_optimization_batch(const orbx_keypoint *kps_un, const float *uright, const int32_t *kp_off, int batch, const uint8_t *has_mp,
+                                 const float *mp_pos, const orbm_pose_camera *cam, const float *Tcw_in, float *Tcw_out, uint8_t *outlier,
+                                 int32_t *ngood, orbm_pose_stats *stats, int is_device, void *stream);
 
 /* Test aid: on != 0 makes the whole-loop projection searches use the one-wave sequential resolver (k_resolve) instead of the
  * parallel fixed-point resolver (k_resolve_par), which otherwise only takes over when the latter does not converge.  Both

@@ -1048,5 +1048,57 @@ private:
     int mNBad = 0, mMaxTrialsAfterFailure = 10;                                                     // :50
 };
 
+// Optimizer::PoseOptimization(Frame *pFrame) (src/Optimizer.cc:264-476) on the flattened frame: one call of
+// orbm_pose_optimization (host arrays) or orbm_frame_pose_optimization (the frame's resident handle).  kpsUn = mvKeysUn,
+// uright = mvuRight (empty: monocular), hasMp[i] = mvpMapPoints[i] != NULL, mpPos[3 i ..] = its GetWorldPos(), Tcw = mTcw
+// (4 x 4 row-major floats, replaced by the optimised pose as SetPose would), outlier = mvbOutlier (written where hasMp).
+// Returns nInitialCorrespondences - nBad, or -1 on a library error (status() has the code).
+class PoseOptimization {
+public:
+    PoseOptimization(float fx, float fy, float cx, float cy, float mbf, std::vector<float> invLevelSigma2)
+        : mInv(std::move(invLevelSigma2))
+    {
+        mCam.fx = fx; mCam.fy = fy; mCam.cx = cx; mCam.cy = cy; mCam.bf = mbf;
+        mCam.nlevels = (int32_t)mInv.size();
+        mCam.inv_level_sigma2 = mInv.data();
+    }
+    PoseOptimization(const PoseOptimization &) = delete;
+    PoseOptimization &operator=(const PoseOptimization &) = delete;
+
+    int operator()(const std::vector<orbx_keypoint> &kpsUn, const std::vector<float> &uright, const std::vector<uint8_t> &hasMp,
+                   const std::vector<float> &mpPos, float Tcw[16], std::vector<uint8_t> &outlier, orbm_pose_stats *stats = nullptr)
+    {
+        const int n = (int)kpsUn.size();
+        if ((int)hasMp.size() != n || (int)mpPos.size() != 3 * n || (!uright.empty() && (int)uright.size() != n)) return fail(ORBX_ERR_ARG);
+        outlier.resize(n, 0);
+        float Tout[16];
+        int ngood = 0;
+        mStatus = orbm_pose_optimization(kpsUn.data(), uright.empty() ? nullptr : uright.data(), n, hasMp.data(), mpPos.data(), &mCam, Tcw,
+                                         Tout, outlier.data(), &ngood, stats);
+        if (mStatus != ORBX_OK) return -1;
+        std::memcpy(Tcw, Tout, sizeof(Tout));
+        return ngood;
+    }
+    int operator()(const orbm_frame *frame, const std::vector<uint8_t> &hasMp, const std::vector<float> &mpPos, float Tcw[16],
+                   std::vector<uint8_t> &outlier, orbm_pose_stats *stats = nullptr)
+    {
+        if (mpPos.size() != 3 * hasMp.size()) return fail(ORBX_ERR_ARG);
+        outlier.resize(hasMp.size(), 0);
+        float Tout[16];
+        int ngood = 0;
+        mStatus = orbm_frame_pose_optimization(frame, hasMp.data(), mpPos.data(), &mCam, Tcw, Tout, outlier.data(), &ngood, stats);
+        if (mStatus != ORBX_OK) return -1;
+        std::memcpy(Tcw, Tout, sizeof(Tout));
+        return ngood;
+    }
+    int status() const { return mStatus; }
+
+private:
+    int fail(int code) { mStatus = code; return -1; }
+    std::vector<float> mInv;
+    orbm_pose_camera mCam;
+    int mStatus = ORBX_OK;
+};
+
 } // namespace orbslam_hip
 #endif // ORBSLAM_HIP_HPP

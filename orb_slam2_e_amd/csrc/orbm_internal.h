@@ -116,4 +116,9 @@ struct StagedCall {
     }
 };
 
+// What another translation unit (orbm_pose.hip) reads of a resident frame: the sorted keypoint records and the permutation in
+// HBM (perm[sorted position] = keypoint index, all n positions), the keypoint count and the octave range.
+struct FrameDeviceView { const SeqKp *kp; const int *perm; int n, min_octave, max_octave; };
+void frame_device_view(const orbm_frame *f, FrameDeviceView &v);
+
 } // namespace orbm_detail

@@ -1,0 +1,684 @@
+// orbm_pose.hip -- Optimizer::PoseOptimization (src/Optimizer.cc:264-476) as ONE launch: one workgroup per pose problem runs
+// the 4 rounds, their Levenberg iterations and trials, the inlier / outlier classification between rounds and the final
+// toCvMat, on g2o's code paths (Thirdparty/g2o/g2o: sparse_optimizer.cpp:425-504, optimization_algorithm_levenberg.cpp:63-267,
+// base_unary_edge.hpp:40-70, robust_kernel_impl.cpp (Huber), types_six_dof_expmap.h:196-260 / .cpp:266-364, se3quat.h,
+// linear_solver_dense.h:64-112 with Eigen's LDLT).  Double precision wherever g2o computes in double; float where the reference
+// has float (the stereo edge's invz, the Huber dsqr member, deltaMono / deltaStereo, the chi2 of the classification).
+//
+// Work split: thread t of the 256 owns keypoints t, t + 256, ... (at most 32 of them: 8,192 keypoints).  Every
+// pass over the edges -- errors + robust chi2 + the 6 x 6 normal equations, the chi2 of a trial, the classification -- sums the
+// owning thread's edges in keypoint order and then combines the 256 partial sums in a fixed tree (wave butterfly, then the four
+// waves in order): no atomics, and a problem's bits do not depend on the batch around it.  The 6 x 6 LDLT, the exp map and the
+// quaternion products are computed by every lane from the same reduced values (identical bits in every lane: the result is
+// wave-uniform without a broadcast barrier).  A keypoint's constants (observation, Xw, information, kind) are staged once in LDS
+// for the first POSE_LDS_KP keypoints and read from the caller's arrays (L2) beyond that.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../include/orbslam_hip.h"
+#include "common.h"
+#include "orbm_internal.h"
+
+using namespace orbm_detail;
+
+namespace {
+
+constexpr int PT = 256;                 // threads per problem
+constexpr int PW = PT / 64;             // waves
+constexpr int POSE_MAXN = 8192;         // keypoints per problem (the resident-frame limit): 32 per thread, one bit each in a mask
+constexpr int POSE_LDS_KP = 1024;       // keypoints whose constants are staged in LDS (32 B each)
+constexpr int POSE_MAXLEVELS = 32;
+
+struct PoseCam {
+    double fx, fy, cx, cy, bf;
+    float inv_sigma2[POSE_MAXLEVELS];
+    int nlevels;
+};
+
+// the keypoint sources: host-array / device-array problems (orbx_keypoint by index) or a resident frame (SeqKp by sorted position)
+struct PoseSrc {
+    const orbx_keypoint *kps;   // [kp_off[B]] (array form) or nullptr
+    const float *uright;        // [kp_off[B]] or nullptr (monocular)
+    const SeqKp *fkp;           // resident frame: keypoints in sorted order
+    const int *fperm;           //                 perm[sorted position] = keypoint index
+    const uint8_t *has_mp;
+    const float *mp_pos;
+    const int *kp_off;          // [B + 1]
+    const float *Tin;           // [B][16]
+};
+
+struct PoseOut {
+    float *Tout;                // [B][16]
+    uint8_t *outlier;           // [kp_off[B]], written where has_mp
+    int32_t *ngood;             // [B]
+    orbm_pose_stats *stats;     // [B] or nullptr
+};
+
+struct Se3 { double q[4], t[3]; };
+
+// ------------------------------------------------------------------ se3quat.h / Eigen, in the restatement's operation order
+
+__device__ __forceinline__ void q_normalize(double q[4])
+{
+    const double n = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    if (n > 0.0) {
+        const double s = sqrt(n);
+        q[0] /= s; q[1] /= s; q[2] /= s; q[3] /= s;
+    }
+}
+
+__device__ __forceinline__ void normalize_rotation(double q[4])   // SE3Quat::normalizeRotation
+{
+    if (q[3] < 0) { q[0] *= -1; q[1] *= -1; q[2] *= -1; q[3] *= -1; }
+    q_normalize(q);
+}
+
+// the trace <= 0 branch with the largest diagonal entry at I (a compile-time index: R and q stay in registers)
+template <int I>
+__device__ __forceinline__ void quat_from_matrix_diag(const double R[9], double q[4])
+{
+#define M(i, j) R[3 * (i) + (j)]
+    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
+    double t = sqrt(M(I, I) - M(J, J) - M(K, K) + 1.0);
+    q[I] = 0.5 * t;
+    t = 0.5 / t;
+    q[3] = (M(K, J) - M(J, K)) * t;
+    q[J] = (M(J, I) + M(I, J)) * t;
+    q[K] = (M(K, I) + M(I, K)) * t;
+#undef M
+}
+
+__device__ void quat_from_matrix(const double R[9], double q[4])   // Quaterniond(const Matrix3d&)
+{
+#define M(i, j) R[3 * (i) + (j)]
+    double t = M(0, 0) + M(1, 1) + M(2, 2);
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (M(2, 1) - M(1, 2)) * t;
+        q[1] = (M(0, 2) - M(2, 0)) * t;
+        q[2] = (M(1, 0) - M(0, 1)) * t;
+    } else {
+        int i = 0;
+        if (M(1, 1) > M(0, 0)) i = 1;
+        if (M(2, 2) > (i == 1 ? M(1, 1) : M(0, 0))) i = 2;
+        if (i == 0) quat_from_matrix_diag<0>(R, q);
+        else if (i == 1) quat_from_matrix_diag<1>(R, q);
+        else quat_from_matrix_diag<2>(R, q);
+    }
+#undef M
+}
+
+__device__ __forceinline__ void quat_to_matrix(const double q[4], double R[9])   // toRotationMatrix
+{
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w;
+    const double txx = tx * x, txy = ty * x, txz = tz * x;
+    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
+    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
+}
+
+__device__ __forceinline__ void q_rotate(const double q[4], const double v[3], double o[3])   // Quaternion * Vector3d
+{
+    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
+    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
+    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+    for (int i = 0; i < 3; ++i) o[i] = v[i] + q[3] * uv[i] + c[i];
+}
+
+__device__ __forceinline__ void se3_map(const Se3 &T, const double X[3], double o[3])   // SE3Quat::map
+{
+    q_rotate(T.q, X, o);
+    o[0] += T.t[0]; o[1] += T.t[1]; o[2] += T.t[2];
+}
+
+__device__ void se3_exp(const double u[6], Se3 &T)   // SE3Quat::exp
+{
+    const double w0 = u[0], w1 = u[1], w2 = u[2];
+    const double theta = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+    const double Om[9] = {0., -w2, w1, w2, 0., -w0, -w1, w0, 0.};
+    double O2[9], R[9], V[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) O2[3 * i + j] = Om[3 * i] * Om[j] + Om[3 * i + 1] * Om[3 + j] + Om[3 * i + 2] * Om[6 + j];
+    if (theta < 0.00001) {
+        for (int k = 0; k < 9; ++k) { R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + Om[k] + O2[k]; V[k] = R[k]; }
+    } else {
+        const double a = sin(theta) / theta, b = (1 - cos(theta)) / (theta * theta), c = (theta - sin(theta)) / (pow(theta, 3.0));
+        for (int k = 0; k < 9; ++k) {
+            const double I = (k % 4 == 0) ? 1.0 : 0.0;
+            R[k] = I + a * Om[k] + b * O2[k];
+            V[k] = I + b * Om[k] + c * O2[k];
+        }
+    }
+    quat_from_matrix(R, T.q);
+    for (int i = 0; i < 3; ++i) T.t[i] = V[3 * i] * u[3] + V[3 * i + 1] * u[4] + V[3 * i + 2] * u[5];
+    normalize_rotation(T.q);
+}
+
+__device__ void se3_compose(const Se3 &A, const Se3 &B, Se3 &O)   // SE3Quat::operator*
+{
+    Se3 r = A;
+    double rt[3];
+    q_rotate(A.q, B.t, rt);
+    r.t[0] += rt[0]; r.t[1] += rt[1]; r.t[2] += rt[2];
+    const double *a = A.q, *b = B.q;
+    r.q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+    r.q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    normalize_rotation(r.q);
+    O = r;
+}
+
+__device__ void se3_from_cv(const float *T, Se3 &o)   // Converter::toSE3Quat
+{
+    const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+    quat_from_matrix(R, o.q);
+    o.t[0] = T[3]; o.t[1] = T[7]; o.t[2] = T[11];
+    normalize_rotation(o.q);
+}
+
+// Eigen::LDLT (Eigen 3.3 ldlt_inplace: diagonal pivoting, lower triangle) + solve; returns isPositive().  Every loop has constant
+// bounds and the pivot swaps are selects over the constant candidates, so the matrix stays in registers (a dynamic index would put
+// it in scratch memory, on the serial path of every trial).
+#define POSE_UNROLL _Pragma("unroll")
+__device__ bool ldlt_solve6(double m[36], const double b[6], double x[6])
+{
+    int tr[6];
+    int sign = 0;   // 0 ZeroSign, 1 PositiveSemiDef, 2 NegativeSemiDef, 3 Indefinite
+    double temp[6];
+#define L(i, j) m[6 * (i) + (j)]
+    POSE_UNROLL for (int k = 0; k < 6; ++k) {
+        int big = k;
+        double bv = fabs(L(k, k));
+        POSE_UNROLL for (int j = k + 1; j < 6; ++j) {
+            const double f = fabs(L(j, j));
+            if (f > bv) { big = j; bv = f; }
+        }
+        tr[k] = big;
+        POSE_UNROLL for (int c = k + 1; c < 6; ++c) {
+            if (big != c) continue;
+            POSE_UNROLL for (int j = 0; j < k; ++j) { const double s = L(k, j); L(k, j) = L(c, j); L(c, j) = s; }
+            POSE_UNROLL for (int i = c + 1; i < 6; ++i) { const double s = L(i, k); L(i, k) = L(i, c); L(i, c) = s; }
+            { const double s = L(k, k); L(k, k) = L(c, c); L(c, c) = s; }
+            POSE_UNROLL for (int i = k + 1; i < c; ++i) { const double s = L(i, k); L(i, k) = L(c, i); L(c, i) = s; }
+        }
+        if (k > 0) {
+            POSE_UNROLL for (int j = 0; j < k; ++j) temp[j] = L(j, j) * L(k, j);
+            double s = L(k, 0) * temp[0];
+            POSE_UNROLL for (int j = 1; j < k; ++j) s = s + L(k, j) * temp[j];
+            L(k, k) -= s;
+            POSE_UNROLL for (int i = k + 1; i < 6; ++i) {
+                double a = L(i, 0) * temp[0];
+                POSE_UNROLL for (int j = 1; j < k; ++j) a = a + L(i, j) * temp[j];
+                L(i, k) -= a;
+            }
+        }
+        const double akk = L(k, k);
+        const bool valid = fabs(akk) > 0.0;
+        if (k == 0 && !valid) { POSE_UNROLL for (int j = 0; j < 6; ++j) x[j] = 0.0; return true; }
+        if (valid)
+            POSE_UNROLL for (int i = k + 1; i < 6; ++i) L(i, k) /= akk;
+        if (sign == 1) { if (akk < 0) sign = 3; }
+        else if (sign == 2) { if (akk > 0) sign = 3; }
+        else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = 2; }
+    }
+    if (!(sign == 1 || sign == 0)) return false;
+    double y[6];
+    POSE_UNROLL for (int i = 0; i < 6; ++i) y[i] = b[i];
+    POSE_UNROLL for (int k = 0; k < 6; ++k)
+        POSE_UNROLL for (int c = k + 1; c < 6; ++c)
+            if (tr[k] == c) { const double s = y[k]; y[k] = y[c]; y[c] = s; }
+    POSE_UNROLL for (int i = 0; i < 6; ++i) POSE_UNROLL for (int j = 0; j < i; ++j) y[i] -= L(i, j) * y[j];
+    POSE_UNROLL for (int i = 0; i < 6; ++i) y[i] = (fabs(L(i, i)) > 2.2250738585072014e-308) ? y[i] / L(i, i) : 0.0;
+    POSE_UNROLL for (int i = 5; i >= 0; --i) POSE_UNROLL for (int j = i + 1; j < 6; ++j) y[i] -= L(j, i) * y[j];
+    POSE_UNROLL for (int k = 5; k >= 0; --k)
+        POSE_UNROLL for (int c = k + 1; c < 6; ++c)
+            if (tr[k] == c) { const double s = y[k]; y[k] = y[c]; y[c] = s; }
+    POSE_UNROLL for (int i = 0; i < 6; ++i) x[i] = y[i];
+#undef L
+    return true;
+}
+
+// ------------------------------------------------------------------ the edges
+
+struct Edge { double obs[3], Xw[3], info; int kind; };   // kind 0: no map point, 1: mono, 2: stereo
+
+// computeError of both pose-only edges (cam_project: .cpp:306-325)
+__device__ __forceinline__ void edge_error(const PoseCam &c, const Edge &e, const Se3 &T, double err[3], double p[3])
+{
+    se3_map(T, e.Xw, p);
+    if (e.kind == 1) {
+        const double u = p[0] / p[2], v = p[1] / p[2];
+        err[0] = e.obs[0] - (u * c.fx + c.cx);
+        err[1] = e.obs[1] - (v * c.fy + c.cy);
+        err[2] = 0.0;
+    } else {
+        const float invz = 1.0f / p[2];
+        const double r0 = p[0] * invz * c.fx + c.cx;
+        const double r1 = p[1] * invz * c.fy + c.cy;
+        const double r2 = r0 - c.bf * invz;
+        err[0] = e.obs[0] - r0; err[1] = e.obs[1] - r1; err[2] = e.obs[2] - r2;
+    }
+}
+
+// BaseEdge::chi2 with a diagonal information matrix (the off-diagonal zeros multiplied, as in the restatement)
+__device__ __forceinline__ double edge_chi2(const Edge &e, const double err[3])
+{
+    const int D = e.kind == 2 ? 3 : 2;
+    double oe[3];
+    POSE_UNROLL for (int i = 0; i < 3; ++i) {
+        double s = ((i == 0) ? e.info : 0.0) * err[0];
+        POSE_UNROLL for (int j = 1; j < 3; ++j) if (j < D) s += ((i == j) ? e.info : 0.0) * err[j];
+        oe[i] = s;
+    }
+    double r = err[0] * oe[0];
+    POSE_UNROLL for (int i = 1; i < 3; ++i) if (i < D) r += err[i] * oe[i];
+    return r;
+}
+
+__device__ __forceinline__ void huber(double e, double delta, double &rho0, double &rho1)   // RobustKernelHuber::robustify
+{
+    const float dsqr = (float)(delta * delta);
+    if (e <= dsqr) { rho0 = e; rho1 = 1.; }
+    else {
+        const double sqrte = sqrt(e);
+        rho0 = 2 * sqrte * delta - dsqr;
+        rho1 = delta / sqrte;
+    }
+}
+
+// linearizeOplus of both edges at the mapped point p
+__device__ __forceinline__ void edge_jacobian(const PoseCam &c, int kind, const double p[3], double J[18])
+{
+    const double x = p[0], y = p[1], invz = 1.0 / p[2], invz_2 = invz * invz;
+    J[0] = x * y * invz_2 * c.fx; J[1] = -(1 + (x * x * invz_2)) * c.fx; J[2] = y * invz * c.fx;
+    J[3] = -invz * c.fx;          J[4] = 0;                               J[5] = x * invz_2 * c.fx;
+    J[6] = (1 + y * y * invz_2) * c.fy; J[7] = -x * y * invz_2 * c.fy; J[8] = -x * invz * c.fy;
+    J[9] = 0;                           J[10] = -invz * c.fy;          J[11] = y * invz_2 * c.fy;
+    if (kind == 2) {
+        J[12] = J[0] - c.bf * y * invz_2; J[13] = J[1] + c.bf * x * invz_2; J[14] = J[2];
+        J[15] = J[3];                     J[16] = 0;                        J[17] = J[5] - c.bf * invz_2;
+    }
+}
+
+// ------------------------------------------------------------------ fixed-order block reductions
+
+constexpr int NSYS = 21 + 6 + 1;    // lower triangle of H, A^T w omega e, robust chi2
+
+template <int NV>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double (*red)[NSYS])
+{
+    for (int j = 0; j < NV; ++j)
+        for (int o = 32; o >= 1; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
+    __syncthreads();                                        // the previous reduction's readers are done with red
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0)
+        for (int j = 0; j < NV; ++j) red[w][j] = v[j];
+    __syncthreads();
+    for (int j = 0; j < NV; ++j) v[j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
+}
+
+__device__ __forceinline__ int block_sum_int(int v, int *ired)
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) ired[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ired[0] + ired[1] + ired[2] + ired[3];
+}
+
+template <bool FRAME>
+__global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam cam, PoseOut out)
+{
+    __shared__ float4 s_a[POSE_LDS_KP], s_b[POSE_LDS_KP];   // (obs x, obs y, ur, info), (Xw, kind)
+    __shared__ uint16_t s_inv[FRAME ? POSE_MAXN : 1];        // resident frame: sorted position of keypoint i
+    __shared__ double s_red[PW][NSYS];
+    __shared__ int s_ired[PW];
+
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int base = src.kp_off[b], n = src.kp_off[b + 1] - base;
+    const float *Tin = src.Tin + 16 * b;
+    if (n < 0 || n > POSE_MAXN) {
+        if (tid == 0) out.ngood[b] = ORBX_ERR_UNSUPPORTED;
+        return;
+    }
+    if (FRAME) {
+        for (int sp = tid; sp < n; sp += PT) s_inv[src.fperm[sp]] = (uint16_t)sp;
+        __syncthreads();
+    }
+
+    // one keypoint's edge constants, from the caller's arrays (Optimizer.cc:303-383)
+    auto fetch = [&](int i, float4 &a, float4 &c) {
+        const int g = base + i;
+        float kx, ky, ur; int oct;
+        if (FRAME) {
+            const SeqKp k = src.fkp[s_inv[i]];
+            kx = k.x; ky = k.y; ur = k.uright; oct = k.octave;
+        } else {
+            const orbx_keypoint &k = src.kps[g];
+            kx = k.x; ky = k.y; oct = k.octave;
+            ur = src.uright ? src.uright[g] : -1.0f;
+        }
+        const bool has = src.has_mp[g] != 0;
+        oct = oct < 0 ? 0 : (oct >= POSE_MAXLEVELS ? POSE_MAXLEVELS - 1 : oct);
+        a = make_float4(kx, ky, ur, cam.inv_sigma2[oct]);
+        c = has ? make_float4(src.mp_pos[3 * (size_t)g], src.mp_pos[3 * (size_t)g + 1], src.mp_pos[3 * (size_t)g + 2], ur < 0 ? 1.f : 2.f)
+                : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    int nloc = 0;
+    for (int i = tid; i < n && i < POSE_LDS_KP; i += PT, ++nloc) fetch(i, s_a[i], s_b[i]);
+    auto edge = [&](int i, Edge &e) {
+        float4 a, c;
+        if (i < POSE_LDS_KP) { a = s_a[i]; c = s_b[i]; }
+        else fetch(i, a, c);
+        e.obs[0] = a.x; e.obs[1] = a.y; e.obs[2] = a.z; e.info = a.w;
+        e.Xw[0] = c.x; e.Xw[1] = c.y; e.Xw[2] = c.z; e.kind = (int)c.w;
+    };
+    (void)nloc;
+
+    // nInitialCorrespondences (every keypoint with a map point gives one edge; mvbOutlier = false)
+    uint32_t lvl = 0;                       // bit k: the k-th owned keypoint's edge is at level 1 (mvbOutlier)
+    int mine = 0;
+    for (int i = tid; i < n; i += PT) mine += src.has_mp[base + i] != 0;
+    const int nInitial = block_sum_int(mine, s_ired);
+
+    const float deltaMono = sqrt(5.991), deltaStereo = sqrt(7.815);
+    const float chi2Mono = 5.991f, chi2Stereo = 7.815f;
+
+    orbm_pose_stats st;
+    memset(&st, 0, sizeof(st));
+    st.ninitial = nInitial;
+    if (nInitial < 3) {
+        for (int i = tid; i < n; i += PT)
+            if (src.has_mp[base + i]) out.outlier[base + i] = 0;
+        if (tid < 16) out.Tout[16 * b + tid] = Tin[tid];
+        if (tid == 0) {
+            out.ngood[b] = 0;
+            if (out.stats) out.stats[b] = st;
+        }
+        return;
+    }
+
+    Se3 est, eval;                          // the estimate; the pose of the last computeActiveErrors
+    int nBad = 0;
+    for (int it = 0; it < 4; ++it) {
+        const bool robust = it < 3;         // setRobustKernel(0) after the classification of it == 2
+        se3_from_cv(Tin, est);
+        const int nactive = nInitial - nBad;
+        int iters = 0, trials = 0;
+        double currentChiOut = 0.0;
+
+        // one pass: errors at T, robust chi2 and (with SYS) the normal equations; returns the block totals in v
+        auto pass = [&](const Se3 &T, bool sys, double (&v)[NSYS]) {
+            for (int j = 0; j < NSYS; ++j) v[j] = 0.0;
+            int k = 0;
+            for (int i = tid; i < n; i += PT, ++k) {
+                if ((lvl >> k) & 1u) continue;
+                Edge e;
+                edge(i, e);
+                if (!e.kind) continue;
+                double err[3], p[3];
+                edge_error(cam, e, T, err, p);
+                const double chi2 = edge_chi2(e, err);
+                double rho0 = chi2, w = 1.0;
+                if (robust) huber(chi2, e.kind == 2 ? (double)deltaStereo : (double)deltaMono, rho0, w);
+                v[27] += rho0;
+                if (!sys) continue;
+                double J[18];
+                edge_jacobian(cam, e.kind, p, J);
+                const int D = e.kind == 2 ? 3 : 2;
+                const double winfo = w * e.info;
+                POSE_UNROLL for (int r = 0; r < 6; ++r) {
+                    double s = 0;
+                    POSE_UNROLL for (int ii = 0; ii < 3; ++ii) if (ii < D) s += J[6 * ii + r] * (e.info * err[ii]);
+                    v[21 + r] += w * s;
+                    POSE_UNROLL for (int c = 0; c <= r; ++c) {
+                        double hh = 0;
+                        POSE_UNROLL for (int ii = 0; ii < 3; ++ii) if (ii < D) hh += J[6 * ii + r] * (winfo * J[6 * ii + c]);
+                        v[r * (r + 1) / 2 + c] += hh;
+                    }
+                }
+            }
+            if (sys) block_sum<NSYS>(v, s_red);
+            else {
+                double c1[1] = {v[27]};
+                block_sum<1>(c1, s_red);
+                v[27] = c1[0];
+            }
+        };
+
+        if (nactive > 0) {
+            double lambda = 0.0;
+            int ni = 2, lmBad = 0;
+            for (int iteration = 0; iteration < 10; ++iteration) {      // SparseOptimizer::optimize
+                ++iters;
+                double v[NSYS];
+                pass(est, true, v);                                     // computeActiveErrors, activeRobustChi2, buildSystem
+                eval = est;
+                double currentChi = v[27];
+                const double iniChi = currentChi;
+                double H[36], bb[6];
+                for (int r = 0, h = 0; r < 6; ++r)
+                    for (int c = 0; c <= r; ++c, ++h) H[6 * r + c] = v[h];
+                for (int r = 0; r < 6; ++r) bb[r] = -v[21 + r];
+                if (iteration == 0) {                                   // computeLambdaInit, tau = 1e-5
+                    double maxDiagonal = 0.;
+                    for (int j = 0; j < 6; ++j) { const double f = fabs(H[7 * j]); maxDiagonal = (f < maxDiagonal) ? maxDiagonal : f; }
+                    lambda = 1e-5 * maxDiagonal;
+                    ni = 2;
+                    lmBad = 0;
+                }
+                double rho = 0;
+                int qmax = 0;
+                do {
+                    double Hl[36], x[6] = {0, 0, 0, 0, 0, 0};
+                    for (int j = 0; j < 36; ++j) Hl[j] = H[j];
+                    for (int j = 0; j < 6; ++j) Hl[7 * j] += lambda;
+                    const bool ok2 = ldlt_solve6(Hl, bb, x);
+                    Se3 up, trial;
+                    se3_exp(x, up);
+                    se3_compose(up, est, trial);
+                    double cv[NSYS];
+                    pass(trial, false, cv);
+                    eval = trial;
+                    double tempChi = cv[27];
+                    if (!ok2) tempChi = 1.7976931348623157e308;
+                    rho = (currentChi - tempChi);
+                    double scale = 0.;
+                    for (int j = 0; j < 6; ++j) scale += x[j] * (lambda * x[j] + bb[j]);
+                    scale += 1e-3;
+                    rho /= scale;
+                    if (rho > 0 && isfinite(tempChi)) {
+                        double alpha = 1. - pow((2 * rho - 1), 3.0);
+                        alpha = (alpha < 2. / 3.) ? alpha : 2. / 3.;
+                        const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;
+                        lambda *= scaleFactor;
+                        ni = 2;
+                        currentChi = tempChi;
+                        est = trial;
+                    } else {
+                        lambda *= ni;
+                        ni *= 2;
+                    }
+                    qmax++;
+                } while (rho < 0 && qmax < 10);
+                trials += qmax;
+                currentChiOut = currentChi;
+                if (qmax == 10 || rho == 0) break;                      // Terminate
+                if ((iniChi - currentChi) * 1e3 < iniChi) lmBad++;      // Raul's stop criterion
+                else lmBad = 0;
+                if (lmBad >= 3) break;
+            }
+        }
+        st.rounds = it + 1; st.iterations[it] = iters; st.trials[it] = trials; st.chi2 = currentChiOut;
+
+        // classification (Optimizer.cc:393-448): level-1 edges recompute their error at the estimate, active edges keep the
+        // error of the last computeActiveErrors (at `eval`, the last TRIED pose)
+        int bad = 0, k = 0;
+        for (int i = tid; i < n; i += PT, ++k) {
+            Edge e;
+            edge(i, e);
+            if (!e.kind) continue;
+            const bool was_out = (lvl >> k) & 1u;
+            double err[3], p[3];
+            edge_error(cam, e, was_out ? est : eval, err, p);
+            const float chi2 = edge_chi2(e, err);
+            if (chi2 > (e.kind == 2 ? chi2Stereo : chi2Mono)) { lvl |= 1u << k; bad++; }
+            else lvl &= ~(1u << k);
+        }
+        nBad = block_sum_int(bad, s_ired);
+        if (nInitial < 10) break;                                       // optimizer.edges().size() < 10
+    }
+
+    int k = 0;
+    for (int i = tid; i < n; i += PT, ++k)
+        if (src.has_mp[base + i]) out.outlier[base + i] = (lvl >> k) & 1u;
+    if (tid == 0) {
+        double R[9];
+        quat_to_matrix(est.q, R);                                       // Converter::toCvMat(SE3Quat)
+        float *T = out.Tout + 16 * b;
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) T[4 * i + j] = (float)R[3 * i + j];
+            T[4 * i + 3] = (float)est.t[i];
+        }
+        T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
+        out.ngood[b] = nInitial - nBad;
+        if (out.stats) {
+            for (int j = 0; j < 4; ++j) st.q[j] = est.q[j];
+            for (int j = 0; j < 3; ++j) st.t[j] = est.t[j];
+            out.stats[b] = st;
+        }
+    }
+}
+
+int make_cam(const orbm_pose_camera *c, PoseCam &pc)
+{
+    if (!c || c->nlevels < 1 || c->nlevels > POSE_MAXLEVELS || !c->inv_level_sigma2) return -1;
+    memset(&pc, 0, sizeof(pc));
+    pc.fx = c->fx; pc.fy = c->fy; pc.cx = c->cx; pc.cy = c->cy; pc.bf = c->bf;
+    for (int l = 0; l < c->nlevels; ++l) pc.inv_sigma2[l] = c->inv_level_sigma2[l];
+    pc.nlevels = c->nlevels;
+    return 0;
+}
+
+int check_octaves_host(const orbx_keypoint *kps, const uint8_t *has_mp, int n, int nlevels)
+{
+    for (int i = 0; i < n; ++i)
+        if (has_mp[i] && (kps[i].octave < 0 || kps[i].octave >= nlevels)) return -1;
+    return 0;
+}
+
+// the host-array forms: stage everything, one launch, one download, scatter the outlier flags where has_mp
+int pose_host(const orbx_keypoint *kps, const float *uright, const int32_t *kp_off, int batch, const uint8_t *has_mp, const float *mp_pos,
+              const PoseCam &pc, const float *Tin, float *Tout, uint8_t *outlier, int32_t *ngood, orbm_pose_stats *stats)
+{
+    const int total = kp_off[batch];
+    StagedCall sc;
+    const size_t o_k = sc.in(kps, sizeof(orbx_keypoint) * (size_t)total), o_u = uright ? sc.in(uright, sizeof(float) * (size_t)total) : 0,
+                 o_h = sc.in(has_mp, (size_t)total), o_p = sc.in(mp_pos, sizeof(float) * 3 * (size_t)total),
+                 o_o = sc.in(kp_off, sizeof(int32_t) * (size_t)(batch + 1)), o_t = sc.in(Tin, sizeof(float) * 16 * (size_t)batch);
+    const size_t r_t = sc.out(sizeof(float) * 16 * (size_t)batch), r_g = sc.out(sizeof(int32_t) * (size_t)batch),
+                 r_s = sc.out(sizeof(orbm_pose_stats) * (size_t)batch), r_o = sc.out((size_t)total);
+    if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
+    PoseSrc src = {sc.d<orbx_keypoint>(o_k), uright ? sc.d<float>(o_u) : nullptr, nullptr, nullptr, sc.d<uint8_t>(o_h), sc.d<float>(o_p),
+                   sc.d<int>(o_o), sc.d<float>(o_t)};
+    PoseOut po = {sc.d<float>(r_t), sc.d<uint8_t>(r_o), sc.d<int32_t>(r_g), sc.d<orbm_pose_stats>(r_s)};
+    hipLaunchKernelGGL(k_pose_optimization<false>, dim3(batch), dim3(PT), 0, sc.stream(), src, pc, po);
+    ORBX_HIP(hipGetLastError());
+    if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
+    memcpy(Tout, sc.r<float>(r_t), sizeof(float) * 16 * (size_t)batch);
+    memcpy(ngood, sc.r<int32_t>(r_g), sizeof(int32_t) * (size_t)batch);
+    if (stats) memcpy(stats, sc.r<orbm_pose_stats>(r_s), sizeof(orbm_pose_stats) * (size_t)batch);
+    const uint8_t *o = sc.r<uint8_t>(r_o);
+    for (int i = 0; i < total; ++i)
+        if (has_mp[i]) outlier[i] = o[i];
+    for (int p = 0; p < batch; ++p)
+        if (ngood[p] < 0) ORBX_FAIL(ngood[p], "pose problem rejected by the kernel");
+    return ORBX_OK;
+}
+
+} // namespace
+
+int orbm_pose_optimization(const orbx_keypoint *kps_un, const float *uright, int n, const uint8_t *has_mp, const float *mp_pos,
+                           const orbm_pose_camera *cam, const float *Tcw_in, float *Tcw_out, uint8_t *outlier, int *ngood,
+                           orbm_pose_stats *stats)
+{
+    PoseCam pc;
+    if (n < 0 || (n && (!kps_un || !has_mp || !mp_pos || !outlier)) || !Tcw_in || !Tcw_out || !ngood || make_cam(cam, pc))
+        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (n > POSE_MAXN) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 8,192 keypoints in one pose problem");
+    if (check_octaves_host(kps_un, has_mp, n, cam->nlevels)) ORBX_FAIL(ORBX_ERR_ARG, "keypoint octave outside mvInvLevelSigma2");
+    ORBX_NEED_DEVICE();
+    const int32_t off[2] = {0, n};
+    return pose_host(kps_un, uright, off, 1, has_mp, mp_pos, pc, Tcw_in, Tcw_out, outlier, ngood, stats);
+}
+
+int orbm_frame_pose_optimization(const orbm_frame *frame, const uint8_t *has_mp, const float *mp_pos, const orbm_pose_camera *cam,
+                                 const float *Tcw_in, float *Tcw_out, uint8_t *outlier, int *ngood, orbm_pose_stats *stats)
+{
+    PoseCam pc;
+    if (!frame || !Tcw_in || !Tcw_out || !ngood || make_cam(cam, pc)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    ORBX_NEED_DEVICE();
+    FrameDeviceView fv;
+    frame_device_view(frame, fv);
+    const int n = fv.n;
+    if (n && (!has_mp || !mp_pos || !outlier)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (n > POSE_MAXN) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 8,192 keypoints in one pose problem");
+    if (fv.min_octave < 0 || fv.max_octave >= cam->nlevels) ORBX_FAIL(ORBX_ERR_ARG, "keypoint octave outside mvInvLevelSigma2");
+    const int32_t off[2] = {0, n};
+    StagedCall sc;
+    const size_t o_h = sc.in(has_mp, (size_t)n), o_p = sc.in(mp_pos, sizeof(float) * 3 * (size_t)n), o_o = sc.in(off, sizeof(off)),
+                 o_t = sc.in(Tcw_in, sizeof(float) * 16);
+    const size_t r_t = sc.out(sizeof(float) * 16), r_g = sc.out(sizeof(int32_t)), r_s = sc.out(sizeof(orbm_pose_stats)), r_o = sc.out((size_t)n);
+    if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
+    PoseSrc src = {nullptr, nullptr, fv.kp, fv.perm, sc.d<uint8_t>(o_h), sc.d<float>(o_p), sc.d<int>(o_o), sc.d<float>(o_t)};
+    PoseOut po = {sc.d<float>(r_t), sc.d<uint8_t>(r_o), sc.d<int32_t>(r_g), sc.d<orbm_pose_stats>(r_s)};
+    hipLaunchKernelGGL(k_pose_optimization<true>, dim3(1), dim3(PT), 0, sc.stream(), src, pc, po);
+    ORBX_HIP(hipGetLastError());
+    if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
+    memcpy(Tcw_out, sc.r<float>(r_t), sizeof(float) * 16);
+    *ngood = *sc.r<int32_t>(r_g);
+    if (stats) memcpy(stats, sc.r<orbm_pose_stats>(r_s), sizeof(orbm_pose_stats));
+    const uint8_t *o = sc.r<uint8_t>(r_o);
+    for (int i = 0; i < n; ++i)
+        if (has_mp[i]) outlier[i] = o[i];
+    return ORBX_OK;
+}
+
+int orbm_pose_optimization_batch(const orbx_keypoint *kps_un, const float *uright, const int32_t *kp_off, int batch, const uint8_t *has_mp,
+                                 const float *mp_pos, const orbm_pose_camera *cam, const float *Tcw_in, float *Tcw_out, uint8_t *outlier,
+                                 int32_t *ngood, orbm_pose_stats *stats, int is_device, void *stream)
+{
+    PoseCam pc;
+    if (batch < 0 || !kp_off || !Tcw_in || !Tcw_out || !ngood || make_cam(cam, pc)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (batch == 0) return ORBX_OK;
+    if (is_device) {
+        if (!kps_un || !has_mp || !mp_pos || !outlier) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+        ORBX_NEED_DEVICE();
+        PoseSrc src = {kps_un, uright, nullptr, nullptr, has_mp, mp_pos, kp_off, Tcw_in};
+        PoseOut po = {Tcw_out, outlier, ngood, stats};
+        hipLaunchKernelGGL(k_pose_optimization<false>, dim3(batch), dim3(PT), 0, (hipStream_t)stream, src, pc, po);
+        ORBX_HIP(hipGetLastError());
+        return ORBX_OK;
+    }
+    if (kp_off[0] != 0) ORBX_FAIL(ORBX_ERR_ARG, "kp_off[0] must be 0");
+    for (int p = 0; p < batch; ++p) {
+        const int np = kp_off[p + 1] - kp_off[p];
+        if (np < 0) ORBX_FAIL(ORBX_ERR_ARG, "kp_off must not decrease");
+        if (np > POSE_MAXN) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 8,192 keypoints in one pose problem");
+    }
+    const int total = kp_off[batch];
+    if (total && (!kps_un || !has_mp || !mp_pos || !outlier)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (check_octaves_host(kps_un, has_mp, total, cam->nlevels)) ORBX_FAIL(ORBX_ERR_ARG, "keypoint octave outside mvInvLevelSigma2");
+    ORBX_NEED_DEVICE();
+    return pose_host(kps_un, uright, kp_off, batch, has_mp, mp_pos, pc, Tcw_in, Tcw_out, outlier, ngood, stats);
+}

@@ -1510,6 +1510,11 @@ struct orbm_frame {
     std::vector<int> inv_host;                              // [n]: sorted position of keypoint index
 };
 
+void orbm_detail::frame_device_view(const orbm_frame *f, FrameDeviceView &v)
+{
+    v.kp = f->kp; v.perm = f->perm; v.n = f->n; v.min_octave = f->min_octave; v.max_octave = f->max_octave;
+}
+
 namespace {
 
 std::mutex g_frame_mu;

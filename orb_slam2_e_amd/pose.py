@@ -1,0 +1,87 @@
+"""ctypes mirror of the pose-only optimisation (include/orbslam_hip.h: orbm_pose_optimization, orbm_frame_pose_optimization,
+orbm_pose_optimization_batch) -- Optimizer::PoseOptimization (src/Optimizer.cc:264-476) on the device."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import bind, check, lib, ptr
+from .extractor import KP_DTYPE
+
+
+class PoseCamera(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float),
+                ("nlevels", C.c_int32), ("inv_level_sigma2", C.c_void_p)]
+
+
+class PoseStats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("iterations", C.c_int32 * 4), ("trials", C.c_int32 * 4), ("ninitial", C.c_int32),
+                ("chi2", C.c_double), ("q", C.c_double * 4), ("t", C.c_double * 3)]
+
+
+def _camera(cam, inv_level_sigma2):
+    inv = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    c = PoseCamera(*[float(v) for v in cam[:5]], len(inv), inv.ctypes.data)
+    c._keep = inv
+    return c
+
+
+def _kps(kps_xy, octave):
+    k = np.zeros(len(octave), KP_DTYPE)
+    xy = np.asarray(kps_xy, np.float32).reshape(-1, 2)
+    k["x"], k["y"], k["octave"] = xy[:, 0], xy[:, 1], np.asarray(octave, np.int32)
+    return k
+
+
+def pose_optimization(kps_xy, octave, uright, has_mp, mp_pos, cam, inv_level_sigma2, Tcw, frame=None):
+    """One PoseOptimization call.  kps_xy[n, 2] / octave[n] = mvKeysUn, uright[n] = mvuRight (None: monocular), has_mp[n],
+    mp_pos[n, 3], cam = (fx, fy, cx, cy, mbf), Tcw = mTcw.  With `frame` (a matcher.Frame / orbm_frame handle on the same
+    keypoints) kps_xy / octave / uright are not sent: the call reads them from the resident frame.
+    Returns (ngood, Tcw_out float32[4, 4], outlier uint8[n] (0 where has_mp is not set), PoseStats)."""
+    L = lib()
+    has_mp = np.ascontiguousarray(has_mp, np.uint8)
+    n = len(has_mp)
+    mp = np.ascontiguousarray(mp_pos, np.float32).reshape(n, 3)
+    Tin = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    Tout = np.zeros(16, np.float32)
+    outlier = np.zeros(n, np.uint8)
+    ng = C.c_int(0)
+    st = PoseStats()
+    c = _camera(cam, inv_level_sigma2)
+    vp = C.c_void_p
+    if frame is not None:
+        h = frame._h if hasattr(frame, "_h") else frame
+        f = bind(L.orbm_frame_pose_optimization, [vp, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, C.POINTER(C.c_int), C.POINTER(PoseStats)])
+        check(f(h, ptr(has_mp), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier), C.byref(ng), C.byref(st)))
+    else:
+        k = _kps(kps_xy, octave)
+        ur = None if uright is None else ptr(np.ascontiguousarray(uright, np.float32))
+        f = bind(L.orbm_pose_optimization, [vp, vp, C.c_int, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, C.POINTER(C.c_int),
+                                            C.POINTER(PoseStats)])
+        check(f(ptr(k), ur, n, ptr(has_mp), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier), C.byref(ng), C.byref(st)))
+    return ng.value, Tout.reshape(4, 4), outlier, st
+
+
+def pose_optimization_batch(problems, cam, inv_level_sigma2):
+    """B problems in one launch (host arrays).  problems: list of dicts with kp_xy, octave, uright (or None), has_mp, mp_pos, Tcw.
+    Returns a list of (ngood, Tcw_out, outlier, PoseStats) as pose_optimization returns them."""
+    L = lib()
+    B = len(problems)
+    sizes = [len(p["has_mp"]) for p in problems]
+    off = np.zeros(B + 1, np.int32)
+    off[1:] = np.cumsum(sizes)
+    k = np.concatenate([_kps(p["kp_xy"], p["octave"]) for p in problems]) if B else np.zeros(0, KP_DTYPE)
+    ur = np.concatenate([np.full(s, -1, np.float32) if p["uright"] is None else np.asarray(p["uright"], np.float32)
+                         for p, s in zip(problems, sizes)])
+    has = np.ascontiguousarray(np.concatenate([np.asarray(p["has_mp"], np.uint8) for p in problems]))
+    mp = np.ascontiguousarray(np.concatenate([np.asarray(p["mp_pos"], np.float32).reshape(-1, 3) for p in problems]))
+    Tin = np.ascontiguousarray(np.stack([np.asarray(p["Tcw"], np.float32).reshape(16) for p in problems]))
+    Tout = np.zeros((B, 16), np.float32)
+    outlier = np.zeros(len(has), np.uint8)
+    ng = np.zeros(B, np.int32)
+    st = (PoseStats * max(B, 1))()
+    c = _camera(cam, inv_level_sigma2)
+    vp = C.c_void_p
+    f = bind(L.orbm_pose_optimization_batch, [vp, vp, vp, C.c_int, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, vp, vp, C.c_int, vp])
+    check(f(ptr(k), ptr(ur), ptr(off), B, ptr(has), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier), ptr(ng),
+            C.cast(st, vp), 0, None))
+    return [(int(ng[p]), Tout[p].reshape(4, 4), outlier[off[p]:off[p + 1]], st[p]) for p in range(B)]
