@@ -572,7 +572,9 @@ int orbm_frame_pose_optimization(const orbm_frame *frame, const uint8_t *has_mp,
  * kp_off[p] .. kp_off[p + 1] - 1 of kps_un / uright / has_mp / mp_pos / outlier (kp_off[0] = 0), Tcw_in[p][16], Tcw_out[p][16],
  * ngood[p], stats[p] (or NULL); one camera.  is_device = 0: host arrays, synchronous.  is_device = 1: every array (kp_off
  * included) is in device memory and the call only enqueues the launch on `stream` (NULL: the null stream); a problem with more
- * than 8,192 keypoints then gets ngood[p] = ORBX_ERR_UNSUPPORTED and no other output. */
+ * than 8,192 keypoints then gets ngood[p] = ORBX_ERR_UNSUPPORTED, and one with a keypoint that has a map point and an octave
+ * outside [0, nlevels) gets ngood[p] = ORBX_ERR_ARG (the host forms refuse both before the launch); such a problem writes no
+ * other output, and the other problems of the batch are unaffected. */
 int orbm_pose_optimization_batch(const orbx_keypoint *kps_un, const float *uright, const int32_t *kp_off, int batch, const uint8_t *has_mp,
                                  const float *mp_pos, const orbm_pose_camera *cam, const float *Tcw_in, float *Tcw_out, uint8_t *outlier,
                                  int32_t *ngood, orbm_pose_stats *stats, int is_device, void *stream);

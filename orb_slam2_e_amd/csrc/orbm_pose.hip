@@ -385,11 +385,22 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
     };
     (void)nloc;
 
-    // nInitialCorrespondences (every keypoint with a map point gives one edge; mvbOutlier = false)
+    // nInitialCorrespondences (every keypoint with a map point gives one edge; mvbOutlier = false).  A map point on a keypoint
+    // whose octave has no mvInvLevelSigma2 entry (the host forms refuse it before the launch) rejects the problem: ORBX_ERR_ARG
+    // and no other output.  Counted as 1 << 16 each: both sums fit in one reduction (at most 8,192 keypoints).
     uint32_t lvl = 0;                       // bit k: the k-th owned keypoint's edge is at level 1 (mvbOutlier)
     int mine = 0;
-    for (int i = tid; i < n; i += PT) mine += src.has_mp[base + i] != 0;
-    const int nInitial = block_sum_int(mine, s_ired);
+    for (int i = tid; i < n; i += PT) {
+        if (!src.has_mp[base + i]) continue;
+        const int oct = FRAME ? src.fkp[s_inv[i]].octave : src.kps[base + i].octave;
+        mine += (oct < 0 || oct >= cam.nlevels) ? (1 << 16) : 1;
+    }
+    const int counts = block_sum_int(mine, s_ired);
+    if (counts >> 16) {
+        if (tid == 0) out.ngood[b] = ORBX_ERR_ARG;
+        return;
+    }
+    const int nInitial = counts;
 
     const float deltaMono = sqrt(5.991), deltaStereo = sqrt(7.815);
     const float chi2Mono = 5.991f, chi2Stereo = 7.815f;

@@ -85,3 +85,23 @@ def pose_optimization_batch(problems, cam, inv_level_sigma2):
     check(f(ptr(k), ptr(ur), ptr(off), B, ptr(has), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier), ptr(ng),
             C.cast(st, vp), 0, None))
     return [(int(ng[p]), Tout[p].reshape(4, 4), outlier[off[p]:off[p + 1]], st[p]) for p in range(B)]
+
+
+def _dptr(a):
+    return None if a is None else C.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else int(a))
+
+
+def pose_optimization_batch_device(kps, uright, kp_off, batch, has_mp, mp_pos, cam, inv_level_sigma2, Tcw_in, Tcw_out, outlier, ngood,
+                                   stats=None, stream=None):
+    """B problems in one launch on device arrays (is_device = 1): every array argument is a device pointer or a tensor on the
+    device -- kps orbx_keypoint[total], uright float[total] (None: every edge monocular), kp_off int32[B + 1], has_mp uint8[total],
+    mp_pos float[total][3], Tcw_in / Tcw_out float[B][16], outlier uint8[total] (written only where has_mp), ngood int32[B],
+    stats orbm_pose_stats[B] (PoseStats bytes, or None).  cam = (fx, fy, cx, cy, mbf) and inv_level_sigma2 are host values.
+    Only enqueues the launch on `stream` (a raw hipStream_t, None: the null stream); a problem the kernel rejects gets
+    ngood[p] < 0 and no other output."""
+    L = lib()
+    c = _camera(cam, inv_level_sigma2)
+    vp = C.c_void_p
+    f = bind(L.orbm_pose_optimization_batch, [vp, vp, vp, C.c_int, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, vp, vp, C.c_int, vp])
+    check(f(_dptr(kps), _dptr(uright), _dptr(kp_off), int(batch), _dptr(has_mp), _dptr(mp_pos), C.byref(c), _dptr(Tcw_in),
+            _dptr(Tcw_out), _dptr(outlier), _dptr(ngood), _dptr(stats), 1, None if stream is None else C.c_void_p(int(stream))))

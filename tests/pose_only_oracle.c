@@ -240,6 +240,7 @@ typedef struct {
     int stereo, kp;                /* edge kind, keypoint index */
     int level, robust;             /* setLevel, robust kernel attached */
     double err[3];                 /* _error as the last computeError left it */
+    int level_r4, pad;             /* the level during round 4 (0: one of its active edges; set only when round 4 runs) */
 } po_edge;
 
 typedef struct { double fx, fy, cx, cy, bf; } po_cam;
@@ -478,6 +479,8 @@ int po_pose_optimization(const float *kp_xy, const int32_t *octave, const float 
     int nBad = 0;
     for (int it = 0; it < 4; it++) {
         po_from_cv(Tcw_in, &g.est);                 /* vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw)) */
+        if (it == 3)
+            for (int k = 0; k < g.ne; ++k) g.e[k].level_r4 = g.e[k].level;
         int nactive = 0;
         for (int k = 0; k < g.ne; ++k) nactive += g.e[k].level == 0;
         po_lm lm;

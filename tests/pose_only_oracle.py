@@ -28,7 +28,9 @@ class Cam(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("bf", C.c_double)]
 
 
-EDGE_BYTES = 8 * (3 + 3 + 1) + 4 * 4 + 8 * 3     # po_edge
+EDGE_DTYPE = np.dtype([("obs", "f8", 3), ("Xw", "f8", 3), ("info", "f8"), ("stereo", "i4"), ("kp", "i4"), ("level", "i4"),
+                       ("robust", "i4"), ("err", "f8", 3), ("level_r4", "i4"), ("pad", "i4")])     # po_edge
+EDGE_BYTES = EDGE_DTYPE.itemsize
 
 
 def lib():
@@ -66,9 +68,10 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def pose_optimization(kp_xy, octave, uright, has_mp, mp_pos, cam, inv_sigma2, Tcw, outlier_in=None):
+def pose_optimization(kp_xy, octave, uright, has_mp, mp_pos, cam, inv_sigma2, Tcw, outlier_in=None, edges=False):
     """Optimizer::PoseOptimization on flat frame arrays.  cam = (fx, fy, cx, cy, mbf).  Returns
-    (ngood, Tcw_out float32[4, 4], outlier uint8[n] (outlier_in, or 0, where has_mp is not set), Stats)."""
+    (ngood, Tcw_out float32[4, 4], outlier uint8[n] (outlier_in, or 0, where has_mp is not set), Stats), and with edges=True
+    also the graph's edges (EDGE_DTYPE, one per keypoint with a map point, in keypoint order) as the call left them."""
     n = len(has_mp)
     kp_xy = np.ascontiguousarray(kp_xy, np.float32).reshape(n, 2)
     octave = np.ascontiguousarray(octave, np.int32)
@@ -84,6 +87,8 @@ def pose_optimization(kp_xy, octave, uright, has_mp, mp_pos, cam, inv_sigma2, Tc
     scratch = np.zeros(max(n, 1) * EDGE_BYTES, np.uint8)
     ng = lib().po_pose_optimization(_p(kp_xy), _p(octave), None if ur is None else _p(ur), n, _p(has_mp), _p(mp_pos), _p(camv), _p(inv),
                                     _p(Tin), _p(Tout), _p(outlier), C.byref(st), _p(scratch))
+    if edges:
+        return ng, Tout, outlier, st, scratch[:int(has_mp.sum()) * EDGE_BYTES].view(EDGE_DTYPE).copy()
     return ng, Tout, outlier, st
 
 

@@ -27,9 +27,10 @@ def inv_level_sigma2(nlevels=8, scale=1.2):
 
 
 def make_problem(seed, n, stereo_frac=0.0, outlier_frac=0.0, noise_px=0.5, rot_deg=3.0, trans_m=0.05, fill=0.85, z0=0, behind=0,
-                 nlevels=8):
-    """n keypoints, about fill * n of them with a map point.  Returns a dict: kp_xy[n,2], octave[n], uright[n] (-1: mono),
-    has_mp[n], mp_pos[n,3], cam, inv_sigma2, Tcw (the start pose), Ttrue."""
+                 nlevels=8, scale=1.2):
+    """n keypoints, about fill * n of them with a map point, on an nlevels pyramid of the given scale (pixel noise noise_px *
+    scale^octave, inv_sigma2 to match).  Returns a dict: kp_xy[n,2], octave[n], uright[n] (-1: mono), has_mp[n], mp_pos[n,3],
+    cam, inv_sigma2, Tcw (the start pose), Ttrue."""
     rng = np.random.default_rng(seed)
     fx, fy, cx, cy, bf = CAM
     Rt = rodrigues(rng.normal(0, 0.3, 3)); tt = rng.normal(0, 0.5, 3)
@@ -42,7 +43,7 @@ def make_problem(seed, n, stereo_frac=0.0, outlier_frac=0.0, noise_px=0.5, rot_d
     Xw = ((Pc - tt) @ Rt).astype(np.float32)            # world = Rt^T (Pc - tt)
     Pc = Xw.astype(np.float64) @ Rt.T + tt
     octave = rng.integers(0, nlevels, n).astype(np.int32)
-    sig = 1.2 ** octave
+    sig = scale ** octave
     with np.errstate(divide="ignore", invalid="ignore"):
         u = Pc[:, 0] / Pc[:, 2] * fx + cx
         v = Pc[:, 1] / Pc[:, 2] * fy + cy
@@ -61,7 +62,7 @@ def make_problem(seed, n, stereo_frac=0.0, outlier_frac=0.0, noise_px=0.5, rot_d
     t0 = tt + rng.normal(0, trans_m / np.sqrt(3), 3)
     kp_xy = np.stack([u, v], 1).astype(np.float32)
     return {"kp_xy": kp_xy, "octave": octave, "uright": uright, "has_mp": has_mp, "mp_pos": Xw, "cam": np.array(CAM, np.float32),
-            "inv_sigma2": inv_level_sigma2(nlevels), "Tcw": pose44(R0, t0), "Ttrue": pose44(Rt, tt), "Rt": Rt, "tt": tt,
+            "inv_sigma2": inv_level_sigma2(nlevels, scale), "Tcw": pose44(R0, t0), "Ttrue": pose44(Rt, tt), "Rt": Rt, "tt": tt,
             "bad": bad & (has_mp > 0)}
 
 
