@@ -143,7 +143,12 @@ int orbx_pyramid_level_padded(orbx_extractor *ex, int frame, int level, uint8_t 
  * parameters, Frame.cc:78-81): row-band Hamming match (+-1 octave, disparity in
  * [0, mbf/mb]), 11x11 L1 sub-pixel refinement on the keypoint's pyramid level,
  * median cut.  Results stay on the device in the left handle; download returns
- * mvuRight[n] / mvDepth[n] (-1 where unmatched) for one frame. */
+ * mvuRight[n] / mvDepth[n] (-1 where unmatched) for one frame.  An extraction that makes
+ * orbx_reserve lay the left handle out anew (another frame size, or a larger batch)
+ * invalidates its stereo results: orbx_stereo_download, orbx_stereo_download_batch and
+ * orbm_frame_from_extractor(..., uright_from_stereo = 1) return ORBX_ERR_ARG ("no stereo
+ * results") until the next orbx_stereo_match.  A new extraction at the same size keeps
+ * them (they then describe the earlier images). */
 int orbx_stereo_match(orbx_extractor *left, orbx_extractor *right, float mb, float mbf, void *stream);
 int orbx_stereo_download(orbx_extractor *left, int frame, float *uRight, float *depth, int cap, int *n);
 /* All frames of the last orbx_stereo_match at once: uRight / depth [batch][capacity] (rows past a frame's count are
@@ -412,7 +417,7 @@ int orbm_sorted_frame(const orbx_keypoint *kps, int n, const uint8_t *skip, cons
  * orbm_frame_from_extractor takes keypoints and descriptors of frame `frame` of the extractor's last call where they are, in
  * HBM (no trip over PCIe): xy_undistorted (n x 2 floats, or NULL when the camera has no distortion: mvKeysUn = mvKeys,
  * Frame.cc:270-275) replaces the keypoint coordinates, uright comes from the host or, with uright_from_stereo, from the
- * last orbx_stereo_match on this (left) handle.  A handle is immutable and may be searched from several threads at once;
+ * last orbx_stereo_match on this (left) handle (ORBX_ERR_ARG when a new frame size came since: see orbx_stereo_match).  A handle is immutable and may be searched from several threads at once;
  * what changes between calls (which keypoints already hold a map point) is an argument of each search. */
 typedef struct orbm_frame orbm_frame;
 int orbm_frame_create(const orbx_keypoint *kps, const uint8_t *desc, int n, const float *uright, float min_x, float min_y,

@@ -2132,7 +2132,7 @@ int orbm_frame_from_extractor(orbx_extractor *ex, int frame, const float *xy_und
     if (!out || !ex || frame < 0 || frame >= ex->last_batch || !(max_x > min_x) || !(max_y > min_y) || (uright && uright_from_stereo))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     if (ex->kcap > FB_MAXN) ORBX_FAIL(ORBX_ERR_CAPACITY, "more than 8,192 keypoints in a resident frame");
-    if (uright_from_stereo && (!ex->d_uright || frame >= ex->st_batch)) ORBX_FAIL(ORBX_ERR_ARG, "no stereo match on this handle");
+    if (uright_from_stereo && (!ex->d_uright || !ex->st_valid || frame >= ex->st_batch)) ORBX_FAIL(ORBX_ERR_ARG, "no stereo results");
     ORBX_NEED_DEVICE();
     const int cap = ex->kcap;
     orbm_frame *f = new orbm_frame();

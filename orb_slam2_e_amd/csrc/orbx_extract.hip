@@ -2263,6 +2263,7 @@ int orbx_reserve(orbx_extractor *ex, int width, int height, int batch)
     if (!ex->stream) ORBX_HIP(hipStreamCreateWithFlags(&ex->stream, hipStreamNonBlocking));
     ORBX_HIP(hipStreamSynchronize(ex->stream));
     free_workspace(ex);
+    ex->st_valid = false;   // stereo results were laid out with the old capacity and belong to the old counts
     std::vector<int2> xt;
     std::vector<int4> yt;
     {

@@ -133,7 +133,8 @@ struct orbx_extractor {
     uint8_t *h_st_pin = nullptr; size_t st_pin_bytes = 0; // pinned block of orbx_stereo_download
     float *d_uright = nullptr, *d_depth = nullptr, *d_st_scale = nullptr;
     int *d_st_sad = nullptr, *d_st_nvalid = nullptr;
-    int st_batch = 0;
+    int st_batch = 0, st_cap = 0;      // frames and keypoints per frame the stereo buffers were sized for
+    bool st_valid = false;             // results of an orbx_stereo_match at the handle's current geometry (orbx_reserve clears it)
     orbx::KernelProfiler prof;
     // ordering of chained *_dev calls that were not given one common stream (orbx_detail::order_after_producer)
     hipEvent_t order_ev = nullptr, reader_ev = nullptr;

@@ -313,7 +313,9 @@ int orbx_stereo_match(orbx_extractor *left, orbx_extractor *right, float mb, flo
     if (left->lv[0].h > ROWS_MAX) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 4,096 image rows");
     // a right keypoint's band: floor(y - r) .. ceil(y + r), r = 2 * scale[octave] -> at most 2 ceil(r) + 3 rows
     const int items_cap = cap * (2 * (int)ceilf(2.0f * left->scale[left->nlevels - 1]) + 3);
-    if (!left->d_st_key || left->st_batch < B) {
+    // sized for the handle's batch and keypoint capacity: a later frame size can raise the capacity (orbx_reserve), so both are
+    // checked, and items_cap follows the capacity
+    if (!left->d_st_key || left->st_batch < B || left->st_cap < cap) {
         if (left->d_st_key) { (void)hipFree(left->d_st_rk); (void)hipFree(left->d_st_rowoff); (void)hipFree(left->d_st_items); (void)hipFree(left->d_st_key); (void)hipFree(left->d_uright); (void)hipFree(left->d_depth); (void)hipFree(left->d_st_sad); (void)hipFree(left->d_st_scale); (void)hipFree(left->d_st_nvalid); }
         ORBX_HIP(hipMalloc(&left->d_st_key, sizeof(unsigned) * (size_t)cap * left->batch));
         ORBX_HIP(hipMalloc(&left->d_st_rk, sizeof(RightKp) * (size_t)cap * left->batch));
@@ -328,7 +330,7 @@ int orbx_stereo_match(orbx_extractor *left, orbx_extractor *right, float mb, flo
         for (int i = 0; i < MAXL; ++i) { sc[i] = left->scale[i]; sc[MAXL + i] = left->inv_scale[i]; }
         ORBX_HIP(hipMemcpyAsync(left->d_st_scale, sc, sizeof(sc), hipMemcpyHostToDevice, st));   // on the call's stream, never the legacy one
         ORBX_HIP(hipStreamSynchronize(st));   // sc lives in this scope
-        left->st_batch = left->batch;
+        left->st_batch = left->batch; left->st_cap = cap;
     }
     // streams: the results of both extractors must be complete before the matching starts -- ordered on the device (an event
     // recorded behind each extraction that ran on another stream), the host does not wait
@@ -353,6 +355,7 @@ int orbx_stereo_match(orbx_extractor *left, orbx_extractor *right, float mb, flo
     hipLaunchKernelGGL(k_stereo_median, dim3(B), dim3(MED_T), 0, st, left->d_counts, cap, left->d_st_sad, left->d_uright,
                        left->d_depth, left->d_st_nvalid);
     ORBX_HIP(hipGetLastError());
+    left->st_valid = true;
     // ... and the next extraction on a handle whose own stream is another one must not overwrite what these kernels still read
     // (keypoints, descriptors, pyramids): it waits for this point of `st` (orbx_extract_batch, reader_pending)
     for (orbx_extractor *e : {left, right})
@@ -362,7 +365,7 @@ int orbx_stereo_match(orbx_extractor *left, orbx_extractor *right, float mb, flo
 
 int orbx_stereo_download(orbx_extractor *left, int frame, float *uRight, float *depth, int cap, int *n)
 {
-    if (!left || !left->d_uright || frame < 0 || frame >= left->last_batch || !n) ORBX_FAIL(ORBX_ERR_ARG, "no stereo results");
+    if (!left || !left->d_uright || !left->st_valid || frame < 0 || frame >= left->last_batch || !n) ORBX_FAIL(ORBX_ERR_ARG, "no stereo results");
     hipStream_t st = left->st_stream;   // queued behind the stereo match on ITS stream, one wait for that stream only
     // {count, mvuRight[kcap], mvDepth[kcap]} of the frame into a pinned block by the compute queue itself (common.h: no
     // hand-over to the copy engine), ONE synchronisation
@@ -392,7 +395,7 @@ int orbx_stereo_download(orbx_extractor *left, int frame, float *uRight, float *
 
 int orbx_stereo_download_batch(orbx_extractor *left, float *uRight, float *depth, int32_t *counts)
 {
-    if (!left || !left->d_uright || left->last_batch <= 0) ORBX_FAIL(ORBX_ERR_ARG, "no stereo results");
+    if (!left || !left->d_uright || !left->st_valid || left->last_batch <= 0) ORBX_FAIL(ORBX_ERR_ARG, "no stereo results");
     hipStream_t st = left->st_stream;
     const size_t n = (size_t)left->last_batch * left->kcap;
     if (counts) ORBX_HIP(hipMemcpyAsync(counts, left->d_counts, sizeof(int) * left->last_batch, hipMemcpyDeviceToHost, st));

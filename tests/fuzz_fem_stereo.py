@@ -1,11 +1,12 @@
 """Differential fuzz of the FEM assembly / K*a path (random surface meshes, C3D6 / C3D8 / tet4, random material)
-and of ComputeStereoMatches (random pair sizes) against the oracle."""
+and of ComputeStereoMatches (tests/stereo_scenes.py with random seeds and settings) against the oracle and the numpy restatement."""
 import sys
 import numpy as np
 import oracle
 from orb_slam2_e_amd import ComputeStereoMatches, ORBextractor
 from orb_slam2_e_amd.fem import FEA2, FEM_C3D6, FEM_C3D8, FEM_TET4, second_layer, extrude_elems
-from orb_slam2_e_amd.synth import synth_stereo_pair
+import stereo_reference
+import stereo_scenes
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -90,32 +91,32 @@ for case in range(n):
                     abs(nsE[0] - onsE) <= max(1e-5 * abs(onsE), slack / (len(oa) // 3))):
                 bad += 1; print("MISMATCH LM trial", case, kind, g, nder, sE[0], osE, flush=True); break
 for case in range(max(4, n // 8)):
-    w = int(rng.integers(400, 1300)); h = int(rng.integers(200, 500))
-    # the reference's stereo settings most of the time, otherwise any pyramid (the row band of a keypoint is +-2 scale[octave] rows)
-    P = (1500, 1.2, 8, 20, 7) if rng.random() < 0.5 else (int(rng.integers(50, 2500)), float(rng.choice([1.1, 1.2, 1.3, 1.5, 2.0])), int(rng.integers(1, 9)),
-                                                          int(rng.integers(8, 30)), int(rng.integers(3, 9)))
-    left, right = synth_stereo_pair(int(rng.integers(0, 1000)), w=w, h=h, dmin=float(rng.uniform(0, 5)), dmax=float(rng.uniform(20, 90)))
+    # a scene of tests/stereo_scenes.py with random seeds, or a random setting (any pyramid, baseline, size) on a sub-pixel pair;
+    # the device against the oracle and against the numpy restatement
+    sc = stereo_scenes.random_scene(rng)
+    P, mb, mbf = sc["prm"], sc["mb"], sc["mbf"]
+    h, w = sc["left"].shape
     oL, oR = oracle.OrbOracle(*P), oracle.OrbOracle(*P)
     try:
-        kL, dL = oL.extract(left); kR, dR = oR.extract(right)
+        kL, dL = oL.extract(sc["left"]); kR, dR = oR.extract(sc["right"])
     except RuntimeError:                               # a size the reference cannot run either (a level below the 30-px cell grid)
         try:
-            ORBextractor(*P)(left)
+            ORBextractor(*P)(sc["left"])
             bad += 1; print("MISMATCH stereo: the oracle rejects", w, h, "the library does not", flush=True)
         except Exception:
             pass
         continue
-    fx, bf = float(rng.uniform(300, 900)), float(rng.uniform(100, 500))
-    mb = np.float32(bf) / np.float32(fx)
-    ou, od, nd = oracle.stereo_matches(oL, oR, kL, dL, kR, dR, mb, np.float32(bf))
+    ou, od, nd = oracle.stereo_matches(oL, oR, kL, dL, kR, dR, mb, mbf)
+    rs = stereo_reference.from_oracle(oL, oR, kL, dL, kR, dR, mb, mbf)
     try:
         eL, eR = ORBextractor(*P), ORBextractor(*P)
-        eL(left); eR(right)
+        eL(sc["left"]); eR(sc["right"])
     except Exception as e:
         if "error -5" in str(e): continue         # a documented capacity limit (one level with a quota above 2047)
         raise
-    gu, gd = ComputeStereoMatches(eL, eR, mb, np.float32(bf))
-    if not (np.array_equal(gu.view(np.uint32), ou.view(np.uint32)) and np.array_equal(gd.view(np.uint32), od.view(np.uint32))):
-        bad += 1; print("MISMATCH stereo", case, w, h, fx, bf, flush=True)
+    gu, gd = ComputeStereoMatches(eL, eR, mb, mbf)
+    same = lambda a, b: np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    if not (same(gu, ou) and same(gd, od) and same(rs["uRight"], ou) and same(rs["depth"], od) and rs["nd"] == nd):
+        bad += 1; print("MISMATCH stereo", case, sc["name"], w, h, P, float(mb), float(mbf), flush=True)
 print("cases", n, "mismatches", bad)
 sys.exit(1 if bad else 0)
