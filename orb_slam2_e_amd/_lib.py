@@ -1,15 +1,24 @@
 """Build + load liborbslam_hip.so (the C-ABI of include/*.h) through ctypes.
 
 There is no CPU fallback: if the library is missing it is built with hipcc, and
-if it cannot be loaded the import fails loudly.
+if it cannot be loaded the import fails loudly.  Every function the headers declare
+gets its ctypes prototype from them when the library is loaded (prototypes()).
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "liborbslam_hip.so")
+# the headers csrc/Makefile compiles against
+HEADERS = tuple(os.path.join(os.path.dirname(_HERE), "include", h) for h in ("orbslam_hip.h", "fem_hip.h"))
 _LIB = None
+
+# C type of a parameter passed by value -> ctypes; every pointer is c_void_p (which takes ptr(), None, an int address, byref() and
+# ctypes arrays).  A type outside these tables is an error, not a guess.
+_ARG = {"int": C.c_int, "int32_t": C.c_int, "unsigned int": C.c_uint, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_RET = {"int": C.c_int, "const char *": C.c_char_p}
 
 
 class OrbxError(RuntimeError):
@@ -47,6 +56,35 @@ def _one_hip_runtime():
         pass
 
 
+def prototypes():
+    """name -> (restype, argtypes) of every function declared in HEADERS."""
+    text = ""
+    for h in HEADERS:
+        with open(h) as f:
+            text += f.read()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    protos = {}
+    for stmt in re.split(r"[;{}]", text):         # declarations, struct fields, enumerators: only a prototype holds a '('
+        if "(" not in stmt:
+            continue
+        m = re.fullmatch(r"\s*(.*?)\b((?:orbx|orbm|fem)_\w+)\s*\((.*)\)\s*", stmt, re.S)
+        if not m:
+            raise RuntimeError("include/*.h: not a prototype: " + " ".join(stmt.split()))
+        ret, name, params = (" ".join(g.replace("*", " * ").split()) for g in m.groups())
+        argtypes = []
+        for p in ([] if params in ("", "void") else params.split(",")):
+            words = [w for w in p.split() if w != "const"]
+            ctype = C.c_void_p if "*" in words else _ARG.get(" ".join(words[:-1]))
+            if ctype is None or "[" in p:
+                raise RuntimeError(f"include/*.h: {name}: no ctypes mapping for parameter '{p.strip()}'")
+            argtypes.append(ctype)
+        if ret not in _RET:
+            raise RuntimeError(f"include/*.h: {name}: no ctypes mapping for return type '{ret}'")
+        protos[name] = (_RET[ret], argtypes)
+    return protos
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -55,8 +93,13 @@ def lib():
         if path == SO_PATH and not os.path.exists(SO_PATH):
             build()
         _one_hip_runtime()
-        _LIB = C.CDLL(path)
-        _LIB.orbx_last_error.restype = C.c_char_p
+        L = C.CDLL(path)
+        for name, (restype, argtypes) in prototypes().items():
+            if not hasattr(L, name):
+                raise RuntimeError(f"{path} does not export {name}, which include/*.h declares")
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _LIB = L
     return _LIB
 
 
@@ -79,10 +122,3 @@ def ptr(a):
         return a.ctypes.data_as(_void_p)
     v._array = a        # as data_as does: the pointer keeps its array alive (callers pass temporaries)
     return v
-
-
-def bind(fn, argtypes):
-    """Sets a C function's argtypes once (assigning them costs ~1.5 us, so not per call)."""
-    if fn.argtypes is None:
-        fn.argtypes = argtypes
-    return fn

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import bind, check, lib, ptr as _p
+from ._lib import check, lib, ptr as _p
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -98,15 +98,14 @@ class ORBextractor:
         images = np.ascontiguousarray(images, dtype=np.uint8)
         B, h, w = images.shape
         self._reserve(w, h, B)
-        check(self._L.orbx_extract_batch(self._h, _p(images), 0, w, h, w, C.c_size_t(w * h), B, None))
+        check(self._L.orbx_extract_batch(self._h, _p(images), 0, w, h, w, w * h, B, None))
         self._shape = (h, w)
         self._last_B = B
 
     def extract_batch_device(self, dev_ptr, B, h, w, stream=None):
         """dev_ptr: device address of [B,H,W] uint8 (e.g. torch tensor .data_ptr())."""
         self._reserve(w, h, B)
-        check(self._L.orbx_extract_batch(self._h, C.c_void_p(dev_ptr), 1, w, h, w, C.c_size_t(w * h), B,
-                                         C.c_void_p(stream) if stream else None))
+        check(self._L.orbx_extract_batch(self._h, dev_ptr, 1, w, h, w, w * h, B, stream))
         self._shape = (h, w)
         self._last_B = B
 
@@ -207,9 +206,7 @@ def extract_pair(left, right, image_left, image_right):
 
 def stereo_match_batch(left, right, mb, mbf, stream=None):
     """orbx_stereo_match on every frame of the last batch extracted on both handles (asynchronous on `stream`)."""
-    L = left._L
-    bind(L.orbx_stereo_match, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p])
-    check(L.orbx_stereo_match(left._h, right._h, mb, mbf, C.c_void_p(stream) if stream else None))
+    check(left._L.orbx_stereo_match(left._h, right._h, mb, mbf, stream))
 
 
 def stereo_download_batch(left):
@@ -225,7 +222,6 @@ def ComputeStereoMatches(left, right, mb, mbf, frame=0):
     ORBextractor objects (left / right images extracted with the same parameters).
     Returns (mvuRight, mvDepth) for `frame`; -1 where unmatched."""
     L = left._L
-    bind(L.orbx_stereo_match, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p])
     check(L.orbx_stereo_match(left._h, right._h, mb, mbf, None))
     u = np.zeros(left.capacity, np.float32); d = np.zeros(left.capacity, np.float32)
     n = C.c_int(0)

@@ -10,36 +10,15 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import bind, check, lib, ptr as _p
+from ._lib import check, lib, ptr as _p
 
 FEM_C3D8, FEM_C3D6, FEM_TET4 = 1, 2, 4
 _NPE = {FEM_C3D8: 8, FEM_C3D6: 6, FEM_TET4: 4}
-_BOUND = False
-
-
-
-
-def _bind(L):
-    global _BOUND
-    if _BOUND:
-        return
-    bind(L.fem_create, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint, C.c_float,
-                             C.c_float, C.c_void_p])
-    bind(L.fem_second_layer, [C.c_void_p, C.c_int, C.c_float, C.c_void_p])
-    bind(L.fem_dirichlet_penalty, [C.c_void_p, C.c_void_p, C.c_int, C.c_float])
-    bind(L.fem_dirichlet_eliminate, [C.c_void_p, C.c_void_p, C.c_int])
-    bind(L.fem_displacement, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p])
-    bind(L.fem_cg, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p])
-    bind(L.fem_cg_iterate, [C.c_void_p, C.c_int, C.c_void_p])
-    bind(L.fem_spmv_repeat, [C.c_void_p, C.c_int, C.c_void_p])
-    for n in ("fem_destroy", "fem_assemble"):
-        getattr(L, n).argtypes = [C.c_void_p]
-    _BOUND = True
 
 
 def second_layer(top, h):
     """FEA2::SetSecondLayer: nodes = top || top - (h,h,h)."""
-    L = lib(); _bind(L)
+    L = lib()
     top = np.ascontiguousarray(top, np.float32)
     out = np.zeros((2 * len(top), 3), np.float32)
     check(L.fem_second_layer(_p(top), len(top), h, _p(out)))
@@ -56,7 +35,7 @@ def extrude_elems(faces, ntop):
 class FEA2:
     def __init__(self, nodes, elems, nElType, E=3500, nu=0.495, fg=0.577350269):
         """nodes: [nn,3] or [nmesh,nn,3] float32; elems: [ne,npe] int32."""
-        self._L = lib(); _bind(self._L)
+        self._L = lib()
         nodes = np.ascontiguousarray(nodes, np.float32)
         if nodes.ndim == 2:
             nodes = nodes[None]
@@ -140,7 +119,6 @@ class FEA2:
         ids = np.ascontiguousarray(ids, np.int32)
         der = np.ascontiguousarray(derived if derived is not None else np.zeros((0, 4)), np.int32).reshape(-1, 4)
         self._npoints = npoints
-        bind(self._L.fem_trial_setup, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int])
         check(self._L.fem_trial_setup(self._h, _p(u0), _p(ids), len(ids), Klarge, npoints, _p(der), len(der)))
 
     def trial_energy(self, points, want_a=True):
@@ -163,17 +141,17 @@ class FEA2:
     def cg_preconditioner(self, kind):
         """fem_cg_preconditioner: "jacobi" (default) or "two_level" (Jacobi + rigid-body modes of 2 x 2 x 2 aggregates)."""
         k = {"jacobi": 0, "two_level": 1}.get(kind, kind)
-        check(bind(self._L.fem_cg_preconditioner, [C.c_void_p, C.c_int])(self._h, int(k)))
+        check(self._L.fem_cg_preconditioner(self._h, int(k)))
 
     def one_launch_stats(self):
         """(launches of the one-launch CG kernel, how many of them gave up and were made good on the launch-per-phase path)."""
         a, b = C.c_int64(0), C.c_int64(0)
-        check(bind(self._L.fem_cg_one_launch_stats, [C.c_void_p, C.c_void_p, C.c_void_p])(self._h, C.byref(a), C.byref(b)))
+        check(self._L.fem_cg_one_launch_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def cg_coarse_matrix(self, mesh=0):
         Ac = np.zeros((48, 48), np.float64)
-        check(bind(self._L.fem_cg_coarse_matrix, [C.c_void_p, C.c_int, C.c_void_p])(self._h, mesh, _p(Ac)))
+        check(self._L.fem_cg_coarse_matrix(self._h, mesh, _p(Ac)))
         return Ac
 
     def cg_setup(self, b):
@@ -181,10 +159,10 @@ class FEA2:
         check(self._L.fem_cg_setup(self._h, _p(b)))
 
     def cg_iterate(self, n, stream=None):
-        check(self._L.fem_cg_iterate(self._h, n, C.c_void_p(stream) if stream else None))
+        check(self._L.fem_cg_iterate(self._h, n, stream))
 
     def spmv_repeat(self, n, stream=None):
-        check(self._L.fem_spmv_repeat(self._h, n, C.c_void_p(stream) if stream else None))
+        check(self._L.fem_spmv_repeat(self._h, n, stream))
 
     def cg_result(self):
         x = np.zeros((self.nmesh, self.Ksize), np.float64); rel = np.zeros(self.nmesh, np.float64)
@@ -216,7 +194,7 @@ class FEA2Batch(FEA2):
     columns.  Methods are those of FEA2 (the LM hook excepted)."""
 
     def __init__(self, nodes_list, elems_list, nElType, E=3500, nu=0.495, fg=0.577350269):
-        self._L = lib(); _bind(self._L)
+        self._L = lib()
         self.npe, self.nElType = _NPE[nElType], nElType
         nodes_list = [np.ascontiguousarray(n, np.float32).reshape(-1, 3) for n in nodes_list]
         elems_list = [np.ascontiguousarray(e, np.int32).reshape(-1, self.npe) for e in elems_list]
@@ -225,8 +203,6 @@ class FEA2Batch(FEA2):
         nodes = np.ascontiguousarray(np.concatenate(nodes_list), np.float32)
         elems = np.ascontiguousarray(np.concatenate(elems_list), np.int32)
         self._h = C.c_void_p()
-        bind(self._L.fem_create_batch, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_float,
-                                             C.c_float, C.c_void_p])
         check(self._L.fem_create_batch(nElType, self.nseg, _p(nn), _p(ne), _p(nodes), _p(elems), int(E), nu, fg, C.byref(self._h)))
         nm, nd, nnz = C.c_int(), C.c_int(), C.c_int64()
         check(self._L.fem_sizes(self._h, C.byref(nm), C.byref(nd), C.byref(nnz)))
@@ -283,7 +259,6 @@ def plan_single_cg(elems, nn, nElType):
     L = lib()
     e = np.ascontiguousarray(elems, np.int32).reshape(-1, _NPE[nElType])
     info = np.zeros(6, np.int32); pl = np.zeros((64, 4), np.int32)
-    bind(L.fem_plan_single_cg, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
     check(L.fem_plan_single_cg(nElType, int(nn), _p(e), len(e), _p(info), _p(pl)))
     pl = pl[:info[1]].copy()
     vec = (pl[:, 1] >> 16) - 1                      # the vector chunk (256 rows) a workgroup owns, or -1
@@ -300,7 +275,6 @@ def plan(elems_list, nn_list, nElType, uniform_copies=0):
     elems_list = [np.ascontiguousarray(e, np.int32).reshape(-1, npe) for e in elems_list]
     nn = np.ascontiguousarray(nn_list, np.int32); ne = np.array([len(e) for e in elems_list], np.int32)
     elems = np.ascontiguousarray(np.concatenate(elems_list), np.int32) if len(elems_list) else np.zeros((0, npe), np.int32)
-    bind(L.fem_plan, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p] * 8)
     info = _PlanInfo()
     args = (nElType, len(nn), _p(nn), _p(ne), _p(elems), int(uniform_copies))
     check(L.fem_plan(*args, C.byref(info), *([None] * 8)))

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import bind, check, lib, ptr as _p
+from ._lib import check, lib, ptr as _p
 
 
 
@@ -68,17 +68,15 @@ class ORBmatcher:
         n = C.c_int(0)
         check(self._L.orbm_match_filter(len(best), _p(np.ascontiguousarray(best, np.int32)),
                                         _p(np.ascontiguousarray(second, np.int32)),
-                                        _p(np.ascontiguousarray(idx, np.int32)), th, C.c_float(self.mfNNratio),
+                                        _p(np.ascontiguousarray(idx, np.int32)), th, self.mfNNratio,
                                         _p(m), C.byref(n)))
         return m, n.value
 
     def match_batch_device(self, desc_dev, counts_dev, cap, pair_a_dev, pair_b_dev, npairs,
                            best_dev, second_dev, idx_dev, match12_dev, nmatch_dev, th=None, stream=None):
         th = self.TH_LOW if th is None else th
-        vp = lambda v: C.c_void_p(v) if v else None
-        check(self._L.orbm_match_batch_dev(vp(desc_dev), vp(counts_dev), cap, vp(pair_a_dev), vp(pair_b_dev), npairs,
-                                           th, C.c_float(self.mfNNratio), vp(best_dev), vp(second_dev), vp(idx_dev),
-                                           vp(match12_dev), vp(nmatch_dev), vp(stream)))
+        check(self._L.orbm_match_batch_dev(desc_dev, counts_dev, cap, pair_a_dev, pair_b_dev, npairs, th, self.mfNNratio, best_dev,
+                                           second_dev, idx_dev, match12_dev, nmatch_dev, stream))
 
     def match_triangulation(self, kps1, desc1, kps2, desc2, cand_off, cand_idx, has_mp1, has_mp2, stereo1, stereo2,
                             F12, ex, ey, scale_factors2, level_sigma2, bOnlyStereo=False):
@@ -93,10 +91,6 @@ class ORBmatcher:
         sc = np.ascontiguousarray(scale_factors2, np.float32); sg = np.ascontiguousarray(level_sigma2, np.float32)
         n1 = len(kps1)
         m12 = np.zeros(n1, np.int32); bd = np.zeros(n1, np.int32)
-        bind(self._L.orbm_match_triangulation, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                     C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
-                                                     C.c_int, C.c_void_p, C.c_void_p])
         check(self._L.orbm_match_triangulation(_p(kps1), _p(d1), n1, _p(kps2), _p(d2), len(kps2), _p(off), _p(ci), _p(m1),
                                                _p(m2), _p(s1), _p(s2), 1 if bOnlyStereo else 0, _p(F), ex, ey, _p(sc),
                                                _p(sg), len(sc), _p(m12), _p(bd)))
@@ -117,8 +111,6 @@ class ORBmatcher:
         F = np.ascontiguousarray(F12, np.float32).reshape(9)
         sf = np.ascontiguousarray(scale_factors2, np.float32); sg = np.ascontiguousarray(level_sigma2, np.float32)
         m12 = np.full(n1, -1, np.int32); nm = C.c_int(0)
-        bind(self._L.orbm_search_for_triangulation, ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] * 2 +
-                                                          [C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]))
         check(self._L.orbm_search_for_triangulation(_p(k1), _p(d1), n1, _p(nd1), _p(of1), _p(it1), len(nd1), _p(h1), _p(s1),
                                                     _p(k2), _p(d2), n2, _p(nd2), _p(of2), _p(it2), len(nd2), _p(h2), _p(s2),
                                                     int(bool(bOnlyStereo)), _p(F), float(ex), float(ey), _p(sf), _p(sg), len(sf),
@@ -168,8 +160,6 @@ class ORBmatcher:
         outs = [np.zeros(nq, np.int32) for _ in range(5)]
         sk = np.ascontiguousarray(skip, np.uint8) if skip is not None else None
         ur = np.ascontiguousarray(uright, np.float32) if uright is not None else None
-        bind(self._L.orbm_search_window, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                               C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 5)
         check(self._L.orbm_search_window(_p(q), _p(qd), nq, _p(kps), _p(d), len(kps), _p(sk) if sk is not None else None,
                                          _p(ur) if ur is not None else None, *[float(b) for b in bounds], init_dist,
                                          *[_p(o) for o in outs]))
@@ -189,12 +179,9 @@ class ORBmatcher:
         nq, n = len(q), len(kps)
         mk = np.zeros(n, np.int32); mq = np.zeros(nq, np.int32); nm = C.c_int(0)
         opt = lambda a: _p(a) if a is not None else None
-        bind(self._L.orbm_search_projection, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p])
         check(self._L.orbm_search_projection(_p(q), _p(qd), opt(qa), opt(qt), nq, _p(kps), _p(d), n, opt(oc), opt(ur),
                                              *[float(b) for b in bounds], self.TH_HIGH if th_accept is None else int(th_accept),
-                                             C.c_float(self.mfNNratio), int(ratio_same_level), int(self.mbCheckOrientation),
+                                             self.mfNNratio, int(ratio_same_level), int(self.mbCheckOrientation),
                                              _p(mk), _p(mq), C.byref(nm)))
         return mk, mq, nm.value
 
@@ -205,8 +192,6 @@ class ORBmatcher:
         ur = np.ascontiguousarray(uright, np.float32) if uright is not None else None
         sg = np.ascontiguousarray(inv_level_sigma2, np.float32) if inv_level_sigma2 is not None else None
         best = np.zeros(len(q), np.int32); idx = np.zeros(len(q), np.int32)
-        bind(self._L.orbm_search_fuse, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                             C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p])
         check(self._L.orbm_search_fuse(_p(q), _p(qd), len(q), _p(kps), _p(d), len(kps), _p(ur) if ur is not None else None,
                                        _p(sg) if sg is not None else None, len(sg) if sg is not None else 0,
                                        *[float(b) for b in bounds], _p(best), _p(idx)))
@@ -232,11 +217,8 @@ class ORBmatcher:
         d1 = np.ascontiguousarray(desc1, np.uint8); d2 = np.ascontiguousarray(desc2, np.uint8)
         pv = np.array(vbPrevMatched, np.float32, copy=True).reshape(-1, 2)
         m12 = np.zeros(len(k1), np.int32); nm = C.c_int(0)
-        bind(self._L.orbm_search_for_initialization, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                           C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
-                                                           C.c_void_p, C.c_void_p])
         check(self._L.orbm_search_for_initialization(_p(k1), _p(d1), len(k1), _p(k2), _p(d2), len(k2), _p(pv),
-                                                     *[float(b) for b in bounds], int(windowSize), C.c_float(self.mfNNratio),
+                                                     *[float(b) for b in bounds], int(windowSize), self.mfNNratio,
                                                      int(self.mbCheckOrientation), _p(m12), C.byref(nm)))
         return m12, pv, nm.value
 
@@ -253,12 +235,9 @@ class ORBmatcher:
         v2 = np.ascontiguousarray(valid2, np.uint8) if kf_kf else None
         n1, n2 = len(d1), len(d2)
         m12 = np.zeros(n1, np.int32); m21 = np.zeros(n2, np.int32); nm = C.c_int(0)
-        bind(self._L.orbm_search_by_bow, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                               C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
         check(self._L.orbm_search_by_bow(_p(nodes1), _p(off1), _p(it1), len(nodes1), _p(v1), _p(d1), _p(a1), n1,
                                          _p(nodes2), _p(off2), _p(it2), len(nodes2), _p(v2) if v2 is not None else None, _p(d2),
-                                         _p(a2), n2, self.TH_LOW, int(kf_kf), C.c_float(self.mfNNratio),
+                                         _p(a2), n2, self.TH_LOW, int(kf_kf), self.mfNNratio,
                                          int(self.mbCheckOrientation), _p(m12), _p(m21), C.byref(nm)))
         return m12, m21, nm.value
 
@@ -279,12 +258,8 @@ class ORBmatcher:
         sc = f32(scale_factors)
         n, m = len(kps), len(pos)
         matched = np.zeros(n, np.int32); proj = np.zeros((m, 4), np.float32); nm = C.c_int(0)
-        bind(self._L.orbm_search_by_projection_map, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                          C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int,
-                                                          C.c_void_p, C.c_void_p, C.c_void_p])
         check(self._L.orbm_search_by_projection_map(_p(kps), _p(d), n, _p(hm), _p(pos), _p(nrm), _p(mn), _p(mx), _p(md), m,
-                                                    _p(R), _p(t), _p(cam), _p(sc), len(sc), th, C.c_float(self.mfNNratio),
+                                                    _p(R), _p(t), _p(cam), _p(sc), len(sc), th, self.mfNNratio,
                                                     self.TH_RELOC, _p(matched), C.byref(nm), _p(proj)))
         return matched, nm.value, proj
 
@@ -304,8 +279,6 @@ class ORBmatcher:
         sc = f32(scale_factors)
         m = len(pos)
         out = np.zeros(m, self.PROJ_DTYPE); q = np.zeros(m, self.WQ_DTYPE)
-        bind(self._L.orbm_project_points, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float] * 3 + \
-                                               [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p])
         check(self._L.orbm_project_points(int(mode), _p(pos), _p(nrm), _p(mn), _p(mx), m, _p(R), _p(t), _p(O), _p(cam), float(mbf),
                                           float(viewing_cos_limit), float(log_scale_factor), _p(sc), len(sc), float(th), _p(out), _p(q)))
         return out, q
@@ -385,7 +358,6 @@ class ORBmatcher:
         nq = len(q)
         outs = [np.zeros(nq, np.int32) for _ in range(5)]
         sk = np.ascontiguousarray(skip, np.uint8) if skip is not None else None
-        bind(self._L.orbm_frame_search_window, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5)
         check(self._L.orbm_frame_search_window(frame._h, _p(q), _p(qd), nq, _p(sk) if sk is not None else None, int(init_dist),
                                                *[_p(o) for o in outs]))
         return tuple(outs)
@@ -394,7 +366,6 @@ class ORBmatcher:
         q = np.ascontiguousarray(queries, self.WQ_DTYPE); qd = np.ascontiguousarray(qdesc, np.uint8)
         sg = np.ascontiguousarray(inv_level_sigma2, np.float32) if inv_level_sigma2 is not None else None
         best = np.zeros(len(q), np.int32); idx = np.zeros(len(q), np.int32)
-        bind(self._L.orbm_frame_search_fuse, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
         check(self._L.orbm_frame_search_fuse(frame._h, _p(q), _p(qd), len(q), _p(sg) if sg is not None else None,
                                              len(sg) if sg is not None else 0, _p(best), _p(idx)))
         return best, idx
@@ -408,22 +379,18 @@ class ORBmatcher:
         oc = asc(occupied, np.uint8) if occupied is not None else None
         nq = len(q)
         mk = np.zeros(max(frame.n, 1), np.int32); mq = np.zeros(nq, np.int32); nm = C.c_int(0)
-        fn = bind(self._L.orbm_frame_search_projection, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int] +
-                  [C.c_void_p] * 3)
-        check(fn(frame._h, _p(q), _p(qd), _p(qa) if qa is not None else None, _p(qt) if qt is not None else None, nq,
-                 _p(oc) if oc is not None else None,
-                 self.TH_HIGH if th_accept is None else int(th_accept), self.mfNNratio, int(ratio_same_level),
-                 int(self.mbCheckOrientation), _p(mk), _p(mq), C.byref(nm)))
+        check(self._L.orbm_frame_search_projection(frame._h, _p(q), _p(qd), _p(qa) if qa is not None else None,
+                                                   _p(qt) if qt is not None else None, nq, _p(oc) if oc is not None else None,
+                                                   self.TH_HIGH if th_accept is None else int(th_accept), self.mfNNratio,
+                                                   int(ratio_same_level), int(self.mbCheckOrientation), _p(mk), _p(mq), C.byref(nm)))
         return mk[:frame.n], mq, nm.value
 
     def frame_search_for_initialization(self, frame2, kps2, kps1, desc1, vbPrevMatched, windowSize=10):
         k1 = np.ascontiguousarray(kps1); k2 = np.ascontiguousarray(kps2); d1 = np.ascontiguousarray(desc1, np.uint8)
         pv = np.array(vbPrevMatched, np.float32, copy=True).reshape(-1, 2)
         m12 = np.zeros(len(k1), np.int32); nm = C.c_int(0)
-        bind(self._L.orbm_frame_search_for_initialization, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int,
-                                                                                    C.c_void_p, C.c_void_p])
         check(self._L.orbm_frame_search_for_initialization(frame2._h, _p(k2), _p(k1), _p(d1), len(k1), _p(pv), int(windowSize),
-                                                           C.c_float(self.mfNNratio), int(self.mbCheckOrientation), _p(m12), C.byref(nm)))
+                                                           self.mfNNratio, int(self.mbCheckOrientation), _p(m12), C.byref(nm)))
         return m12, pv, nm.value
 
     def frame_search_by_projection_map(self, frame, has_mp, mp_pos, mp_normal, mp_min_dist, mp_max_dist, mp_desc, Rcw, tcw, cam,
@@ -437,10 +404,8 @@ class ORBmatcher:
         sc = f32(scale_factors)
         m = len(pos)
         matched = np.zeros(max(frame.n, 1), np.int32); proj = np.zeros((m, 4), np.float32); nm = C.c_int(0)
-        bind(self._L.orbm_frame_search_by_projection_map, [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 4 + \
-                                                               [C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 3)
         check(self._L.orbm_frame_search_by_projection_map(frame._h, _p(hm), _p(pos), _p(nrm), _p(mn), _p(mx), _p(md), m, _p(R), _p(t),
-                                                          _p(cam), _p(sc), len(sc), th, C.c_float(self.mfNNratio), self.TH_RELOC,
+                                                          _p(cam), _p(sc), len(sc), th, self.mfNNratio, self.TH_RELOC,
                                                           _p(matched), C.byref(nm), _p(proj)))
         return matched[:frame.n], nm.value, proj
 
@@ -452,11 +417,9 @@ class ORBmatcher:
         v1 = np.ascontiguousarray(valid1, np.uint8)
         v2 = np.ascontiguousarray(valid2, np.uint8) if kf_kf else None
         m12 = np.zeros(max(frame1.n, 1), np.int32); m21 = np.zeros(max(frame2.n, 1), np.int32); nm = C.c_int(0)
-        fn = bind(self._L.orbm_frame_search_by_bow, [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p] +
-                  [C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 3)
-        check(fn(frame1._h, _p(nodes1), _p(off1), _p(it1), len(nodes1), _p(v1), frame2._h, _p(nodes2), _p(off2), _p(it2), len(nodes2),
-                 _p(v2) if v2 is not None else None, self.TH_LOW, int(kf_kf), self.mfNNratio, int(self.mbCheckOrientation),
-                 _p(m12), _p(m21), C.byref(nm)))
+        check(self._L.orbm_frame_search_by_bow(frame1._h, _p(nodes1), _p(off1), _p(it1), len(nodes1), _p(v1), frame2._h, _p(nodes2),
+                                               _p(off2), _p(it2), len(nodes2), _p(v2) if v2 is not None else None, self.TH_LOW, int(kf_kf),
+                                               self.mfNNratio, int(self.mbCheckOrientation), _p(m12), _p(m21), C.byref(nm)))
         return m12[:frame1.n], m21[:frame2.n], nm.value
 
     def frame_search_for_triangulation(self, kf1, fv1, has_mp1, kf2, fv2, has_mp2, F12, ex, ey, scale_factors2, level_sigma2,
@@ -469,11 +432,9 @@ class ORBmatcher:
         F = np.ascontiguousarray(F12, np.float32).reshape(9)
         sf = np.ascontiguousarray(scale_factors2, np.float32); sg = np.ascontiguousarray(level_sigma2, np.float32)
         m12 = np.full(max(kf1.n, 1), -1, np.int32); nm = C.c_int(0)
-        fn = bind(self._L.orbm_frame_search_for_triangulation, [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_void_p] * 4 +
-                  [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p])
-        check(fn(kf1._h, _p(nd1), _p(of1), _p(it1), len(nd1), _p(h1), kf2._h, _p(nd2), _p(of2), _p(it2), len(nd2), _p(h2),
-                 int(bool(bOnlyStereo)), _p(F), float(ex), float(ey), _p(sf), _p(sg), len(sf), int(self.mbCheckOrientation), _p(m12),
-                 C.byref(nm)))
+        check(self._L.orbm_frame_search_for_triangulation(kf1._h, _p(nd1), _p(of1), _p(it1), len(nd1), _p(h1), kf2._h, _p(nd2), _p(of2),
+                                                          _p(it2), len(nd2), _p(h2), int(bool(bOnlyStereo)), _p(F), float(ex), float(ey),
+                                                          _p(sf), _p(sg), len(sf), int(self.mbCheckOrientation), _p(m12), C.byref(nm)))
         m12 = m12[:kf1.n]
         i1 = np.nonzero(m12 >= 0)[0]
         return np.stack([i1, m12[i1]], 1), nm.value, m12
@@ -484,7 +445,7 @@ class ORBmatcher:
         current frame, view = View(...), last = Points(valid, pos, desc, takes, octave, angle) per keypoint of the last frame,
         occupied[j] = mvpMapPoints[j] holds an observed point.  Returns (match_kp, match_q, nmatches[, queries])."""
         return self._whole(self._L.orbm_search_by_projection_last, cur, view, [Tcw, Tlw], last, occupied,
-                           [C.c_float(th), int(bool(bMono)), self.TH_HIGH, int(self.mbCheckOrientation)], want_queries)
+                           [th, int(bool(bMono)), self.TH_HIGH, int(self.mbCheckOrientation)], want_queries)
 
     def SearchByProjectionPoints(self, cur, view, Tcw, points, occupied, th=1.0, viewing_cos_limit=0.5):
         """Tracking::SearchLocalPoints' data plane: Frame::isInFrustum for every listed point chained into
@@ -494,16 +455,15 @@ class ORBmatcher:
         oc = np.ascontiguousarray(occupied, np.uint8) if occupied is not None else None
         mk = np.zeros(max(cur.n, 1), np.int32); mq = np.zeros(max(points.n, 1), np.int32); nm = C.c_int(0)
         proj = np.zeros(max(points.n, 1), self.PROJ_DTYPE); q = np.zeros(max(points.n, 1), self.WQ_DTYPE)
-        fn = self._L.orbm_search_by_projection_points
-        fn.argtypes = None
-        check(fn(cur._h, C.byref(view.c), _p(T), C.byref(points.c), _p(oc) if oc is not None else None, C.c_float(th),
-                 C.c_float(viewing_cos_limit), self.TH_HIGH, C.c_float(self.mfNNratio), _p(mk), _p(mq), C.byref(nm), _p(proj), _p(q)))
+        check(self._L.orbm_search_by_projection_points(cur._h, C.byref(view.c), _p(T), C.byref(points.c),
+                                                       _p(oc) if oc is not None else None, th, viewing_cos_limit, self.TH_HIGH,
+                                                       self.mfNNratio, _p(mk), _p(mq), C.byref(nm), _p(proj), _p(q)))
         return mk[:cur.n], mq[:points.n], nm.value, proj[:points.n], q[:points.n]
 
     def SearchByProjectionKeyFrame(self, cur, view, Tcw, kf, occupied, th, ORBdist, want_queries=False):
         """ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1673-1800)."""
         return self._whole(self._L.orbm_search_by_projection_keyframe, cur, view, [Tcw], kf, occupied,
-                           [C.c_float(th), int(ORBdist), int(self.mbCheckOrientation)], want_queries)
+                           [th, int(ORBdist), int(self.mbCheckOrientation)], want_queries)
 
     def SearchByProjectionSim3(self, kf, view, Scw, points, occupied, th, want_queries=False):
         """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cc:491-604)."""
@@ -514,7 +474,6 @@ class ORBmatcher:
         oc = np.ascontiguousarray(occupied, np.uint8) if occupied is not None else None
         mk = np.zeros(max(frame.n, 1), np.int32); mq = np.zeros(max(pts.n, 1), np.int32); nm = C.c_int(0)
         q = np.zeros(max(pts.n, 1), self.WQ_DTYPE) if want_queries else None
-        fn.argtypes = None
         check(fn(frame._h, C.byref(view.c), *[_p(m) for m in mats], C.byref(pts.c), _p(oc) if oc is not None else None, *scalars,
                  _p(mk), _p(mq), C.byref(nm), _p(q) if q is not None else None))
         out = (mk[:frame.n], mq[:pts.n], nm.value)
@@ -527,11 +486,9 @@ class ORBmatcher:
         n1, n2 = kf1.n, kf2.n
         v1 = np.zeros(max(n1, 1), np.int32); v2 = np.zeros(max(n2, 1), np.int32); m12 = np.zeros(max(n1, 1), np.int32); nf = C.c_int(0)
         q12 = np.zeros(max(n1, 1), self.WQ_DTYPE) if want_queries else None; q21 = np.zeros(max(n2, 1), self.WQ_DTYPE) if want_queries else None
-        fn = self._L.orbm_search_by_sim3
-        fn.argtypes = None
-        check(fn(kf1._h, kf2._h, C.byref(view.c), _p(T1), _p(T2), C.c_float(s12), _p(R), _p(t), C.byref(points1.c), C.byref(points2.c),
-                 C.c_float(th), self.TH_HIGH, _p(v1), _p(v2), _p(m12), C.byref(nf), _p(q12) if want_queries else None,
-                 _p(q21) if want_queries else None))
+        check(self._L.orbm_search_by_sim3(kf1._h, kf2._h, C.byref(view.c), _p(T1), _p(T2), s12, _p(R), _p(t), C.byref(points1.c),
+                                          C.byref(points2.c), th, self.TH_HIGH, _p(v1), _p(v2), _p(m12), C.byref(nf),
+                                          _p(q12) if want_queries else None, _p(q21) if want_queries else None))
         out = (m12[:n1], nf.value, v1[:n1], v2[:n2])
         return out + (q12[:n1], q21[:n2]) if want_queries else out
 
@@ -580,8 +537,6 @@ class Frame:
         else:
             k = np.ascontiguousarray(kps); d = np.ascontiguousarray(desc, np.uint8)
             ur = np.ascontiguousarray(uright, np.float32) if uright is not None else None
-            bind(self._L.orbm_frame_create, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
-                                                  C.c_void_p])
             check(self._L.orbm_frame_create(_p(k), _p(d), len(k), _p(ur) if ur is not None else None, *self.bounds, C.byref(self._h)))
         n = C.c_int(0); ns = C.c_int(0)
         check(self._L.orbm_frame_size(self._h, C.byref(n), C.byref(ns)))
@@ -593,8 +548,6 @@ class Frame:
         h = C.c_void_p()
         xy = np.ascontiguousarray(xy_undistorted, np.float32) if xy_undistorted is not None else None
         ur = np.ascontiguousarray(uright, np.float32) if uright is not None else None
-        bind(L.orbm_frame_from_extractor, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float,
-                                                C.c_float, C.c_void_p])
         check(L.orbm_frame_from_extractor(ex._h, int(frame), _p(xy) if xy is not None else None, _p(ur) if ur is not None else None,
                                           int(bool(uright_from_stereo)), *[float(b) for b in bounds], C.byref(h)))
         return cls(bounds=bounds, _handle=h)
@@ -602,7 +555,6 @@ class Frame:
     def alias(self, bounds):
         """orbm_frame_alias: the same device data searched with other bounds (a KeyFrame's int-valued mnMinX .. mnMaxY)."""
         h = C.c_void_p()
-        bind(self._L.orbm_frame_alias, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p])
         check(self._L.orbm_frame_alias(self._h, *[float(b) for b in bounds], C.byref(h)))
         return Frame(bounds=bounds, _handle=h)
 

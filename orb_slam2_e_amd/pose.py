@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import bind, check, lib, ptr
+from ._lib import check, lib, ptr
 from .extractor import KP_DTYPE
 
 
@@ -47,17 +47,15 @@ def pose_optimization(kps_xy, octave, uright, has_mp, mp_pos, cam, inv_level_sig
     ng = C.c_int(0)
     st = PoseStats()
     c = _camera(cam, inv_level_sigma2)
-    vp = C.c_void_p
     if frame is not None:
         h = frame._h if hasattr(frame, "_h") else frame
-        f = bind(L.orbm_frame_pose_optimization, [vp, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, C.POINTER(C.c_int), C.POINTER(PoseStats)])
-        check(f(h, ptr(has_mp), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier), C.byref(ng), C.byref(st)))
+        check(L.orbm_frame_pose_optimization(h, ptr(has_mp), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier), C.byref(ng),
+                                             C.byref(st)))
     else:
         k = _kps(kps_xy, octave)
         ur = None if uright is None else ptr(np.ascontiguousarray(uright, np.float32))
-        f = bind(L.orbm_pose_optimization, [vp, vp, C.c_int, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, C.POINTER(C.c_int),
-                                            C.POINTER(PoseStats)])
-        check(f(ptr(k), ur, n, ptr(has_mp), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier), C.byref(ng), C.byref(st)))
+        check(L.orbm_pose_optimization(ptr(k), ur, n, ptr(has_mp), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier), C.byref(ng),
+                                       C.byref(st)))
     return ng.value, Tout.reshape(4, 4), outlier, st
 
 
@@ -80,15 +78,13 @@ def pose_optimization_batch(problems, cam, inv_level_sigma2):
     ng = np.zeros(B, np.int32)
     st = (PoseStats * max(B, 1))()
     c = _camera(cam, inv_level_sigma2)
-    vp = C.c_void_p
-    f = bind(L.orbm_pose_optimization_batch, [vp, vp, vp, C.c_int, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, vp, vp, C.c_int, vp])
-    check(f(ptr(k), ptr(ur), ptr(off), B, ptr(has), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier), ptr(ng),
-            C.cast(st, vp), 0, None))
+    check(L.orbm_pose_optimization_batch(ptr(k), ptr(ur), ptr(off), B, ptr(has), ptr(mp), C.byref(c), ptr(Tin), ptr(Tout), ptr(outlier),
+                                         ptr(ng), st, 0, None))
     return [(int(ng[p]), Tout[p].reshape(4, 4), outlier[off[p]:off[p + 1]], st[p]) for p in range(B)]
 
 
 def _dptr(a):
-    return None if a is None else C.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else int(a))
+    return None if a is None else a.data_ptr() if hasattr(a, "data_ptr") else int(a)
 
 
 def pose_optimization_batch_device(kps, uright, kp_off, batch, has_mp, mp_pos, cam, inv_level_sigma2, Tcw_in, Tcw_out, outlier, ngood,
@@ -101,7 +97,5 @@ def pose_optimization_batch_device(kps, uright, kp_off, batch, has_mp, mp_pos, c
     ngood[p] < 0 and no other output."""
     L = lib()
     c = _camera(cam, inv_level_sigma2)
-    vp = C.c_void_p
-    f = bind(L.orbm_pose_optimization_batch, [vp, vp, vp, C.c_int, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, vp, vp, C.c_int, vp])
-    check(f(_dptr(kps), _dptr(uright), _dptr(kp_off), int(batch), _dptr(has_mp), _dptr(mp_pos), C.byref(c), _dptr(Tcw_in),
-            _dptr(Tcw_out), _dptr(outlier), _dptr(ngood), _dptr(stats), 1, None if stream is None else C.c_void_p(int(stream))))
+    check(L.orbm_pose_optimization_batch(_dptr(kps), _dptr(uright), _dptr(kp_off), int(batch), _dptr(has_mp), _dptr(mp_pos), C.byref(c),
+                                         _dptr(Tcw_in), _dptr(Tcw_out), _dptr(outlier), _dptr(ngood), _dptr(stats), 1, _dptr(stream)))

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import bind, check, lib, ptr as _p
+from ._lib import check, lib, ptr as _p
 
 
 
@@ -34,16 +34,14 @@ class ORBVocabulary:
         f = np.ascontiguousarray(features, np.uint8)
         n = len(f)
         word = np.zeros(n, np.int32); node = np.zeros(n, np.int32); w = np.zeros(n, np.float64)
-        bind(self._L.orbm_bow_transform, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
         check(self._L.orbm_bow_transform(self._h, _p(f), n, levelsup, _p(word), _p(node), _p(w)))
         return word, node, w
 
     def descend_batch_device(self, desc_dev, counts_dev, cap, nsets, levelsup, word_id_dev, node_id_dev, stream=None):
         """orbm_bow_transform_batch_dev: descriptor sets resident in HBM ([nsets][cap][32] bytes, counts[nsets]) ->
         word / node ids [nsets][cap] int32 on the device (rows past a set's count are not written).  Asynchronous."""
-        vp = lambda v: C.c_void_p(v) if v else None
-        check(self._L.orbm_bow_transform_batch_dev(self._h, vp(desc_dev), vp(counts_dev), cap, nsets, levelsup, vp(word_id_dev),
-                                                   vp(node_id_dev), vp(stream)))
+        check(self._L.orbm_bow_transform_batch_dev(self._h, desc_dev, counts_dev, cap, nsets, levelsup, word_id_dev, node_id_dev,
+                                                   stream))
 
     def transform(self, features, levelsup=4):
         """Returns (BowVector: {word id: value}, FeatureVector: {node id: [feature indices]})."""

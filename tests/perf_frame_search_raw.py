@@ -31,6 +31,5 @@ fr = Frame(kps, desc, bounds, ur)
 q = np.ascontiguousarray(q, ORBmatcher.WQ_DTYPE)
 mk2 = np.zeros(fr.n, np.int32); mq2 = np.zeros(len(q), np.int32)
 fn2 = L.orbm_frame_search_projection
-fn2.argtypes = None
 a2 = (fr._h, p(q), p(qd), p(qa), p(takes), len(q), p(occ2), 95, C.c_float(0.6), 0, 1, p(mk2), p(mq2), C.byref(nm))
 print("orbm_frame_search_projection raw: %.4f ms (nmatches %d)" % (t(lambda: fn2(*a2)), nm.value))

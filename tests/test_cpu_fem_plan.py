@@ -137,7 +137,6 @@ def test_symbolic_phase_two_formulations_agree():
     import ctypes as C
     from orb_slam2_e_amd._lib import check, lib
     L = lib()
-    L.fem_plan_selfcheck.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int]
     def run(eltype, nn, elems):
         elems = np.ascontiguousarray(elems, np.int32)
         check(L.fem_plan_selfcheck(eltype, nn, elems.ctypes.data_as(C.c_void_p), len(elems)))

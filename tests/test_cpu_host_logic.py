@@ -15,7 +15,6 @@ def _sorted_frame(kps, skip, uright, bounds):
     L = lib()
     n = len(kps)
     perm = np.zeros(max(n, 1), np.int32); off = np.zeros(64 * 48 + 1, np.int32); ns = C.c_int(0)
-    L.orbm_sorted_frame.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p] * 3
     p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
     check(L.orbm_sorted_frame(p(kps), n, p(skip), p(uright), *bounds, p(perm), p(off), C.byref(ns)))
     return perm[:ns.value].copy(), off

@@ -11,6 +11,7 @@ import pytest
 import pose_only_oracle as po
 import pose_only_scene as ps
 import pose_optimum as pm
+from test_cpu_integration_shells import _declarations, _strip_comments
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -137,27 +138,9 @@ def test_round_four_is_not_robustified():
 NAMES = ("orbm_pose_optimization", "orbm_frame_pose_optimization", "orbm_pose_optimization_batch")
 
 
-def _strip_comments(t):
-    t = re.sub(r"/\*.*?\*/", " ", t, flags=re.S)
-    return re.sub(r"//[^\n]*", " ", t)
-
-
-def _declarations():
-    text = ""
-    for h in ("orbslam_hip.h", "fem_hip.h"):
-        text += _strip_comments(open(os.path.join(ROOT, "include", h)).read())
-    decl = {}
-    for m in re.finditer(r"\b(?:int|const char \*)\s*((?:orbx|orbm|fem)_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, re.S):
-        args = m.group(2).strip()
-        decl[m.group(1)] = 0 if args in ("", "void") else args.count(",") + 1
-    return decl, text
-
-
 def _lib():
-    from orb_slam2_e_amd._lib import SO_PATH, build
-    if not os.path.exists(SO_PATH):
-        build()
-    return ctypes.CDLL(SO_PATH)
+    from orb_slam2_e_amd._lib import lib
+    return lib()
 
 
 def test_new_symbols_declared_and_exported():
@@ -254,7 +237,6 @@ def _raw_host_forms(p, inv=None, nlevels=None, off=None):
     inv_level_sigma2 / nlevels and the batch's kp_off overridable.  Returns their two status codes."""
     from orb_slam2_e_amd.pose import PoseCamera, PoseStats, _kps
     L = _lib()
-    vp = ctypes.c_void_p
     n = len(p["has_mp"])
     k = _kps(p["kp_xy"], p["octave"])
     ur = np.ascontiguousarray(p["uright"], np.float32)
@@ -269,7 +251,6 @@ def _raw_host_forms(p, inv=None, nlevels=None, off=None):
     ng = np.zeros(2, np.int32)
     st = PoseStats()
     a = ctypes.c_void_p
-    L.orbm_pose_optimization.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     r1 = L.orbm_pose_optimization(a(k.ctypes.data), a(ur.ctypes.data), n, a(has.ctypes.data), a(mp.ctypes.data), ctypes.byref(cam),
                                   a(Tin.ctypes.data), a(Tout.ctypes.data), a(out.ctypes.data), a(ng.ctypes.data), ctypes.byref(st))
     off = np.array([0, n] if off is None else off, np.int32)
@@ -277,7 +258,6 @@ def _raw_host_forms(p, inv=None, nlevels=None, off=None):
     Tin_b = np.ascontiguousarray(np.tile(Tin.reshape(16), (max(B, 1), 1)))
     Tout_b = np.zeros_like(Tin_b)
     ng_b = np.zeros(max(B, 1), np.int32)
-    L.orbm_pose_optimization_batch.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]
     r2 = L.orbm_pose_optimization_batch(a(k.ctypes.data), a(ur.ctypes.data), a(off.ctypes.data), B, a(has.ctypes.data), a(mp.ctypes.data),
                                         ctypes.byref(cam), a(Tin_b.ctypes.data), a(Tout_b.ctypes.data), a(out.ctypes.data),
                                         a(ng_b.ctypes.data), None, 0, None)

@@ -17,9 +17,9 @@ import pose_only_oracle as po
 import pose_only_scene as ps
 import pose_optimum as pm
 from orb_slam2_e_amd import ORBextractor, pose_optimization, pose_optimization_batch, pose_optimization_batch_device
-from orb_slam2_e_amd._lib import SO_PATH
+from orb_slam2_e_amd._lib import SO_PATH, lib
 from orb_slam2_e_amd.matcher import Frame
-from orb_slam2_e_amd.pose import PoseCamera, PoseStats, _camera, _kps
+from orb_slam2_e_amd.pose import PoseStats, _camera, _kps
 from orb_slam2_e_amd.synth import synth_frame
 from test_gpu_pose import _agree, _margins_ok
 
@@ -229,8 +229,8 @@ def test_uright_zero_and_negative_zero_are_stereo():
 
 def _raw(p, form, frame=None, fill=0xAA):
     """One raw ctypes call with the outlier array pre-filled with `fill` (the Python wrappers zero it).  form: 'single',
-    'frame' or 'batch' (host arrays).  Returns the outlier array.  A handle of its own: its argtypes are not the wrappers'."""
-    L = C.CDLL(SO_PATH)
+    'frame' or 'batch' (host arrays).  Returns the outlier array."""
+    L = lib()
     n = len(p["has_mp"])
     k = _kps(p["kp_xy"], p["octave"])
     ur = np.ascontiguousarray(p["uright"], np.float32)
@@ -244,14 +244,11 @@ def _raw(p, form, frame=None, fill=0xAA):
     vp = C.c_void_p
     a = lambda x: vp(x.ctypes.data)                    # noqa: E731
     if form == "single":
-        L.orbm_pose_optimization.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, vp, vp]
         rc = L.orbm_pose_optimization(a(k), a(ur), n, a(has), a(mp), C.byref(cam), a(Tin), a(Tout), a(out), a(ng), None)
     elif form == "frame":
-        L.orbm_frame_pose_optimization.argtypes = [vp, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, vp, vp]
         rc = L.orbm_frame_pose_optimization(frame._h, a(has), a(mp), C.byref(cam), a(Tin), a(Tout), a(out), a(ng), None)
     else:
         off = np.array([0, n], np.int32)
-        L.orbm_pose_optimization_batch.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.POINTER(PoseCamera), vp, vp, vp, vp, vp, C.c_int, vp]
         rc = L.orbm_pose_optimization_batch(a(k), a(ur), a(off), 1, a(has), a(mp), C.byref(cam), a(Tin), a(Tout), a(out), a(ng), None, 0,
                                             None)
     assert rc == 0

@@ -50,8 +50,6 @@ def test_frame_layout_equals_host_sort(case):
     perm, cell_off = f.layout()
     L = lib()
     rp = np.zeros(max(n, 1), np.int32); rc = np.zeros(64 * 48 + 1, np.int32); ns = C.c_int(0)
-    L.orbm_sorted_frame.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
-                                    C.c_void_p, C.c_void_p, C.c_void_p]
     assert L.orbm_sorted_frame(kps.ctypes.data_as(C.c_void_p), n, None, None, *bounds, rp.ctypes.data_as(C.c_void_p),
                                rc.ctypes.data_as(C.c_void_p), C.byref(ns)) == 0
     assert f.n == n and f.ns == ns.value

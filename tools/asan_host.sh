@@ -1,5 +1,5 @@
 #!/bin/bash
-# CPU sanitizer pass over the library's HOST code (GPU sanitizers are not available on the pool): the five translation
+# CPU sanitizer pass over the library's HOST code (GPU sanitizers are not available on the pool): the six translation
 # units compiled with the HOST side instrumented (-fno-gpu-sanitize: device code as usual; without a device every compute entry point
 # returns ORBX_ERR_NO_DEVICE) under AddressSanitizer + UndefinedBehaviorSanitizer, then the CPU tests that drive host
 # logic -- the symbolic CSR / chunk tables / resident-CG chunk table (fem_plan), the frame-grid counting sort
@@ -11,7 +11,7 @@ OUT=${ASAN_OUT:-/tmp/orbx_asan}
 mkdir -p "$OUT"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -fno-gpu-sanitize -O1 -g -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -shared-libasan"
-for f in orbx_extract orbx_stereo orbm_match orbm_search fem; do
+for f in orbx_extract orbx_stereo orbm_match orbm_search orbm_pose fem; do
     $HIPCC $FLAGS -c orb_slam2_e_amd/csrc/$f.hip -o "$OUT/$f.o" &
 done
 wait

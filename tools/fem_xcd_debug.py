@@ -11,8 +11,8 @@ b = load.copy()[None]; b[:, fixed] = 0
 fea.cg_setup(b)
 L = lib()
 info = np.zeros(8, np.int32); plan = np.zeros((64, 4), np.int32)
-L.fem_debug_xcd.argtypes = [C.c_void_p] * 4 + [C.c_int]
-L.fem_debug_xcd(fea._h, info.ctypes.data, plan.ctypes.data, None, 0)
+p = lambda a: a.ctypes.data_as(C.c_void_p)      # (fem_debug_xcd is not declared in include/: pointers as c_void_p)
+L.fem_debug_xcd(fea._h, p(info), p(plan), None, 0)
 print("info cg_xcd,P,ldr,ldq,lds,total,nchunk,nchunk_s:", info.tolist()); print("plan", plan[:info[1]].tolist())
 fea.cg_iterate(iters)
 try:
@@ -20,7 +20,7 @@ try:
 except Exception as e:
     print("FAILED", e)
 g = np.zeros((info[5], 4), np.uint32)
-L.fem_debug_xcd(fea._h, info.ctypes.data, plan.ctypes.data, g.ctypes.data, int(info[5]))
+L.fem_debug_xcd(fea._h, p(info), p(plan), p(g), int(info[5]))
 a = int(info[4]) & 0xffffffff
 print("abort word: %#x -> where %d rank %d wave %d it %d" % (a, a & 0xff, (a >> 8) & 0xff, (a >> 16) & 0xf, (a >> 20) & 0x7ff))
 ndof, nchunk, ns = fea.Ksize, int(info[6]), int(info[7])

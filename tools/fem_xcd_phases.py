@@ -15,8 +15,7 @@ if len(sys.argv) > 3 and sys.argv[3] == "two_level": fea.cg_preconditioner("two_
 fea.cg_setup(b); fea.cg_iterate(iters); fea.cg_result()
 fea.cg_setup(b); fea.cg_iterate(iters); fea.cg_result()
 out = np.zeros(32 + 8 * 64, np.uint32)
-L = lib(); L.fem_debug_xcd_timing.argtypes = [C.c_void_p, C.c_void_p]
-assert L.fem_debug_xcd_timing(fea._h, out.ctypes.data) == 0
+assert lib().fem_debug_xcd_timing(fea._h, out.ctypes.data_as(C.c_void_p)) == 0   # (not declared in include/: pointers as c_void_p)
 names = ["spmv phase 1", "spmv phase 2 + puts", "hop A (poll pAp, Ap row)", "update + puts", "hop B + new p (two-level: the new p only)",
          "(two-level) hop B poll", "(two-level) restriction + puts", "(two-level) hop C + coarse solve"]
 for r in range(3):

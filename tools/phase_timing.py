@@ -18,11 +18,11 @@ for _ in range(3):
     ex.extract_batch(frames)
 ex.download_batch()
 acc = np.zeros((4, 65536, 16), np.uint64)
-L.orbx_debug_phases.argtypes = [C.c_void_p, C.c_int]
-assert L.orbx_debug_phases(acc.ctypes.data, 1) == 0
+p = acc.ctypes.data_as(C.c_void_p)              # (orbx_debug_phases is not declared in include/: pointers as c_void_p)
+assert L.orbx_debug_phases(p, 1) == 0
 ex.extract_batch(frames)
 ex.download_batch()
-assert L.orbx_debug_phases(acc.ctypes.data, 0) == 0
+assert L.orbx_debug_phases(p, 0) == 0
 for k, (title, names) in enumerate([("k_fast_cells, per wave", ["tile load", "stage A", "stage B", "zero + score", "nms + emit", "epilogue", "(timer)"]),
                                     ("k_describe, per workgroup (wave 0)", ["lookup", "moments", "atan/sincos", "brief kp0", "brief kp1", "brief kp2", "brief kp3", "tail"]),
                                     ("k_pyr_resize, per wave (records of the launches that wrote last; [12] = level width)", ["row table", "columns + rows + math", "store"]),
