@@ -111,6 +111,11 @@ void oracle_three_maxima(const int *histo_size, int L, int *ind1, int *ind2, int
     else if (max3 < 0.1f * (float)max1) { *ind3 = -1; }
 }
 
+/* (int)x as x86-64's cvttss2si computes it: truncation, and INT_MIN for NaN and for x outside [-2^31, 2^31).  C leaves those
+ * cases undefined (a compiler may fold them to anything); the reference runs on x86-64, so its answer is this one.  Reached by
+ * PosInGrid of a NaN keypoint and by PredictScale of a ratio of +inf (a point at the camera centre, an infinite max distance). */
+static int f2i_x86(float x) { return (x >= -2147483648.0f && x < 2147483648.0f) ? (int)x : INT_MIN; }
+
 /* ---- Frame grid: AssignFeaturesToGrid / PosInGrid / GetFeaturesInArea ------- */
 #define FRAME_GRID_ROWS 48 /* include/Frame.h:37 */
 #define FRAME_GRID_COLS 64 /* include/Frame.h:38 */
@@ -125,8 +130,8 @@ typedef struct {
 /* Frame::PosInGrid, Frame.cc:397-407 */
 static int pos_in_grid(const oracle_grid *g, float x, float y, int *px, int *py)
 {
-    *px = (int)roundf((x - g->minX) * g->invW);
-    *py = (int)roundf((y - g->minY) * g->invH);
+    *px = f2i_x86(roundf((x - g->minX) * g->invW));
+    *py = f2i_x86(roundf((y - g->minY) * g->invH));
     if (*px < 0 || *px >= FRAME_GRID_COLS || *py < 0 || *py >= FRAME_GRID_ROWS) return 0;
     return 1;
 }
@@ -741,7 +746,7 @@ typedef struct { float u, v, ur, view_cos, dist; int level, visible; } oracle_pr
 static int oracle_predict_scale(float mfMaxDistance, float currentDist, float logScaleFactor, int nScaleLevels)
 {
     const float ratio = mfMaxDistance / currentDist;
-    int nScale = (int)ceilf(logf(ratio) / logScaleFactor);
+    int nScale = f2i_x86(ceilf(logf(ratio) / logScaleFactor));
     if (nScale < 0) nScale = 0;
     else if (nScale >= nScaleLevels) nScale = nScaleLevels - 1;
     return nScale;

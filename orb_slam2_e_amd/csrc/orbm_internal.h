@@ -11,6 +11,7 @@
 
 #include "../../include/orbslam_hip.h"
 #include "common.h"
+#include "orbx_math.h"
 
 namespace orbm_detail {
 
@@ -40,7 +41,7 @@ inline void build_winkp(const orbx_keypoint *kps, int n, const uint8_t *skip, co
     const float invW = (float)FRAME_GRID_COLS / (max_x - min_x), invH = (float)FRAME_GRID_ROWS / (max_y - min_y);
     wk.resize(n ? n : 1);
     for (int j = 0; j < n; ++j) {
-        const int px = (int)roundf((kps[j].x - min_x) * invW), py = (int)roundf((kps[j].y - min_y) * invH);
+        const int px = orbx_f2i_x86(roundf((kps[j].x - min_x) * invW)), py = orbx_f2i_x86(roundf((kps[j].y - min_y) * invH));
         const bool in = !(px < 0 || px >= FRAME_GRID_COLS || py < 0 || py >= FRAME_GRID_ROWS);
         wk[j].x = kps[j].x; wk[j].y = kps[j].y; wk[j].octave = kps[j].octave;
         wk[j].uright = uright ? uright[j] : -1.0f;

@@ -1057,7 +1057,7 @@ __global__ __launch_bounds__(MT) void k_project_points(const uint8_t *__restrict
     // PredictScale: ratio = mfMaxDistance / dist; ceil(log(ratio) / mfLogScaleFactor), clamped
     const float ratio = maxd[i] / dist;
     const float lg = orbx_logf_glibc_f32(ratio);        // log(float) = logf under the reference's headers; glibc's logf restated (orbx_math.h)
-    int level = (int)ceilf(lg / cam.log_scale);
+    int level = orbx_f2i_x86(ceilf(lg / cam.log_scale));   // ratio +inf: INT_MIN -> level 0, as on x86-64
     if (level < 0) level = 0; else if (level >= cam.nlevels) level = cam.nlevels - 1;
     if (ok) {
         o.u = u; o.v = v; o.ur = ur; o.view_cos = viewCos; o.dist = dist; o.level = level; o.visible = 1;
@@ -1200,7 +1200,7 @@ __global__ __launch_bounds__(FB_T) void k_frame_build(const orbx_keypoint *__res
     __syncthreads();
     for (int j = tid; j < n; j += FB_T) {
         const float x = xy_un ? xy_un[j].x : kps[j].x, y = xy_un ? xy_un[j].y : kps[j].y;
-        const int px = (int)roundf((x - gp.min_x) * gp.inv_w), py = (int)roundf((y - gp.min_y) * gp.inv_h);
+        const int px = orbx_f2i_x86(roundf((x - gp.min_x) * gp.inv_w)), py = orbx_f2i_x86(roundf((y - gp.min_y) * gp.inv_h));   // NaN: outside
         const bool in = !(px < 0 || px >= FRAME_GRID_COLS || py < 0 || py >= FRAME_GRID_ROWS);
         const int c = in ? px * FRAME_GRID_ROWS + py : FB_NC;   // FB_NC: outside the grid -- kept behind the sorted part, in index order
         s_cell[j] = (unsigned short)c;
@@ -1387,7 +1387,7 @@ __global__ __launch_bounds__(MT) void k_project_form(const uint8_t *__restrict__
             ok = ok && !(dist3D < minDistance || dist3D > maxDistance);
             if (ok) {
                 const float ratio = maxd[i] / dist3D;
-                int level = (int)ceilf(orbx_logf_glibc_f32(ratio) / cam.log_scale);
+                int level = orbx_f2i_x86(ceilf(orbx_logf_glibc_f32(ratio) / cam.log_scale));
                 if (level < 0) level = 0; else if (level >= cam.nlevels) level = cam.nlevels - 1;
                 w.u = u; w.v = v; w.r = cam.th * scale[level]; w.min_level = level - 1; w.max_level = level + 1;
             }
@@ -1416,7 +1416,7 @@ __global__ __launch_bounds__(MT) void k_project_form(const uint8_t *__restrict__
             }
             if (ok) {
                 const float ratio = maxd[i] / dist;
-                int level = (int)ceilf(orbx_logf_glibc_f32(ratio) / cam.log_scale);
+                int level = orbx_f2i_x86(ceilf(orbx_logf_glibc_f32(ratio) / cam.log_scale));
                 if (level < 0) level = 0; else if (level >= cam.nlevels) level = cam.nlevels - 1;
                 w.u = u; w.v = v; w.r = cam.th * scale[level]; w.min_level = level - 1; w.max_level = level;
             }

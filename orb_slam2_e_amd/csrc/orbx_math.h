@@ -15,6 +15,13 @@
 
 #include <math.h>
 
+// (int)x with the meaning x86-64's cvttss2si gives it: truncation toward zero, and INT_MIN (the "integer indefinite" value) for
+// NaN and for every x outside [-2^31, 2^31).  C leaves those cases undefined; the reference and the CPU oracle run on x86-64,
+// while the GPU's v_cvt_i32_f32 saturates (NaN -> 0, +inf -> INT_MAX).  Used where a degenerate input can reach a float -> int
+// conversion whose result decides something: PredictScale's level of a ratio of +inf (a map point at the camera centre, an
+// infinite mfMaxDistance) and PosInGrid's cell of a NaN keypoint.
+ORBX_HD int orbx_f2i_x86(float x) { return (x >= -2147483648.0f && x < 2147483648.0f) ? (int)x : -2147483647 - 1; }
+
 // cvRound(float): round-half-to-even.
 ORBX_HD int orbx_cvround(float v) { return (int)rintf(v); }
 
