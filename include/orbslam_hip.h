@@ -584,6 +584,51 @@ int orbm_pose_optimization_batch(const orbx_keypoint *kps_un, const float *urigh
                                  const float *mp_pos, const orbm_pose_camera *cam, const float *Tcw_in, float *Tcw_out, uint8_t *outlier,
                                  int32_t *ngood, orbm_pose_stats *stats, int is_device, void *stream);
 
+/* ------------------------------------------------------------------ a frame tracked in one call
+ * The two functions the tracking thread runs on every frame, each as ONE call: the projection search chained into the pose solve
+ * on one stream -- prefix, window search, resolver, pose kernel -- with one staged upload and one host wait; the pose kernel forms
+ * its edges on the device from the resolver's match_kp (no has_mp / mp_pos array is built on the host) and counts the matches
+ * that survive in its epilogue.  Results are, bit for bit, those of the search call followed by orbm_frame_pose_optimization
+ * over the gathered matches.  When the search has to be repeated (a window list that outgrew its region, a resolver that did not
+ * reach its fixed point, too few matches) the pose kernel leaves without solving and the host repeats the chain: more waits, same
+ * results.  The frame's mvKeysUn / mvuRight are the handle's.  At most 8,192 keypoints (ORBX_ERR_UNSUPPORTED); a keypoint octave
+ * outside [0, nlevels) of the view or of the pose camera is ORBX_ERR_ARG; both before anything is launched. */
+typedef struct orbm_track_result {
+    int32_t tracked;                    /* 0: fewer than min_matches after both searches, no pose solve (Tracking.cc:1251-1252) */
+    int32_t search_used;                /* 1: the search with th, 2: the one with 2 * th (:1245-1249) */
+    int32_t nsearch;                    /* what that search returned */
+    int32_t ngood;                      /* PoseOptimization's return value */
+    int32_t nmatches;                   /* slots that hold a point and are not outliers (:1271; mnMatchesInliers with mbOnlyTracking, :1314) */
+    int32_t nmatches_map;               /* ... of them, those whose point has Observations() > 0 (nmatchesMap :1274; mnMatchesInliers :1311) */
+} orbm_track_result;
+/* Tracking::TrackWithMotionModel   src/Tracking.cc:1232-1284 (behind UpdateLastFrame): SearchByProjection(Cur, Last, th, mono) with
+ * every slot free (mvpMapPoints was filled with NULL, :1234), again from scratch with 2 * th if it returns fewer than min_matches
+ * (20 in the reference, :1245-1249); if still fewer: result->tracked = 0, Tcw_out = Tcw, outlier untouched (:1251-1252).  Else
+ * PoseOptimization from Tcw over the matches (keypoint j holds the point last->pos[match_kp[j]] iff match_kp[j] >= 0) and the
+ * counts of the discard loop (:1257-1276).  Tcw = mVelocity * mLastFrame.mTcw: the pose the search projects with AND the
+ * solve's start (:1232).  last, th, mono, th_high, check_orientation as for orbm_search_by_projection_last.  match_kp[n] /
+ * match_q[last->n] are returned as the accepted search left them (the discard does not edit them: -1 never matched, -2 cleared
+ * by the rotation check, an outlier keeps its index); outlier[n] is written only where match_kp[j] >= 0.  stats may be NULL. */
+int orbm_track_with_motion_model(const orbm_frame *cur, const orbm_view *view, const orbm_pose_camera *cam, const float *Tcw, const float *Tlw,
+                                 const orbm_points *last, float th, int mono, int th_high, int check_orientation, int min_matches,
+                                 int32_t *match_kp, int32_t *match_q, uint8_t *outlier, float *Tcw_out, orbm_track_result *result,
+                                 orbm_pose_stats *stats);
+/* Tracking::TrackLocalMap   src/Tracking.cc:1294-1320 (behind UpdateLocalMap): SearchLocalPoints as
+ * orbm_search_by_projection_points (points, th, viewing_cos_limit, th_high, nnratio as there), then PoseOptimization from Tcw over the
+ * UNION of the new matches and the slots the frame holds already, given by keypoint index: base_has[n] (mvpMapPoints[j] != NULL),
+ * base_pos[n][3] (its GetWorldPos()), base_takes[n] (its Observations() > 0; NULL: all).  occupied[j] = base_has[j] && base_takes[j]
+ * is derived here (ORBmatcher.cc:87-89); a new match overrides the base entry of its slot (the reference overwrites
+ * mvpMapPoints[idx]).  base_has may be NULL (the frame holds nothing).  Then the counts of :1301-1320: result->nmatches_map =
+ * mnMatchesInliers, result->nmatches = the same with mbOnlyTracking.  outlier[n] is written where the union holds a point;
+ * dropping stereo outliers from mvpMapPoints (:1316-1317) stays the caller's.  result->tracked = 1, search_used = 1 always.
+ * projected_out (optional) as for orbm_search_by_projection_points. */
+int orbm_track_local_map(const orbm_frame *cur, const orbm_view *view, const orbm_pose_camera *cam, const float *Tcw, const orbm_points *points,
+                         const uint8_t *base_has, const float *base_pos, const uint8_t *base_takes, float th, float viewing_cos_limit,
+                         int th_high, float nnratio, int32_t *match_kp, int32_t *match_q, orbm_projected_point *projected_out,
+                         uint8_t *outlier, float *Tcw_out, orbm_track_result *result, orbm_pose_stats *stats);
+/* Host waits (stream synchronisations) of the last orbm_track_* call of this process: 1 on the common path. */
+int orbm_debug_last_track_waits(void);
+
 /* Test aid: on != 0 makes the whole-loop projection searches use the one-wave sequential resolver (k_resolve) instead of the
  * parallel fixed-point resolver (k_resolve_par), which otherwise only takes over when the latter does not converge.  Both
  * give the reference loop's result.  Process-wide; returns the previous setting. */

@@ -538,6 +538,44 @@ public:
                                                    mfNNratio, slotOwner.data(), mScratch.data(), &nm, projected ? projected->data() : nullptr, nullptr);
         return mStatus == ORBX_OK ? nm : 0;
     }
+    // ---- a frame tracked in one call (mvInvLevelSigma2 = Frame::mvInvLevelSigma2: what the pose solve needs beside the Calibration)
+    // Tracking::TrackWithMotionModel (src/Tracking.cc:1232-1284, behind UpdateLastFrame) in one call: SearchByProjection(Cur, Last,
+    // th, bMono) with every slot free, again with 2 * th below minMatches, PoseOptimization from Tcw (the predicted pose, 4 x 4
+    // row-major) over the matches, the counts of the discard loop.  slotOwner[j] as SearchByProjection(Cur, Last) leaves it (the
+    // discard does not edit it); vbOutlier[j] is written only where slotOwner[j] >= 0; TcwOut[16] = what SetPose receives.
+    orbm_track_result TrackWithMotionModel(const ResidentFrame &Cur, const Calibration &K, const std::vector<float> &mvInvLevelSigma2,
+                                           const float *Tcw, const float *Tlw, const PointList &last, float th, bool bMono,
+                                           std::vector<int32_t> &slotOwner, std::vector<uint8_t> &vbOutlier, float *TcwOut,
+                                           int minMatches = 20)
+    {
+        const orbm_points p = last.view(); const orbm_view v = K.view();
+        const orbm_pose_camera c = {K.fx, K.fy, K.cx, K.cy, K.mbf, (int32_t)mvInvLevelSigma2.size(), mvInvLevelSigma2.data()};
+        slotOwner.assign(Cur.N, -1); vbOutlier.resize(Cur.N, 0); mScratch.resize(p.n);
+        orbm_track_result r = {0, 0, 0, 0, 0, 0};
+        mStatus = orbm_track_with_motion_model(Cur.handle(), &v, &c, Tcw, Tlw, &p, th, bMono, TH_HIGH, mbCheckOrientation, minMatches,
+                                               slotOwner.data(), mScratch.data(), vbOutlier.data(), TcwOut, &r, nullptr);
+        return r;
+    }
+    // Tracking::TrackLocalMap (src/Tracking.cc:1294-1320, behind UpdateLocalMap) in one call: SearchLocalPoints, PoseOptimization over
+    // the union of the new matches and the slots the frame holds (baseHas / basePos / baseTakes by keypoint index: mvpMapPoints[j] !=
+    // NULL, its GetWorldPos(), its Observations() > 0), the counts of the statistics loop (nmatches_map = mnMatchesInliers,
+    // nmatches = the same with mbOnlyTracking).  vbOutlier[j] is written where the union holds a point.
+    orbm_track_result TrackLocalMap(const ResidentFrame &Cur, const Calibration &K, const std::vector<float> &mvInvLevelSigma2, const float *Tcw,
+                                    const PointList &points, const std::vector<uint8_t> &baseHas, const std::vector<float> &basePos,
+                                    const std::vector<uint8_t> &baseTakes, float th, std::vector<int32_t> &slotOwner,
+                                    std::vector<uint8_t> &vbOutlier, float *TcwOut, std::vector<orbm_projected_point> *projected = nullptr)
+    {
+        const orbm_points p = points.view(); const orbm_view v = K.view();
+        const orbm_pose_camera c = {K.fx, K.fy, K.cx, K.cy, K.mbf, (int32_t)mvInvLevelSigma2.size(), mvInvLevelSigma2.data()};
+        slotOwner.assign(Cur.N, -1); vbOutlier.resize(Cur.N, 0); mScratch.resize(p.n);
+        if (projected) projected->resize(p.n);
+        orbm_track_result r = {0, 0, 0, 0, 0, 0};
+        const bool base = !baseHas.empty();
+        mStatus = orbm_track_local_map(Cur.handle(), &v, &c, Tcw, &p, base ? baseHas.data() : nullptr, base ? basePos.data() : nullptr,
+                                       base && !baseTakes.empty() ? baseTakes.data() : nullptr, th, 0.5f, TH_HIGH, mfNNratio, slotOwner.data(),
+                                       mScratch.data(), projected ? projected->data() : nullptr, vbOutlier.data(), TcwOut, &r, nullptr);
+        return r;
+    }
     // SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (:1303-1527), whole: vnMatches12[i1] = idx2 where both directions
     // agree (the entries of vpMatches12 the reference overwrites), else -1; returns nFound.
     int SearchBySim3(const ResidentFrame &KF1, const ResidentFrame &KF2, const Calibration &K, const float *T1w, const float *T2w, float s12,

@@ -122,4 +122,41 @@ struct StagedCall {
 struct FrameDeviceView { const SeqKp *kp; const int *perm; int n, min_octave, max_octave; };
 void frame_device_view(const orbm_frame *f, FrameDeviceView &v);
 
+// Work a caller appends to a whole-loop projection search, on the search's stream, behind the resolver and in front of the call's
+// host wait (orbm_pose.hip: the pose solve of the tracking functions).  The driver (run_sequential, orbm_search.hip) asks the chain
+// for its arrays while it lays the workspace out -- inputs inside the staged block (they travel with the call's one upload),
+// results behind the search's result block (a result at offset o is read back at w.pin + (o - o_res)) -- and launches it once per
+// attempt.  A search attempt may have to be repeated (see run_sequential); the flags that say so are only known on the device
+// when the chain's kernel runs, so that kernel reads them itself and must leave at once if the attempt does not stand.
+// collect() runs after the wait of the attempt that stands.
+struct SearchChain {
+    struct Ctx {
+        const Workspace *w;
+        hipStream_t st;
+        const int *match_kp;        // [n], device: the resolver's result by keypoint index
+        const int *flags;           // device: match count, "a list outgrew its region" (== gen), "fixed point reached" (== gen), iterations
+        const uint8_t *qtakes;      // [nq], device: orbm_points::takes as staged (all 1 when the caller gave none)
+        int n, nq, gen;
+        bool check_overflow, check_converged;   // which of the two flags this attempt can raise
+        size_t o_res;
+    };
+    int waits = 0;                  // host waits of the call so far
+    bool launched = false;          // launch() ran in the attempt that stands
+    virtual void carve_inputs(Workspace &w) = 0;
+    virtual void fill_inputs(Workspace &w) = 0;
+    virtual void carve_results(Workspace &w) = 0;
+    virtual int launch(const Ctx &c) = 0;
+    virtual void collect(const Ctx &c) = 0;
+    virtual ~SearchChain() {}
+};
+
+// orbm_search_by_projection_last / orbm_search_by_projection_points with a chain (nullptr: the public functions)
+int search_by_projection_last_chain(const orbm_frame *cur, const orbm_view *view, const float *Tcw, const float *Tlw, const orbm_points *last,
+                                    const uint8_t *occupied, float th, int mono, int th_high, int check_orientation, int32_t *match_kp,
+                                    int32_t *match_q, int *nmatches, orbm_window_query *queries_out, SearchChain *chain);
+int search_by_projection_points_chain(const orbm_frame *cur, const orbm_view *view, const float *Tcw, const orbm_points *points,
+                                      const uint8_t *occupied, float th, float viewing_cos_limit, int th_high, float nnratio,
+                                      int32_t *match_kp, int32_t *match_q, int *nmatches, orbm_projected_point *projected_out,
+                                      orbm_window_query *queries_out, SearchChain *chain);
+
 } // namespace orbm_detail

@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <atomic>
 #include <vector>
 
 #include "../../include/orbslam_hip.h"
@@ -49,6 +50,17 @@ struct PoseSrc {
     const float *mp_pos;
     const int *kp_off;          // [B + 1]
     const float *Tin;           // [B][16]
+    // chained form (behind a projection search on the same stream): has_mp / mp_pos are not given, a keypoint's map point is formed
+    // from the search's result -- the point match_kp[i] of the searched list, else the keypoint's base entry
+    const int *match_kp;        // [n] by keypoint index: entry of the point list, < 0 none (device memory, written by the resolver)
+    const float *pt_pos;        // [nq][3]
+    const uint8_t *pt_takes;    // [nq]
+    const uint8_t *base_has;    // [n] or nullptr: the slots the frame holds already (TrackLocalMap) ...
+    const float *base_pos;      // [n][3]          ... their positions ...
+    const uint8_t *base_takes;  // [n] or nullptr  ... and Observations() > 0 (nullptr: all)
+    float4 *gathered;           // [n] scratch: (Xw, kind) of the keypoints behind the LDS-staged ones, formed once by the prologue
+    const int *flags;           // the search's count and its generation-stamped flags (SearchChain::Ctx)
+    int nq, gen, check_overflow, check_converged, min_matches;
 };
 
 struct PoseOut {
@@ -56,7 +68,10 @@ struct PoseOut {
     uint8_t *outlier;           // [kp_off[B]], written where has_mp
     int32_t *ngood;             // [B]
     orbm_pose_stats *stats;     // [B] or nullptr
+    int32_t *track;             // chained form: status (TRACK_*), slots that are not outliers, those of them whose point is observed
 };
+
+enum { TRACK_SOLVED = 0, TRACK_SEARCH_AGAIN = 1, TRACK_FEW_MATCHES = 2, TRACK_REJECTED = 3 };
 
 struct Se3 { double q[4], t[3]; };
 
@@ -336,9 +351,11 @@ __device__ __forceinline__ int block_sum_int(int v, int *ired)
     return ired[0] + ired[1] + ired[2] + ired[3];
 }
 
-template <bool FRAME>
+// SRC 0: keypoints from arrays, 1: from a resident frame, 2: resident frame + the map points of a search's result (chained)
+template <int SRC>
 __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam cam, PoseOut out)
 {
+    constexpr bool FRAME = SRC >= 1, CHAIN = SRC == 2;
     __shared__ float4 s_a[POSE_LDS_KP], s_b[POSE_LDS_KP];   // (obs x, obs y, ur, info), (Xw, kind)
     __shared__ uint16_t s_inv[FRAME ? POSE_MAXN : 1];        // resident frame: sorted position of keypoint i
     __shared__ double s_red[PW][NSYS];
@@ -348,15 +365,32 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
     const int base = src.kp_off[b], n = src.kp_off[b + 1] - base;
     const float *Tin = src.Tin + 16 * b;
     if (n < 0 || n > POSE_MAXN) {
-        if (tid == 0) out.ngood[b] = ORBX_ERR_UNSUPPORTED;
+        if (tid == 0) { out.ngood[b] = ORBX_ERR_UNSUPPORTED; if (CHAIN) out.track[0] = TRACK_REJECTED; }
         return;
     }
+    if (CHAIN) {
+        // the search in front may have to be repeated (a window list outgrew its region, the resolver's fixed point was not reached)
+        // or found too few matches: the host sees the same words after its wait; nothing is solved on such a result
+        const bool again = (src.check_overflow && src.flags[1] == src.gen) || (src.check_converged && src.flags[2] != src.gen);
+        if (again || src.flags[0] < src.min_matches) {
+            if (tid == 0) out.track[0] = again ? TRACK_SEARCH_AGAIN : TRACK_FEW_MATCHES;
+            return;
+        }
+    }
+    // mvpMapPoints[i] != NULL; chained: the entry of the searched list (>= 0), the base entry (-1) or none (-2)
+    auto slot = [&](int i) -> int {
+        const int q = src.match_kp[i];
+        if (q >= 0 && q < src.nq) return q;
+        return (src.base_has && src.base_has[i]) ? -1 : -2;
+    };
+    auto has_at = [&](int i) -> bool { return CHAIN ? slot(i) > -2 : src.has_mp[base + i] != 0; };
     if (FRAME) {
         for (int sp = tid; sp < n; sp += PT) s_inv[src.fperm[sp]] = (uint16_t)sp;
         __syncthreads();
     }
 
     // one keypoint's edge constants, from the caller's arrays (Optimizer.cc:303-383)
+    bool staged = false;
     auto fetch = [&](int i, float4 &a, float4 &c) {
         const int g = base + i;
         float kx, ky, ur; int oct;
@@ -368,14 +402,26 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
             kx = k.x; ky = k.y; oct = k.octave;
             ur = src.uright ? src.uright[g] : -1.0f;
         }
-        const bool has = src.has_mp[g] != 0;
         oct = oct < 0 ? 0 : (oct >= POSE_MAXLEVELS ? POSE_MAXLEVELS - 1 : oct);
         a = make_float4(kx, ky, ur, cam.inv_sigma2[oct]);
-        c = has ? make_float4(src.mp_pos[3 * (size_t)g], src.mp_pos[3 * (size_t)g + 1], src.mp_pos[3 * (size_t)g + 2], ur < 0 ? 1.f : 2.f)
-                : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (CHAIN && staged && i >= POSE_LDS_KP) { c = src.gathered[i]; return; }     // (its own thread wrote it: no barrier needed)
+        const float *P = nullptr;
+        if (CHAIN) {
+            const int q = slot(i);
+            if (q > -2) P = q >= 0 ? src.pt_pos + 3 * (size_t)q : src.base_pos + 3 * (size_t)i;
+        } else if (src.has_mp[g]) P = src.mp_pos + 3 * (size_t)g;
+        c = P ? make_float4(P[0], P[1], P[2], ur < 0 ? 1.f : 2.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     };
     int nloc = 0;
     for (int i = tid; i < n && i < POSE_LDS_KP; i += PT, ++nloc) fetch(i, s_a[i], s_b[i]);
+    if (CHAIN) {        // the gather runs once, here: the passes read one float4 per keypoint behind the LDS-staged ones
+        for (int i = POSE_LDS_KP + tid; i < n; i += PT) {
+            float4 a, c;
+            fetch(i, a, c);
+            src.gathered[i] = c;
+        }
+        staged = true;
+    }
     auto edge = [&](int i, Edge &e) {
         float4 a, c;
         if (i < POSE_LDS_KP) { a = s_a[i]; c = s_b[i]; }
@@ -388,16 +434,15 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
     // nInitialCorrespondences (every keypoint with a map point gives one edge; mvbOutlier = false).  A map point on a keypoint
     // whose octave has no mvInvLevelSigma2 entry (the host forms refuse it before the launch) rejects the problem: ORBX_ERR_ARG
     // and no other output.  Counted as 1 << 16 each: both sums fit in one reduction (at most 8,192 keypoints).
-    uint32_t lvl = 0;                       // bit k: the k-th owned keypoint's edge is at level 1 (mvbOutlier)
     int mine = 0;
     for (int i = tid; i < n; i += PT) {
-        if (!src.has_mp[base + i]) continue;
+        if (!has_at(i)) continue;
         const int oct = FRAME ? src.fkp[s_inv[i]].octave : src.kps[base + i].octave;
         mine += (oct < 0 || oct >= cam.nlevels) ? (1 << 16) : 1;
     }
     const int counts = block_sum_int(mine, s_ired);
     if (counts >> 16) {
-        if (tid == 0) out.ngood[b] = ORBX_ERR_ARG;
+        if (tid == 0) { out.ngood[b] = ORBX_ERR_ARG; if (CHAIN) out.track[0] = TRACK_REJECTED; }
         return;
     }
     const int nInitial = counts;
@@ -405,12 +450,28 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
     const float deltaMono = sqrt(5.991), deltaStereo = sqrt(7.815);
     const float chi2Mono = 5.991f, chi2Stereo = 7.815f;
 
+    uint32_t lvl = 0;                       // bit k: the k-th owned keypoint's edge is at level 1 (mvbOutlier)
+    // chained: the loops behind the solve (Tracking.cc:1257-1276, :1301-1320) -- slots that are not outliers, and those of them
+    // whose point has Observations() > 0 -- as one block sum (16 bits each: at most 8,192 keypoints)
+    auto tally = [&]() {
+        int mine = 0, k = 0;
+        for (int i = tid; i < n; i += PT, ++k) {
+            const int q = slot(i);
+            if (q == -2 || ((lvl >> k) & 1u)) continue;
+            const bool takes = q >= 0 ? src.pt_takes[q] != 0 : (!src.base_takes || src.base_takes[i] != 0);
+            mine += 1 + (takes ? (1 << 16) : 0);
+        }
+        const int c = block_sum_int(mine, s_ired);
+        if (tid == 0) { out.track[0] = TRACK_SOLVED; out.track[1] = c & 0xffff; out.track[2] = c >> 16; }
+    };
+
     orbm_pose_stats st;
     memset(&st, 0, sizeof(st));
     st.ninitial = nInitial;
     if (nInitial < 3) {
         for (int i = tid; i < n; i += PT)
-            if (src.has_mp[base + i]) out.outlier[base + i] = 0;
+            if (has_at(i)) out.outlier[base + i] = 0;
+        if (CHAIN) tally();
         if (tid < 16) out.Tout[16 * b + tid] = Tin[tid];
         if (tid == 0) {
             out.ngood[b] = 0;
@@ -552,7 +613,8 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
 
     int k = 0;
     for (int i = tid; i < n; i += PT, ++k)
-        if (src.has_mp[base + i]) out.outlier[base + i] = (lvl >> k) & 1u;
+        if (has_at(i)) out.outlier[base + i] = (lvl >> k) & 1u;
+    if (CHAIN) tally();
     if (tid == 0) {
         double R[9];
         quat_to_matrix(est.q, R);                                       // Converter::toCvMat(SE3Quat)
@@ -603,7 +665,7 @@ int pose_host(const orbx_keypoint *kps, const float *uright, const int32_t *kp_o
     PoseSrc src = {sc.d<orbx_keypoint>(o_k), uright ? sc.d<float>(o_u) : nullptr, nullptr, nullptr, sc.d<uint8_t>(o_h), sc.d<float>(o_p),
                    sc.d<int>(o_o), sc.d<float>(o_t)};
     PoseOut po = {sc.d<float>(r_t), sc.d<uint8_t>(r_o), sc.d<int32_t>(r_g), sc.d<orbm_pose_stats>(r_s)};
-    hipLaunchKernelGGL(k_pose_optimization<false>, dim3(batch), dim3(PT), 0, sc.stream(), src, pc, po);
+    hipLaunchKernelGGL(k_pose_optimization<0>, dim3(batch), dim3(PT), 0, sc.stream(), src, pc, po);
     ORBX_HIP(hipGetLastError());
     if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
     memcpy(Tout, sc.r<float>(r_t), sizeof(float) * 16 * (size_t)batch);
@@ -614,6 +676,92 @@ int pose_host(const orbx_keypoint *kps, const float *uright, const int32_t *kp_o
         if (has_mp[i]) outlier[i] = o[i];
     for (int p = 0; p < batch; ++p)
         if (ngood[p] < 0) ORBX_FAIL(ngood[p], "pose problem rejected by the kernel");
+    return ORBX_OK;
+}
+
+std::atomic<int> g_last_track_waits{0};    // host waits of the last tracking call of this process
+
+// The pose solve as the tail of a projection search (SearchChain): its inputs travel with the search's upload, the kernel is
+// enqueued behind the resolver and forms its edges from the resolver's match_kp in device memory, and its results are written
+// into the pinned result block behind the search's.
+struct PoseChain : SearchChain {
+    // set by the caller
+    FrameDeviceView fv;
+    PoseCam pc;
+    const float *Tcw = nullptr;
+    const orbm_points *pts = nullptr;
+    const uint8_t *base_has = nullptr, *base_takes = nullptr;
+    const float *base_pos = nullptr;
+    int min_matches = 0;
+    const int32_t *match_kp = nullptr;      // the search's host result (filled when collect() runs)
+    float *Tcw_out = nullptr;
+    uint8_t *outlier = nullptr;
+    orbm_pose_stats *stats = nullptr;
+    // results
+    int status = -1, ngood = 0, nmatches = 0, nmatches_map = 0;
+
+    size_t o_t = 0, o_off = 0, o_pp = 0, o_bh = 0, o_bp = 0, o_bt = 0, r_t = 0, r_g = 0, r_s = 0, r_k = 0, r_o = 0, x_g = 0;
+    void carve_inputs(Workspace &w) override
+    {
+        const size_t n = fv.n ? (size_t)fv.n : 1, m = pts->n ? (size_t)pts->n : 1;
+        o_t = w.carve(sizeof(float) * 16); o_off = w.carve(2 * sizeof(int32_t)); o_pp = w.carve(sizeof(float) * 3 * m);
+        o_bh = w.carve(base_has ? n : 1); o_bp = w.carve(base_has ? sizeof(float) * 3 * n : 1); o_bt = w.carve(base_has && base_takes ? n : 1);
+    }
+    void fill_inputs(Workspace &w) override
+    {
+        const int32_t off[2] = {0, fv.n};
+        memcpy(w.h<char>(o_t), Tcw, sizeof(float) * 16);
+        memcpy(w.h<char>(o_off), off, sizeof(off));
+        if (pts->n) memcpy(w.h<char>(o_pp), pts->pos, sizeof(float) * 3 * (size_t)pts->n);
+        if (base_has && fv.n) {
+            memcpy(w.h<char>(o_bh), base_has, (size_t)fv.n);
+            memcpy(w.h<char>(o_bp), base_pos, sizeof(float) * 3 * (size_t)fv.n);
+            if (base_takes) memcpy(w.h<char>(o_bt), base_takes, (size_t)fv.n);
+        }
+    }
+    void carve_results(Workspace &w) override
+    {
+        r_t = w.carve(sizeof(float) * 16); r_g = w.carve(sizeof(int32_t)); r_s = w.carve(sizeof(orbm_pose_stats));
+        r_k = w.carve(4 * sizeof(int32_t)); r_o = w.carve(fv.n ? (size_t)fv.n : 1);
+        x_g = w.carve(sizeof(float4) * (size_t)(fv.n ? fv.n : 1));      // device scratch (behind the results: never read back)
+    }
+    template <typename T> static T *res(const Ctx &c, size_t off) { return reinterpret_cast<T *>(c.w->pin + (off - c.o_res)); }
+    int launch(const Ctx &c) override
+    {
+        const Workspace &w = *c.w;
+        PoseSrc src = {nullptr, nullptr, fv.kp, fv.perm, nullptr, nullptr, w.d<int>(o_off), w.d<float>(o_t),
+                       c.match_kp, w.d<float>(o_pp), c.qtakes, base_has ? w.d<uint8_t>(o_bh) : nullptr, w.d<float>(o_bp),
+                       base_has && base_takes ? w.d<uint8_t>(o_bt) : nullptr, w.d<float4>(x_g), c.flags, c.nq, c.gen, c.check_overflow ? 1 : 0,
+                       c.check_converged ? 1 : 0, min_matches};
+        // (the results go straight into the pinned block, as the parallel resolver's do: posted writes, no copy behind the kernel)
+        PoseOut po = {res<float>(c, r_t), res<uint8_t>(c, r_o), res<int32_t>(c, r_g), res<orbm_pose_stats>(c, r_s), res<int32_t>(c, r_k)};
+        hipLaunchKernelGGL(k_pose_optimization<2>, dim3(1), dim3(PT), 0, c.st, src, pc, po);
+        ORBX_HIP(hipGetLastError());
+        return ORBX_OK;
+    }
+    void collect(const Ctx &c) override
+    {
+        const int32_t *k = res<int32_t>(c, r_k);
+        status = k[0];
+        if (status != TRACK_SOLVED) return;
+        nmatches = k[1]; nmatches_map = k[2];
+        ngood = *res<int32_t>(c, r_g);
+        memcpy(Tcw_out, res<float>(c, r_t), sizeof(float) * 16);
+        if (stats) memcpy(stats, res<orbm_pose_stats>(c, r_s), sizeof(orbm_pose_stats));
+        const uint8_t *o = res<uint8_t>(c, r_o);
+        for (int j = 0; j < fv.n; ++j)
+            if (match_kp[j] >= 0 || (base_has && base_has[j])) outlier[j] = o[j];
+    }
+};
+
+// what both tracking calls check before anything is launched
+int track_prepare(const orbm_frame *cur, const orbm_view *view, const orbm_pose_camera *cam, PoseChain &ch)
+{
+    if (make_cam(cam, ch.pc)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    frame_device_view(cur, ch.fv);
+    if (ch.fv.n > POSE_MAXN) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 8,192 keypoints in one pose problem");
+    if (ch.fv.min_octave < 0 || ch.fv.max_octave >= cam->nlevels || ch.fv.max_octave >= view->nlevels)
+        ORBX_FAIL(ORBX_ERR_ARG, "keypoint octave outside the view's or the pose camera's levels");
     return ORBX_OK;
 }
 
@@ -653,7 +801,7 @@ int orbm_frame_pose_optimization(const orbm_frame *frame, const uint8_t *has_mp,
     if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
     PoseSrc src = {nullptr, nullptr, fv.kp, fv.perm, sc.d<uint8_t>(o_h), sc.d<float>(o_p), sc.d<int>(o_o), sc.d<float>(o_t)};
     PoseOut po = {sc.d<float>(r_t), sc.d<uint8_t>(r_o), sc.d<int32_t>(r_g), sc.d<orbm_pose_stats>(r_s)};
-    hipLaunchKernelGGL(k_pose_optimization<true>, dim3(1), dim3(PT), 0, sc.stream(), src, pc, po);
+    hipLaunchKernelGGL(k_pose_optimization<1>, dim3(1), dim3(PT), 0, sc.stream(), src, pc, po);
     ORBX_HIP(hipGetLastError());
     if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
     memcpy(Tcw_out, sc.r<float>(r_t), sizeof(float) * 16);
@@ -677,7 +825,7 @@ int orbm_pose_optimization_batch(const orbx_keypoint *kps_un, const float *urigh
         ORBX_NEED_DEVICE();
         PoseSrc src = {kps_un, uright, nullptr, nullptr, has_mp, mp_pos, kp_off, Tcw_in};
         PoseOut po = {Tcw_out, outlier, ngood, stats};
-        hipLaunchKernelGGL(k_pose_optimization<false>, dim3(batch), dim3(PT), 0, (hipStream_t)stream, src, pc, po);
+        hipLaunchKernelGGL(k_pose_optimization<0>, dim3(batch), dim3(PT), 0, (hipStream_t)stream, src, pc, po);
         ORBX_HIP(hipGetLastError());
         return ORBX_OK;
     }
@@ -692,4 +840,82 @@ int orbm_pose_optimization_batch(const orbx_keypoint *kps_un, const float *urigh
     if (check_octaves_host(kps_un, has_mp, total, cam->nlevels)) ORBX_FAIL(ORBX_ERR_ARG, "keypoint octave outside mvInvLevelSigma2");
     ORBX_NEED_DEVICE();
     return pose_host(kps_un, uright, kp_off, batch, has_mp, mp_pos, pc, Tcw_in, Tcw_out, outlier, ngood, stats);
+}
+
+int orbm_debug_last_track_waits(void) { return g_last_track_waits.load(std::memory_order_relaxed); }
+
+int orbm_track_with_motion_model(const orbm_frame *cur, const orbm_view *view, const orbm_pose_camera *cam, const float *Tcw, const float *Tlw,
+                                 const orbm_points *last, float th, int mono, int th_high, int check_orientation, int min_matches,
+                                 int32_t *match_kp, int32_t *match_q, uint8_t *outlier, float *Tcw_out, orbm_track_result *result,
+                                 orbm_pose_stats *stats)
+{
+    if (!cur || !view || !cam || !Tcw || !Tlw || !last || !Tcw_out || !result) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    ORBX_NEED_DEVICE();
+    PoseChain ch;
+    const int rc0 = track_prepare(cur, view, cam, ch);
+    if (rc0 != ORBX_OK) return rc0;
+    if (ch.fv.n && (!match_kp || !outlier)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    memset(result, 0, sizeof(*result));
+    memcpy(Tcw_out, Tcw, sizeof(float) * 16);
+    if (stats) memset(stats, 0, sizeof(*stats));
+    ch.Tcw = Tcw; ch.pts = last; ch.min_matches = min_matches; ch.match_kp = match_kp; ch.Tcw_out = Tcw_out; ch.outlier = outlier;
+    ch.stats = stats;
+    int nm = 0;
+    for (int pass = 1; pass <= 2; ++pass) {     // Tracking.cc:1242-1249: th, then 2 * th from scratch
+        ch.status = -1;
+        const int rc = search_by_projection_last_chain(cur, view, Tcw, Tlw, last, nullptr, pass == 1 ? th : 2 * th, mono, th_high,
+                                                       check_orientation, match_kp, match_q, &nm, nullptr, &ch);
+        g_last_track_waits.store(ch.waits, std::memory_order_relaxed);
+        if (rc != ORBX_OK) return rc;
+        result->search_used = pass; result->nsearch = nm;
+        if (nm >= min_matches) break;
+    }
+    if (nm < min_matches) return ORBX_OK;       // :1251-1252
+    result->tracked = 1;
+    if (!ch.launched) return ORBX_OK;           // nothing was searched (no point, no keypoint in the grid): no edge, the pose stands
+    if (ch.status != TRACK_SOLVED) ORBX_FAIL(ch.status == TRACK_REJECTED ? ORBX_ERR_ARG : ORBX_ERR_HIP, "the chained pose solve did not run");
+    result->ngood = ch.ngood; result->nmatches = ch.nmatches; result->nmatches_map = ch.nmatches_map;
+    return ORBX_OK;
+}
+
+int orbm_track_local_map(const orbm_frame *cur, const orbm_view *view, const orbm_pose_camera *cam, const float *Tcw, const orbm_points *points,
+                         const uint8_t *base_has, const float *base_pos, const uint8_t *base_takes, float th, float viewing_cos_limit,
+                         int th_high, float nnratio, int32_t *match_kp, int32_t *match_q, orbm_projected_point *projected_out,
+                         uint8_t *outlier, float *Tcw_out, orbm_track_result *result, orbm_pose_stats *stats)
+{
+    if (!cur || !view || !cam || !Tcw || !points || !Tcw_out || !result || (base_has && !base_pos)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    ORBX_NEED_DEVICE();
+    PoseChain ch;
+    const int rc0 = track_prepare(cur, view, cam, ch);
+    if (rc0 != ORBX_OK) return rc0;
+    const int n = ch.fv.n;
+    if (n && (!match_kp || !outlier)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    memset(result, 0, sizeof(*result));
+    memcpy(Tcw_out, Tcw, sizeof(float) * 16);
+    if (stats) memset(stats, 0, sizeof(*stats));
+    std::vector<uint8_t> occ((size_t)(n ? n : 1), 0);       // ORBmatcher.cc:87-89: the slot holds an observed point
+    for (int j = 0; j < n && base_has; ++j) occ[j] = base_has[j] && (!base_takes || base_takes[j]);
+    ch.Tcw = Tcw; ch.pts = points; ch.min_matches = INT32_MIN; ch.match_kp = match_kp; ch.Tcw_out = Tcw_out; ch.outlier = outlier;
+    ch.stats = stats; ch.base_has = base_has; ch.base_pos = base_pos; ch.base_takes = base_takes;
+    int nm = 0;
+    const int rc = search_by_projection_points_chain(cur, view, Tcw, points, base_has ? occ.data() : nullptr, th, viewing_cos_limit, th_high,
+                                                     nnratio, match_kp, match_q, &nm, projected_out, nullptr, &ch);
+    g_last_track_waits.store(ch.waits, std::memory_order_relaxed);
+    if (rc != ORBX_OK) return rc;
+    result->search_used = 1; result->nsearch = nm; result->tracked = 1;
+    if (ch.launched) {
+        if (ch.status != TRACK_SOLVED) ORBX_FAIL(ch.status == TRACK_REJECTED ? ORBX_ERR_ARG : ORBX_ERR_HIP, "the chained pose solve did not run");
+        result->ngood = ch.ngood; result->nmatches = ch.nmatches; result->nmatches_map = ch.nmatches_map;
+        return ORBX_OK;
+    }
+    // nothing was searched (an empty point list, no keypoint inside the grid): the solve over the slots the frame holds already
+    if (!n || !base_has) return ORBX_OK;
+    int ngood = 0;
+    const int rcp = orbm_frame_pose_optimization(cur, base_has, base_pos, cam, Tcw, Tcw_out, outlier, &ngood, stats);
+    g_last_track_waits.store(ch.waits + 1, std::memory_order_relaxed);
+    if (rcp != ORBX_OK) return rcp;
+    result->ngood = ngood;
+    for (int j = 0; j < n; ++j)
+        if (base_has[j] && !outlier[j]) { result->nmatches++; result->nmatches_map += !base_takes || base_takes[j]; }
+    return ORBX_OK;
 }

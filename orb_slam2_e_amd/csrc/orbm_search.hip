@@ -419,8 +419,11 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
                                                        const float *__restrict__ qangle, const float *__restrict__ kangle,
                                                        const int *__restrict__ perm, int check, int *__restrict__ match_q,
                                                        int *__restrict__ match_kp, int n, const int *__restrict__ flags, int gen,
-                                                       int *__restrict__ host_q, int *__restrict__ host_kp, int *__restrict__ host_nm)
+                                                       int *__restrict__ host_q, int *__restrict__ host_kp, int *__restrict__ host_nm,
+                                                       int *__restrict__ dev_nm)
 {
+    // dev_nm: the device copy of the count ([0]) and of the "fixed point reached" word ([2]) for work chained behind this kernel
+    // (SearchChain), which must not wait for the host to read them; flags[1] of the same block is only read here.
     // host_*: the call's result block in PINNED HOST memory.  The kernel's last phase writes the results there itself (posted
     // writes over PCIe, each element once): a device-to-host copy behind the kernel cost the call its 5 us plus ~9 us of
     // hand-over between the compute queue and the copy engine.  match_q / match_kp stay the device-side working copies.
@@ -554,10 +557,10 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
     }
     if (tid == 0) host_nm[1] = flags[1];      // "a list outgrew its region" as k_win_wave left it
     if (!done) {            // chains longer than RES_MAXIT: the host repeats the call on the sequential kernel
-        if (tid == 0) host_nm[2] = 0;
+        if (tid == 0) { host_nm[2] = 0; dev_nm[2] = 0; }
         return;
     }
-    if (tid == 0) { host_nm[2] = gen; host_nm[3] = it + 1; }   // reached the fixed point (+ the number of iterations it took)
+    if (tid == 0) { host_nm[2] = gen; host_nm[3] = it + 1; dev_nm[2] = gen; }   // reached the fixed point (+ the number of iterations it took)
     // ---- tail: match_kp = the LAST accepted query of a slot (:125), the rotation histogram, ComputeThreeMaxima, rejection
     int *s_a = f_nxt;       // (f_nxt holds this iteration's claims = f_cur's content: no longer needed)
     for (int j = tid; j < ns; j += RES_T) s_a[j] = -1;
@@ -618,7 +621,7 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
     }
     __syncthreads();
     for (int j = tid; j < n; j += RES_T) host_kp[j] = match_kp[j];
-    if (tid == 0) host_nm[0] = s_nm - removed;
+    if (tid == 0) { host_nm[0] = s_nm - removed; dev_nm[0] = s_nm - removed; }
 }
 
 // SearchForInitialization's loop (ORBmatcher.cc:626-696) as a parallel fixed point.  What couples its queries is
@@ -1703,8 +1706,10 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
                    int nq, FrameSrc &fs, int n, const uint8_t *occupied, int has_uright, int th, float nnratio, int accept_mode, int check,
                    int32_t *match_kp, int32_t *match_q, int *nmatches, WinQuery *queries_out = nullptr, const int32_t *cand_off = nullptr,
                    const int32_t *cand_beg = nullptr, const int32_t *cand_idx = nullptr, int ncand = 0,
-                   const int32_t *seg = nullptr, int nseg = 0, const orbm_frame *qframe = nullptr, const int32_t *qsrc = nullptr)
+                   const int32_t *seg = nullptr, int nseg = 0, const orbm_frame *qframe = nullptr, const int32_t *qsrc = nullptr,
+                   SearchChain *chain = nullptr)
 {
+    // chain (the projection family on a resident frame, one segment): work appended behind the resolver, in front of the wait
     // qframe / qsrc (explicit candidate lists only): query i = the feature at sorted position qsrc[i] of the resident frame qframe;
     // qdesc and qangle are not read
     const int ns = fs.ns();
@@ -1718,6 +1723,7 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
     const size_t lds = sizeof(int) * (3 * (size_t)ns + (mode == 1 ? nq : 0)) + 16;
     if (lds > 160 * 1024) ORBX_FAIL(ORBX_ERR_CAPACITY, "resolver state exceeds LDS");
     if (mode != 0) { seg = nullptr; nseg = 0; }
+    if (chain && (mode != 0 || seg || !prefix)) ORBX_FAIL(ORBX_ERR_ARG, "a chain follows a whole-function projection search only");
 
     WorkspaceLease lease;
     Workspace &w = *lease.w;
@@ -1754,6 +1760,7 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
                      o_off = w.carve(sizeof(int) * (nq + 1)),
                      o_cbeg = w.carve(sizeof(int) * (size_t)nq), o_cand = w.carve(sizeof(int) * (size_t)(ncand ? ncand : 1)),
                      o_seg = w.carve(sizeof(int) * (size_t)(nseg + 1));
+        if (chain) chain->carve_inputs(w);
         const size_t staged = w.used;
         if (prefix) prefix->carve(w);              // read by the prefix kernel where they are staged: not part of the upload
         const size_t pin_in = w.used;
@@ -1765,6 +1772,8 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
                      o_state = w.carve(sizeof(int) * (size_t)std::max(std::max(ns, nq), 1));
         const size_t o_res = w.used;
         const size_t o_mq = w.carve(sizeof(int) * nq), o_mk = w.carve(sizeof(int) * (size_t)(n ? n : 1)), o_nm = w.carve(4 * sizeof(int));
+        const size_t search_res_bytes = w.used - o_res;
+        if (chain) chain->carve_results(w);
         const size_t total_bytes = w.used, res_bytes = total_bytes - o_res;
         // optional outputs that are not part of the result block travel through the tail of the pinned arena
         const size_t tq_bytes = queries_out ? (sizeof(WinQuery) * nq + 255) & ~(size_t)255 : 0;
@@ -1790,6 +1799,7 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
         }
         if (seg) memcpy(w.h<char>(o_seg), seg, sizeof(int) * (size_t)(nseg + 1));
         if (prefix) prefix->fill(w);
+        if (chain) { chain->fill_inputs(w); chain->launched = false; }
         const bool fused_upload = prefix && orbx::stage_ok(w.dev, w.pin, staged);
         if (!fused_upload) ORBX_HIP(orbx::stage_in(w.dev, w.pin, staged, st));
         // ONE fill for everything that needs a preset (a launch each was 3-4 us of a 0.1-ms call): match_kp = -1 (slot untouched);
@@ -1811,6 +1821,7 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
         if (tp_bytes) ORBX_HIP(hipMemcpyAsync(tp_pin, w.d<char>(prefix->o_proj), sizeof(orbm_projected_point) * (size_t)nq, hipMemcpyDeviceToHost, st));
         if (ns == 0) {      // nothing to search: the prefix's outputs are the whole result
             ORBX_HIP(hipStreamSynchronize(st));
+            if (chain) chain->waits++;
             if (tq_bytes) memcpy(queries_out, tq_pin, sizeof(WinQuery) * nq);
             if (tp_bytes) memcpy(prefix->proj_host, tp_pin, sizeof(orbm_projected_point) * (size_t)nq);
             return ORBX_OK;
@@ -1842,6 +1853,7 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
                 int total = 0;
                 ORBX_HIP(hipMemcpyAsync(&total, dnm + 1, sizeof(int), hipMemcpyDeviceToHost, st));
                 ORBX_HIP(hipStreamSynchronize(st));
+                if (chain) chain->waits++;
                 ent_need = (size_t)total;
                 if (w.reserve_entries(ent_need)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
             }
@@ -1859,7 +1871,7 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
             hipLaunchKernelGGL(k_resolve_par, dim3(1), dim3(RES_T), sizeof(int) * 4 * (size_t)ns, st, (const unsigned *)w.ent, (const unsigned *)dtop, lbeg, lend,
                                nq, ns, (const uint8_t *)w.d<uint8_t>(o_tk), th, nnratio, accept_mode, (const float *)w.d<float>(o_qang),
                                fv.angle, fv.perm, check, w.d<int>(o_mq), w.d<int>(o_mk), n, (const int *)dnm, gen,
-                               reinterpret_cast<int *>(w.pin + (o_mq - o_res)), reinterpret_cast<int *>(w.pin + (o_mk - o_res)), reinterpret_cast<int *>(w.pin + (o_nm - o_res)));
+                               reinterpret_cast<int *>(w.pin + (o_mq - o_res)), reinterpret_cast<int *>(w.pin + (o_mk - o_res)), reinterpret_cast<int *>(w.pin + (o_nm - o_res)), dnm);
         } else if (mode == 0) {
             hipLaunchKernelGGL(k_resolve<0>, gr, dim3(64), lds, st, (const unsigned *)w.ent, (const unsigned *)dtop, lbeg, lend, nq, ns,
                                (const uint8_t *)w.d<uint8_t>(o_tk), th, nnratio, accept_mode, w.d<int>(o_acc), w.d<int>(o_state), dnm, dseg);
@@ -1874,8 +1886,15 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
                                w.d<int>(o_mq), w.d<int>(o_mk), dnm);
         }
         ORBX_HIP(hipGetLastError());
-        if (sequential) ORBX_HIP(orbx::stage_out(w.pin, w.dev + o_res, res_bytes, st));   // (k_resolve_par wrote the block itself)
+        if (sequential) ORBX_HIP(orbx::stage_out(w.pin, w.dev + o_res, search_res_bytes, st));   // (k_resolve_par wrote the block itself)
+        const SearchChain::Ctx cx = {&w, st, w.d<int>(o_mk), dnm, w.d<uint8_t>(o_tk), n, nq, gen, windows && !exact, !sequential, o_res};
+        if (chain) {        // its kernel reads the flags the host reads below, and leaves if this attempt does not stand
+            const int rc = chain->launch(cx);
+            if (rc != ORBX_OK) return rc;
+            chain->launched = true;
+        }
         ORBX_HIP(hipStreamSynchronize(st));
+        if (chain) chain->waits++;
         int flag = 0;
         memcpy(&flag, w.pin + (o_nm - o_res) + sizeof(int), sizeof(int));
         if (windows && !exact && flag == gen) { // a window list outgrew its region: once more on the exact path
@@ -1895,6 +1914,7 @@ int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, cons
         if (tq_bytes) memcpy(queries_out, tq_pin, sizeof(WinQuery) * nq);
         if (tp_bytes) memcpy(prefix->proj_host, tp_pin, sizeof(orbm_projected_point) * (size_t)nq);
         if (seg && sequential) *nmatches += 1;   // the segments added their counts to the preset -1
+        if (chain) chain->collect(cx);
         break;
     }
     return ORBX_OK;
@@ -2621,6 +2641,17 @@ int orbm_search_by_projection_points(const orbm_frame *cur, const orbm_view *vie
                                      const uint8_t *occupied, float th, float viewing_cos_limit, int th_high, float nnratio, int32_t *match_kp,
                                      int32_t *match_q, int *nmatches, orbm_projected_point *projected_out, orbm_window_query *queries_out)
 {
+    return search_by_projection_points_chain(cur, view, Tcw, points, occupied, th, viewing_cos_limit, th_high, nnratio, match_kp, match_q,
+                                             nmatches, projected_out, queries_out, nullptr);
+}
+
+} // extern "C"
+
+int orbm_detail::search_by_projection_points_chain(const orbm_frame *cur, const orbm_view *view, const float *Tcw, const orbm_points *points,
+                                                   const uint8_t *occupied, float th, float viewing_cos_limit, int th_high, float nnratio,
+                                                   int32_t *match_kp, int32_t *match_q, int *nmatches, orbm_projected_point *projected_out,
+                                                   orbm_window_query *queries_out, SearchChain *chain)
+{
     if (!cur || bad_view(view) || !Tcw || bad_points(points, true, true, false, view->nlevels) || !nmatches || (points->n && !match_q) ||
         (cur->n && !match_kp))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
@@ -2638,12 +2669,14 @@ int orbm_search_by_projection_points(const orbm_frame *cur, const orbm_view *vie
     if (projected_out) for (int i = 0; i < points->n; ++i) projected_out[i] = {0.f, 0.f, 0.f, 0.f, 0.f, -1, 0};
     FrameSrc fs(cur);
     return run_sequential(0, nullptr, &px, points->desc, nullptr, points->takes, points->n, fs, cur->n, occupied, cur->has_uright, th_high,
-                          nnratio, ACCEPT_RATIO_SAME_LEVEL, 0, match_kp, match_q, nmatches, reinterpret_cast<WinQuery *>(queries_out));
+                          nnratio, ACCEPT_RATIO_SAME_LEVEL, 0, match_kp, match_q, nmatches, reinterpret_cast<WinQuery *>(queries_out),
+                          nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, chain);
 }
 
-int orbm_search_by_projection_last(const orbm_frame *cur, const orbm_view *view, const float *Tcw, const float *Tlw, const orbm_points *last,
-                                   const uint8_t *occupied, float th, int mono, int th_high, int check_orientation, int32_t *match_kp,
-                                   int32_t *match_q, int *nmatches, orbm_window_query *queries_out)
+int orbm_detail::search_by_projection_last_chain(const orbm_frame *cur, const orbm_view *view, const float *Tcw, const float *Tlw,
+                                                 const orbm_points *last, const uint8_t *occupied, float th, int mono, int th_high,
+                                                 int check_orientation, int32_t *match_kp, int32_t *match_q, int *nmatches,
+                                                 orbm_window_query *queries_out, SearchChain *chain)
 {
     if (!cur || bad_view(view) || !Tcw || !Tlw || bad_points(last, false, false, true, view->nlevels) || !nmatches ||
         (last->n && !match_q) || (cur->n && !match_kp) || (check_orientation && last->n && !last->angle))
@@ -2661,7 +2694,18 @@ int orbm_search_by_projection_last(const orbm_frame *cur, const orbm_view *view,
     px.cam.backward = -tlc[2] > view->mb && !mono;
     FrameSrc fs(cur);
     return run_sequential(0, nullptr, &px, last->desc, last->angle, last->takes, last->n, fs, cur->n, occupied, cur->has_uright, th_high, 0.f,
-                          ACCEPT_BEST, check_orientation, match_kp, match_q, nmatches, reinterpret_cast<WinQuery *>(queries_out));
+                          ACCEPT_BEST, check_orientation, match_kp, match_q, nmatches, reinterpret_cast<WinQuery *>(queries_out),
+                          nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, chain);
+}
+
+extern "C" {
+
+int orbm_search_by_projection_last(const orbm_frame *cur, const orbm_view *view, const float *Tcw, const float *Tlw, const orbm_points *last,
+                                   const uint8_t *occupied, float th, int mono, int th_high, int check_orientation, int32_t *match_kp,
+                                   int32_t *match_q, int *nmatches, orbm_window_query *queries_out)
+{
+    return search_by_projection_last_chain(cur, view, Tcw, Tlw, last, occupied, th, mono, th_high, check_orientation, match_kp, match_q,
+                                           nmatches, queries_out, nullptr);
 }
 
 int orbm_search_by_projection_keyframe(const orbm_frame *cur, const orbm_view *view, const float *Tcw, const orbm_points *kf,

@@ -479,6 +479,49 @@ class ORBmatcher:
         out = (mk[:frame.n], mq[:pts.n], nm.value)
         return out + (q[:pts.n],) if want_queries else out
 
+    # ---------------------------------------------------------------- a frame tracked in one call
+    def TrackWithMotionModel(self, cur, view, cam, inv_level_sigma2, Tcw, Tlw, last, th, bMono, min_matches=20, outlier_fill=0):
+        """Tracking::TrackWithMotionModel (Tracking.cc:1232-1284, behind UpdateLastFrame) in one call (orbm_track_with_motion_model):
+        SearchByProjection(Cur, Last, th, bMono), again with 2 * th below min_matches, PoseOptimization from Tcw over the matches
+        and the counts of the discard loop.  cam = (fx, fy, cx, cy, mbf), inv_level_sigma2 = mvInvLevelSigma2 (the pose solve's);
+        Tcw = the predicted pose.  outlier_fill presets the outlier array (written only where match_kp >= 0).
+        Returns (TrackResult, match_kp, match_q, outlier, Tcw_out float32[4, 4], PoseStats)."""
+        from .pose import PoseStats, _camera
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16); Tl = np.ascontiguousarray(Tlw, np.float32).reshape(16)
+        mk = np.zeros(max(cur.n, 1), np.int32); mq = np.zeros(max(last.n, 1), np.int32)
+        out = np.full(max(cur.n, 1), outlier_fill, np.uint8); Tout = np.zeros(16, np.float32)
+        res = TrackResult(); st = PoseStats(); c = _camera(cam, inv_level_sigma2)
+        check(self._L.orbm_track_with_motion_model(cur._h, C.byref(view.c), C.byref(c), _p(T), _p(Tl), C.byref(last.c), th, int(bool(bMono)),
+                                                   self.TH_HIGH, int(self.mbCheckOrientation), int(min_matches), _p(mk), _p(mq), _p(out),
+                                                   _p(Tout), C.byref(res), C.byref(st)))
+        return res, mk[:cur.n], mq[:last.n], out[:cur.n], Tout.reshape(4, 4), st
+
+    def TrackLocalMap(self, cur, view, cam, inv_level_sigma2, Tcw, points, base_has, base_pos, base_takes, th=1.0, viewing_cos_limit=0.5,
+                      outlier_fill=0):
+        """Tracking::TrackLocalMap (Tracking.cc:1294-1320, behind UpdateLocalMap) in one call (orbm_track_local_map): isInFrustum +
+        SearchByProjection(F, vpMapPoints, th), PoseOptimization over the union of the new matches and the slots the frame holds
+        (base_has[n], base_pos[n, 3], base_takes[n]; base_has None: none) and the counts of the statistics loop.
+        Returns (TrackResult, match_kp, match_q, projected[PROJ_DTYPE], outlier, Tcw_out float32[4, 4], PoseStats)."""
+        from .pose import PoseStats, _camera
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        bh = np.ascontiguousarray(base_has, np.uint8) if base_has is not None else None
+        bp = np.ascontiguousarray(base_pos, np.float32) if base_has is not None else None
+        bt = np.ascontiguousarray(base_takes, np.uint8) if base_has is not None and base_takes is not None else None
+        mk = np.zeros(max(cur.n, 1), np.int32); mq = np.zeros(max(points.n, 1), np.int32)
+        proj = np.zeros(max(points.n, 1), self.PROJ_DTYPE)
+        out = np.full(max(cur.n, 1), outlier_fill, np.uint8); Tout = np.zeros(16, np.float32)
+        res = TrackResult(); st = PoseStats(); c = _camera(cam, inv_level_sigma2)
+        opt = lambda a: _p(a) if a is not None else None
+        check(self._L.orbm_track_local_map(cur._h, C.byref(view.c), C.byref(c), _p(T), C.byref(points.c), opt(bh), opt(bp), opt(bt), th,
+                                           viewing_cos_limit, self.TH_HIGH, self.mfNNratio, _p(mk), _p(mq), _p(proj), _p(out), _p(Tout),
+                                           C.byref(res), C.byref(st)))
+        return res, mk[:cur.n], mq[:points.n], proj[:points.n], out[:cur.n], Tout.reshape(4, 4), st
+
+    @staticmethod
+    def last_track_waits():
+        """orbm_debug_last_track_waits: host waits of the last Track* call of this process (1 on the common path)."""
+        return lib().orbm_debug_last_track_waits()
+
     def SearchBySim3Whole(self, kf1, kf2, view, T1w, T2w, s12, R12, t12, points1, points2, th, want_queries=False):
         """ORBmatcher::SearchBySim3 (ORBmatcher.cc:1303-1527) in one call.  Returns (match12, nFound, vnMatch1, vnMatch2[, q12, q21])."""
         f32 = lambda a, k: np.ascontiguousarray(a, np.float32).reshape(k)
@@ -491,6 +534,12 @@ class ORBmatcher:
                                           _p(q12) if want_queries else None, _p(q21) if want_queries else None))
         out = (m12[:n1], nf.value, v1[:n1], v2[:n2])
         return out + (q12[:n1], q21[:n2]) if want_queries else out
+
+
+class TrackResult(C.Structure):
+    """orbm_track_result"""
+    _fields_ = [("tracked", C.c_int32), ("search_used", C.c_int32), ("nsearch", C.c_int32), ("ngood", C.c_int32), ("nmatches", C.c_int32),
+                ("nmatches_map", C.c_int32)]
 
 
 class _CPoints(C.Structure):
