@@ -34,6 +34,60 @@ __device__ __forceinline__ int popc256(const uint4 &a0, const uint4 &a1, const u
            __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
+// ---- the rotation-consistency check of every ORBmatcher search, one definition each for the device and the host code
+constexpr int HISTO_LENGTH = 30;   // ORBmatcher.cc:40
+
+// Bin of an angle difference angle1 - angle2 in the rotation histogram (e.g. ORBmatcher.cc:108-115, :994-1001).  Keypoint
+// angles lie in [0, 360): the result is 0 .. HISTO_LENGTH - 1 (the reference asserts it; callers that take angles from outside
+// check the range).
+__host__ __device__ __forceinline__ int rotation_bin(float rot)
+{
+    const float factor = 1.0f / HISTO_LENGTH;
+    if (rot < 0.0f) rot += 360.0f;
+    const int bin = (int)roundf(rot * factor);
+    return bin == HISTO_LENGTH ? 0 : bin;
+}
+
+// ORBmatcher::ComputeThreeMaxima (:1802-1843): keep[0..2] = the bins of the three largest counts (first wins a tie), the second
+// and third only if they reach 10 % of the largest; -1 = none.
+__host__ __device__ __forceinline__ void three_maxima(const int *hist, int *keep)
+{
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int i = 0; i < HISTO_LENGTH; i++) {
+        const int s = hist[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+        else if (s > max3) { max3 = s; ind3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
+    keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
+}
+
+// The host tail of the SearchForTriangulation entry points (src/ORBmatcher.cc:992-1025): the rotation histogram over the matches
+// (rot_of(i) = angle1 - angle2 of keypoint i's pair), ComputeThreeMaxima, rejection, and the count of what is left.
+template <typename RotOf>
+inline int triangulation_rotation_check(int32_t *match12, int n1, int check_orientation, RotOf rot_of, int *nmatches)
+{
+    if (check_orientation) {
+        int hist[HISTO_LENGTH] = {0}, keep[3];
+        std::vector<int> bin((size_t)n1, -1);
+        for (int i = 0; i < n1; ++i)
+            if (match12[i] >= 0) {
+                const int b = rotation_bin(rot_of(i));
+                if (b < 0 || b >= HISTO_LENGTH) ORBX_FAIL(ORBX_ERR_ARG, "keypoint angles outside [0, 360)");   // (the reference asserts)
+                bin[i] = b; hist[b]++;
+            }
+        three_maxima(hist, keep);
+        for (int i = 0; i < n1; ++i)
+            if (bin[i] >= 0 && bin[i] != keep[0] && bin[i] != keep[1] && bin[i] != keep[2]) match12[i] = -1;
+    }
+    int nm = 0;
+    for (int i = 0; i < n1; ++i) nm += match12[i] >= 0;
+    *nmatches = nm;
+    return ORBX_OK;
+}
+
 // Frame::AssignFeaturesToGrid / PosInGrid (src/Frame.cc:245-260,397-407), on the host: n float ops.
 inline void build_winkp(const orbx_keypoint *kps, int n, const uint8_t *skip, const float *uright, float min_x, float min_y,
                         float max_x, float max_y, std::vector<WinKp> &wk)

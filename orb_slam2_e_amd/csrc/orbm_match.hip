@@ -1054,35 +1054,8 @@ int orbm_search_for_triangulation(const orbx_keypoint *kps1, const uint8_t *desc
     const int rc = orbm_match_triangulation(kps1, desc1, n1, kps2, desc2, n2, cand_off.data(), cand.data(), has_mappoint1, has_mappoint2,
                                             stereo1, stereo2, only_stereo, F12, ex, ey, scale_factors2, level_sigma2, nlevels, match12, best.data());
     if (rc != ORBX_OK) return rc;
-    if (check_orientation) {
-        constexpr int HL = 30;     // HISTO_LENGTH, ORBmatcher.cc:40
-        int hist[HL] = {0};
-        std::vector<int> bin((size_t)n1, -1);
-        const float factor = 1.0f / HL;
-        for (int i = 0; i < n1; ++i)
-            if (match12[i] >= 0) {
-                float rot = kps1[i].angle - kps2[match12[i]].angle;     // :994-1001
-                if (rot < 0.0f) rot += 360.0f;
-                int b = (int)roundf(rot * factor);
-                if (b == HL) b = 0;
-                bin[i] = b; hist[b]++;
-            }
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;      // ComputeThreeMaxima, :1802-1843
-        for (int i = 0; i < HL; i++) {
-            const int sz = hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-            else if (sz > max3) { max3 = sz; ind3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-        for (int i = 0; i < n1; ++i)
-            if (bin[i] >= 0 && bin[i] != ind1 && bin[i] != ind2 && bin[i] != ind3) match12[i] = -1;
-    }
-    int nm = 0;
-    for (int i = 0; i < n1; ++i) nm += match12[i] >= 0;
-    *nmatches = nm;
-    return ORBX_OK;
+    return triangulation_rotation_check(match12, n1, check_orientation,
+                                        [&](int i) { return kps1[i].angle - kps2[match12[i]].angle; }, nmatches);     // :994
 }
 
 int orbm_hamming_matrix(const uint8_t *A, int nA, const uint8_t *B, int nB, uint16_t *out)

@@ -13,19 +13,21 @@
 //   2. k_win_wave (count, then fill; one wave per query) builds every query's candidate list
 //      with its Hamming distances, k_topk keeps each list's 8 best sorted -- the expensive
 //      part, fully parallel;
-//   3. k_resolve walks the queries in order, 64 at a time: every lane selects best / second
-//      for its query against the committed state; a lane whose best or second candidate
-//      is claimed by an earlier lane of the same batch is a conflict; lanes below the
-//      first conflict commit, the rest select again.  A lane's selection can only change
-//      when an earlier query claims its best or second candidate, so the committed
-//      results are the sequential loop's results;
+//   3. the resolver commits the queries' choices in the loop's order: as a parallel fixed point (k_resolve_par,
+//      k_resolve_init_par, rotation check fused), or, when that does not settle, k_resolve: it walks the queries in order, 64 at
+//      a time: every lane selects best / second for its query against the committed state; a lane whose best or second
+//      candidate is claimed by an earlier lane of the same batch is a conflict; lanes below the first conflict commit, the
+//      rest select again.  A lane's selection can only change when an earlier query claims its best or second candidate, so
+//      the committed results are the sequential loop's results.  The decisions are written once and shared by all four
+//      resolvers: load_top, select_two (short list, d7 shortcut, whole-list scan), accepts_projection / accepts_initialization;
+//      for_each_query walks a fixed-point thread's queries; rotation_bin and three_maxima (orbm_internal.h) are the check's;
 //      Queries whose candidate sets cannot meet are independent of each other: the BoW searches hand
 //      k_resolve one SEGMENT per vocabulary node (a feature belongs to one node, ORBmatcher.cc:384-456),
 //      one workgroup per segment, so the nodes resolve side by side instead of one after the other;
 //   4. k_rotation builds the 30-bin rotation histogram, ORBmatcher::ComputeThreeMaxima
 //      (:1802-1843) and rejects the matches outside the three main bins.
-// The host never waits in the middle of a call: the entry buffer is sized from a running estimate and the
-// real total comes back with the results (a call that outgrew it is repeated once with the right size).
+// The host never waits in the middle of a call (run_sequential over a SeqSearch: seq_layout, seq_stage, seq_lists, seq_resolve,
+// seq_collect): the entry buffer is sized per query and the flags that ask for a repeat come back with the results.
 #include <limits.h>
 #include <stdint.h>
 
@@ -44,7 +46,6 @@ using namespace orbm_detail;
 namespace {
 
 constexpr int SEQ_MAXN = 8192;     // keypoints per frame the resolver's LDS state holds
-constexpr int HISTO_LENGTH = 30;   // ORBmatcher.cc:40
 enum { ACCEPT_BEST = 0, ACCEPT_RATIO_SAME_LEVEL = 1, ACCEPT_RATIO = 2 };
 
 
@@ -246,13 +247,109 @@ __global__ __launch_bounds__(MT) void k_scan_counts(const int *__restrict__ cnt,
     for (int i = lo; i < hi; ++i) { off[i] = r; r += cnt[i]; }
 }
 
+// ---- The decisions every resolver shares, each written once.
+// A list entry is dist << 20 | octave << 16 | sorted position; 0xffffffff = none.
+__device__ __forceinline__ int entry_slot(unsigned en) { return (int)(en & 0xffffu); }
+__device__ __forceinline__ int entry_level(unsigned en) { return (int)((en >> 16) & 15); }
+__device__ __forceinline__ int entry_dist(unsigned en) { return (int)(en >> 20); }
+
+// Query i's short list (the TOPK best entries of its candidate list, sorted) as two 16-byte loads.
+__device__ __forceinline__ void load_top(const unsigned *__restrict__ top, int i, unsigned (&tp)[TOPK])
+{
+    const uint4 t0 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i], t1 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i + 1];
+    tp[0] = t0.x; tp[1] = t0.y; tp[2] = t0.z; tp[3] = t0.w; tp[4] = t1.x; tp[5] = t1.y; tp[6] = t1.z; tp[7] = t1.w;
+}
+
+// The acceptance rule of the projection family and the BoW searches: bestDist <= th, then the ratio test of the form --
+// ACCEPT_RATIO_SAME_LEVEL: rejected if best and second sit on the same level and best > ratio * second (:121);
+// ACCEPT_RATIO: accepted only if best < ratio * second (:431, :801).  Without a second candidate bestDist2 keeps its
+// initial 256 (:79-81).
+__device__ __forceinline__ bool accepts_projection(int accept_mode, int best, int second, bool has_second, int l1, int l2, float nnratio, int th)
+{
+    bool acc = best <= th;
+    const int sec = has_second ? second : 256;
+    if (accept_mode == ACCEPT_RATIO_SAME_LEVEL && has_second && l1 == l2 && (float)best > nnratio * (float)sec) acc = false;
+    if (accept_mode == ACCEPT_RATIO && !((float)best < nnratio * (float)sec)) acc = false;
+    return acc;
+}
+// SearchForInitialization's (:674-676); second = INT_MAX when the best candidate is alone (:637-638).
+__device__ __forceinline__ bool accepts_initialization(int best, int second, float nnratio, int th)
+{
+    return best <= th && (float)best < (float)second * nnratio;
+}
+
+// Best and second-best eligible candidate of one query: en1 / en2 = their entries (0xffffffff: none), best / second = their
+// distances (INT_MAX: none).  state(sp) = the state of slot sp as this query sees it, open(state, dist) = "the slot is
+// eligible"; `want` = 2, or 1 where only the best matters (en2 is then none).
+//   1. The first two eligible entries of the short list, which is sorted by (distance, list position) = the reference's
+//      strict-'<' first-wins order.  EAGER: the state of all TOPK slots is read at once (one after the other, each behind the
+//      test of the one before, they are up to eight dependent LDS round trips); otherwise slot by slot, while still needed.
+//   2. The short list ran dry and the list is longer: the whole list is needed only if it can change the DECISION.  Every entry
+//      beyond the short list is at least as far as its last one, d7.  With nothing eligible so far, a best beyond d7 must
+//      still be <= th.  With one eligible entry, the second best is >= d7 (and <= 256, the reference's initial bestDist2): a best
+//      that is rejected by th anyway, or that passes its ratio test against d7 on the same level -- accepts(best, d7) --
+//      is decided whatever the second is; `second` is then d7, a lower bound, and en2 none.  Most of a late query's short
+//      list is taken by earlier matches, so this case is the common one.
+//   3. Otherwise: the two smallest keys dist << 16 | list position among the eligible entries of the whole list.
+struct TwoBest { unsigned en1, en2; int best, second; };
+template <bool EAGER, typename State, typename Open, typename Accepts>
+__device__ __forceinline__ TwoBest select_two(const unsigned (&tp)[TOPK], const unsigned *__restrict__ ent, int b, int e, int want, int th,
+                                              State state, Open open, Accepts accepts)
+{
+    TwoBest s = {0xffffffffu, 0xffffffffu, INT_MAX, INT_MAX};
+    int found = 0, st[TOPK];
+    if (EAGER) {
+#pragma unroll
+        for (int r = 0; r < TOPK; ++r) st[r] = state(tp[r] == 0xffffffffu ? 0 : entry_slot(tp[r]));
+        if (want < 2) {     // "best only" (wave-uniform): the first open entry of the sorted short list, a select chain
+            unsigned en1 = 0xffffffffu;
+#pragma unroll
+            for (int r = TOPK - 1; r >= 0; --r) en1 = (tp[r] != 0xffffffffu && open(st[r], entry_dist(tp[r]))) ? tp[r] : en1;
+            if (en1 != 0xffffffffu || e - b <= TOPK) return {en1, 0xffffffffu, en1 != 0xffffffffu ? entry_dist(en1) : INT_MAX, INT_MAX};
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < TOPK; ++r) {
+        const unsigned en = tp[r];
+        if (en != 0xffffffffu && found < 2) {
+            const int dist = entry_dist(en);
+            if (open(EAGER ? st[r] : state(entry_slot(en)), dist)) {
+                if (found == 0) { s.en1 = en; s.best = dist; } else { s.en2 = en; s.second = dist; }
+                ++found;
+            }
+        }
+    }
+    bool scan = found < want && e - b > TOPK;
+    if (scan) {
+        const int d7 = entry_dist(tp[TOPK - 1]);
+        if (found == 0) scan = d7 <= th;
+        else if (s.best > th || accepts(s.best, d7)) { scan = false; s.second = d7; }
+    }
+    if (scan) {
+        unsigned k1 = 0xffffffffu, k2 = 0xffffffffu;
+        for (int k = b; k < e; ++k) {
+            const unsigned en = ent[k];
+            if (en != 0xffffffffu && open(state(entry_slot(en)), entry_dist(en))) {
+                const unsigned key = ((en >> 20) << 16) | (unsigned)(k - b);
+                const unsigned hi = max(k1, key);
+                k2 = min(k2, hi);
+                k1 = min(k1, key);
+            }
+        }
+        s = {0xffffffffu, 0xffffffffu, INT_MAX, INT_MAX};
+        if (k1 != 0xffffffffu) { s.en1 = ent[b + (k1 & 0xffffu)]; s.best = (int)(k1 >> 16); }
+        if (k2 != 0xffffffffu) { s.en2 = ent[b + (k2 & 0xffffu)]; s.second = (int)(k2 >> 16); }
+    }
+    if (want < 2) s.en2 = 0xffffffffu;
+    return s;
+}
+
 // The sequential loop, 64 queries per batch (see the file header).  MODE 0 = projection
 // family / BoW: state = blocked[sp] ("the slot holds a point later queries must skip"),
 // match_kp[sp] = last query assigned to the slot.  MODE 1 = SearchForInitialization:
 // state = vMatchedDistance[sp], vnMatches21[sp], vnMatches12[i].
-// A lane selects the first two eligible entries of its query's TOPK list (sorted by
-// distance, then list position = the reference's strict-'<' first-wins order); only when
-// fewer than it needs remain there and the list is longer does it scan the whole list.
+// A lane selects with select_two: a slot is open while it is not blocked (MODE 0) / while
+// its recorded distance is above the query's (MODE 1).
 // Conflicts go through a claim table: every accepted lane whose match blocks its slot
 // claims it with its lane number (minimum wins); a lane whose best or second slot is
 // claimed by a lower lane has to select again after that lane has committed.
@@ -281,84 +378,45 @@ __global__ __launch_bounds__(64) void k_resolve(const unsigned *__restrict__ ent
     // a batch's inputs are fetched while the previous batch is resolved (they do not depend on the state): without
     // this every batch starts with a ~1.5 us round trip to L2 / HBM
     int nb_ = 0, ne_ = 0, ntk = 1;
-    uint4 nt0 = make_uint4(~0u, ~0u, ~0u, ~0u), nt1 = nt0;
+    unsigned ntp[TOPK];
     auto fetch = [&](int i) {
-        nb_ = ne_ = 0; ntk = 1; nt0 = nt1 = make_uint4(~0u, ~0u, ~0u, ~0u);
+        nb_ = ne_ = 0; ntk = 1;
+#pragma unroll
+        for (int k = 0; k < TOPK; ++k) ntp[k] = 0xffffffffu;
         if (i < nq) {
             nb_ = lbeg[i]; ne_ = lend[i];
-            nt0 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i]; nt1 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i + 1];
+            load_top(top, i, ntp);
             if (MODE == 0) ntk = takes[i];
         }
     };
     fetch(q_begin + lane);
+    const int *s_elig = MODE == 0 ? s_b : s_a;    // what decides whether a slot is open to a query
     for (int i0 = q_begin; i0 < nq; i0 += 64) {
         const int i = i0 + lane;
         const bool in = i < nq;
         const int b = nb_, e = ne_;
-        const uint4 t0 = nt0, t1 = nt1;
-        const unsigned tp[TOPK] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+        unsigned tp[TOPK];
+#pragma unroll
+        for (int k = 0; k < TOPK; ++k) tp[k] = ntp[k];
         const int tk = ntk;
         fetch(i + 64);
         unsigned long long pending = __ballot(in);
         bool dirty = true;
-        int sp1 = -1, sp2 = -1, best = INT_MAX, second = INT_MAX, l1 = -1, l2 = -1;
+        TwoBest sel = {0xffffffffu, 0xffffffffu, INT_MAX, INT_MAX};
         while (pending) {
             const bool mine = (pending >> lane) & 1ull;
-            if (mine && dirty) {
-                sp1 = sp2 = -1; best = second = INT_MAX; l1 = l2 = -1;
-                int found = 0;
-                // the state of all TOPK short-list slots is read at once (one after the other, each behind the test of the one
-                // before, they were up to eight dependent LDS round trips per pass on a workgroup of ONE wave)
-                int st[TOPK];
-#pragma unroll
-                for (int r = 0; r < TOPK; ++r) st[r] = MODE == 0 ? s_b[tp[r] == 0xffffffffu ? 0 : (tp[r] & 0xffffu)] : s_a[tp[r] == 0xffffffffu ? 0 : (tp[r] & 0xffffu)];
-#pragma unroll
-                for (int r = 0; r < TOPK; ++r) {
-                    const unsigned en = tp[r];
-                    if (en != 0xffffffffu && found < 2) {
-                        const int sp = en & 0xffffu, dist = (int)(en >> 20);
-                        if (MODE == 0 ? st[r] == 0 : st[r] > dist) {
-                            if (found == 0) { sp1 = sp; best = dist; l1 = (en >> 16) & 15; }
-                            else { sp2 = sp; second = dist; l2 = (en >> 16) & 15; }
-                            ++found;
-                        }
-                    }
-                }
-                bool scan = found < (need2 ? 2 : 1) && e - b > TOPK;   // the short list ran dry: the whole list ...
-                if (scan) {    // ... unless it cannot change the decision (see k_resolve_init_par / k_resolve_par)
-                    const int d7 = (int)(tp[TOPK - 1] >> 20);
-                    const bool passes = MODE == 1 ? (float)best < (float)d7 * nnratio
-                                                  : (accept_mode == ACCEPT_RATIO ? (float)best < nnratio * (float)d7 : !((float)best > nnratio * (float)d7));
-                    if (found == 0) scan = d7 <= th;
-                    else if (best > th || passes) { scan = false; second = d7; sp2 = -1; l2 = -2; }
-                }
-                if (scan) {
-                    unsigned k1 = 0xffffffffu, k2 = 0xffffffffu;
-                    for (int k = b; k < e; ++k) {
-                        const unsigned en = ent[k];
-                        const int sp = en & 0xffffu, dist = (int)(en >> 20);
-                        if (en != 0xffffffffu && (MODE == 0 ? s_b[sp] == 0 : s_a[sp] > dist)) {
-                            const unsigned key = ((unsigned)dist << 16) | (unsigned)(k - b);
-                            const unsigned hi = max(k1, key);
-                            k2 = min(k2, hi);
-                            k1 = min(k1, key);
-                        }
-                    }
-                    sp1 = sp2 = -1; best = second = INT_MAX; l1 = l2 = -1;
-                    if (k1 != 0xffffffffu) { const unsigned en = ent[b + (k1 & 0xffffu)]; sp1 = en & 0xffffu; l1 = (en >> 16) & 15; best = (int)(k1 >> 16); }
-                    if (k2 != 0xffffffffu) { const unsigned en = ent[b + (k2 & 0xffffu)]; sp2 = en & 0xffffu; l2 = (en >> 16) & 15; second = (int)(k2 >> 16); }
-                }
-                if (!need2) sp2 = -1;
-            }
-            bool acc = mine && sp1 >= 0 && best <= th;
-            if (MODE == 0) {
-                // initial bestDist2 = 256 when there is no second candidate (:79-81)
-                const int sec = sp2 >= 0 ? second : 256;
-                if (accept_mode == ACCEPT_RATIO_SAME_LEVEL && l1 == l2 && (float)best > nnratio * (float)sec) acc = false; // :121
-                if (accept_mode == ACCEPT_RATIO && !((float)best < nnratio * (float)sec)) acc = false;                    // :431, :801
-            } else {
-                acc = acc && (float)best < (float)second * nnratio; // INT_MAX when alone (:637-638,674-676)
-            }
+            if (mine && dirty)
+                sel = select_two<true>(tp, ent, b, e, need2 ? 2 : 1, th, [&](int sp) { return s_elig[sp]; },
+                                       [&](int st, int dist) { return MODE == 0 ? st == 0 : st > dist; },
+                                       [&](int best, int d) {
+                                           return MODE == 1 ? accepts_initialization(best, d, nnratio, th)
+                                                            : accepts_projection(accept_mode, best, d, true, 0, 0, nnratio, th);
+                                       });
+            const int sp1 = sel.en1 != 0xffffffffu ? entry_slot(sel.en1) : -1, sp2 = sel.en2 != 0xffffffffu ? entry_slot(sel.en2) : -1;
+            const int best = sel.best;
+            const bool acc = mine && sp1 >= 0 &&
+                             (MODE == 1 ? accepts_initialization(best, sel.second, nnratio, th)
+                                        : accepts_projection(accept_mode, best, sel.second, sp2 >= 0, entry_level(sel.en1), entry_level(sel.en2), nnratio, th));
             // claims of this pass
             const bool claims = acc && tk;
             if (claims) atomicMin(&s_claim[sp1], lane);
@@ -413,6 +471,17 @@ __global__ __launch_bounds__(64) void k_resolve(const unsigned *__restrict__ ent
 // If the claims still change after RES_MAXIT iterations the kernel says so (*converged = 0) and the host repeats the call on
 // k_resolve: the result never depends on how the chains fall.
 constexpr int RES_T = 1024, RES_QREG = 2, RES_MAXIT = 48;
+// The queries of thread tid of a fixed-point kernel: tid, tid + RES_T, ...  The first RES_QREG of them have a register slot r (their
+// short lists, bounds, angles and selections stay in registers from phase to phase); the others (r = -1) go through global
+// memory.  f(i, r) is inlined with r a constant, so `r >= 0 ? regs[r] : global[i]` in it costs nothing.
+template <typename F>
+__device__ __forceinline__ void for_each_query(int tid, int nq, F f)
+{
+#pragma unroll
+    for (int r = 0; r < RES_QREG; ++r)
+        if (tid + r * RES_T < nq) f(tid + r * RES_T, r);
+    for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) f(i, -1);
+}
 __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restrict__ ent, const unsigned *__restrict__ top,
                                                        const int *__restrict__ lbeg, const int *__restrict__ lend, int nq, int ns,
                                                        const uint8_t *__restrict__ takes, int th, float nnratio, int accept_mode,
@@ -446,78 +515,21 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
         br[r] = er[r] = 0; tkr[r] = 1; qar[r] = 0.f;
 #pragma unroll
         for (int k = 0; k < TOPK; ++k) tpr[r][k] = 0xffffffffu;
-        if (i < nq) {
-            const uint4 t0 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i], t1 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i + 1];
-            tpr[r][0] = t0.x; tpr[r][1] = t0.y; tpr[r][2] = t0.z; tpr[r][3] = t0.w;
-            tpr[r][4] = t1.x; tpr[r][5] = t1.y; tpr[r][6] = t1.z; tpr[r][7] = t1.w;
-            br[r] = lbeg[i]; er[r] = lend[i]; tkr[r] = takes[i]; qar[r] = qangle[i];
-        }
+        if (i < nq) { load_top(top, i, tpr[r]); br[r] = lbeg[i]; er[r] = lend[i]; tkr[r] = takes[i]; qar[r] = qangle[i]; }
     }
     for (int j = tid; j < ns; j += RES_T) { f_cur[j] = INT_MAX; f_nxt[j] = INT_MAX; s_perm[j] = perm[j]; s_kang[j] = kangle[j]; }
     for (int j = tid; j < n; j += RES_T) match_kp[j] = -1;
     for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) match_q[i] = -2;   // queries beyond the registers keep their last selection here
     if (tid == 0) { s_changed = 0; s_nm = 0; removed = 0; }
     if (tid < HISTO_LENGTH) hist[tid] = 0;
-    // query i's accepted candidate against `first` (or -1): the selection of k_resolve<0>, eligibility = first[sp] >= i
+    // query i's accepted candidate against `first` (or -1): the selection of k_resolve<0>, a slot is open while first[sp] >= i
     auto select = [&](int i, const unsigned (&tp)[TOPK], int b, int e, const int *first) -> int {
-        int sp1 = -1, sp2 = -1, best = INT_MAX, second = INT_MAX, l1 = -1, l2 = -1, found = 0;
-        int st[TOPK];
-#pragma unroll
-        for (int r = 0; r < TOPK; ++r) st[r] = first[tp[r] == 0xffffffffu ? 0 : (tp[r] & 0xffffu)];
-        if (!need2) {       // "best only" (wave-uniform): the first eligible entry of the sorted short list, a select chain
-            unsigned en1 = 0xffffffffu;
-#pragma unroll
-            for (int r = TOPK - 1; r >= 0; --r) en1 = (tp[r] != 0xffffffffu && st[r] >= i) ? tp[r] : en1;
-            if (en1 != 0xffffffffu || e - b <= TOPK) return en1 != 0xffffffffu && (int)(en1 >> 20) <= th ? (int)(en1 & 0xffffu) : -1;
-        }
-#pragma unroll
-        for (int r = 0; r < TOPK; ++r) {
-            const unsigned en = tp[r];
-            if (en != 0xffffffffu && found < 2 && st[r] >= i) {
-                const int sp = en & 0xffffu, dist = (int)(en >> 20);
-                if (found == 0) { sp1 = sp; best = dist; l1 = (en >> 16) & 15; }
-                else { sp2 = sp; second = dist; l2 = (en >> 16) & 15; }
-                ++found;
-            }
-        }
-        // the short list ran dry: the whole list -- unless it cannot change the decision (every entry beyond the short list is at
-        // least as far as its last one, d7: nothing eligible so far and d7 > th rejects; one eligible entry that passes its ratio
-        // test against d7, a lower bound of the second best (256 at most, the reference's initial bestDist2), passes)
-        bool scan = found < (need2 ? 2 : 1) && e - b > TOPK;
-        if (scan) {
-            const int d7 = (int)(tp[TOPK - 1] >> 20);
-            if (found == 0) scan = d7 <= th;
-            else if (best > th || (accept_mode == ACCEPT_RATIO ? (float)best < nnratio * (float)d7 : !((float)best > nnratio * (float)d7))) {
-                scan = false; sp2 = -1; second = d7; l2 = -2;     // (l2 = -2: never equal to l1, and the bound passes the same-level test anyway)
-            }
-        }
-        if (scan) {
-            unsigned k1 = 0xffffffffu, k2 = 0xffffffffu;
-            for (int k = b; k < e; ++k) {
-                const unsigned en = ent[k];
-                if (en != 0xffffffffu && first[en & 0xffffu] >= i) {
-                    const unsigned key = ((en >> 20) << 16) | (unsigned)(k - b);
-                    const unsigned hi = max(k1, key);
-                    k2 = min(k2, hi);
-                    k1 = min(k1, key);
-                }
-            }
-            sp1 = sp2 = -1; best = second = INT_MAX; l1 = l2 = -1;
-            if (k1 != 0xffffffffu) { const unsigned en = ent[b + (k1 & 0xffffu)]; sp1 = en & 0xffffu; l1 = (en >> 16) & 15; best = (int)(k1 >> 16); }
-            if (k2 != 0xffffffffu) { const unsigned en = ent[b + (k2 & 0xffffu)]; sp2 = en & 0xffffu; l2 = (en >> 16) & 15; second = (int)(k2 >> 16); }
-        }
-        if (!need2) sp2 = -1;
-        bool acc = sp1 >= 0 && best <= th;
-        const int sec = sp2 >= 0 ? second : 256;     // initial bestDist2 = 256 when there is no second candidate (:79-81)
-        if (accept_mode == ACCEPT_RATIO_SAME_LEVEL && l1 == l2 && (float)best > nnratio * (float)sec) acc = false; // :121
-        if (accept_mode == ACCEPT_RATIO && !((float)best < nnratio * (float)sec)) acc = false;                    // :431, :801
-        return acc ? sp1 : -1;
-    };
-    auto select_global = [&](int i, const int *first) -> int {
-        unsigned tp[TOPK];
-        const uint4 t0 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i], t1 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i + 1];
-        tp[0] = t0.x; tp[1] = t0.y; tp[2] = t0.z; tp[3] = t0.w; tp[4] = t1.x; tp[5] = t1.y; tp[6] = t1.z; tp[7] = t1.w;
-        return select(i, tp, lbeg[i], lend[i], first);
+        const TwoBest s = select_two<true>(tp, ent, b, e, need2 ? 2 : 1, th, [&](int sp) { return first[sp]; },
+                                           [&](int st, int) { return st >= i; },
+                                           [&](int best, int d) { return accepts_projection(accept_mode, best, d, true, 0, 0, nnratio, th); });
+        const bool acc = s.en1 != 0xffffffffu && accepts_projection(accept_mode, s.best, s.second, s.en2 != 0xffffffffu, entry_level(s.en1),
+                                                                    entry_level(s.en2), nnratio, th);
+        return acc ? entry_slot(s.en1) : -1;
     };
     __syncthreads();
     int selr[RES_QREG];
@@ -527,24 +539,16 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
     int it = 0;
     for (; it < RES_MAXIT; ++it) {
         bool changed = false;
-#pragma unroll
-        for (int r = 0; r < RES_QREG; ++r) {
-            const int i = tid + r * RES_T;
-            if (i < nq) {
-                const int sel = select(i, tpr[r], br[r], er[r], f_cur);
-                const int claim = sel >= 0 && tkr[r] ? sel : -1, was = selr[r] >= 0 && tkr[r] ? selr[r] : -1;
-                changed |= claim != was || (selr[r] == -2);
-                selr[r] = sel;
-                if (claim >= 0) atomicMin(&f_nxt[claim], i);
-            }
-        }
-        for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) {
-            const int sel = select_global(i, f_cur), prev = match_q[i], tk = takes[i];
+        for_each_query(tid, nq, [&](int i, int r) __attribute__((always_inline)) {
+            unsigned tpg[TOPK];
+            if (r < 0) load_top(top, i, tpg);
+            const int sel = r >= 0 ? select(i, tpr[r], br[r], er[r], f_cur) : select(i, tpg, lbeg[i], lend[i], f_cur);
+            const int prev = r >= 0 ? selr[r] : match_q[i], tk = r >= 0 ? tkr[r] : (int)takes[i];
             const int claim = sel >= 0 && tk ? sel : -1, was = prev >= 0 && tk ? prev : -1;
             changed |= claim != was || prev == -2;
-            match_q[i] = sel;
+            if (r >= 0) selr[r] = sel; else match_q[i] = sel;
             if (claim >= 0) atomicMin(&f_nxt[claim], i);
-        }
+        });
         if (changed) s_changed = 1;
         __syncthreads();
         done = s_changed == 0;
@@ -565,60 +569,33 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
     int *s_a = f_nxt;       // (f_nxt holds this iteration's claims = f_cur's content: no longer needed)
     for (int j = tid; j < ns; j += RES_T) s_a[j] = -1;
     __syncthreads();
-    const float factor = 1.0f / HISTO_LENGTH;
-    auto bin_of = [&](float qa, int sp) {
-        float rot = qa - s_kang[sp];
-        if (rot < 0.0f) rot += 360.0f;
-        const int bin = (int)roundf(rot * factor);
-        return bin == HISTO_LENGTH ? 0 : bin;
-    };
-    int binr[RES_QREG], nacc = 0;
+    auto bin_of = [&](float qa, int sp) { return rotation_bin(qa - s_kang[sp]); };
+    int binr[RES_QREG], nacc = 0;     // (the register queries keep their bin for the rejection pass)
 #pragma unroll
-    for (int r = 0; r < RES_QREG; ++r) {
-        const int i = tid + r * RES_T;
-        binr[r] = -1;
-        if (i < nq && selr[r] >= 0) {
-            atomicMax(&s_a[selr[r]], i);
-            ++nacc;
-            if (check) { binr[r] = bin_of(qar[r], selr[r]); atomicAdd(&hist[binr[r]], 1); }
+    for (int r = 0; r < RES_QREG; ++r) binr[r] = -1;
+    for_each_query(tid, nq, [&](int i, int r) __attribute__((always_inline)) {
+        const int sel = r >= 0 ? selr[r] : match_q[i];
+        if (sel < 0) return;
+        atomicMax(&s_a[sel], i);
+        ++nacc;
+        if (check) {
+            const int bin = bin_of(r >= 0 ? qar[r] : qangle[i], sel);
+            if (r >= 0) binr[r] = bin;
+            atomicAdd(&hist[bin], 1);
         }
-    }
-    for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) {
-        const int sel = match_q[i];
-        if (sel >= 0) {
-            atomicMax(&s_a[sel], i);
-            ++nacc;
-            if (check) atomicAdd(&hist[bin_of(qangle[i], sel)], 1);
-        }
-    }
+    });
     if (nacc) atomicAdd(&s_nm, nacc);
     __syncthreads();
-    if (tid == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            const int sz = hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-            else if (sz > max3) { max3 = sz; ind3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-        keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-    }
+    if (tid == 0) three_maxima(hist, keep);
     for (int j = tid; j < ns; j += RES_T)
         if (s_a[j] >= 0) match_kp[s_perm[j]] = s_a[j];        // (the other slots keep their preset -1)
     __syncthreads();
-    auto finish = [&](int i, int sp, int bin) {
+    for_each_query(tid, nq, [&](int i, int r) __attribute__((always_inline)) {
+        const int sp = r >= 0 ? selr[r] : match_q[i];
+        const int bin = r >= 0 ? binr[r] : (check && sp >= 0 ? bin_of(qangle[i], sp) : -1);
         if (check && sp >= 0 && bin != keep[0] && bin != keep[1] && bin != keep[2]) { match_kp[s_perm[sp]] = -2; atomicAdd(&removed, 1); }
         host_q[i] = sp >= 0 ? s_perm[sp] : -1;
-    };
-#pragma unroll
-    for (int r = 0; r < RES_QREG; ++r)
-        if (tid + r * RES_T < nq) finish(tid + r * RES_T, selr[r], binr[r]);
-    for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) {
-        const int sp = match_q[i];
-        finish(i, sp, check && sp >= 0 ? bin_of(qangle[i], sp) : -1);
-    }
+    });
     __syncthreads();
     for (int j = tid; j < n; j += RES_T) host_kp[j] = match_kp[j];
     if (tid == 0) { host_nm[0] = s_nm - removed; dev_nm[0] = s_nm - removed; }
@@ -657,12 +634,7 @@ __global__ __launch_bounds__(RES_T) void k_resolve_init_par(const unsigned *__re
         br[r] = er[r] = 0; qar[r] = 0.f;
 #pragma unroll
         for (int k = 0; k < TOPK; ++k) tpr[r][k] = 0xffffffffu;
-        if (i < nq) {
-            const uint4 t0 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i], t1 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i + 1];
-            tpr[r][0] = t0.x; tpr[r][1] = t0.y; tpr[r][2] = t0.z; tpr[r][3] = t0.w;
-            tpr[r][4] = t1.x; tpr[r][5] = t1.y; tpr[r][6] = t1.z; tpr[r][7] = t1.w;
-            br[r] = lbeg[i]; er[r] = lend[i]; qar[r] = qangle[i];
-        }
+        if (i < nq) { load_top(top, i, tpr[r]); br[r] = lbeg[i]; er[r] = lend[i]; qar[r] = qangle[i]; }
     }
     for (int j = tid; j < ns; j += RES_T) { s_cnt[j] = 0; s_perm[j] = perm[j]; s_kang[j] = kangle[j]; }
     for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) sel_g[i] = 0xfffffffeu;   // queries beyond the registers keep their selection here
@@ -680,52 +652,10 @@ __global__ __launch_bounds__(RES_T) void k_resolve_init_par(const unsigned *__re
     };
     // query i's accepted entry (dist << 20 | octave << 16 | sp) or 0xffffffff: the selection of k_resolve<1>
     auto select = [&](int i, const unsigned (&tp)[TOPK], int b, int e) -> unsigned {
-        unsigned en1 = 0xffffffffu;
-        int best = INT_MAX, second = INT_MAX, found = 0;
-#pragma unroll
-        for (int r = 0; r < TOPK; ++r) {
-            const unsigned en = tp[r];
-            if (en != 0xffffffffu && found < 2) {
-                const int dist = (int)(en >> 20);
-                if (matched_before((int)(en & 0xffffu), i) > dist) {
-                    if (found == 0) { en1 = en; best = dist; } else second = dist;
-                    ++found;
-                }
-            }
-        }
-        // The short list ran dry -- but the rest of the list (every entry's key is above the short list's last) is needed only if it
-        // can change the DECISION: with no eligible entry so far, a best beyond the last short-list distance d7 must still be <= th;
-        // with one, the second best is >= d7, so best < d7 * ratio already passes the ratio test (:674-676) whatever it is.  Most of a
-        // late query's short list is taken by earlier matches at small distances (:645-646), so this case is the common one.
-        bool scan = found < 2 && e - b > TOPK;
-        if (scan) {
-            const int d7 = (int)(tp[TOPK - 1] >> 20);
-            if (found == 0) scan = d7 <= th;
-            else if (best > th || (float)best < (float)d7 * nnratio) { scan = false; second = d7; }
-        }
-        if (scan) {
-            unsigned k1 = 0xffffffffu, k2 = 0xffffffffu;
-            for (int k = b; k < e; ++k) {
-                const unsigned en = ent[k];
-                if (en != 0xffffffffu && matched_before((int)(en & 0xffffu), i) > (int)(en >> 20)) {
-                    const unsigned key = ((en >> 20) << 16) | (unsigned)(k - b);
-                    const unsigned hi = max(k1, key);
-                    k2 = min(k2, hi);
-                    k1 = min(k1, key);
-                }
-            }
-            en1 = 0xffffffffu; best = second = INT_MAX;
-            if (k1 != 0xffffffffu) { en1 = ent[b + (k1 & 0xffffu)]; best = (int)(k1 >> 16); }
-            if (k2 != 0xffffffffu) second = (int)(k2 >> 16);
-        }
-        const bool acc = en1 != 0xffffffffu && best <= th && (float)best < (float)second * nnratio;   // INT_MAX when alone (:637-638, :674-676)
-        return acc ? en1 : 0xffffffffu;
-    };
-    auto select_global = [&](int i) -> unsigned {
-        unsigned tp[TOPK];
-        const uint4 t0 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i], t1 = reinterpret_cast<const uint4 *>(top)[2 * (size_t)i + 1];
-        tp[0] = t0.x; tp[1] = t0.y; tp[2] = t0.z; tp[3] = t0.w; tp[4] = t1.x; tp[5] = t1.y; tp[6] = t1.z; tp[7] = t1.w;
-        return select(i, tp, lbeg[i], lend[i]);
+        const TwoBest s = select_two<false>(tp, ent, b, e, 2, th, [&](int sp) { return matched_before(sp, i); },
+                                            [&](int st, int dist) { return st > dist; },
+                                            [&](int best, int d) { return accepts_initialization(best, d, nnratio, th); });
+        return s.en1 != 0xffffffffu && accepts_initialization(s.best, s.second, nnratio, th) ? s.en1 : 0xffffffffu;
     };
     auto claim = [&](int i, unsigned en) {
         if (en == 0xffffffffu) return;
@@ -740,20 +670,13 @@ __global__ __launch_bounds__(RES_T) void k_resolve_init_par(const unsigned *__re
     int it = 0;
     for (; it < RES_MAXIT; ++it) {
         bool changed = false;
-#pragma unroll
-        for (int r = 0; r < RES_QREG; ++r) {
-            const int i = tid + r * RES_T;
-            if (i < nq) {
-                const unsigned en = select(i, tpr[r], br[r], er[r]);
-                changed |= en != selr[r];
-                selr[r] = en;
-            }
-        }
-        for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) {
-            const unsigned en = select_global(i);
-            changed |= en != sel_g[i];
-            sel_g[i] = en;
-        }
+        for_each_query(tid, nq, [&](int i, int r) __attribute__((always_inline)) {
+            unsigned tpg[TOPK];
+            if (r < 0) load_top(top, i, tpg);
+            const unsigned en = r >= 0 ? select(i, tpr[r], br[r], er[r]) : select(i, tpg, lbeg[i], lend[i]);
+            changed |= en != (r >= 0 ? selr[r] : sel_g[i]);
+            if (r >= 0) selr[r] = en; else sel_g[i] = en;
+        });
         if (changed) s_changed = 1;
         __syncthreads();
         done = s_changed == 0;
@@ -762,10 +685,7 @@ __global__ __launch_bounds__(RES_T) void k_resolve_init_par(const unsigned *__re
         if (tid == 0) s_changed = 0;
         for (int j = tid; j < ns; j += RES_T) s_cnt[j] = 0;
         __syncthreads();
-#pragma unroll
-        for (int r = 0; r < RES_QREG; ++r)
-            if (tid + r * RES_T < nq) claim(tid + r * RES_T, selr[r]);
-        for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) claim(i, sel_g[i]);
+        for_each_query(tid, nq, [&](int i, int r) __attribute__((always_inline)) { claim(i, r >= 0 ? selr[r] : sel_g[i]); });
         __syncthreads();
         if (s_over) break;
     }
@@ -779,66 +699,36 @@ __global__ __launch_bounds__(RES_T) void k_resolve_init_par(const unsigned *__re
     int *s_last = s_cnt;
     for (int j = tid; j < ns; j += RES_T) s_last[j] = -1;
     __syncthreads();
-    const float factor = 1.0f / HISTO_LENGTH;
-    auto bin_of = [&](float qa, int sp) {
-        float rot = qa - s_kang[sp];
-        if (rot < 0.0f) rot += 360.0f;
-        const int bin = (int)roundf(rot * factor);
-        return bin == HISTO_LENGTH ? 0 : bin;
-    };
+    auto bin_of = [&](float qa, int sp) { return rotation_bin(qa - s_kang[sp]); };
     int binr[RES_QREG];
 #pragma unroll
-    for (int r = 0; r < RES_QREG; ++r) {
-        const int i = tid + r * RES_T;
-        binr[r] = -1;
-        if (i < nq && selr[r] != 0xffffffffu) {
-            const int sp = (int)(selr[r] & 0xffffu);
-            atomicMax(&s_last[sp], i);
-            if (check) { binr[r] = bin_of(qar[r], sp); atomicAdd(&hist[binr[r]], 1); }
+    for (int r = 0; r < RES_QREG; ++r) binr[r] = -1;
+    for_each_query(tid, nq, [&](int i, int r) __attribute__((always_inline)) {
+        const unsigned en = r >= 0 ? selr[r] : sel_g[i];
+        if (en == 0xffffffffu) return;
+        atomicMax(&s_last[entry_slot(en)], i);
+        if (check) {
+            const int bin = bin_of(r >= 0 ? qar[r] : qangle[i], entry_slot(en));
+            if (r >= 0) binr[r] = bin;
+            atomicAdd(&hist[bin], 1);
         }
-    }
-    for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) {
-        const unsigned en = sel_g[i];
-        if (en != 0xffffffffu) {
-            atomicMax(&s_last[(int)(en & 0xffffu)], i);
-            if (check) atomicAdd(&hist[bin_of(qangle[i], (int)(en & 0xffffu))], 1);
-        }
-    }
+    });
     __syncthreads();
-    if (tid == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            const int sz = hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-            else if (sz > max3) { max3 = sz; ind3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-        keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-    }
+    if (tid == 0) three_maxima(hist, keep);
     int nst = 0;
     for (int j = tid; j < ns; j += RES_T) nst += s_last[j] >= 0;     // nmatches before the rotation check = slots that hold a match
     if (nst) atomicAdd(&s_nm, nst);
     __syncthreads();
-    auto finish = [&](int i, unsigned en, int bin) {
+    for_each_query(tid, nq, [&](int i, int r) __attribute__((always_inline)) {
+        const unsigned en = r >= 0 ? selr[r] : sel_g[i];
         int out = -1;
-        if (en != 0xffffffffu) {
-            const int sp = (int)(en & 0xffffu);
-            if (s_last[sp] == i) {      // still standing
-                out = s_perm[sp];
-                if (check && bin != keep[0] && bin != keep[1] && bin != keep[2]) { out = -1; atomicAdd(&removed, 1); }
-            }
+        if (en != 0xffffffffu && s_last[entry_slot(en)] == i) {      // still standing
+            const int bin = r >= 0 ? binr[r] : (check ? bin_of(qangle[i], entry_slot(en)) : -1);
+            out = s_perm[entry_slot(en)];
+            if (check && bin != keep[0] && bin != keep[1] && bin != keep[2]) { out = -1; atomicAdd(&removed, 1); }
         }
         host_q[i] = out;
-    };
-#pragma unroll
-    for (int r = 0; r < RES_QREG; ++r)
-        if (tid + r * RES_T < nq) finish(tid + r * RES_T, selr[r], binr[r]);
-    for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) {
-        const unsigned en = sel_g[i];
-        finish(i, en, check && en != 0xffffffffu ? bin_of(qangle[i], (int)(en & 0xffffu)) : -1);
-    }
+    });
     __syncthreads();
     if (tid == 0) host_nm[0] = s_nm - removed;
 }
@@ -1107,13 +997,7 @@ __global__ __launch_bounds__(MT) void k_rotation(const int *__restrict__ acc_sp,
     if (tid < HISTO_LENGTH) hist[tid] = 0;
     if (tid == 0) removed = 0;
     __syncthreads();
-    const float factor = 1.0f / HISTO_LENGTH;
-    auto bin_of = [&](int i, int sp) {
-        float rot = qangle[i] - kangle[sp];
-        if (rot < 0.0f) rot += 360.0f;
-        int bin = (int)roundf(rot * factor);
-        return bin == HISTO_LENGTH ? 0 : bin;
-    };
+    auto bin_of = [&](int i, int sp) { return rotation_bin(qangle[i] - kangle[sp]); };
     // the first RPT * MT queries keep (candidate, bin) in registers between the two passes: one dependent gather chain
     // instead of two (the kernel is one block of pure latency)
     constexpr int RPT = 12;
@@ -1134,18 +1018,7 @@ __global__ __launch_bounds__(MT) void k_rotation(const int *__restrict__ acc_sp,
             if (sp >= 0) atomicAdd(&hist[bin_of(i, sp)], 1);
         }
     __syncthreads();
-    if (tid == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            const int s = hist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-        keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-    }
+    if (tid == 0) three_maxima(hist, keep);
     if (MODE == 0) for (int j = tid; j < ns; j += MT) match_kp[perm[j]] = state[j];
     __syncthreads();
     auto finish = [&](int i, int sp, int bin) {
@@ -1698,223 +1571,316 @@ struct PointsPrefix {
     }
 };
 
-// Shared driver.  mode 0: projection family / BoW lists; mode 1: SearchForInitialization.
-// Inputs are staged in the workspace's pinned arena and uploaded with one copy; results
-// come back with one copy.  Everything runs on the workspace's stream.  The window queries come from the host (`queries`)
-// or from `prefix` on the device (then queries_out, if given, receives them).
-int run_sequential(int mode, const WinQuery *queries, PointsPrefix *prefix, const uint8_t *qdesc, const float *qangle, const uint8_t *qtakes,
-                   int nq, FrameSrc &fs, int n, const uint8_t *occupied, int has_uright, int th, float nnratio, int accept_mode, int check,
-                   int32_t *match_kp, int32_t *match_q, int *nmatches, WinQuery *queries_out = nullptr, const int32_t *cand_off = nullptr,
-                   const int32_t *cand_beg = nullptr, const int32_t *cand_idx = nullptr, int ncand = 0,
-                   const int32_t *seg = nullptr, int nseg = 0, const orbm_frame *qframe = nullptr, const int32_t *qsrc = nullptr,
-                   SearchChain *chain = nullptr)
+// ---- The shared driver of the whole-loop searches.  One search as it takes it; a caller sets the fields it uses by name.
+struct SeqSearch {
+    // The candidates come from ONE of: windows from the host (`queries`), windows made on the device by `prefix` (queries_out, if
+    // given, receives them), or explicit candidate lists (BoW-node members).
+    const WinQuery *queries = nullptr;
+    PointsPrefix *prefix = nullptr;
+    struct Lists {      // query i's candidates are idx[beg[i] .. beg[i] + off[i + 1] - off[i]): the queries of a node share one copy
+        const int32_t *off = nullptr, *beg = nullptr, *idx = nullptr, *seg = nullptr;
+        int n = 0, nseg = 0;    // entries of idx; optional segments: queries [seg[s], seg[s + 1]) share no candidate with the others
+    } lists;
+    // The queries' descriptors and angles come from ONE of: host arrays (angle = nullptr: all 0), or (candidate lists only) a
+    // resident frame: query i is the feature at sorted position pos[i] of `frame`.
+    struct Features { const uint8_t *desc = nullptr; const float *angle = nullptr; const orbm_frame *frame = nullptr; const int32_t *pos = nullptr; } q;
+    const uint8_t *qtakes = nullptr;        // [nq] "the query's match blocks its slot" (nullptr: all do)
+    int nq = 0;
+    // the frame searched, its keypoint count, the slots that hold a point from the start (by keypoint index), the windows' stereo test
+    FrameSrc *fs = nullptr;
+    int n = 0;
+    const uint8_t *occupied = nullptr;
+    int has_uright = 0;
+    // the rule.  mode 0: projection family / BoW lists; mode 1: SearchForInitialization (no accept_mode, no takes, no match_kp)
+    int mode = 0, th = 0;
+    float nnratio = 0.f;
+    int accept_mode = ACCEPT_BEST, check = 0;       // check: the rotation-consistency check
+    // the results: match_kp [n], match_q [nq], the count
+    int32_t *match_kp = nullptr, *match_q = nullptr;
+    int *nmatches = nullptr;
+    WinQuery *queries_out = nullptr;
+    SearchChain *chain = nullptr;           // work appended behind the resolver, in front of the wait (mode 0 on a prefix, one segment)
+    bool windows() const { return queries || prefix; }
+};
+
+// What the retry loop carries from attempt to attempt.
+struct SeqPlan {
+    bool exact = false;         // window lists by count, scan, fill (a strided attempt overflowed)
+    bool sized = false;         // ... whose total has been read once
+    bool sequential = false;    // k_resolve + k_rotation instead of the parallel fixed point
+    size_t ent_need = 0;        // candidate entries
+    int win_stride = 0, init_c = 0, gen = 0;
+    size_t lds = 0;             // k_resolve's state
+    bool fused_upload = false;  // the prefix kernel uploads the staged block
+    const int *lbeg = nullptr, *lend = nullptr;     // every query's list bounds in w.ent, as the list kernels leave them
+};
+
+// Workspace offsets of one attempt: the staged inputs (same offsets in the pinned and the device arena: ONE upload), the prefix's
+// inputs (read where they are staged), device-only arrays, then the result block [o_res, ...): the search's results, the chain's.
+struct SeqLayout {
+    size_t o_qh, o_a, o_qang, o_tk, o_occ, o_off, o_cbeg, o_cand, o_seg, staged;
+    size_t o_q, o_top, o_cnt, o_acc, o_lend, o_state;
+    size_t o_res, o_mq, o_mk, o_nm, search_res_bytes;
+    size_t tq_bytes, tp_bytes;      // optional outputs that are not part of the result block travel through the tail of the pinned arena
+    char *tq_pin, *tp_pin;
+    template <typename T> T *res(const Workspace &w, size_t o) const { return reinterpret_cast<T *>(w.pin + (o - o_res)); }   // a result, host side
+};
+
+int seq_check(const SeqSearch &r)
 {
-    // chain (the projection family on a resident frame, one segment): work appended behind the resolver, in front of the wait
-    // qframe / qsrc (explicit candidate lists only): query i = the feature at sorted position qsrc[i] of the resident frame qframe;
-    // qdesc and qangle are not read
-    const int ns = fs.ns();
-    if (ns > SEQ_MAXN || nq > 65536) ORBX_FAIL(ORBX_ERR_CAPACITY, "frame too large for the sequential resolver");
-    for (int j = 0; j < n && mode == 0; ++j) match_kp[j] = -1;
-    for (int i = 0; i < nq; ++i) match_q[i] = -1;
-    *nmatches = 0;
-    const bool windows = queries || prefix;
-    if (queries_out) for (int i = 0; i < nq; ++i) queries_out[i] = {0.f, 0.f, -1.f, 0.f, 0, -1};
-    if (nq == 0 || (ns == 0 && !queries_out && !(prefix && prefix->proj_host))) return ORBX_OK;
-    const size_t lds = sizeof(int) * (3 * (size_t)ns + (mode == 1 ? nq : 0)) + 16;
-    if (lds > 160 * 1024) ORBX_FAIL(ORBX_ERR_CAPACITY, "resolver state exceeds LDS");
-    if (mode != 0) { seg = nullptr; nseg = 0; }
-    if (chain && (mode != 0 || seg || !prefix)) ORBX_FAIL(ORBX_ERR_ARG, "a chain follows a whole-function projection search only");
+    if (r.fs->ns() > SEQ_MAXN || r.nq > 65536) ORBX_FAIL(ORBX_ERR_CAPACITY, "frame too large for the sequential resolver");
+    if (r.mode != 0 && r.lists.seg) ORBX_FAIL(ORBX_ERR_ARG, "SearchForInitialization does not resolve in segments");
+    if (r.chain && (r.mode != 0 || r.lists.seg || !r.prefix)) ORBX_FAIL(ORBX_ERR_ARG, "a chain follows a whole-function projection search only");
+    return ORBX_OK;
+}
+
+int seq_layout(const SeqSearch &r, Workspace &w, const SeqPlan &p, SeqLayout &L)
+{
+    const int nq = r.nq, ns = r.fs->ns(), n = r.n;
+    w.used = 0;
+    L.o_qh = w.carve(r.queries ? sizeof(WinQuery) * nq : 1);
+    L.o_a = w.carve(r.q.frame ? sizeof(int) * (size_t)nq : (size_t)32 * nq);
+    r.fs->carve(w);
+    L.o_qang = w.carve(sizeof(float) * nq); L.o_tk = w.carve(nq); L.o_occ = w.carve(r.occupied && ns ? (size_t)ns : 1);
+    L.o_off = w.carve(sizeof(int) * (nq + 1));
+    L.o_cbeg = w.carve(sizeof(int) * (size_t)nq); L.o_cand = w.carve(sizeof(int) * (size_t)(r.lists.n ? r.lists.n : 1));
+    L.o_seg = w.carve(sizeof(int) * (size_t)(r.lists.nseg + 1));
+    if (r.chain) r.chain->carve_inputs(w);
+    L.staged = w.used;
+    if (r.prefix) r.prefix->carve(w);              // read by the prefix kernel where they are staged: not part of the upload
+    const size_t pin_in = w.used;
+    if (r.prefix) r.prefix->carve_scratch(w);
+    const size_t o_qd = w.carve(r.queries ? 1 : sizeof(WinQuery) * nq);
+    L.o_q = r.queries ? L.o_qh : o_qd;
+    L.o_top = w.carve(sizeof(unsigned) * TOPK * (size_t)nq); L.o_cnt = w.carve(sizeof(int) * nq); L.o_acc = w.carve(sizeof(int) * nq);
+    L.o_lend = w.carve(sizeof(int) * nq);
+    L.o_state = w.carve(sizeof(int) * (size_t)std::max(std::max(ns, nq), 1));
+    L.o_res = w.used;
+    L.o_mq = w.carve(sizeof(int) * nq); L.o_mk = w.carve(sizeof(int) * (size_t)(n ? n : 1)); L.o_nm = w.carve(4 * sizeof(int));
+    L.search_res_bytes = w.used - L.o_res;
+    if (r.chain) r.chain->carve_results(w);
+    const size_t total_bytes = w.used, res_bytes = total_bytes - L.o_res;
+    L.tq_bytes = r.queries_out ? (sizeof(WinQuery) * nq + 255) & ~(size_t)255 : 0;
+    L.tp_bytes = r.prefix && r.prefix->frustum && r.prefix->proj_host ? (sizeof(orbm_projected_point) * (size_t)nq + 255) & ~(size_t)255 : 0;
+    if (w.reserve(total_bytes, std::max(pin_in, res_bytes) + L.tq_bytes + L.tp_bytes)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
+    L.tq_pin = w.pin + w.pin_cap - L.tq_bytes; L.tp_pin = L.tq_pin - L.tp_bytes;
+    if (w.reserve_entries(p.ent_need)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
+    return ORBX_OK;
+}
+
+// The inputs into the pinned arena, their upload (one copy, or left to the prefix kernel's launch), the presets, the prefix
+// kernel and the copies of its optional outputs.
+int seq_stage(const SeqSearch &r, Workspace &w, const SeqLayout &L, SeqPlan &p)
+{
+    const int nq = r.nq, ns = r.fs->ns();
+    hipStream_t st = w.st;
+    if (r.queries) memcpy(w.h<char>(L.o_qh), r.queries, sizeof(WinQuery) * nq);
+    if (r.q.frame) memcpy(w.h<char>(L.o_a), r.q.pos, sizeof(int) * (size_t)nq);
+    else memcpy(w.h<char>(L.o_a), r.q.desc, (size_t)32 * nq);
+    r.fs->fill(w);
+    if (!r.q.frame) {   // (from a resident frame: k_list_fill sets the angles down)
+        if (r.q.angle) memcpy(w.h<char>(L.o_qang), r.q.angle, sizeof(float) * nq); else memset(w.h<char>(L.o_qang), 0, sizeof(float) * nq);
+    }
+    if (r.qtakes) memcpy(w.h<char>(L.o_tk), r.qtakes, nq); else memset(w.h<char>(L.o_tk), 1, nq);
+    if (r.occupied && ns) r.fs->fill_occ(w.h<uint8_t>(L.o_occ), r.occupied);
+    if (r.lists.off) {
+        memcpy(w.h<char>(L.o_off), r.lists.off, sizeof(int) * (nq + 1));
+        memcpy(w.h<char>(L.o_cbeg), r.lists.beg, sizeof(int) * (size_t)nq);
+        if (r.lists.n) memcpy(w.h<char>(L.o_cand), r.lists.idx, sizeof(int) * r.lists.n);
+    }
+    if (r.lists.seg) memcpy(w.h<char>(L.o_seg), r.lists.seg, sizeof(int) * (size_t)(r.lists.nseg + 1));
+    if (r.prefix) r.prefix->fill(w);
+    if (r.chain) { r.chain->fill_inputs(w); r.chain->launched = false; }
+    p.fused_upload = r.prefix && orbx::stage_ok(w.dev, w.pin, L.staged);
+    if (!p.fused_upload) ORBX_HIP(orbx::stage_in(w.dev, w.pin, L.staged, st));
+    // ONE fill for everything that needs a preset (a launch each was 3-4 us of a 0.1-ms call): match_kp = -1 (slot untouched);
+    // segments write back touched slots of the state only, so it is preset to -1 as well (the span in between, match_q, is
+    // rewritten in full anyway); and the two counters START AT -1: the match count is overwritten (one workgroup) or added
+    // to (segments: the host adds the 1 back), the overflow flag is CLEARED to 0 by a list that does not fit
+    // (k_resolve_par writes every slot and its count itself; the two flags behind the count -- "a list outgrew its region",
+    // "the fixed point was reached" -- are raised by writing this call's generation number, so nothing needs a preset there)
+    p.gen = (int)(w.gen = (w.gen % 0x7ffffffe) + 1);
+    if (p.sequential) {
+        const size_t f0 = r.lists.seg ? L.o_state : L.o_mk;
+        ORBX_HIP(hipMemsetAsync(w.d<char>(f0), 0xff, L.o_nm + sizeof(int) - f0, st));
+    }
+    WinQuery *dq = w.d<WinQuery>(L.o_q);
+    if (r.prefix) r.prefix->launch(w, dq, st, p.fused_upload ? stage_job(w.dev, w.pin, L.staged) : StageJob{nullptr, nullptr, 0, 0});
+    if (L.tq_bytes) ORBX_HIP(hipMemcpyAsync(L.tq_pin, dq, sizeof(WinQuery) * nq, hipMemcpyDeviceToHost, st));
+    if (L.tp_bytes) ORBX_HIP(hipMemcpyAsync(L.tp_pin, w.d<char>(r.prefix->o_proj), sizeof(orbm_projected_point) * (size_t)nq, hipMemcpyDeviceToHost, st));
+    return ORBX_OK;
+}
+
+// Every query's candidate list with its distances and its short list: explicit lists, or window lists.  Window lists: their
+// lengths are known only on the device.  First attempt: every query fills its own region of win_stride entries in one pass (no
+// count, no scan, no host wait); if a list does not fit, the overflow flag comes back with the results and the call is repeated
+// on the exact path (count, scan, fill), whose total is needed to size the buffer: the one extra host wait of that (rare) path.
+int seq_lists(const SeqSearch &r, Workspace &w, const SeqLayout &L, SeqPlan &p)
+{
+    const int nq = r.nq;
+    hipStream_t st = w.st;
+    const FrameView fv = r.fs->view(w);
+    const WinQuery *dq = w.d<WinQuery>(L.o_q);
+    const uint4 *da = w.d<uint4>(L.o_a);
+    const uint8_t *docc = r.occupied ? w.d<uint8_t>(L.o_occ) : nullptr;
+    int *doff = w.d<int>(L.o_off), *dnm = w.d<int>(L.o_nm);
+    unsigned *dtop = w.d<unsigned>(L.o_top);
+    const int init_dist = r.mode == 0 ? 256 : INT_MAX;
+    const dim3 g((nq + MT / 64 - 1) / (MT / 64)); // one wave per query
+    p.lbeg = doff; p.lend = doff + 1;             // CSR lists; the strided path has its own bounds
+    if (!r.windows()) {
+        const orbm_frame *qf = r.q.frame;
+        hipLaunchKernelGGL(k_list_fill, g, dim3(MT), 0, st, qf ? (const uint4 *)qf->desc : da, nq, fv.desc, (const int *)doff,
+                           (const int *)w.d<int>(L.o_cbeg), (const int *)w.d<int>(L.o_cand), w.ent, dtop,
+                           qf ? (const int *)w.d<int>(L.o_a) : (const int *)nullptr, qf ? (const float *)qf->angle : (const float *)nullptr,
+                           w.d<float>(L.o_qang));
+    } else if (!p.exact) {
+        p.lbeg = w.d<int>(L.o_cnt); p.lend = w.d<int>(L.o_lend);
+        hipLaunchKernelGGL(k_win_wave<2>, g, dim3(MT), 0, st, dq, da, nq, fv.kp, fv.desc, fv.cell_off, docc, fv.gp, r.has_uright,
+                           init_dist, (int *)nullptr, (const int *)nullptr, w.ent, p.win_stride, w.d<int>(L.o_cnt), w.d<int>(L.o_lend), dnm + 1, dtop, p.gen);
+    } else {
+        hipLaunchKernelGGL(k_win_wave<0>, g, dim3(MT), 0, st, dq, da, nq, fv.kp, fv.desc, fv.cell_off, docc, fv.gp, r.has_uright,
+                           init_dist, w.d<int>(L.o_cnt), (const int *)nullptr, (unsigned *)nullptr, 0, (int *)nullptr, (int *)nullptr,
+                           (int *)nullptr, (unsigned *)nullptr, p.gen);
+        hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(MT), 0, st, (const int *)w.d<int>(L.o_cnt), nq, doff, dnm + 1);
+        if (!p.sized) {
+            p.sized = true;
+            int total = 0;
+            ORBX_HIP(hipMemcpyAsync(&total, dnm + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+            ORBX_HIP(hipStreamSynchronize(st));
+            if (r.chain) r.chain->waits++;
+            p.ent_need = (size_t)total;
+            if (w.reserve_entries(p.ent_need)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
+        }
+        hipLaunchKernelGGL(k_win_wave<1>, g, dim3(MT), 0, st, dq, da, nq, fv.kp, fv.desc, fv.cell_off, docc, fv.gp, r.has_uright,
+                           init_dist, (int *)nullptr, (const int *)doff, w.ent, 0, (int *)nullptr, (int *)nullptr, (int *)nullptr, dtop, p.gen);
+    }
+    return ORBX_OK;
+}
+
+// The resolver.  The projection family and the BoW lists (mode 0) resolve as a parallel fixed point with the rotation check
+// fused (k_resolve_par), SearchForInitialization (mode 1) likewise (k_resolve_init_par: its per-slot acceptor lists take
+// init_c + 3 ints of LDS per keypoint); these write the result block in pinned memory themselves.  p.sequential: the one-wave
+// sequential resolver and k_rotation, then the copy of the result block.  (The BoW searches' segments -- one per vocabulary
+// node -- only matter to the sequential resolver: the fixed point needs no partition, queries of different nodes never meet.)
+int seq_resolve(const SeqSearch &r, Workspace &w, const SeqLayout &L, const SeqPlan &p)
+{
+    const int nq = r.nq, ns = r.fs->ns();
+    hipStream_t st = w.st;
+    const FrameView fv = r.fs->view(w);
+    const unsigned *dent = w.ent, *dtop = w.d<unsigned>(L.o_top);
+    const float *dqang = w.d<float>(L.o_qang);
+    const uint8_t *dtk = w.d<uint8_t>(L.o_tk);
+    int *dnm = w.d<int>(L.o_nm);
+    if (!p.sequential && r.mode == 1) {
+        hipLaunchKernelGGL(k_resolve_init_par, dim3(1), dim3(RES_T), sizeof(int) * (size_t)(p.init_c + 3) * ns, st, dent, dtop, p.lbeg, p.lend,
+                           nq, ns, p.init_c, r.th, r.nnratio, dqang, fv.angle, fv.perm, r.check, w.d<unsigned>(L.o_acc), (const int *)dnm, p.gen,
+                           L.res<int>(w, L.o_mq), L.res<int>(w, L.o_nm));
+    } else if (!p.sequential) {
+        hipLaunchKernelGGL(k_resolve_par, dim3(1), dim3(RES_T), sizeof(int) * 4 * (size_t)ns, st, dent, dtop, p.lbeg, p.lend, nq, ns, dtk, r.th,
+                           r.nnratio, r.accept_mode, dqang, fv.angle, fv.perm, r.check, w.d<int>(L.o_mq), w.d<int>(L.o_mk), r.n, (const int *)dnm,
+                           p.gen, L.res<int>(w, L.o_mq), L.res<int>(w, L.o_mk), L.res<int>(w, L.o_nm), dnm);
+    } else {
+        const int *dseg = r.lists.seg ? w.d<int>(L.o_seg) : nullptr;
+        const dim3 gr(r.lists.seg ? r.lists.nseg : 1);
+        int *dacc = w.d<int>(L.o_acc), *dstate = w.d<int>(L.o_state);
+        if (r.mode == 0) {
+            hipLaunchKernelGGL(k_resolve<0>, gr, dim3(64), p.lds, st, dent, dtop, p.lbeg, p.lend, nq, ns, dtk, r.th, r.nnratio, r.accept_mode,
+                               dacc, dstate, dnm, dseg);
+            hipLaunchKernelGGL(k_rotation<0>, dim3(1), dim3(MT), 0, st, (const int *)dacc, (const int *)dstate, nq, ns, dqang, fv.angle,
+                               fv.perm, r.check, w.d<int>(L.o_mq), w.d<int>(L.o_mk), dnm);
+        } else {
+            hipLaunchKernelGGL(k_resolve<1>, gr, dim3(64), p.lds, st, dent, dtop, p.lbeg, p.lend, nq, ns, dtk, r.th, r.nnratio, 0,
+                               dacc, dstate, dnm, dseg);
+            hipLaunchKernelGGL(k_rotation<1>, dim3(1), dim3(MT), 0, st, (const int *)dacc, (const int *)dstate, nq, ns, dqang, fv.angle,
+                               fv.perm, r.check, w.d<int>(L.o_mq), w.d<int>(L.o_mk), dnm);
+        }
+    }
+    ORBX_HIP(hipGetLastError());
+    if (p.sequential) ORBX_HIP(orbx::stage_out(w.pin, w.dev + L.o_res, L.search_res_bytes, st));
+    return ORBX_OK;
+}
+
+// The results of the attempt that stands, from the pinned arena to the caller's arrays (searched = false: the prefix's only).
+void seq_collect(const SeqSearch &r, const Workspace &w, const SeqLayout &L, const SeqPlan &p, bool searched)
+{
+    const int nq = r.nq;
+    if (searched) {
+        memcpy(r.match_q, L.res<char>(w, L.o_mq), sizeof(int) * nq);
+        if (r.mode == 0 && r.n) memcpy(r.match_kp, L.res<char>(w, L.o_mk), sizeof(int) * r.n);
+        memcpy(r.nmatches, L.res<char>(w, L.o_nm), sizeof(int));
+        if (r.lists.seg && p.sequential) *r.nmatches += 1;   // the segments added their counts to the preset -1
+    }
+    if (L.tq_bytes) memcpy(r.queries_out, L.tq_pin, sizeof(WinQuery) * nq);
+    if (L.tp_bytes) memcpy(r.prefix->proj_host, L.tp_pin, sizeof(orbm_projected_point) * (size_t)nq);
+}
+
+// The LDS limits of the four resolvers (the largest request each can make; the fixed-point kernels also have static LDS), raised
+// once per process whichever thread calls first.  A failure stays and fails every call.
+int resolver_lds_limits()
+{
+    static const hipError_t err = [] {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (!e) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (!e) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_par), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+        if (!e) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_init_par), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+        return e;
+    }();
+    ORBX_HIP(err);
+    return ORBX_OK;
+}
+
+// Inputs are staged in the workspace's pinned arena and uploaded with one copy; results come back in one block.  Everything
+// runs on the workspace's stream, and the host waits ONCE, at the end of an attempt.  An attempt is repeated when its flags,
+// which come back with the results, say so: a window list outgrew its region (strided -> exact lists), or the fixed point did
+// not settle (parallel -> sequential resolver: the result never depends on how the dependency chains fall).
+int run_sequential(const SeqSearch &r)
+{
+    if (const int rc = seq_check(r)) return rc;
+    const int ns = r.fs->ns(), nq = r.nq;
+    for (int j = 0; j < r.n && r.mode == 0; ++j) r.match_kp[j] = -1;
+    for (int i = 0; i < nq; ++i) r.match_q[i] = -1;
+    *r.nmatches = 0;
+    if (r.queries_out) for (int i = 0; i < nq; ++i) r.queries_out[i] = {0.f, 0.f, -1.f, 0.f, 0, -1};
+    if (nq == 0 || (ns == 0 && !r.queries_out && !(r.prefix && r.prefix->proj_host))) return ORBX_OK;
+    SeqPlan p;
+    p.lds = sizeof(int) * (3 * (size_t)ns + (r.mode == 1 ? nq : 0)) + 16;
+    if (p.lds > 160 * 1024) ORBX_FAIL(ORBX_ERR_CAPACITY, "resolver state exceeds LDS");
+    // (SearchForInitialization's windows are 200 px wide: a few hundred candidates each, where the projection searches see tens)
+    p.win_stride = r.mode == 1 ? 1024 : 256;
+    p.ent_need = r.lists.off ? (size_t)r.lists.off[nq] : (size_t)nq * p.win_stride;
+    p.init_c = ns ? std::min(7, (144 * 1024 / 4) / ns - 3) : 7;
+    p.sequential = g_force_sequential.load(std::memory_order_relaxed) != 0 || (r.mode == 1 && p.init_c < 2);
 
     WorkspaceLease lease;
     Workspace &w = *lease.w;
-    static bool lds_attr_set = false;
-    if (!lds_attr_set) { // the largest request either instantiation can make
-        ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_par), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));   // (it also has static LDS)
-        ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_init_par), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-        lds_attr_set = true;
-    }
-    // Window lists: their lengths are known only on the device.  First attempt: every query fills its own region of
-    // WIN_STRIDE entries in one pass (no count, no scan, no host wait); if a list does not fit, the overflow flag comes
-    // back with the results and the call is repeated on the exact path (count, scan, fill), whose total also travels
-    // with the results -- the host never waits in the middle of a call.
-    // (SearchForInitialization's windows are 200 px wide: a few hundred candidates each, where the projection searches see tens)
-    const int WIN_STRIDE = mode == 1 ? 1024 : 256;
-    bool exact = false, sized = false;
-    size_t ent_need = cand_off ? (size_t)cand_off[nq] : (size_t)nq * WIN_STRIDE;
-    // the projection family (one segment, MODE 0) resolves as a parallel fixed point (k_resolve_par, rotation check fused); if its
-    // dependency chains are longer than the kernel iterates, the call is repeated on the one-wave sequential resolver
-    // SearchForInitialization (MODE 1) likewise (k_resolve_init_par): its per-slot acceptor lists take C + 3 ints of LDS per keypoint
-    // (the BoW searches' segments -- one per vocabulary node, disjoint candidate sets -- only matter to the sequential resolver:
-    // the fixed point needs no partition, queries of different nodes simply never meet)
-    bool sequential = g_force_sequential.load(std::memory_order_relaxed) != 0;
-    const int init_c = ns ? std::min(7, (144 * 1024 / 4) / ns - 3) : 7;
-    if (mode == 1 && init_c < 2) sequential = true;
+    if (const int rc = resolver_lds_limits()) return rc;
     for (int attempt = 0; attempt < 4; ++attempt) {
-        w.used = 0;
-        // staged inputs (same offsets on both sides), then device-only arrays, then the result block
-        const size_t o_qh = w.carve(queries ? sizeof(WinQuery) * nq : 1), o_a = w.carve(qframe ? sizeof(int) * (size_t)nq : (size_t)32 * nq);
-        fs.carve(w);
-        const size_t o_qang = w.carve(sizeof(float) * nq), o_tk = w.carve(nq), o_occ = w.carve(occupied && ns ? (size_t)ns : 1),
-                     o_off = w.carve(sizeof(int) * (nq + 1)),
-                     o_cbeg = w.carve(sizeof(int) * (size_t)nq), o_cand = w.carve(sizeof(int) * (size_t)(ncand ? ncand : 1)),
-                     o_seg = w.carve(sizeof(int) * (size_t)(nseg + 1));
-        if (chain) chain->carve_inputs(w);
-        const size_t staged = w.used;
-        if (prefix) prefix->carve(w);              // read by the prefix kernel where they are staged: not part of the upload
-        const size_t pin_in = w.used;
-        if (prefix) prefix->carve_scratch(w);
-        const size_t o_qd = w.carve(queries ? 1 : sizeof(WinQuery) * nq);
-        const size_t o_q = queries ? o_qh : o_qd;
-        const size_t o_top = w.carve(sizeof(unsigned) * TOPK * (size_t)nq), o_cnt = w.carve(sizeof(int) * nq), o_acc = w.carve(sizeof(int) * nq),
-                     o_lend = w.carve(sizeof(int) * nq),
-                     o_state = w.carve(sizeof(int) * (size_t)std::max(std::max(ns, nq), 1));
-        const size_t o_res = w.used;
-        const size_t o_mq = w.carve(sizeof(int) * nq), o_mk = w.carve(sizeof(int) * (size_t)(n ? n : 1)), o_nm = w.carve(4 * sizeof(int));
-        const size_t search_res_bytes = w.used - o_res;
-        if (chain) chain->carve_results(w);
-        const size_t total_bytes = w.used, res_bytes = total_bytes - o_res;
-        // optional outputs that are not part of the result block travel through the tail of the pinned arena
-        const size_t tq_bytes = queries_out ? (sizeof(WinQuery) * nq + 255) & ~(size_t)255 : 0;
-        const size_t tp_bytes = prefix && prefix->frustum && prefix->proj_host ? (sizeof(orbm_projected_point) * (size_t)nq + 255) & ~(size_t)255 : 0;
-        if (w.reserve(total_bytes, std::max(pin_in, res_bytes) + tq_bytes + tp_bytes)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
-        char *tq_pin = w.pin + w.pin_cap - tq_bytes, *tp_pin = tq_pin - tp_bytes;
-        if (w.reserve_entries(ent_need)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
-        hipStream_t st = w.st;
-
-        if (queries) memcpy(w.h<char>(o_qh), queries, sizeof(WinQuery) * nq);
-        if (qframe) memcpy(w.h<char>(o_a), qsrc, sizeof(int) * (size_t)nq);
-        else memcpy(w.h<char>(o_a), qdesc, (size_t)32 * nq);
-        fs.fill(w);
-        if (!qframe) {   // (from a resident frame: k_list_fill sets the angles down)
-            if (qangle) memcpy(w.h<char>(o_qang), qangle, sizeof(float) * nq); else memset(w.h<char>(o_qang), 0, sizeof(float) * nq);
+        SeqLayout L;
+        if (const int rc = seq_layout(r, w, p, L)) return rc;
+        if (const int rc = seq_stage(r, w, L, p)) return rc;
+        if (ns) {
+            if (const int rc = seq_lists(r, w, L, p)) return rc;
+            if (const int rc = seq_resolve(r, w, L, p)) return rc;
+        }               // (else nothing to search: the prefix's outputs are the whole result)
+        const SearchChain::Ctx cx = {&w, w.st, w.d<int>(L.o_mk), w.d<int>(L.o_nm), w.d<uint8_t>(L.o_tk), r.n, nq, p.gen, r.windows() && !p.exact,
+                                     !p.sequential, L.o_res};
+        if (r.chain && ns) {    // its kernel reads the flags the host reads below, and leaves if this attempt does not stand
+            if (const int rc = r.chain->launch(cx)) return rc;
+            r.chain->launched = true;
         }
-        if (qtakes) memcpy(w.h<char>(o_tk), qtakes, nq); else memset(w.h<char>(o_tk), 1, nq);
-        if (occupied && ns) fs.fill_occ(w.h<uint8_t>(o_occ), occupied);
-        if (cand_off) {
-            memcpy(w.h<char>(o_off), cand_off, sizeof(int) * (nq + 1));
-            memcpy(w.h<char>(o_cbeg), cand_beg, sizeof(int) * (size_t)nq);
-            if (ncand) memcpy(w.h<char>(o_cand), cand_idx, sizeof(int) * ncand);
-        }
-        if (seg) memcpy(w.h<char>(o_seg), seg, sizeof(int) * (size_t)(nseg + 1));
-        if (prefix) prefix->fill(w);
-        if (chain) { chain->fill_inputs(w); chain->launched = false; }
-        const bool fused_upload = prefix && orbx::stage_ok(w.dev, w.pin, staged);
-        if (!fused_upload) ORBX_HIP(orbx::stage_in(w.dev, w.pin, staged, st));
-        // ONE fill for everything that needs a preset (a launch each was 3-4 us of a 0.1-ms call): match_kp = -1 (slot untouched);
-        // segments write back touched slots of the state only, so it is preset to -1 as well (the span in between, match_q, is
-        // rewritten in full anyway); and the two counters START AT -1: the match count is overwritten (one workgroup) or added
-        // to (segments: the host adds the 1 back), the overflow flag is CLEARED to 0 by a list that does not fit
-        // (k_resolve_par writes every slot and its count itself; the two flags behind the count -- "a list outgrew its region",
-        // "the fixed point was reached" -- are raised by writing this call's generation number, so nothing needs a preset there)
-        const int gen = (int)(w.gen = (w.gen % 0x7ffffffe) + 1);
-        if (sequential) {
-            const size_t f0 = seg ? o_state : o_mk;
-            ORBX_HIP(hipMemsetAsync(w.d<char>(f0), 0xff, o_nm + sizeof(int) - f0, st));
-        }
-
-        const FrameView fv = fs.view(w);
-        WinQuery *dq = w.d<WinQuery>(o_q);
-        if (prefix) prefix->launch(w, dq, st, fused_upload ? stage_job(w.dev, w.pin, staged) : StageJob{nullptr, nullptr, 0, 0});
-        if (tq_bytes) ORBX_HIP(hipMemcpyAsync(tq_pin, dq, sizeof(WinQuery) * nq, hipMemcpyDeviceToHost, st));
-        if (tp_bytes) ORBX_HIP(hipMemcpyAsync(tp_pin, w.d<char>(prefix->o_proj), sizeof(orbm_projected_point) * (size_t)nq, hipMemcpyDeviceToHost, st));
-        if (ns == 0) {      // nothing to search: the prefix's outputs are the whole result
-            ORBX_HIP(hipStreamSynchronize(st));
-            if (chain) chain->waits++;
-            if (tq_bytes) memcpy(queries_out, tq_pin, sizeof(WinQuery) * nq);
-            if (tp_bytes) memcpy(prefix->proj_host, tp_pin, sizeof(orbm_projected_point) * (size_t)nq);
-            return ORBX_OK;
-        }
-        const uint4 *da = w.d<uint4>(o_a), *db = fv.desc;
-        const SeqKp *dk = fv.kp;
-        const uint8_t *docc = occupied ? w.d<uint8_t>(o_occ) : nullptr;
-        int *doff = w.d<int>(o_off), *dnm = w.d<int>(o_nm);
-        const int init_dist = mode == 0 ? 256 : INT_MAX;
-        const dim3 g((nq + MT / 64 - 1) / (MT / 64)); // one wave per query
-        unsigned *dtop = w.d<unsigned>(o_top);
-        const int *lbeg = doff, *lend = doff + 1; // CSR lists; the strided path has its own bounds
-        if (!windows) { // explicit candidate lists
-            hipLaunchKernelGGL(k_list_fill, g, dim3(MT), 0, st, qframe ? (const uint4 *)qframe->desc : da, nq, db, (const int *)doff,
-                               (const int *)w.d<int>(o_cbeg), (const int *)w.d<int>(o_cand), w.ent, dtop,
-                               qframe ? (const int *)w.d<int>(o_a) : (const int *)nullptr, qframe ? (const float *)qframe->angle : (const float *)nullptr,
-                               w.d<float>(o_qang));
-        } else if (!exact) {
-            lbeg = w.d<int>(o_cnt); lend = w.d<int>(o_lend);
-            hipLaunchKernelGGL(k_win_wave<2>, g, dim3(MT), 0, st, (const WinQuery *)dq, da, nq, dk, db, fv.cell_off, docc, fv.gp, has_uright,
-                               init_dist, (int *)nullptr, (const int *)nullptr, w.ent, WIN_STRIDE, w.d<int>(o_cnt), w.d<int>(o_lend), dnm + 1, dtop, gen);
-        } else {
-            hipLaunchKernelGGL(k_win_wave<0>, g, dim3(MT), 0, st, (const WinQuery *)dq, da, nq, dk, db, fv.cell_off, docc, fv.gp, has_uright,
-                               init_dist, w.d<int>(o_cnt), (const int *)nullptr, (unsigned *)nullptr, 0, (int *)nullptr, (int *)nullptr,
-                               (int *)nullptr, (unsigned *)nullptr, gen);
-            hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(MT), 0, st, (const int *)w.d<int>(o_cnt), nq, doff, dnm + 1);
-            if (!sized) { // the total is needed to size the buffer: the one host wait of this (rare) path
-                sized = true;
-                int total = 0;
-                ORBX_HIP(hipMemcpyAsync(&total, dnm + 1, sizeof(int), hipMemcpyDeviceToHost, st));
-                ORBX_HIP(hipStreamSynchronize(st));
-                if (chain) chain->waits++;
-                ent_need = (size_t)total;
-                if (w.reserve_entries(ent_need)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
+        ORBX_HIP(hipStreamSynchronize(w.st));
+        if (r.chain) r.chain->waits++;
+        if (ns) {
+            if (r.windows() && !p.exact && *L.res<int>(w, L.o_nm + sizeof(int)) == p.gen) { p.exact = true; continue; }
+            if (!p.sequential) {
+                const int conv = *L.res<int>(w, L.o_nm + 2 * sizeof(int));
+                g_last_iterations.store(conv == p.gen ? *L.res<int>(w, L.o_nm + 3 * sizeof(int)) : -1, std::memory_order_relaxed);
+                if (conv != p.gen) { p.sequential = true; continue; }
             }
-            hipLaunchKernelGGL(k_win_wave<1>, g, dim3(MT), 0, st, (const WinQuery *)dq, da, nq, dk, db, fv.cell_off, docc, fv.gp, has_uright,
-                               init_dist, (int *)nullptr, (const int *)doff, w.ent, 0, (int *)nullptr, (int *)nullptr, (int *)nullptr, dtop, gen);
         }
-        const int *dseg = seg ? w.d<int>(o_seg) : nullptr;
-        const dim3 gr(seg ? nseg : 1);
-        if (!sequential && mode == 1) {
-            hipLaunchKernelGGL(k_resolve_init_par, dim3(1), dim3(RES_T), sizeof(int) * (size_t)(init_c + 3) * ns, st, (const unsigned *)w.ent,
-                               (const unsigned *)dtop, lbeg, lend, nq, ns, init_c, th, nnratio, (const float *)w.d<float>(o_qang),
-                               fv.angle, fv.perm, check, w.d<unsigned>(o_acc), (const int *)dnm, gen,
-                               reinterpret_cast<int *>(w.pin + (o_mq - o_res)), reinterpret_cast<int *>(w.pin + (o_nm - o_res)));
-        } else if (!sequential) {
-            hipLaunchKernelGGL(k_resolve_par, dim3(1), dim3(RES_T), sizeof(int) * 4 * (size_t)ns, st, (const unsigned *)w.ent, (const unsigned *)dtop, lbeg, lend,
-                               nq, ns, (const uint8_t *)w.d<uint8_t>(o_tk), th, nnratio, accept_mode, (const float *)w.d<float>(o_qang),
-                               fv.angle, fv.perm, check, w.d<int>(o_mq), w.d<int>(o_mk), n, (const int *)dnm, gen,
-                               reinterpret_cast<int *>(w.pin + (o_mq - o_res)), reinterpret_cast<int *>(w.pin + (o_mk - o_res)), reinterpret_cast<int *>(w.pin + (o_nm - o_res)), dnm);
-        } else if (mode == 0) {
-            hipLaunchKernelGGL(k_resolve<0>, gr, dim3(64), lds, st, (const unsigned *)w.ent, (const unsigned *)dtop, lbeg, lend, nq, ns,
-                               (const uint8_t *)w.d<uint8_t>(o_tk), th, nnratio, accept_mode, w.d<int>(o_acc), w.d<int>(o_state), dnm, dseg);
-            hipLaunchKernelGGL(k_rotation<0>, dim3(1), dim3(MT), 0, st, (const int *)w.d<int>(o_acc), (const int *)w.d<int>(o_state), nq, ns,
-                               (const float *)w.d<float>(o_qang), fv.angle, fv.perm, check,
-                               w.d<int>(o_mq), w.d<int>(o_mk), dnm);
-        } else {
-            hipLaunchKernelGGL(k_resolve<1>, gr, dim3(64), lds, st, (const unsigned *)w.ent, (const unsigned *)dtop, lbeg, lend, nq, ns,
-                               (const uint8_t *)w.d<uint8_t>(o_tk), th, nnratio, 0, w.d<int>(o_acc), w.d<int>(o_state), dnm, dseg);
-            hipLaunchKernelGGL(k_rotation<1>, dim3(1), dim3(MT), 0, st, (const int *)w.d<int>(o_acc), (const int *)w.d<int>(o_state), nq, ns,
-                               (const float *)w.d<float>(o_qang), fv.angle, fv.perm, check,
-                               w.d<int>(o_mq), w.d<int>(o_mk), dnm);
-        }
-        ORBX_HIP(hipGetLastError());
-        if (sequential) ORBX_HIP(orbx::stage_out(w.pin, w.dev + o_res, search_res_bytes, st));   // (k_resolve_par wrote the block itself)
-        const SearchChain::Ctx cx = {&w, st, w.d<int>(o_mk), dnm, w.d<uint8_t>(o_tk), n, nq, gen, windows && !exact, !sequential, o_res};
-        if (chain) {        // its kernel reads the flags the host reads below, and leaves if this attempt does not stand
-            const int rc = chain->launch(cx);
-            if (rc != ORBX_OK) return rc;
-            chain->launched = true;
-        }
-        ORBX_HIP(hipStreamSynchronize(st));
-        if (chain) chain->waits++;
-        int flag = 0;
-        memcpy(&flag, w.pin + (o_nm - o_res) + sizeof(int), sizeof(int));
-        if (windows && !exact && flag == gen) { // a window list outgrew its region: once more on the exact path
-            exact = true;
-            continue;
-        }
-        if (!sequential) {
-            int conv = 0;
-            memcpy(&conv, w.pin + (o_nm - o_res) + 2 * sizeof(int), sizeof(int));
-            if (conv != gen) { sequential = true; g_last_iterations.store(-1, std::memory_order_relaxed); continue; }
-            memcpy(&conv, w.pin + (o_nm - o_res) + 3 * sizeof(int), sizeof(int));
-            g_last_iterations.store(conv, std::memory_order_relaxed);
-        }
-        memcpy(match_q, w.pin + (o_mq - o_res), sizeof(int) * nq);
-        if (mode == 0 && n) memcpy(match_kp, w.pin + (o_mk - o_res), sizeof(int) * n);
-        memcpy(nmatches, w.pin + (o_nm - o_res), sizeof(int));
-        if (tq_bytes) memcpy(queries_out, tq_pin, sizeof(WinQuery) * nq);
-        if (tp_bytes) memcpy(prefix->proj_host, tp_pin, sizeof(orbm_projected_point) * (size_t)nq);
-        if (seg && sequential) *nmatches += 1;   // the segments added their counts to the preset -1
-        if (chain) chain->collect(cx);
+        seq_collect(r, w, L, p, ns != 0);
+        if (r.chain && ns) r.chain->collect(cx);
         break;
     }
     return ORBX_OK;
@@ -2073,7 +2039,7 @@ int search_map_core(FrameSrc &fs, int n, const uint8_t *has_mappoint, const floa
     return ORBX_OK;
 }
 
-int search_init_core(FrameSrc &fs, int n2, const orbx_keypoint *kps1, const uint8_t *desc1, int n1, float *prev_matched, int window_size,
+int search_init_core(FrameSrc &fs, int n2, const orbx_keypoint *kps2, const orbx_keypoint *kps1, const uint8_t *desc1, int n1, float *prev_matched, int window_size,
                      float nnratio, int check_orientation, int32_t *matches12, int *nmatches)
 {
     // queries: level-0 keypoints of F1 around their previous match (:619-626); others get an empty window
@@ -2084,9 +2050,15 @@ int search_init_core(FrameSrc &fs, int n2, const orbx_keypoint *kps1, const uint
         q[i] = {prev_matched[2 * i], prev_matched[2 * i + 1], use ? (float)window_size : -1.0f, 0.f, kps1[i].octave, kps1[i].octave};
         ang[i] = kps1[i].angle;
     }
-    std::vector<int32_t> dummy(n2 ? n2 : 1);
-    return run_sequential(1, q.data(), nullptr, desc1, ang.data(), nullptr, n1, fs, n2, nullptr, 0, 45 /* TH_LOW, :38 */, nnratio, 0,
-                          check_orientation, dummy.data(), matches12, nmatches);
+    SeqSearch r;
+    r.queries = q.data(); r.q.desc = desc1; r.q.angle = ang.data(); r.nq = n1;
+    r.fs = &fs; r.n = n2;
+    r.mode = 1; r.th = 45 /* TH_LOW, :38 */; r.nnratio = nnratio; r.check = check_orientation;
+    r.match_q = matches12; r.nmatches = nmatches;
+    const int rc = run_sequential(r);
+    for (int i = 0; i < n1 && rc == ORBX_OK; ++i) // :715-718
+        if (matches12[i] >= 0) { prev_matched[2 * i] = kps2[matches12[i]].x; prev_matched[2 * i + 1] = kps2[matches12[i]].y; }
+    return rc;
 }
 
 } // namespace
@@ -2379,9 +2351,12 @@ int orbm_search_projection(const orbm_window_query *queries, const uint8_t *qdes
     SortedFrame sf;
     sort_frame(kps, desc, n, nullptr, uright, min_x, min_y, max_x, max_y, sf);
     FrameSrc fs(sf);
-    return run_sequential(0, reinterpret_cast<const WinQuery *>(queries), nullptr, qdesc, qangle, qtakes, nq, fs, n, occupied, uright ? 1 : 0,
-                          th_accept, nnratio, ratio_same_level ? ACCEPT_RATIO_SAME_LEVEL : ACCEPT_BEST, check_orientation, match_kp,
-                          match_q, nmatches);
+    SeqSearch r;
+    r.queries = reinterpret_cast<const WinQuery *>(queries); r.q.desc = qdesc; r.q.angle = qangle; r.qtakes = qtakes; r.nq = nq;
+    r.fs = &fs; r.n = n; r.occupied = occupied; r.has_uright = uright ? 1 : 0;
+    r.th = th_accept; r.nnratio = nnratio; r.accept_mode = ratio_same_level ? ACCEPT_RATIO_SAME_LEVEL : ACCEPT_BEST; r.check = check_orientation;
+    r.match_kp = match_kp; r.match_q = match_q; r.nmatches = nmatches;
+    return run_sequential(r);
 }
 
 int orbm_frame_search_projection(const orbm_frame *frame, const orbm_window_query *queries, const uint8_t *qdesc, const float *qangle,
@@ -2392,9 +2367,12 @@ int orbm_frame_search_projection(const orbm_frame *frame, const orbm_window_quer
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     ORBX_NEED_DEVICE();
     FrameSrc fs(frame);
-    return run_sequential(0, reinterpret_cast<const WinQuery *>(queries), nullptr, qdesc, qangle, qtakes, nq, fs, frame->n, occupied,
-                          frame->has_uright, th_accept, nnratio, ratio_same_level ? ACCEPT_RATIO_SAME_LEVEL : ACCEPT_BEST, check_orientation,
-                          match_kp, match_q, nmatches);
+    SeqSearch r;
+    r.queries = reinterpret_cast<const WinQuery *>(queries); r.q.desc = qdesc; r.q.angle = qangle; r.qtakes = qtakes; r.nq = nq;
+    r.fs = &fs; r.n = frame->n; r.occupied = occupied; r.has_uright = frame->has_uright;
+    r.th = th_accept; r.nnratio = nnratio; r.accept_mode = ratio_same_level ? ACCEPT_RATIO_SAME_LEVEL : ACCEPT_BEST; r.check = check_orientation;
+    r.match_kp = match_kp; r.match_q = match_q; r.nmatches = nmatches;
+    return run_sequential(r);
 }
 
 int orbm_search_for_initialization(const orbx_keypoint *kps1, const uint8_t *desc1, int n1, const orbx_keypoint *kps2,
@@ -2409,11 +2387,7 @@ int orbm_search_for_initialization(const orbx_keypoint *kps1, const uint8_t *des
     SortedFrame sf;
     sort_frame(kps2, desc2, n2, nullptr, nullptr, min_x, min_y, max_x, max_y, sf);
     FrameSrc fs(sf);
-    const int rc = search_init_core(fs, n2, kps1, desc1, n1, prev_matched, window_size, nnratio, check_orientation, matches12, nmatches);
-    if (rc != ORBX_OK) return rc;
-    for (int i = 0; i < n1; ++i) // :715-718
-        if (matches12[i] >= 0) { prev_matched[2 * i] = kps2[matches12[i]].x; prev_matched[2 * i + 1] = kps2[matches12[i]].y; }
-    return ORBX_OK;
+    return search_init_core(fs, n2, kps2, kps1, desc1, n1, prev_matched, window_size, nnratio, check_orientation, matches12, nmatches);
 }
 
 int orbm_frame_search_for_initialization(const orbm_frame *frame2, const orbx_keypoint *kps2, const orbx_keypoint *kps1, const uint8_t *desc1,
@@ -2424,11 +2398,7 @@ int orbm_frame_search_for_initialization(const orbm_frame *frame2, const orbx_ke
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     ORBX_NEED_DEVICE();
     FrameSrc fs(frame2);
-    const int rc = search_init_core(fs, frame2->n, kps1, desc1, n1, prev_matched, window_size, nnratio, check_orientation, matches12, nmatches);
-    if (rc != ORBX_OK) return rc;
-    for (int i = 0; i < n1; ++i)
-        if (matches12[i] >= 0) { prev_matched[2 * i] = kps2[matches12[i]].x; prev_matched[2 * i + 1] = kps2[matches12[i]].y; }
-    return ORBX_OK;
+    return search_init_core(fs, frame2->n, kps2, kps1, desc1, n1, prev_matched, window_size, nnratio, check_orientation, matches12, nmatches);
 }
 
 } // extern "C"
@@ -2441,6 +2411,13 @@ namespace {
 struct BowLists {
     std::vector<int32_t> qidx, cand_off, cand_beg, cand, seg;
     bool disjoint = true;   // a feature sits in one node of a FeatureVector; arrays that break this resolve as one segment
+    SeqSearch::Lists lists() const
+    {
+        SeqSearch::Lists l;
+        l.off = cand_off.data(); l.beg = cand_beg.data(); l.idx = cand.data(); l.n = (int)cand.size();
+        if (disjoint) { l.seg = seg.data(); l.nseg = (int)seg.size() - 1; }
+        return l;
+    }
 };
 void bow_lists(const int32_t *nodes1, const int32_t *off1, const int32_t *items1, int nn1, const uint8_t *valid1, const int32_t *nodes2,
                const int32_t *off2, const int32_t *items2, int nn2, const uint8_t *valid2, int n2, const int *inv2, BowLists &L)
@@ -2512,10 +2489,12 @@ int orbm_search_by_bow(const int32_t *nodes1, const int32_t *off1, const int32_t
     for (int i = 0; i < nq; ++i) { memcpy(&qd[32 * (size_t)i], desc1 + 32 * (size_t)L.qidx[i], 32); qa[i] = angle1 ? angle1[L.qidx[i]] : 0.f; }
     std::vector<int32_t> mk(n2), mq(nq);
     FrameSrc fs(sf);
-    // bestDist1 < TH_LOW (:799) == bestDist1 <= TH_LOW - 1
-    const int rc = run_sequential(0, nullptr, nullptr, qd.data(), qa.data(), nullptr, nq, fs, n2, nullptr, 0, strict_th ? th - 1 : th, nnratio,
-                                  ACCEPT_RATIO, check_orientation, mk.data(), mq.data(), nmatches, nullptr, L.cand_off.data(), L.cand_beg.data(), L.cand.data(),
-                                  (int)L.cand.size(), L.disjoint ? L.seg.data() : nullptr, L.disjoint ? (int)L.seg.size() - 1 : 0);
+    SeqSearch r;
+    r.lists = L.lists(); r.q.desc = qd.data(); r.q.angle = qa.data(); r.nq = nq;
+    r.fs = &fs; r.n = n2;
+    r.th = strict_th ? th - 1 : th; r.nnratio = nnratio; r.accept_mode = ACCEPT_RATIO; r.check = check_orientation;   // bestDist1 < TH_LOW (:799) == bestDist1 <= TH_LOW - 1
+    r.match_kp = mk.data(); r.match_q = mq.data(); r.nmatches = nmatches;
+    const int rc = run_sequential(r);
     if (rc != ORBX_OK) return rc;
     for (int i = 0; i < nq; ++i) // every accepted query blocks its candidate, so slot mq[i] still names i unless rejected
         if (mq[i] >= 0 && mk[mq[i]] == i) { match12[L.qidx[i]] = mq[i]; if (match21) match21[mq[i]] = L.qidx[i]; }
@@ -2543,9 +2522,12 @@ int orbm_frame_search_by_bow(const orbm_frame *frame1, const int32_t *nodes1, co
     std::vector<int32_t> qsrc(nq), mk(n2), mq(nq);
     for (int i = 0; i < nq; ++i) qsrc[i] = frame1->inv_host[L.qidx[i]];
     FrameSrc fs(frame2, true);
-    const int rc = run_sequential(0, nullptr, nullptr, nullptr, nullptr, nullptr, nq, fs, n2, nullptr, 0, strict_th ? th - 1 : th, nnratio,
-                                  ACCEPT_RATIO, check_orientation, mk.data(), mq.data(), nmatches, nullptr, L.cand_off.data(), L.cand_beg.data(), L.cand.data(),
-                                  (int)L.cand.size(), L.disjoint ? L.seg.data() : nullptr, L.disjoint ? (int)L.seg.size() - 1 : 0, frame1, qsrc.data());
+    SeqSearch r;
+    r.lists = L.lists(); r.q.frame = frame1; r.q.pos = qsrc.data(); r.nq = nq;
+    r.fs = &fs; r.n = n2;
+    r.th = strict_th ? th - 1 : th; r.nnratio = nnratio; r.accept_mode = ACCEPT_RATIO; r.check = check_orientation;
+    r.match_kp = mk.data(); r.match_q = mq.data(); r.nmatches = nmatches;
+    const int rc = run_sequential(r);
     if (rc != ORBX_OK) return rc;
     for (int i = 0; i < nq; ++i)
         if (mq[i] >= 0 && mk[mq[i]] == i) { match12[L.qidx[i]] = mq[i]; if (match21) match21[mq[i]] = L.qidx[i]; }
@@ -2602,37 +2584,8 @@ int orbm_frame_search_for_triangulation(const orbm_frame *kf1, const int32_t *no
     ORBX_HIP(hipGetLastError());
     if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
     memcpy(match12, sc.r<int>(o_o), sizeof(int) * (size_t)n1);
-    if (check_orientation) {
-        const float *rot = reinterpret_cast<const float *>(sc.r<int>(o_o) + n1);
-        constexpr int HL = 30;     // HISTO_LENGTH, ORBmatcher.cc:40
-        int hist[HL] = {0};
-        std::vector<int> bin((size_t)n1, -1);
-        const float factor = 1.0f / HL;
-        for (int i = 0; i < n1; ++i)
-            if (match12[i] >= 0) {
-                float r = rot[i];                                      // :994-1001
-                if (r < 0.0f) r += 360.0f;
-                int b = (int)roundf(r * factor);
-                if (b == HL) b = 0;
-                if (b < 0 || b > HL) ORBX_FAIL(ORBX_ERR_ARG, "keypoint angles outside [0, 360)");   // (the reference asserts)
-                bin[i] = b; hist[b]++;
-            }
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;      // ComputeThreeMaxima, :1802-1843
-        for (int i = 0; i < HL; i++) {
-            const int sz = hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-            else if (sz > max3) { max3 = sz; ind3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-        for (int i = 0; i < n1; ++i)
-            if (bin[i] >= 0 && bin[i] != ind1 && bin[i] != ind2 && bin[i] != ind3) match12[i] = -1;
-    }
-    int nm = 0;
-    for (int i = 0; i < n1; ++i) nm += match12[i] >= 0;
-    *nmatches = nm;
-    return ORBX_OK;
+    const float *rot = reinterpret_cast<const float *>(sc.r<int>(o_o) + n1);      // angle1 - angle2 of every pair (:994)
+    return triangulation_rotation_check(match12, n1, check_orientation, [&](int i) { return rot[i]; }, nmatches);
 }
 
 // ------------------------------------------------------- the projection searches as whole functions, on resident frames
@@ -2668,9 +2621,13 @@ int orbm_detail::search_by_projection_points_chain(const orbm_frame *cur, const 
     pc.nlevels = view->nlevels; pc.mode = ORBM_PROJECT_FRUSTUM;
     if (projected_out) for (int i = 0; i < points->n; ++i) projected_out[i] = {0.f, 0.f, 0.f, 0.f, 0.f, -1, 0};
     FrameSrc fs(cur);
-    return run_sequential(0, nullptr, &px, points->desc, nullptr, points->takes, points->n, fs, cur->n, occupied, cur->has_uright, th_high,
-                          nnratio, ACCEPT_RATIO_SAME_LEVEL, 0, match_kp, match_q, nmatches, reinterpret_cast<WinQuery *>(queries_out),
-                          nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, chain);
+    SeqSearch r;
+    r.prefix = &px; r.q.desc = points->desc; r.qtakes = points->takes; r.nq = points->n;
+    r.fs = &fs; r.n = cur->n; r.occupied = occupied; r.has_uright = cur->has_uright;
+    r.th = th_high; r.nnratio = nnratio; r.accept_mode = ACCEPT_RATIO_SAME_LEVEL;
+    r.match_kp = match_kp; r.match_q = match_q; r.nmatches = nmatches; r.queries_out = reinterpret_cast<WinQuery *>(queries_out);
+    r.chain = chain;
+    return run_sequential(r);
 }
 
 int orbm_detail::search_by_projection_last_chain(const orbm_frame *cur, const orbm_view *view, const float *Tcw, const float *Tlw,
@@ -2693,9 +2650,13 @@ int orbm_detail::search_by_projection_last_chain(const orbm_frame *cur, const or
     px.cam.forward = tlc[2] > view->mb && !mono;            // :1549-1550
     px.cam.backward = -tlc[2] > view->mb && !mono;
     FrameSrc fs(cur);
-    return run_sequential(0, nullptr, &px, last->desc, last->angle, last->takes, last->n, fs, cur->n, occupied, cur->has_uright, th_high, 0.f,
-                          ACCEPT_BEST, check_orientation, match_kp, match_q, nmatches, reinterpret_cast<WinQuery *>(queries_out),
-                          nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, chain);
+    SeqSearch r;
+    r.prefix = &px; r.q.desc = last->desc; r.q.angle = last->angle; r.qtakes = last->takes; r.nq = last->n;
+    r.fs = &fs; r.n = cur->n; r.occupied = occupied; r.has_uright = cur->has_uright;
+    r.th = th_high; r.check = check_orientation;
+    r.match_kp = match_kp; r.match_q = match_q; r.nmatches = nmatches; r.queries_out = reinterpret_cast<WinQuery *>(queries_out);
+    r.chain = chain;
+    return run_sequential(r);
 }
 
 extern "C" {
@@ -2722,9 +2683,12 @@ int orbm_search_by_projection_keyframe(const orbm_frame *cur, const orbm_view *v
     pose_parts(Tcw, px.cam.R, px.cam.t);
     neg_Rt_t(px.cam.R, px.cam.t, px.cam.Ow);                // Ow = -Rcw.t() * tcw (:1679)
     FrameSrc fs(cur);
-    // no stereo test in this form, every assignment blocks its slot (:1741-1742)
-    return run_sequential(0, nullptr, &px, kf->desc, kf->angle, nullptr, kf->n, fs, cur->n, occupied, 0, orb_dist, 0.f, ACCEPT_BEST,
-                          check_orientation, match_kp, match_q, nmatches, reinterpret_cast<WinQuery *>(queries_out));
+    SeqSearch r;     // no stereo test in this form, every assignment blocks its slot (:1741-1742)
+    r.prefix = &px; r.q.desc = kf->desc; r.q.angle = kf->angle; r.nq = kf->n;
+    r.fs = &fs; r.n = cur->n; r.occupied = occupied;
+    r.th = orb_dist; r.check = check_orientation;
+    r.match_kp = match_kp; r.match_q = match_q; r.nmatches = nmatches; r.queries_out = reinterpret_cast<WinQuery *>(queries_out);
+    return run_sequential(r);
 }
 
 int orbm_search_by_projection_sim3(const orbm_frame *kf, const orbm_view *view, const float *Scw, const orbm_points *points,
@@ -2749,8 +2713,12 @@ int orbm_search_by_projection_sim3(const orbm_frame *kf, const orbm_view *view, 
         neg_Rt_t(px.cam.R, px.cam.t, px.cam.Ow);
     }
     FrameSrc fs(kf);
-    return run_sequential(0, nullptr, &px, points->desc, nullptr, nullptr, points->n, fs, kf->n, occupied, 0, th_low, 0.f, ACCEPT_BEST, 0,
-                          match_kp, match_q, nmatches, reinterpret_cast<WinQuery *>(queries_out));
+    SeqSearch r;
+    r.prefix = &px; r.q.desc = points->desc; r.nq = points->n;
+    r.fs = &fs; r.n = kf->n; r.occupied = occupied;
+    r.th = th_low;
+    r.match_kp = match_kp; r.match_q = match_q; r.nmatches = nmatches; r.queries_out = reinterpret_cast<WinQuery *>(queries_out);
+    return run_sequential(r);
 }
 
 int orbm_search_by_sim3(const orbm_frame *kf1, const orbm_frame *kf2, const orbm_view *view, const float *T1w, const float *T2w, float s12,
