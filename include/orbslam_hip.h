@@ -31,7 +31,8 @@ enum {
 };
 
 const char *orbx_last_error(void);
-/* ABI version of this header (major*100+minor).  136 (additions only): the pose-only optimisation (orbm_pose_*). */
+/* ABI version of this header (major*100+minor).  136 (additions only): the pose-only optimisation (orbm_pose_*).  Added since
+ * without a new number (additions only): orbm_create_new_map_points, orbm_debug_last_create_points_waits. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -470,6 +471,56 @@ int orbm_frame_search_for_triangulation(const orbm_frame *kf1, const int32_t *no
                                         const int32_t *items2, int nn2, const uint8_t *has_mappoint2, int only_stereo, const float *F12,
                                         float ex, float ey, const float *scale_factors2, const float *level_sigma2, int nlevels,
                                         int check_orientation, int32_t *match12, int *nmatches);
+
+/* ------------------------------------------- LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:243-520) in one call
+ * The loop over the neighbour keyframes -- SearchForTriangulation(cur, neighbour, F12, .., false) chained into the parallax test,
+ * the linear triangulation (cv::SVD) or UnprojectStereo, the depth tests, the two reprojection gates and the scale-consistency
+ * gate -- for all K neighbours in ONE launch, one upload and one host wait.  What one neighbour hands to the next is only "this
+ * keypoint of the current keyframe owns a point now" (ORBmatcher.cc:900-904); the device carries it from k to k + 1.
+ *
+ * The caller passes the neighbours that passed the baseline test of :288-308 (it needs ComputeSceneMedianDepth, a walk over the
+ * map), in the order of GetBestCovisibilityKeyFrames, each with its F12 (LocalMapping::ComputeF12) and the epipole (ex, ey) as for
+ * orbm_frame_search_for_triangulation.  One pyramid (scale_factors, level_sigma2 [nlevels], scale_factor = mfScaleFactor) serves
+ * all keyframes: a map's keyframes share the extractor.  With the caller stay new MapPoint, AddObservation, AddMapPoint,
+ * ComputeDistinctiveDescriptors, UpdateNormalAndDepth -- to be replayed over the results in (k, i) ascending order, the
+ * reference's creation order -- and the CheckNewKeyFrames() early return between neighbours (:283): one call cannot be
+ * interrupted, so a caller that needs the early return calls with the neighbours in chunks, updating has_mappoint of the current
+ * keyframe from the results in between.
+ *
+ * Positions are the frames' (mvKeysUn) coordinates, also in UnprojectStereo (which reads mvKeys: the same for rectified stereo;
+ * for an RGB-D camera with distortion they differ).  A stereo keypoint (uright >= 0) whose depth is not > 0, where the reference
+ * cannot go on, is rejected as ORBM_TRI_PARALLAX. */
+typedef struct orbm_triang_keyframe {
+    const orbm_frame *frame;        /* mvKeysUn / mvuRight / descriptors resident (at most 8,192 keypoints) */
+    const float *Tcw;               /* 4 x 4 row-major, as cv::Mat mTcw */
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+    const float *depth;             /* mvDepth[n]; NULL only if no keypoint of the frame has uright >= 0 (a frame made from device arrays with right coordinates always needs it) */
+    const uint8_t *has_mappoint;    /* [n]: GetMapPoint(i) != NULL before the call */
+    const int32_t *nodes, *off, *items; int32_t nn;   /* mFeatVec, flat as for orbm_search_by_bow */
+    const float *F12; float ex, ey; /* neighbours only: LocalMapping::ComputeF12 and the epipole, computed by the caller */
+} orbm_triang_keyframe;
+
+/* What became of keypoint i of the current keyframe against neighbour k.  The reference's counters: nTriangulationRejects =
+ * SVD_ZERO, nParalaxRejects = PARALLAX, nDepthRejects = DEPTH, nRepErrorRejects = REPROJ1 (:465 / :476 count nothing),
+ * nScaleConsRejects = SCALE, each summed over k. */
+enum { ORBM_TRI_NO_MATCH = -1, ORBM_TRI_CREATED = 0, ORBM_TRI_SKIPPED = 1 /* owns a point */, ORBM_TRI_SVD_ZERO = 2,
+       ORBM_TRI_PARALLAX = 3, ORBM_TRI_DEPTH = 4, ORBM_TRI_REPROJ1 = 5, ORBM_TRI_REPROJ2 = 6, ORBM_TRI_DIST_ZERO = 7,
+       ORBM_TRI_SCALE = 8, ORBM_TRI_NSTATUS = 9 };
+
+/* K = 0 .. 32 neighbours (more: ORBX_ERR_UNSUPPORTED; K = 0 or an empty current keyframe: ORBX_OK, *nnew = 0, nothing is
+ * launched).  An octave outside [0, nlevels) in any frame, or depth = NULL on a frame with a stereo keypoint, is
+ * ORBX_ERR_ARG before the launch.  Results by keypoint index i of the current keyframe (n1 of them), row k per neighbour:
+ *   match12[k][i]   keypoint of neighbour k the search gave i, or -1
+ *   status[k][i]    ORBM_TRI_*
+ *   x3d[k][i][3]    the new point, written ONLY where status[k][i] == ORBM_TRI_CREATED
+ *   counts[k][s]    (optional) how many i have status s = 0 .. 8, [K][ORBM_TRI_NSTATUS]
+ *   *nnew           number of points created = the reference's nnew. */
+int orbm_create_new_map_points(const orbm_triang_keyframe *cur, const orbm_triang_keyframe *neigh, int K,
+                               const float *scale_factors, const float *level_sigma2, int nlevels, float scale_factor,
+                               int32_t *match12, int8_t *status, float *x3d, int32_t *counts, int *nnew);
+/* Host waits (stream synchronisations) of the last orbm_create_new_map_points call of this process: 1 when it launched, 0 when it
+ * returned before the launch. */
+int orbm_debug_last_create_points_waits(void);
 
 /* ------------------------------------------- the SearchByProjection forms and SearchBySim3 as WHOLE functions
  * Projection prefix, candidate search, in-loop assignment, acceptance and rotation check in one call, nothing in between

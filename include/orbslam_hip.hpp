@@ -672,6 +672,62 @@ public:
         return (int)vMatchedPairs.size();
     }
 
+    // LocalMapping::CreateNewMapPoints' loop over the neighbour keyframes (LocalMapping.cc:281-517) in one call
+    // (orbm_create_new_map_points): the searches, triangulations and gates of all neighbours in one launch.  The neighbours are
+    // the ones that passed the baseline test, in the reference's order.  Returns the creation list in the reference's order
+    // ((k, idx1) ascending) and the reject counters; one call cannot be interrupted between neighbours -- a caller that needs
+    // CheckNewKeyFrames() in between calls with the neighbours in chunks.
+    struct TriangKeyFrame {
+        const ResidentFrame *frame;
+        const float *Tcw;                          // 4 x 4 row-major
+        float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+        const float *depth;                        // mvDepth, or nullptr if no keypoint of the frame is stereo
+        const std::vector<uint8_t> *hasMP;
+        const FeatureVector *fv;
+    };
+    struct Neighbour { TriangKeyFrame kf; float F12[9]; float ex, ey; };
+    struct NewPoint { int k; int idx1, idx2; float x3D[3]; };
+    struct NewPointCounters { int nnew = 0, nTriangulationRejects = 0, nParalaxRejects = 0, nDepthRejects = 0, nRepErrorRejects = 0, nScaleConsRejects = 0; };
+    int CreateNewMapPoints(const TriangKeyFrame &cur, const std::vector<float> &scaleFactors, const std::vector<float> &levelSigma2,
+                           float scaleFactor, const std::vector<Neighbour> &neighbours, std::vector<NewPoint> &created,
+                           NewPointCounters &counters)
+    {
+        created.clear();
+        counters = NewPointCounters();
+        const int K = (int)neighbours.size(), n1 = cur.frame->N;
+        auto flat = [](const TriangKeyFrame &k, const float *F12, float ex, float ey) {
+            orbm_triang_keyframe o;
+            o.frame = k.frame->handle(); o.Tcw = k.Tcw;
+            o.fx = k.fx; o.fy = k.fy; o.cx = k.cx; o.cy = k.cy; o.invfx = k.invfx; o.invfy = k.invfy; o.mb = k.mb; o.mbf = k.mbf;
+            o.depth = k.depth; o.has_mappoint = k.hasMP->data();
+            o.nodes = k.fv->nodes.data(); o.off = k.fv->off.data(); o.items = k.fv->items.data(); o.nn = (int32_t)k.fv->nodes.size();
+            o.F12 = F12; o.ex = ex; o.ey = ey;
+            return o;
+        };
+        const orbm_triang_keyframe c = flat(cur, nullptr, 0.f, 0.f);
+        std::vector<orbm_triang_keyframe> nb;
+        for (const Neighbour &n : neighbours) nb.push_back(flat(n.kf, n.F12, n.ex, n.ey));
+        const size_t kn = (size_t)K * (size_t)(n1 > 0 ? n1 : 0);
+        std::vector<int32_t> m12(kn ? kn : 1, -1), counts((size_t)(K ? K : 1) * ORBM_TRI_NSTATUS, 0);
+        std::vector<int8_t> status(kn ? kn : 1, (int8_t)ORBM_TRI_NO_MATCH);
+        std::vector<float> x3d(3 * (kn ? kn : 1), 0.f);
+        int nnew = 0;
+        mStatus = orbm_create_new_map_points(&c, nb.data(), K, scaleFactors.data(), levelSigma2.data(), (int)scaleFactors.size(), scaleFactor,
+                                             m12.data(), status.data(), x3d.data(), counts.data(), &nnew);
+        if (mStatus != ORBX_OK) return 0;
+        for (size_t o = 0; o < kn; ++o)
+            if (status[o] == ORBM_TRI_CREATED)
+                created.push_back({(int)(o / (size_t)n1), (int)(o % (size_t)n1), m12[o], {x3d[3 * o], x3d[3 * o + 1], x3d[3 * o + 2]}});
+        for (int k = 0; k < K; ++k) {
+            const int32_t *ck = counts.data() + (size_t)k * ORBM_TRI_NSTATUS;
+            counters.nTriangulationRejects += ck[ORBM_TRI_SVD_ZERO]; counters.nParalaxRejects += ck[ORBM_TRI_PARALLAX];
+            counters.nDepthRejects += ck[ORBM_TRI_DEPTH]; counters.nRepErrorRejects += ck[ORBM_TRI_REPROJ1];
+            counters.nScaleConsRejects += ck[ORBM_TRI_SCALE];
+        }
+        counters.nnew = nnew;
+        return nnew;
+    }
+
     // ORBmatcher::SearchForTriangulation (ORBmatcher.cc:858-1024).  The FeatureVector co-iteration builds the candidate
     // list of every keypoint of KF1 (the members of the same vocabulary node in KF2, in member order), the device
     // runs the loop with its epipolar gates, the rotation histogram and the pair list are finished here.

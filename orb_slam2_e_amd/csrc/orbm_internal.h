@@ -138,6 +138,7 @@ struct StagedCall {
     struct In { size_t off; const void *src; size_t bytes; };
     std::vector<In> ins;
     size_t staged = 0, res_off = 0, res_bytes = 0;
+    int waits = 0;                  // host waits (stream synchronisations) of this call so far
     StagedCall() : w(*lease.w) { w.used = 0; }
     size_t in(const void *src, size_t bytes)
     {
@@ -167,6 +168,7 @@ struct StagedCall {
     int download()
     {
         if (orbx::stage_out(w.pin, w.dev + res_off, res_bytes, w.st) != hipSuccess) return -1;
+        ++waits;
         return hipStreamSynchronize(w.st) == hipSuccess ? 0 : -1;
     }
 };

@@ -522,6 +522,32 @@ class ORBmatcher:
         """orbm_debug_last_track_waits: host waits of the last Track* call of this process (1 on the common path)."""
         return lib().orbm_debug_last_track_waits()
 
+    # ---------------------------------------------------------------- LocalMapping::CreateNewMapPoints in one call
+    TRI_NO_MATCH, TRI_CREATED, TRI_SKIPPED, TRI_SVD_ZERO, TRI_PARALLAX, TRI_DEPTH, TRI_REPROJ1, TRI_REPROJ2, TRI_DIST_ZERO, TRI_SCALE = range(-1, 9)
+    TRI_NSTATUS = 9
+
+    @staticmethod
+    def CreateNewMapPoints(cur, neighbours, scale_factors, level_sigma2, scale_factor):
+        """LocalMapping::CreateNewMapPoints' loop over the neighbour keyframes (LocalMapping.cc:281-517) in one call
+        (orbm_create_new_map_points): cur / neighbours = TriangKeyFrame, the neighbours in the reference's order, each with its
+        F12 and epipole.  Returns a CreatedPoints: match12[K, n1], status[K, n1] (TRI_*), x3d[K, n1, 3] (NaN where nothing was
+        created), counts[K, TRI_NSTATUS], nnew, and created() = the creation list in the reference's order."""
+        sf = np.ascontiguousarray(scale_factors, np.float32); sg = np.ascontiguousarray(level_sigma2, np.float32)
+        if len(sf) != len(sg):
+            raise ValueError("scale_factors and level_sigma2 differ in length")
+        K, n1 = len(neighbours), cur.n
+        arr = (_CTriangKeyFrame * max(K, 1))(*[nb.c for nb in neighbours])
+        m12 = np.full((K, n1), -1, np.int32); st = np.full((K, n1), -1, np.int8); x3d = np.full((K, n1, 3), np.nan, np.float32)
+        counts = np.zeros((K, ORBmatcher.TRI_NSTATUS), np.int32); nnew = C.c_int(0)
+        check(lib().orbm_create_new_map_points(C.byref(cur.c), arr if K else None, K, _p(sf), _p(sg), len(sf), float(scale_factor),
+                                               _p(m12), _p(st), _p(x3d), _p(counts), C.byref(nnew)))
+        return CreatedPoints(m12, st, x3d, counts, nnew.value)
+
+    @staticmethod
+    def last_create_points_waits():
+        """orbm_debug_last_create_points_waits: host waits of the last CreateNewMapPoints call of this process."""
+        return lib().orbm_debug_last_create_points_waits()
+
     def SearchBySim3Whole(self, kf1, kf2, view, T1w, T2w, s12, R12, t12, points1, points2, th, want_queries=False):
         """ORBmatcher::SearchBySim3 (ORBmatcher.cc:1303-1527) in one call.  Returns (match12, nFound, vnMatch1, vnMatch2[, q12, q21])."""
         f32 = lambda a, k: np.ascontiguousarray(a, np.float32).reshape(k)
@@ -550,6 +576,44 @@ class _CPoints(C.Structure):
 class _CView(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float),
                 ("log_scale_factor", C.c_float), ("nlevels", C.c_int32), ("scale_factors", C.c_void_p)]
+
+
+class _CTriangKeyFrame(C.Structure):
+    """orbm_triang_keyframe"""
+    _fields_ = [("frame", C.c_void_p), ("Tcw", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("invfx", C.c_float), ("invfy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float), ("depth", C.c_void_p),
+                ("has_mappoint", C.c_void_p), ("nodes", C.c_void_p), ("off", C.c_void_p), ("items", C.c_void_p), ("nn", C.c_int32),
+                ("F12", C.c_void_p), ("ex", C.c_float), ("ey", C.c_float)]
+
+
+class TriangKeyFrame:
+    """orbm_triang_keyframe: a resident keyframe with what CreateNewMapPoints reads of it.  cam = (fx, fy, cx, cy, mb, mbf)
+    (invfx = 1 / fx in float, as KeyFrame holds it); fv = feature_vector_arrays(...); depth = mvDepth, or None if no keypoint
+    of the frame is stereo; F12 / ex / ey: for a neighbour."""
+
+    def __init__(self, frame, Tcw, cam, fv, has_mappoint, depth=None, F12=None, ex=0.0, ey=0.0):
+        f32 = lambda a: np.ascontiguousarray(a, np.float32) if a is not None else None
+        fx, fy, cx, cy, mb, mbf = (np.float32(v) for v in cam)
+        nodes, off, items = (np.ascontiguousarray(a, np.int32) for a in fv)
+        self.frame, self.n = frame, frame.n
+        self._keep = dict(Tcw=f32(Tcw).reshape(16), depth=f32(depth), has=np.ascontiguousarray(has_mappoint, np.uint8), nodes=nodes, off=off,
+                          items=items, F12=f32(F12).reshape(9) if F12 is not None else None)
+        k = self._keep
+        opt = lambda a: _p(a) if a is not None else None
+        self.c = _CTriangKeyFrame(frame._h, _p(k["Tcw"]), fx, fy, cx, cy, np.float32(1) / fx, np.float32(1) / fy, mb, mbf, opt(k["depth"]),
+                                  _p(k["has"]), _p(nodes), _p(off), _p(items), len(nodes), opt(k["F12"]), float(ex), float(ey))
+
+
+class CreatedPoints:
+    """Results of ORBmatcher.CreateNewMapPoints."""
+
+    def __init__(self, match12, status, x3d, counts, nnew):
+        self.match12, self.status, self.x3d, self.counts, self.nnew = match12, status, x3d, counts, nnew
+
+    def created(self):
+        """(k, idx1, idx2, x3D[3]) arrays of the created points, (k, idx1) ascending: the reference's creation order."""
+        k, i = np.nonzero(self.status == ORBmatcher.TRI_CREATED)
+        return k, i, self.match12[k, i], self.x3d[k, i]
 
 
 class Points:
