@@ -32,7 +32,8 @@ enum {
 
 const char *orbx_last_error(void);
 /* ABI version of this header (major*100+minor).  136 (additions only): the pose-only optimisation (orbm_pose_*).  Added since
- * without a new number (additions only): orbm_create_new_map_points, orbm_debug_last_create_points_waits. */
+ * without a new number (additions only): orbm_create_new_map_points, orbm_debug_last_create_points_waits; orbm_sim3_hypotheses,
+ * orbm_debug_last_sim3_waits. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -521,6 +522,41 @@ int orbm_create_new_map_points(const orbm_triang_keyframe *cur, const orbm_trian
 /* Host waits (stream synchronisations) of the last orbm_create_new_map_points call of this process: 1 when it launched, 0 when it
  * returned before the launch. */
 int orbm_debug_last_create_points_waits(void);
+
+/* ------------------------------------------- Sim3Solver: every RANSAC hypothesis of a loop detection in one call
+ * Sim3Solver::iterate (src/Sim3Solver.cc:140-207) draws three indices per iteration from a freshly reset list (:163-177), so no
+ * iteration depends on an earlier one: the caller draws the triples of all iterations first, this call evaluates ComputeSim3
+ * (:226-337) and CheckInliers (:340-364) for each, and what iterate returns is a fold over the inlier counts that the caller runs
+ * on the host (include/orbslam_hip.hpp: Sim3Solver).  One problem per candidate keyframe; the pointer walk of the constructor
+ * (:62-103) stays with the caller, who passes what it keeps, flat. */
+typedef struct orbm_sim3_problem {
+    const float *X1w, *X2w;            /* [n][3] world positions of the pairs the constructor keeps (:64-101), in that order */
+    const int32_t *octave1, *octave2;  /* [n] kp.octave of the two keypoints */
+    const float *Tcw1, *Tcw2;          /* 4 x 4 row-major */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    const int32_t *triples;            /* [H][3] indices into 0..n-1 as the draw loop :166-177 leaves them */
+    int32_t n, H, fix_scale;
+} orbm_sim3_problem;
+
+typedef struct orbm_sim3_hypothesis {
+    float T12[16], R12[9], t12[3], s12; /* mT12i, mR12i, mt12i, ms12i of the hypothesis */
+    int32_t ninliers;                   /* mnInliersi */
+} orbm_sim3_hypothesis;
+
+/* P = 0 .. 64 problems, n <= 8,192 correspondences and H <= 1,024 hypotheses each (beyond: ORBX_ERR_UNSUPPORTED).  P = 0, or H = 0
+ * in every problem: ORBX_OK, nothing is launched.  ORBX_ERR_ARG before the launch: n < 3 with H > 0, a triple index outside
+ * [0, n), a triple that repeats an index, an octave outside [0, nlevels).  level_sigma2 [nlevels] = mvLevelSigma2 (one pyramid: a
+ * map's keyframes share the extractor).
+ *   hyp[sum H]   the hypotheses of problem 0, then of problem 1, ...
+ *   inliers      (void *: the binder maps no uint64_t pointer of its own; the words are uint64_t) per problem, behind each other,
+ *                [H][(n + 63) / 64] 64-bit words: bit i % 64 of word i / 64 = mvbInliersi[i]; bits past n are 0.
+ * There is no depth test in Project (:382-403): a correspondence with z <= 0 is projected like any other, and a NaN position is
+ * never an inlier.  The exact identity rotation gives NaN throughout, as the reference's 0 / 0 at :280 does: 0 inliers. */
+int orbm_sim3_hypotheses(const orbm_sim3_problem *problems, int P, const float *level_sigma2, int nlevels,
+                         orbm_sim3_hypothesis *hyp, void *inliers);
+/* Host waits (stream synchronisations) of the last orbm_sim3_hypotheses call of this process: 1 when it launched, 0 when it
+ * returned before the launch. */
+int orbm_debug_last_sim3_waits(void);
 
 /* ------------------------------------------- the SearchByProjection forms and SearchBySim3 as WHOLE functions
  * Projection prefix, candidate search, in-loop assignment, acceptance and rotation check in one call, nothing in between

@@ -1194,5 +1194,174 @@ private:
     int mStatus = ORBX_OK;
 };
 
+// Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) over orbm_sim3_hypotheses.  The constructor takes the flat problem -- what
+// the reference's constructor keeps of the two keyframes (:62-103): world positions and keypoint octaves of the kept pairs, where
+// each pair stands in vpMatched12 (indices1 = mvnIndices1, N1 = vpMatched12.size()), the two poses and calibrations -- and a
+// source of draws: a callback int(int lo, int hi) (inclusive, as DUtils::Random::RandomInt) or pre-drawn triples.  The first
+// iterate() draws the triples of all mRansacMaxIts iterations in the reference's order (:163-177) and evaluates them in one
+// orbm_sim3_hypotheses call; every iterate() is then the reference's fold (:158-206) over the stored inlier counts, with no device
+// work.  EvaluateBatch does the first evaluation of all candidates of a loop detection in one call.
+// One difference to the reference: the draws of one solver are made together; in LoopClosing::ComputeSim3 they interleave with the
+// other candidates' draws in five-iteration rounds.  Results equal the reference run whose RNG hands each solver these triples
+// (the reference seeds nothing here).  iterate() returns true and fills T12 where the reference returns a non-empty matrix.
+class Sim3Solver {
+public:
+    struct Problem {
+        std::vector<float> X1w, X2w;            // [n][3]
+        std::vector<int32_t> octave1, octave2;  // [n]
+        std::vector<int32_t> indices1;          // [n] mvnIndices1; empty: 0 .. n-1
+        int N1 = -1;                            // vpMatched12.size(); -1: n
+        float Tcw1[16], Tcw2[16];
+        float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+        std::vector<float> levelSigma2;         // mvLevelSigma2
+        bool bFixScale = false;
+    };
+    typedef int (*DrawFn)(int lo, int hi);
+
+    Sim3Solver(Problem problem, DrawFn draw) : mP(std::move(problem)), mDraw(draw) { init(); }
+    Sim3Solver(Problem problem, std::vector<int32_t> triples) : mP(std::move(problem)), mDraw(nullptr), mTriples(std::move(triples)) { init(); }
+    Sim3Solver(const Sim3Solver &) = delete;
+    Sim3Solver &operator=(const Sim3Solver &) = delete;
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300)
+    {
+        mRansacProb = probability; mRansacMinInliers = minInliers; mRansacMaxIts = maxIterations;
+        const float epsilon = (float)mRansacMinInliers / N;                                  // :125
+        int nIterations;
+        if (mRansacMinInliers == N) nIterations = 1;
+        else {
+            const double v = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow((double)epsilon, 3)));
+            nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : std::numeric_limits<int>::min();   // what x86 makes of it
+        }
+        mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+        mnIterations = 0;
+    }
+
+    // The first evaluation of every solver that has not had it (and has N >= mRansacMinInliers), at most 64 per launch.
+    static int EvaluateBatch(const std::vector<Sim3Solver *> &solvers)
+    {
+        std::vector<Sim3Solver *> todo;
+        for (Sim3Solver *s : solvers) if (s && !s->mEvaluated && s->N >= s->mRansacMinInliers) todo.push_back(s);
+        int rc = ORBX_OK;
+        for (size_t b = 0; b < todo.size() && rc == ORBX_OK; b += 64) {
+            const size_t e = std::min(todo.size(), b + 64);
+            std::vector<orbm_sim3_problem> probs;
+            size_t total = 0, words = 0;
+            for (size_t k = b; k < e; ++k) {
+                Sim3Solver &s = *todo[k];
+                if ((rc = s.draw()) != ORBX_OK) break;
+                const Problem &p = s.mP;
+                orbm_sim3_problem q;
+                q.X1w = p.X1w.data(); q.X2w = p.X2w.data(); q.octave1 = p.octave1.data(); q.octave2 = p.octave2.data();
+                q.Tcw1 = p.Tcw1; q.Tcw2 = p.Tcw2;
+                q.fx1 = p.fx1; q.fy1 = p.fy1; q.cx1 = p.cx1; q.cy1 = p.cy1; q.fx2 = p.fx2; q.fy2 = p.fy2; q.cx2 = p.cx2; q.cy2 = p.cy2;
+                q.triples = s.mTriples.data(); q.n = s.N; q.H = s.mRansacMaxIts; q.fix_scale = p.bFixScale ? 1 : 0;
+                probs.push_back(q);
+                total += (size_t)q.H; words += (size_t)q.H * (size_t)((q.n + 63) / 64);
+            }
+            if (rc != ORBX_OK) break;
+            std::vector<orbm_sim3_hypothesis> hyp(total ? total : 1);
+            std::vector<uint64_t> masks(words ? words : 1);
+            const std::vector<float> &sg = todo[b]->mP.levelSigma2;
+            rc = orbm_sim3_hypotheses(probs.data(), (int)probs.size(), sg.data(), (int)sg.size(), hyp.data(), masks.data());
+            size_t h0 = 0, w0 = 0;
+            for (size_t k = b; k < e; ++k) {
+                Sim3Solver &s = *todo[k];
+                s.mStatus = rc;
+                const size_t H = (size_t)s.mRansacMaxIts, W = H * (size_t)((s.N + 63) / 64);
+                if (rc == ORBX_OK) {
+                    s.mHyp.assign(hyp.begin() + h0, hyp.begin() + h0 + H);
+                    s.mMasks.assign(masks.begin() + w0, masks.begin() + w0 + W);
+                    s.mEvaluated = true;
+                }
+                h0 += H; w0 += W;
+            }
+        }
+        return rc;
+    }
+
+    // iterate (:140-207).  T12: 4 x 4 row-major, written when the result is true.
+    bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, float T12[16])
+    {
+        bNoMore = false;
+        vbInliers = std::vector<bool>(mN1, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers) { bNoMore = true; return false; }
+        if (!mEvaluated) {
+            std::vector<Sim3Solver *> one(1, this);
+            if (EvaluateBatch(one) != ORBX_OK) { bNoMore = true; return false; }      // status() has the code
+        }
+        int nCurrentIterations = 0;
+        while (mnIterations < mRansacMaxIts && nCurrentIterations < nIterations) {
+            const int h = mnIterations;
+            nCurrentIterations++;
+            mnIterations++;
+            const int cnt = mHyp[h].ninliers;
+            if (cnt >= mnBestInliers) {
+                mnBestInliers = cnt; mBest = h;
+                if (cnt > mRansacMinInliers) {
+                    nInliers = cnt;
+                    const int W = (N + 63) / 64;
+                    for (int i = 0; i < N; i++)
+                        if ((mMasks[(size_t)h * W + i / 64] >> (i % 64)) & 1u) vbInliers[mP.indices1.empty() ? i : mP.indices1[i]] = true;
+                    std::memcpy(T12, mHyp[h].T12, sizeof(float) * 16);
+                    return true;
+                }
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) bNoMore = true;
+        return false;
+    }
+
+    bool find(std::vector<bool> &vbInliers12, int &nInliers, float T12[16])
+    {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers, T12);
+    }
+
+    // mBestRotation (3 x 3 row-major), mBestTranslation, mBestScale; false before any hypothesis was held as best
+    bool GetEstimatedRotation(float R[9]) const { if (mBest < 0) return false; std::memcpy(R, mHyp[mBest].R12, sizeof(float) * 9); return true; }
+    bool GetEstimatedTranslation(float t[3]) const { if (mBest < 0) return false; std::memcpy(t, mHyp[mBest].t12, sizeof(float) * 3); return true; }
+    float GetEstimatedScale() const { return mBest < 0 ? 0.f : mHyp[mBest].s12; }
+    int GetRansacMaxIts() const { return mRansacMaxIts; }
+    int status() const { return mStatus; }
+
+private:
+    void init()
+    {
+        N = (int)(mP.X1w.size() / 3);
+        mN1 = mP.N1 < 0 ? N : mP.N1;
+        SetRansacParameters();
+    }
+    int draw()      // the draw loop of :163-177 for all mRansacMaxIts iterations
+    {
+        const size_t need = 3 * (size_t)mRansacMaxIts;
+        if (!mDraw) return mTriples.size() >= need ? ORBX_OK : (mStatus = ORBX_ERR_ARG);
+        if (N < 3) return mStatus = ORBX_ERR_ARG;
+        mTriples.resize(need);
+        std::vector<int32_t> avail;
+        for (int h = 0; h < mRansacMaxIts; ++h) {
+            avail.resize((size_t)N);
+            for (int i = 0; i < N; ++i) avail[i] = i;
+            for (int i = 0; i < 3; ++i) {
+                const int randi = mDraw(0, (int)avail.size() - 1);
+                if (randi < 0 || randi >= (int)avail.size()) return mStatus = ORBX_ERR_ARG;
+                mTriples[3 * (size_t)h + i] = avail[randi];
+                avail[randi] = avail.back();
+                avail.pop_back();
+            }
+        }
+        return ORBX_OK;
+    }
+    Problem mP;
+    DrawFn mDraw;
+    std::vector<int32_t> mTriples;
+    std::vector<orbm_sim3_hypothesis> mHyp;
+    std::vector<uint64_t> mMasks;
+    double mRansacProb = 0.99;
+    int N = 0, mN1 = 0, mRansacMinInliers = 6, mRansacMaxIts = 300, mnIterations = 0, mnBestInliers = 0, mBest = -1, mStatus = ORBX_OK;
+    bool mEvaluated = false;
+};
+
 } // namespace orbslam_hip
 #endif // ORBSLAM_HIP_HPP
