@@ -33,7 +33,7 @@ enum {
 const char *orbx_last_error(void);
 /* ABI version of this header (major*100+minor).  136 (additions only): the pose-only optimisation (orbm_pose_*).  Added since
  * without a new number (additions only): orbm_create_new_map_points, orbm_debug_last_create_points_waits; orbm_sim3_hypotheses,
- * orbm_debug_last_sim3_waits. */
+ * orbm_debug_last_sim3_waits; orbm_optimize_sim3, orbm_debug_last_sim3_opt_waits. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -557,6 +557,43 @@ int orbm_sim3_hypotheses(const orbm_sim3_problem *problems, int P, const float *
 /* Host waits (stream synchronisations) of the last orbm_sim3_hypotheses call of this process: 1 when it launched, 0 when it
  * returned before the launch. */
 int orbm_debug_last_sim3_waits(void);
+
+/* ------------------------------------------- Optimizer::OptimizeSim3: the loop-closing Sim3 refinement in one call
+ * The whole of src/Optimizer.cc:1564-1624 -- optimize(5), the outlier cut, optimize(5 or 10), the final count -- for up to 64 loop
+ * candidates in ONE launch, on g2o's code paths (VertexSim3Expmap, EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ with g2o's numeric
+ * Jacobians, Levenberg, the dense LDLT solver, the Huber kernel).  The pointer walk of :1483-1520 stays with the caller,
+ * who passes the correspondences it keeps, flat and in that order. */
+typedef struct orbm_sim3_opt_problem {
+    const float *X1w, *X2w;            /* [n][3] GetWorldPos() of pMP1 / pMP2 */
+    const float *obs1, *obs2;          /* [n][2] mvKeysUn[i].pt of pKF1, mvKeysUn[i2].pt of pKF2 */
+    const int32_t *octave1, *octave2;  /* [n] the two keypoints' octaves */
+    const float *Tcw1, *Tcw2;          /* 4 x 4 row-major: R1w, t1w, R2w, t2w */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    float R12[9], t12[3], s12;         /* the Sim3 as LoopClosing.cc:320-325 hands it over (Sim3(Matrix3d, Vector3d, double)) */
+    float th2;
+    int32_t fix_scale, n;
+} orbm_sim3_opt_problem;
+
+typedef struct orbm_sim3_opt_result {
+    double q[4], t[3], s;               /* g2oS12 on return: rotation x y z w, translation, scale (the input when nin is :1596's 0) */
+    int32_t nin;                        /* the return value */
+    int32_t nbad, ncorrespondences;     /* nBad of the first cut, nCorrespondences */
+    int32_t iterations[2], trials[2];   /* test aids: Levenberg iterations and damped solves of the two optimize() calls */
+    double chi2;                        /* currentChi after the last iteration run (0 if none) */
+} orbm_sim3_opt_result;
+
+/* P = 0 .. 64 problems, n <= 8,192 correspondences each (beyond: ORBX_ERR_UNSUPPORTED).  P = 0, or n = 0 in every problem: ORBX_OK,
+ * nothing is launched (results are still filled: the input Sim3, nin = 0).  An octave outside [0, nlevels): ORBX_ERR_ARG before the
+ * launch.  inv_level_sigma2 [nlevels] = mvInvLevelSigma2 (one pyramid: a map's keyframes share the extractor).
+ *   results[P]
+ *   kept         the problems behind each other, [n] each: 1 where the reference leaves vpMatches1[idx] non-NULL.  When fewer than
+ *                10 pairs survive the first cut (:1595) the cut is applied, nin = 0 and the Sim3 is the input.
+ * A NaN position makes every sum NaN: no step is accepted, no chi2 is > th2, every pair is kept and counted, as in the reference. */
+int orbm_optimize_sim3(const orbm_sim3_opt_problem *problems, int P, const float *inv_level_sigma2, int nlevels,
+                       orbm_sim3_opt_result *results, uint8_t *kept);
+/* Host waits (stream synchronisations) of the last orbm_optimize_sim3 call of this process: 1 when it launched, 0 when it returned
+ * before the launch. */
+int orbm_debug_last_sim3_opt_waits(void);
 
 /* ------------------------------------------- the SearchByProjection forms and SearchBySim3 as WHOLE functions
  * Projection prefix, candidate search, in-loop assignment, acceptance and rotation check in one call, nothing in between

@@ -1363,5 +1363,51 @@ private:
     bool mEvaluated = false;
 };
 
+// Optimizer::OptimizeSim3 (src/Optimizer.cc:1425-1625) over orbm_optimize_sim3: the caller does the pointer walk of :1483-1520 and
+// passes the correspondences it keeps, flat and in that order; the whole of :1564-1624 -- both optimisation rounds, the cut between
+// them and the final count -- is then ONE library call for up to 64 problems.  kept[i] of a problem says whether the reference
+// leaves vpMatches1[idx] of pair i non-NULL; result.nin is the reference's return value and (q, t, s) its g2oS12 on return.
+struct Sim3OptProblem {
+    std::vector<float> X1w, X2w;                // [n][3] GetWorldPos() of pMP1 / pMP2
+    std::vector<float> obs1, obs2;              // [n][2] mvKeysUn[i].pt, mvKeysUn[i2].pt
+    std::vector<int32_t> octave1, octave2;      // [n]
+    float Tcw1[16], Tcw2[16];
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    float R12[9], t12[3], s12;                  // the Sim3 as LoopClosing.cc:320-325 hands it over
+    float th2 = 10.f;
+    bool bFixScale = false;
+};
+
+// results: one per problem; kept: one vector per problem.  invLevelSigma2 = mvInvLevelSigma2 (one pyramid).
+inline int OptimizeSim3(const std::vector<Sim3OptProblem> &problems, const std::vector<float> &invLevelSigma2,
+                        std::vector<orbm_sim3_opt_result> &results, std::vector<std::vector<uint8_t> > &kept)
+{
+    std::vector<orbm_sim3_opt_problem> flat(problems.size());
+    size_t total = 0;
+    for (size_t k = 0; k < problems.size(); ++k) {
+        const Sim3OptProblem &p = problems[k];
+        orbm_sim3_opt_problem &q = flat[k];
+        const size_t n = p.octave1.size();
+        if (p.X1w.size() != 3 * n || p.X2w.size() != 3 * n || p.obs1.size() != 2 * n || p.obs2.size() != 2 * n || p.octave2.size() != n) return ORBX_ERR_ARG;
+        q.X1w = p.X1w.data(); q.X2w = p.X2w.data(); q.obs1 = p.obs1.data(); q.obs2 = p.obs2.data();
+        q.octave1 = p.octave1.data(); q.octave2 = p.octave2.data(); q.Tcw1 = p.Tcw1; q.Tcw2 = p.Tcw2;
+        q.fx1 = p.fx1; q.fy1 = p.fy1; q.cx1 = p.cx1; q.cy1 = p.cy1; q.fx2 = p.fx2; q.fy2 = p.fy2; q.cx2 = p.cx2; q.cy2 = p.cy2;
+        memcpy(q.R12, p.R12, sizeof(q.R12)); memcpy(q.t12, p.t12, sizeof(q.t12));
+        q.s12 = p.s12; q.th2 = p.th2; q.fix_scale = p.bFixScale ? 1 : 0; q.n = (int32_t)n;
+        total += n;
+    }
+    results.assign(problems.size(), orbm_sim3_opt_result());
+    std::vector<uint8_t> all(total ? total : 1, 0);
+    const int rc = orbm_optimize_sim3(flat.data(), (int)flat.size(), invLevelSigma2.data(), (int)invLevelSigma2.size(), results.data(), all.data());
+    kept.assign(problems.size(), std::vector<uint8_t>());
+    if (rc != ORBX_OK) return rc;
+    size_t at = 0;
+    for (size_t k = 0; k < problems.size(); ++k) {
+        kept[k].assign(all.begin() + at, all.begin() + at + flat[k].n);
+        at += (size_t)flat[k].n;
+    }
+    return ORBX_OK;
+}
+
 } // namespace orbslam_hip
 #endif // ORBSLAM_HIP_HPP

@@ -20,6 +20,20 @@ class _CSim3Problem(C.Structure):
                 ("fix_scale", C.c_int32)]
 
 
+class _CSim3OptProblem(C.Structure):
+    """orbm_sim3_opt_problem"""
+    _fields_ = [("X1w", C.c_void_p), ("X2w", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p), ("octave1", C.c_void_p),
+                ("octave2", C.c_void_p), ("Tcw1", C.c_void_p), ("Tcw2", C.c_void_p), ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float),
+                ("cy1", C.c_float), ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float), ("R12", C.c_float * 9),
+                ("t12", C.c_float * 3), ("s12", C.c_float), ("th2", C.c_float), ("fix_scale", C.c_int32), ("n", C.c_int32)]
+
+
+class Sim3OptResult(C.Structure):
+    """orbm_sim3_opt_result: the final g2o::Sim3 (q = x y z w), nin = the reference's return value"""
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("nin", C.c_int32), ("nbad", C.c_int32),
+                ("ncorrespondences", C.c_int32), ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("chi2", C.c_double)]
+
+
 HYPOTHESIS_DTYPE = np.dtype([("T12", "f4", 16), ("R12", "f4", 9), ("t12", "f4", 3), ("s12", "f4"), ("ninliers", "i4")])   # orbm_sim3_hypothesis
 
 MAX_PROBLEMS, MAX_N, MAX_H = 64, 8192, 1024
@@ -59,6 +73,50 @@ def sim3_hypotheses(problems, level_sigma2):
         out.append((hyp[h0:h0 + p.H], masks[w0:w0 + w].reshape(p.H, (p.n + 63) // 64)))
         h0 += p.H; w0 += w
     return out
+
+
+class Sim3OptProblem:
+    """orbm_sim3_opt_problem: the correspondences that survive the pointer tests of Optimizer.cc:1485-1520, flat and in that order.
+    cam = (fx, fy, cx, cy); R12, t12, s12: the Sim3 as LoopClosing.cc:320-325 hands it over."""
+
+    def __init__(self, X1w, X2w, obs1, obs2, octave1, octave2, Tcw1, Tcw2, cam1, cam2, R12, t12, s12, th2, fix_scale=False):
+        f = np.ascontiguousarray
+        self.X1w, self.X2w = f(X1w, np.float32).reshape(-1, 3), f(X2w, np.float32).reshape(-1, 3)
+        self.obs1, self.obs2 = f(obs1, np.float32).reshape(-1, 2), f(obs2, np.float32).reshape(-1, 2)
+        self.octave1, self.octave2 = f(octave1, np.int32), f(octave2, np.int32)
+        self.Tcw1, self.Tcw2 = f(Tcw1, np.float32).reshape(16), f(Tcw2, np.float32).reshape(16)
+        self.cam1, self.cam2 = tuple(float(v) for v in cam1), tuple(float(v) for v in cam2)
+        self.R12, self.t12 = f(R12, np.float32).reshape(9), f(t12, np.float32).reshape(3)
+        self.s12, self.th2, self.fix_scale = float(np.float32(s12)), float(np.float32(th2)), bool(fix_scale)
+        self.n = len(self.X1w)
+        if not (len(self.X2w) == len(self.obs1) == len(self.obs2) == len(self.octave1) == len(self.octave2) == self.n):
+            raise ValueError("X1w, X2w, obs1, obs2, octave1, octave2 differ in length")
+
+    def c(self):
+        return _CSim3OptProblem(_p(self.X1w), _p(self.X2w), _p(self.obs1), _p(self.obs2), _p(self.octave1), _p(self.octave2), _p(self.Tcw1),
+                                _p(self.Tcw2), *self.cam1, *self.cam2, (C.c_float * 9)(*self.R12), (C.c_float * 3)(*self.t12), self.s12,
+                                self.th2, int(self.fix_scale), self.n)
+
+
+def optimize_sim3(problems, inv_level_sigma2):
+    """orbm_optimize_sim3 (Optimizer::OptimizeSim3 of every problem in one launch): per problem (Sim3OptResult, kept [n] bool) --
+    kept[i] where the reference leaves vpMatches1[idx] non-NULL"""
+    P = len(problems)
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    arr = (_CSim3OptProblem * max(P, 1))(*[p.c() for p in problems])
+    res = (Sim3OptResult * max(P, 1))()
+    kept = np.zeros(max(sum(p.n for p in problems), 1), np.uint8)
+    check(lib().orbm_optimize_sim3(arr if P else None, P, _p(sg), len(sg), res, _p(kept)))
+    out, k0 = [], 0
+    for i, p in enumerate(problems):
+        out.append((res[i], kept[k0:k0 + p.n].astype(bool)))
+        k0 += p.n
+    return out
+
+
+def last_sim3_opt_waits():
+    """orbm_debug_last_sim3_opt_waits: host waits of the last orbm_optimize_sim3 call of this process."""
+    return lib().orbm_debug_last_sim3_opt_waits()
 
 
 def last_sim3_waits():
