@@ -156,6 +156,7 @@ struct StagedCall {
         res_bytes = w.used - res_off;
         return o;
     }
+    bool offsets_fit_32_bits() const { return w.used <= 0xffffffffu; }  // for calls whose device records hold offsets as unsigned
     hipStream_t stream() const { return w.st; }
     template <typename T> T *d(size_t off) const { return reinterpret_cast<T *>(w.dev + off); }
     template <typename T> const T *r(size_t off) const { return reinterpret_cast<const T *>(w.pin + (off - res_off)); }
@@ -172,6 +173,33 @@ struct StagedCall {
         return hipStreamSynchronize(w.st) == hipSuccess ? 0 : -1;
     }
 };
+
+// ---- the problems over two keyframes (orbm_sim3_problem / orbm_sim3_opt_problem, staged as Sim3Dev / Sim3OptDev): what the two
+// public structs share has the same member names in both, and so have the two device records.
+
+// every octave of both keyframes names a level
+template <typename Problem>
+inline bool octaves_in_range(const Problem &q, int nlevels)
+{
+    for (int i = 0; i < q.n; ++i)
+        if (q.octave1[i] < 0 || q.octave1[i] >= nlevels || q.octave2[i] < 0 || q.octave2[i] >= nlevels) return false;
+    return true;
+}
+
+// the points and octaves of both keyframes as staged inputs, Tcw1 / Tcw2 as R, t and the two cameras, into the device record
+template <typename Problem, typename Dev>
+inline void stage_two_keyframes(StagedCall &sc, const Problem &q, Dev &d)
+{
+    const size_t n = (size_t)q.n;
+    d.o_X1w = (unsigned)sc.in(q.X1w, sizeof(float) * 3 * n); d.o_X2w = (unsigned)sc.in(q.X2w, sizeof(float) * 3 * n);
+    d.o_oct1 = (unsigned)sc.in(q.octave1, sizeof(int32_t) * n); d.o_oct2 = (unsigned)sc.in(q.octave2, sizeof(int32_t) * n);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) { d.R1[3 * r + c] = q.Tcw1[4 * r + c]; d.R2[3 * r + c] = q.Tcw2[4 * r + c]; }
+        d.t1[r] = q.Tcw1[4 * r + 3]; d.t2[r] = q.Tcw2[4 * r + 3];
+    }
+    d.cam1[0] = q.fx1; d.cam1[1] = q.fy1; d.cam1[2] = q.cx1; d.cam1[3] = q.cy1;
+    d.cam2[0] = q.fx2; d.cam2[1] = q.fy2; d.cam2[2] = q.cx2; d.cam2[3] = q.cy2;
+}
 
 // What another translation unit (orbm_pose.hip) reads of a resident frame: the sorted keypoint records and the permutation in
 // HBM (perm[sorted position] = keypoint index, all n positions), the keypoint count and the octave range.

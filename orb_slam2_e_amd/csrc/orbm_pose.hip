@@ -22,6 +22,7 @@
 
 #include "../../include/orbslam_hip.h"
 #include "common.h"
+#include "orbm_g2o_math.h"
 #include "orbm_internal.h"
 
 using namespace orbm_detail;
@@ -75,7 +76,7 @@ enum { TRACK_SOLVED = 0, TRACK_SEARCH_AGAIN = 1, TRACK_FEW_MATCHES = 2, TRACK_RE
 
 struct Se3 { double q[4], t[3]; };
 
-// ------------------------------------------------------------------ se3quat.h / Eigen, in the restatement's operation order
+// ------------------------------------------------------------------ se3quat.h, in the restatement's operation order (Eigen: orbm_g2o_math.h)
 
 __device__ __forceinline__ void q_normalize(double q[4])
 {
@@ -92,43 +93,6 @@ __device__ __forceinline__ void normalize_rotation(double q[4])   // SE3Quat::no
     q_normalize(q);
 }
 
-// the trace <= 0 branch with the largest diagonal entry at I (a compile-time index: R and q stay in registers)
-template <int I>
-__device__ __forceinline__ void quat_from_matrix_diag(const double R[9], double q[4])
-{
-#define M(i, j) R[3 * (i) + (j)]
-    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
-    double t = sqrt(M(I, I) - M(J, J) - M(K, K) + 1.0);
-    q[I] = 0.5 * t;
-    t = 0.5 / t;
-    q[3] = (M(K, J) - M(J, K)) * t;
-    q[J] = (M(J, I) + M(I, J)) * t;
-    q[K] = (M(K, I) + M(I, K)) * t;
-#undef M
-}
-
-__device__ void quat_from_matrix(const double R[9], double q[4])   // Quaterniond(const Matrix3d&)
-{
-#define M(i, j) R[3 * (i) + (j)]
-    double t = M(0, 0) + M(1, 1) + M(2, 2);
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (M(2, 1) - M(1, 2)) * t;
-        q[1] = (M(0, 2) - M(2, 0)) * t;
-        q[2] = (M(1, 0) - M(0, 1)) * t;
-    } else {
-        int i = 0;
-        if (M(1, 1) > M(0, 0)) i = 1;
-        if (M(2, 2) > (i == 1 ? M(1, 1) : M(0, 0))) i = 2;
-        if (i == 0) quat_from_matrix_diag<0>(R, q);
-        else if (i == 1) quat_from_matrix_diag<1>(R, q);
-        else quat_from_matrix_diag<2>(R, q);
-    }
-#undef M
-}
-
 __device__ __forceinline__ void quat_to_matrix(const double q[4], double R[9])   // toRotationMatrix
 {
     const double x = q[0], y = q[1], z = q[2], w = q[3];
@@ -139,14 +103,6 @@ __device__ __forceinline__ void quat_to_matrix(const double q[4], double R[9])  
     R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
     R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
     R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
-__device__ __forceinline__ void q_rotate(const double q[4], const double v[3], double o[3])   // Quaternion * Vector3d
-{
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    for (int i = 0; i < 3; ++i) o[i] = v[i] + q[3] * uv[i] + c[i];
 }
 
 __device__ __forceinline__ void se3_map(const Se3 &T, const double X[3], double o[3])   // SE3Quat::map
@@ -201,68 +157,6 @@ __device__ void se3_from_cv(const float *T, Se3 &o)   // Converter::toSE3Quat
     normalize_rotation(o.q);
 }
 
-// Eigen::LDLT (Eigen 3.3 ldlt_inplace: diagonal pivoting, lower triangle) + solve; returns isPositive().  Every loop has constant
-// bounds and the pivot swaps are selects over the constant candidates, so the matrix stays in registers (a dynamic index would put
-// it in scratch memory, on the serial path of every trial).
-#define POSE_UNROLL _Pragma("unroll")
-__device__ bool ldlt_solve6(double m[36], const double b[6], double x[6])
-{
-    int tr[6];
-    int sign = 0;   // 0 ZeroSign, 1 PositiveSemiDef, 2 NegativeSemiDef, 3 Indefinite
-    double temp[6];
-#define L(i, j) m[6 * (i) + (j)]
-    POSE_UNROLL for (int k = 0; k < 6; ++k) {
-        int big = k;
-        double bv = fabs(L(k, k));
-        POSE_UNROLL for (int j = k + 1; j < 6; ++j) {
-            const double f = fabs(L(j, j));
-            if (f > bv) { big = j; bv = f; }
-        }
-        tr[k] = big;
-        POSE_UNROLL for (int c = k + 1; c < 6; ++c) {
-            if (big != c) continue;
-            POSE_UNROLL for (int j = 0; j < k; ++j) { const double s = L(k, j); L(k, j) = L(c, j); L(c, j) = s; }
-            POSE_UNROLL for (int i = c + 1; i < 6; ++i) { const double s = L(i, k); L(i, k) = L(i, c); L(i, c) = s; }
-            { const double s = L(k, k); L(k, k) = L(c, c); L(c, c) = s; }
-            POSE_UNROLL for (int i = k + 1; i < c; ++i) { const double s = L(i, k); L(i, k) = L(c, i); L(c, i) = s; }
-        }
-        if (k > 0) {
-            POSE_UNROLL for (int j = 0; j < k; ++j) temp[j] = L(j, j) * L(k, j);
-            double s = L(k, 0) * temp[0];
-            POSE_UNROLL for (int j = 1; j < k; ++j) s = s + L(k, j) * temp[j];
-            L(k, k) -= s;
-            POSE_UNROLL for (int i = k + 1; i < 6; ++i) {
-                double a = L(i, 0) * temp[0];
-                POSE_UNROLL for (int j = 1; j < k; ++j) a = a + L(i, j) * temp[j];
-                L(i, k) -= a;
-            }
-        }
-        const double akk = L(k, k);
-        const bool valid = fabs(akk) > 0.0;
-        if (k == 0 && !valid) { POSE_UNROLL for (int j = 0; j < 6; ++j) x[j] = 0.0; return true; }
-        if (valid)
-            POSE_UNROLL for (int i = k + 1; i < 6; ++i) L(i, k) /= akk;
-        if (sign == 1) { if (akk < 0) sign = 3; }
-        else if (sign == 2) { if (akk > 0) sign = 3; }
-        else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = 2; }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double y[6];
-    POSE_UNROLL for (int i = 0; i < 6; ++i) y[i] = b[i];
-    POSE_UNROLL for (int k = 0; k < 6; ++k)
-        POSE_UNROLL for (int c = k + 1; c < 6; ++c)
-            if (tr[k] == c) { const double s = y[k]; y[k] = y[c]; y[c] = s; }
-    POSE_UNROLL for (int i = 0; i < 6; ++i) POSE_UNROLL for (int j = 0; j < i; ++j) y[i] -= L(i, j) * y[j];
-    POSE_UNROLL for (int i = 0; i < 6; ++i) y[i] = (fabs(L(i, i)) > 2.2250738585072014e-308) ? y[i] / L(i, i) : 0.0;
-    POSE_UNROLL for (int i = 5; i >= 0; --i) POSE_UNROLL for (int j = i + 1; j < 6; ++j) y[i] -= L(j, i) * y[j];
-    POSE_UNROLL for (int k = 5; k >= 0; --k)
-        POSE_UNROLL for (int c = k + 1; c < 6; ++c)
-            if (tr[k] == c) { const double s = y[k]; y[k] = y[c]; y[c] = s; }
-    POSE_UNROLL for (int i = 0; i < 6; ++i) x[i] = y[i];
-#undef L
-    return true;
-}
-
 // ------------------------------------------------------------------ the edges
 
 struct Edge { double obs[3], Xw[3], info; int kind; };   // kind 0: no map point, 1: mono, 2: stereo
@@ -290,25 +184,14 @@ __device__ __forceinline__ double edge_chi2(const Edge &e, const double err[3])
 {
     const int D = e.kind == 2 ? 3 : 2;
     double oe[3];
-    POSE_UNROLL for (int i = 0; i < 3; ++i) {
+    ORBM_UNROLL for (int i = 0; i < 3; ++i) {
         double s = ((i == 0) ? e.info : 0.0) * err[0];
-        POSE_UNROLL for (int j = 1; j < 3; ++j) if (j < D) s += ((i == j) ? e.info : 0.0) * err[j];
+        ORBM_UNROLL for (int j = 1; j < 3; ++j) if (j < D) s += ((i == j) ? e.info : 0.0) * err[j];
         oe[i] = s;
     }
     double r = err[0] * oe[0];
-    POSE_UNROLL for (int i = 1; i < 3; ++i) if (i < D) r += err[i] * oe[i];
+    ORBM_UNROLL for (int i = 1; i < 3; ++i) if (i < D) r += err[i] * oe[i];
     return r;
-}
-
-__device__ __forceinline__ void huber(double e, double delta, double &rho0, double &rho1)   // RobustKernelHuber::robustify
-{
-    const float dsqr = (float)(delta * delta);
-    if (e <= dsqr) { rho0 = e; rho1 = 1.; }
-    else {
-        const double sqrte = sqrt(e);
-        rho0 = 2 * sqrte * delta - dsqr;
-        rho1 = delta / sqrte;
-    }
 }
 
 // linearizeOplus of both edges at the mapped point p
@@ -325,31 +208,7 @@ __device__ __forceinline__ void edge_jacobian(const PoseCam &c, int kind, const 
     }
 }
 
-// ------------------------------------------------------------------ fixed-order block reductions
-
-constexpr int NSYS = 21 + 6 + 1;    // lower triangle of H, A^T w omega e, robust chi2
-
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double (*red)[NSYS])
-{
-    for (int j = 0; j < NV; ++j)
-        for (int o = 32; o >= 1; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
-    __syncthreads();                                        // the previous reduction's readers are done with red
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int j = 0; j < NV; ++j) red[w][j] = v[j];
-    __syncthreads();
-    for (int j = 0; j < NV; ++j) v[j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
-}
-
-__device__ __forceinline__ int block_sum_int(int v, int *ired)
-{
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) ired[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ired[0] + ired[1] + ired[2] + ired[3];
-}
+constexpr int NSYS = 21 + 6 + 1;    // lower triangle of H, A^T w omega e, robust chi2 (the block sums: orbm_g2o_math.h)
 
 // SRC 0: keypoints from arrays, 1: from a resident frame, 2: resident frame + the map points of a search's result (chained)
 template <int SRC>
@@ -440,7 +299,7 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
         const int oct = FRAME ? src.fkp[s_inv[i]].octave : src.kps[base + i].octave;
         mine += (oct < 0 || oct >= cam.nlevels) ? (1 << 16) : 1;
     }
-    const int counts = block_sum_int(mine, s_ired);
+    const int counts = block_sum_int<PW>(mine, s_ired);
     if (counts >> 16) {
         if (tid == 0) { out.ngood[b] = ORBX_ERR_ARG; if (CHAIN) out.track[0] = TRACK_REJECTED; }
         return;
@@ -461,7 +320,7 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
             const bool takes = q >= 0 ? src.pt_takes[q] != 0 : (!src.base_takes || src.base_takes[i] != 0);
             mine += 1 + (takes ? (1 << 16) : 0);
         }
-        const int c = block_sum_int(mine, s_ired);
+        const int c = block_sum_int<PW>(mine, s_ired);
         if (tid == 0) { out.track[0] = TRACK_SOLVED; out.track[1] = c & 0xffff; out.track[2] = c >> 16; }
     };
 
@@ -509,21 +368,21 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
                 edge_jacobian(cam, e.kind, p, J);
                 const int D = e.kind == 2 ? 3 : 2;
                 const double winfo = w * e.info;
-                POSE_UNROLL for (int r = 0; r < 6; ++r) {
+                ORBM_UNROLL for (int r = 0; r < 6; ++r) {
                     double s = 0;
-                    POSE_UNROLL for (int ii = 0; ii < 3; ++ii) if (ii < D) s += J[6 * ii + r] * (e.info * err[ii]);
+                    ORBM_UNROLL for (int ii = 0; ii < 3; ++ii) if (ii < D) s += J[6 * ii + r] * (e.info * err[ii]);
                     v[21 + r] += w * s;
-                    POSE_UNROLL for (int c = 0; c <= r; ++c) {
+                    ORBM_UNROLL for (int c = 0; c <= r; ++c) {
                         double hh = 0;
-                        POSE_UNROLL for (int ii = 0; ii < 3; ++ii) if (ii < D) hh += J[6 * ii + r] * (winfo * J[6 * ii + c]);
+                        ORBM_UNROLL for (int ii = 0; ii < 3; ++ii) if (ii < D) hh += J[6 * ii + r] * (winfo * J[6 * ii + c]);
                         v[r * (r + 1) / 2 + c] += hh;
                     }
                 }
             }
-            if (sys) block_sum<NSYS>(v, s_red);
+            if (sys) block_sum<NSYS, PW>(v, s_red);
             else {
                 double c1[1] = {v[27]};
-                block_sum<1>(c1, s_red);
+                block_sum<1, PW>(c1, s_red);
                 v[27] = c1[0];
             }
         };
@@ -555,7 +414,7 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
                     double Hl[36], x[6] = {0, 0, 0, 0, 0, 0};
                     for (int j = 0; j < 36; ++j) Hl[j] = H[j];
                     for (int j = 0; j < 6; ++j) Hl[7 * j] += lambda;
-                    const bool ok2 = ldlt_solve6(Hl, bb, x);
+                    const bool ok2 = ldlt_solve<6, LdltZeroDiagonal::ReturnZero>(Hl, bb, x);
                     Se3 up, trial;
                     se3_exp(x, up);
                     se3_compose(up, est, trial);
@@ -607,7 +466,7 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
             if (chi2 > (e.kind == 2 ? chi2Stereo : chi2Mono)) { lvl |= 1u << k; bad++; }
             else lvl &= ~(1u << k);
         }
-        nBad = block_sum_int(bad, s_ired);
+        nBad = block_sum_int<PW>(bad, s_ired);
         if (nInitial < 10) break;                                       // optimizer.edges().size() < 10
     }
 

@@ -367,8 +367,7 @@ int orbm_sim3_hypotheses(const orbm_sim3_problem *problems, int P, const float *
             if (a < 0 || a >= q.n || b < 0 || b >= q.n || c < 0 || c >= q.n) ORBX_FAIL(ORBX_ERR_ARG, "triple index out of range");
             if (a == b || a == c || b == c) ORBX_FAIL(ORBX_ERR_ARG, "a triple repeats an index");
         }
-        for (int i = 0; i < q.n; ++i)
-            if (q.octave1[i] < 0 || q.octave1[i] >= nlevels || q.octave2[i] < 0 || q.octave2[i] >= nlevels) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
+        if (!octaves_in_range(q, nlevels)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
         total += q.H;
         max_n = std::max(max_n, (int)q.n);
     }
@@ -383,16 +382,8 @@ int orbm_sim3_hypotheses(const orbm_sim3_problem *problems, int P, const float *
         memset(&d, 0, sizeof(d));
         d.n = q.n; d.H = q.H; d.fix_scale = q.fix_scale ? 1 : 0;
         if (q.H == 0) continue;
-        const size_t n = (size_t)q.n;
-        d.o_X1w = (unsigned)sc.in(q.X1w, sizeof(float) * 3 * n); d.o_X2w = (unsigned)sc.in(q.X2w, sizeof(float) * 3 * n);
-        d.o_oct1 = (unsigned)sc.in(q.octave1, sizeof(int32_t) * n); d.o_oct2 = (unsigned)sc.in(q.octave2, sizeof(int32_t) * n);
+        stage_two_keyframes(sc, q, d);
         d.o_tri = (unsigned)sc.in(q.triples, sizeof(int32_t) * 3 * (size_t)q.H);
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) { d.R1[3 * r + c] = q.Tcw1[4 * r + c]; d.R2[3 * r + c] = q.Tcw2[4 * r + c]; }
-            d.t1[r] = q.Tcw1[4 * r + 3]; d.t2[r] = q.Tcw2[4 * r + 3];
-        }
-        d.cam1[0] = q.fx1; d.cam1[1] = q.fy1; d.cam1[2] = q.cx1; d.cam1[3] = q.cy1;
-        d.cam2[0] = q.fx2; d.cam2[1] = q.fy2; d.cam2[2] = q.cx2; d.cam2[3] = q.cy2;
     }
     for (int p = 0; p < P; ++p) {
         Sim3Dev &d = dev[p];
@@ -410,7 +401,7 @@ int orbm_sim3_hypotheses(const orbm_sim3_problem *problems, int P, const float *
         h0 += d.H;
         if (d.H) d.o_mask = (unsigned)sc.out(sizeof(uint64_t) * (size_t)d.H * (size_t)((d.n + 63) / 64));
     }
-    if (sc.w.used > 0xffffffffu) ORBX_FAIL(ORBX_ERR_CAPACITY, "the call's arrays exceed 4 GiB");
+    if (!sc.offsets_fit_32_bits()) ORBX_FAIL(ORBX_ERR_CAPACITY, "the call's arrays exceed 4 GiB");
     if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
     hipLaunchKernelGGL(k_sim3_prepare, dim3((unsigned)((max_n + MT - 1) / MT), (unsigned)P), dim3(MT), 0, sc.stream(), sc.d<const Sim3Dev>(o_dev),
                        sc.d<char>(0), sc.d<const float>(o_sg));

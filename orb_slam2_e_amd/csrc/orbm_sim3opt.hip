@@ -12,10 +12,11 @@
 // tree (wave butterfly, then the waves in order): no atomics, and a problem's bits do not depend on the batch around it.  The
 // 7 x 7 LDLT, Sim3(update), the compose and the inverse are computed by every lane from the same reduced values (identical bits in
 // every lane: wave-uniform without a broadcast barrier).  A pair's constants are staged once, in LDS for the first SO_LDS_PAIRS
-// pairs and in the workspace beyond.  The quaternion / LDLT / Huber helpers are orbm_pose.hip's, copied: that kernel's register
-// allocation stays as it is.
+// pairs and in the workspace beyond.  The quaternion / LDLT / Huber helpers and the reductions are the ones orbm_pose.hip uses
+// (orbm_g2o_math.h).
 #include <atomic>
 
+#include "orbm_g2o_math.h"
 #include "orbm_internal.h"
 
 using namespace orbm_detail;
@@ -43,54 +44,6 @@ struct Sim3OptDev {
 
 struct PairC { float v[12]; };          // Xc1 [3], Xc2 [3], obs1 [2], obs2 [2], info1, info2
 
-#define SO_UNROLL _Pragma("unroll")
-
-// ------------------------------------------------------------------ Eigen, in the restatement's operation order (as orbm_pose.hip)
-
-template <int I>
-__host__ __device__ __forceinline__ void quat_from_matrix_diag(const double R[9], double q[4])
-{
-#define M(i, j) R[3 * (i) + (j)]
-    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
-    double t = sqrt(M(I, I) - M(J, J) - M(K, K) + 1.0);
-    q[I] = 0.5 * t;
-    t = 0.5 / t;
-    q[3] = (M(K, J) - M(J, K)) * t;
-    q[J] = (M(J, I) + M(I, J)) * t;
-    q[K] = (M(K, I) + M(I, K)) * t;
-#undef M
-}
-
-__host__ __device__ inline void quat_from_matrix(const double R[9], double q[4])   // Quaterniond(const Matrix3d&): not normalised
-{
-#define M(i, j) R[3 * (i) + (j)]
-    double t = M(0, 0) + M(1, 1) + M(2, 2);
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (M(2, 1) - M(1, 2)) * t;
-        q[1] = (M(0, 2) - M(2, 0)) * t;
-        q[2] = (M(1, 0) - M(0, 1)) * t;
-    } else {
-        int i = 0;
-        if (M(1, 1) > M(0, 0)) i = 1;
-        if (M(2, 2) > (i == 1 ? M(1, 1) : M(0, 0))) i = 2;
-        if (i == 0) quat_from_matrix_diag<0>(R, q);
-        else if (i == 1) quat_from_matrix_diag<1>(R, q);
-        else quat_from_matrix_diag<2>(R, q);
-    }
-#undef M
-}
-
-__device__ __forceinline__ void q_rotate(const double q[4], const double v[3], double o[3])   // Quaternion * Vector3d
-{
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    SO_UNROLL for (int i = 0; i < 3; ++i) o[i] = v[i] + q[3] * uv[i] + c[i];
-}
-
 // ------------------------------------------------------------------ sim3.h
 
 __host__ __device__ inline void sim3_from_rts(const float *R, const float *t, float s, Sim3 &o)   // :64-67 from the float inputs
@@ -109,8 +62,8 @@ __device__ void sim3_exp(const double u[7], Sim3 &o)   // Sim3(const Vector7d&),
     const double Om[9] = {0., -w2, w1, w2, 0., -w0, -w1, w0, 0.};
     const double s = exp(sigma);
     double O2[9], R[9], A, B, C;
-    SO_UNROLL for (int i = 0; i < 3; ++i)
-        SO_UNROLL for (int j = 0; j < 3; ++j) O2[3 * i + j] = Om[3 * i] * Om[j] + Om[3 * i + 1] * Om[3 + j] + Om[3 * i + 2] * Om[6 + j];
+    ORBM_UNROLL for (int i = 0; i < 3; ++i)
+        ORBM_UNROLL for (int j = 0; j < 3; ++j) O2[3 * i + j] = Om[3 * i] * Om[j] + Om[3 * i + 1] * Om[3 + j] + Om[3 * i + 2] * Om[6 + j];
     const double eps = 0.00001;
     const bool small_theta = theta < eps;
     if (fabs(sigma) < eps) {
@@ -134,15 +87,15 @@ __device__ void sim3_exp(const double u[7], Sim3 &o)   // Sim3(const Vector7d&),
         }
     }
     if (small_theta) {      // the first-order rotation: not orthogonal, and its quaternion is taken unnormalised
-        SO_UNROLL for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + Om[k] + O2[k];
+        ORBM_UNROLL for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + Om[k] + O2[k];
     } else {
         const double ra = sin(theta) / theta, rb = (1 - cos(theta)) / (theta * theta);
-        SO_UNROLL for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + ra * Om[k] + rb * O2[k];
+        ORBM_UNROLL for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + ra * Om[k] + rb * O2[k];
     }
     quat_from_matrix(R, o.q);
     double W[9];
-    SO_UNROLL for (int k = 0; k < 9; ++k) W[k] = A * Om[k] + B * O2[k] + C * ((k % 4 == 0) ? 1.0 : 0.0);
-    SO_UNROLL for (int i = 0; i < 3; ++i) o.t[i] = W[3 * i] * u[3] + W[3 * i + 1] * u[4] + W[3 * i + 2] * u[5];
+    ORBM_UNROLL for (int k = 0; k < 9; ++k) W[k] = A * Om[k] + B * O2[k] + C * ((k % 4 == 0) ? 1.0 : 0.0);
+    ORBM_UNROLL for (int i = 0; i < 3; ++i) o.t[i] = W[3 * i] * u[3] + W[3 * i + 1] * u[4] + W[3 * i + 2] * u[5];
     o.s = s;
 }
 
@@ -156,7 +109,7 @@ __device__ __forceinline__ void sim3_mul(const Sim3 &A, const Sim3 &B, Sim3 &O) 
     r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
     r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
     q_rotate(A.q, B.t, rt);
-    SO_UNROLL for (int k = 0; k < 3; ++k) r.t[k] = A.s * rt[k] + A.t[k];
+    ORBM_UNROLL for (int k = 0; k < 3; ++k) r.t[k] = A.s * rt[k] + A.t[k];
     r.s = A.s * B.s;
     O = r;
 }
@@ -178,7 +131,7 @@ __device__ __forceinline__ void edge_error(const Sim3 &S, const double X[3], con
 {
     double p[3];
     q_rotate(S.q, X, p);
-    SO_UNROLL for (int k = 0; k < 3; ++k) p[k] = S.s * p[k] + S.t[k];
+    ORBM_UNROLL for (int k = 0; k < 3; ++k) p[k] = S.s * p[k] + S.t[k];
     const double u = p[0] / p[2], v = p[1] / p[2];
     e[0] = obs[0] - (u * (double)cam[0] + (double)cam[2]);
     e[1] = obs[1] - (v * (double)cam[1] + (double)cam[3]);
@@ -188,114 +141,6 @@ __device__ __forceinline__ double edge_chi2(double info, const double e[2])   //
 {
     const double o0 = info * e[0] + 0.0 * e[1], o1 = 0.0 * e[0] + info * e[1];
     return e[0] * o0 + e[1] * o1;
-}
-
-__device__ __forceinline__ void huber(double e, double delta, double &rho0, double &rho1)   // RobustKernelHuber::robustify
-{
-    const float dsqr = (float)(delta * delta);
-    if (e <= dsqr) { rho0 = e; rho1 = 1.; }
-    else {
-        const double sqrte = sqrt(e);
-        rho0 = 2 * sqrte * delta - dsqr;
-        rho1 = delta / sqrte;
-    }
-}
-
-// Eigen::LDLT (Eigen 3.3 ldlt_inplace: diagonal pivoting, lower triangle) + solve; returns isPositive().  Every loop has constant
-// bounds and the pivot swaps are selects over the constant candidates, so the matrix stays in registers.
-template <int N>
-__device__ bool ldlt_solve(double (&m)[N * N], const double (&b)[N], double (&x)[N])
-{
-    int tr[N];
-    int sign = 0;   // 0 ZeroSign, 1 PositiveSemiDef, 2 NegativeSemiDef, 3 Indefinite
-    double temp[N];
-#define L(i, j) m[N * (i) + (j)]
-    bool zero_diagonal = false;     // Eigen's "the entire diagonal is zero" exit at k = 0: ZeroSign, identity transpositions, the matrix as
-                                    // it is -- also taken by a NaN matrix, whose solve below then gives NaN (orbm_pose.hip returns 0 there)
-    SO_UNROLL for (int k = 0; k < N; ++k) {
-        if (zero_diagonal) { tr[k] = k; continue; }
-        int big = k;
-        double bv = fabs(L(k, k));
-        SO_UNROLL for (int j = k + 1; j < N; ++j) {
-            const double f = fabs(L(j, j));
-            if (f > bv) { big = j; bv = f; }
-        }
-        tr[k] = big;
-        SO_UNROLL for (int c = k + 1; c < N; ++c) {
-            if (big != c) continue;
-            SO_UNROLL for (int j = 0; j < k; ++j) { const double s = L(k, j); L(k, j) = L(c, j); L(c, j) = s; }
-            SO_UNROLL for (int i = c + 1; i < N; ++i) { const double s = L(i, k); L(i, k) = L(i, c); L(i, c) = s; }
-            { const double s = L(k, k); L(k, k) = L(c, c); L(c, c) = s; }
-            SO_UNROLL for (int i = k + 1; i < c; ++i) { const double s = L(i, k); L(i, k) = L(c, i); L(c, i) = s; }
-        }
-        if (k > 0) {
-            SO_UNROLL for (int j = 0; j < k; ++j) temp[j] = L(j, j) * L(k, j);
-            double s = L(k, 0) * temp[0];
-            SO_UNROLL for (int j = 1; j < k; ++j) s = s + L(k, j) * temp[j];
-            L(k, k) -= s;
-            SO_UNROLL for (int i = k + 1; i < N; ++i) {
-                double a = L(i, 0) * temp[0];
-                SO_UNROLL for (int j = 1; j < k; ++j) a = a + L(i, j) * temp[j];
-                L(i, k) -= a;
-            }
-        }
-        const double akk = L(k, k);
-        const bool valid = fabs(akk) > 0.0;
-        if (k == 0 && !valid) { zero_diagonal = true; continue; }
-        if (valid)
-            SO_UNROLL for (int i = k + 1; i < N; ++i) L(i, k) /= akk;
-        if (sign == 1) { if (akk < 0) sign = 3; }
-        else if (sign == 2) { if (akk > 0) sign = 3; }
-        else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = 2; }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double y[N];
-    SO_UNROLL for (int i = 0; i < N; ++i) y[i] = b[i];
-    SO_UNROLL for (int k = 0; k < N; ++k)
-        SO_UNROLL for (int c = k + 1; c < N; ++c)
-            if (tr[k] == c) { const double s = y[k]; y[k] = y[c]; y[c] = s; }
-    SO_UNROLL for (int i = 0; i < N; ++i) SO_UNROLL for (int j = 0; j < i; ++j) y[i] -= L(i, j) * y[j];
-    SO_UNROLL for (int i = 0; i < N; ++i) y[i] = (fabs(L(i, i)) > 2.2250738585072014e-308) ? y[i] / L(i, i) : 0.0;
-    SO_UNROLL for (int i = N - 1; i >= 0; --i) SO_UNROLL for (int j = i + 1; j < N; ++j) y[i] -= L(j, i) * y[j];
-    SO_UNROLL for (int k = N - 1; k >= 0; --k)
-        SO_UNROLL for (int c = k + 1; c < N; ++c)
-            if (tr[k] == c) { const double s = y[k]; y[k] = y[c]; y[c] = s; }
-    SO_UNROLL for (int i = 0; i < N; ++i) x[i] = y[i];
-#undef L
-    return true;
-}
-
-// ------------------------------------------------------------------ fixed-order block reductions (NW waves)
-
-template <int NV, int NW>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double (*red)[SO_NSYS])
-{
-    for (int j = 0; j < NV; ++j)
-        for (int o = 32; o >= 1; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
-    if (NW == 1) return;
-    __syncthreads();                                        // the previous reduction's readers are done with red
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int j = 0; j < NV; ++j) red[w][j] = v[j];
-    __syncthreads();
-    for (int j = 0; j < NV; ++j) {
-        double s = red[0][j];
-        SO_UNROLL for (int k = 1; k < NW; ++k) s = s + red[k][j];
-        v[j] = s;
-    }
-}
-
-template <int NW>
-__device__ __forceinline__ int block_sum_int(int v, int *ired)
-{
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (NW == 1) return v;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) ired[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = ired[0];
-    SO_UNROLL for (int k = 1; k < NW; ++k) s += ired[k];
-    return s;
 }
 
 // NT: a multiple of 64 (the reductions are written for any number of waves; the library instantiates SO_NT)
@@ -322,8 +167,8 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
     res.ncorrespondences = n;
     auto store = [&](const Sim3 &S) {
         if (tid != 0) return;
-        SO_UNROLL for (int k = 0; k < 4; ++k) res.q[k] = S.q[k];
-        SO_UNROLL for (int k = 0; k < 3; ++k) res.t[k] = S.t[k];
+        ORBM_UNROLL for (int k = 0; k < 4; ++k) res.q[k] = S.q[k];
+        ORBM_UNROLL for (int k = 0; k < 3; ++k) res.t[k] = S.t[k];
         res.s = S.s;
         results[blockIdx.x] = res;
     };
@@ -336,7 +181,7 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
         const int *l1 = reinterpret_cast<const int *>(ws + d.o_oct1), *l2 = reinterpret_cast<const int *>(ws + d.o_oct2);
         for (int i = tid; i < n; i += NT) {
             PairC c;
-            SO_UNROLL for (int r = 0; r < 3; ++r) {
+            ORBM_UNROLL for (int r = 0; r < 3; ++r) {
                 const float a = d.R1[3 * r] * X1[3 * i] + d.R1[3 * r + 1] * X1[3 * i + 1] + d.R1[3 * r + 2] * X1[3 * i + 2];
                 const float b = d.R2[3 * r] * X2[3 * i] + d.R2[3 * r + 1] * X2[3 * i + 1] + d.R2[3 * r + 2] * X2[3 * i + 2];
                 c.v[r] = (float)((double)a * 1.0 + (double)d.t1[r] * 1.0);
@@ -397,15 +242,15 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
             s_J[dd][tid] = scalar * (ep[0] - em[0]);
             s_J[7 + dd][tid] = scalar * (ep[1] - em[1]);
         }
-        SO_UNROLL for (int dd = 0; dd < 7; ++dd) { J0[dd] = s_J[dd][tid]; J1[dd] = s_J[7 + dd][tid]; }   // (its own thread wrote them: no barrier)
+        ORBM_UNROLL for (int dd = 0; dd < 7; ++dd) { J0[dd] = s_J[dd][tid]; J1[dd] = s_J[7 + dd][tid]; }   // (its own thread wrote them: no barrier)
         double rho0, w;
         huber(edge_chi2(info, e), delta_h, rho0, w);
         v[35] += rho0;
         const double winfo = w * info;
         const double r0 = -(info * e[0]) * w, r1 = -(info * e[1]) * w;
-        SO_UNROLL for (int r = 0; r < 7; ++r) {
+        ORBM_UNROLL for (int r = 0; r < 7; ++r) {
             v[28 + r] += J0[r] * r0 + J1[r] * r1;
-            SO_UNROLL for (int c = 0; c <= r; ++c) v[r * (r + 1) / 2 + c] += J0[r] * (winfo * J0[c]) + J1[r] * (winfo * J1[c]);
+            ORBM_UNROLL for (int c = 0; c <= r; ++c) v[r * (r + 1) / 2 + c] += J0[r] * (winfo * J0[c]) + J1[r] * (winfo * J1[c]);
         }
     };
 
@@ -422,7 +267,7 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
             if (tid < 14) {
                 double u[7] = {0, 0, 0, 0, 0, 0, 0};
                 const double step = (tid & 1) ? -1e-9 : 1e-9;
-                SO_UNROLL for (int k = 0; k < 7; ++k) if ((tid >> 1) == k) u[k] = step;
+                ORBM_UNROLL for (int k = 0; k < 7; ++k) if ((tid >> 1) == k) u[k] = step;
                 if (d.fix_scale) u[6] = 0;                              // oplusImpl, also inside the numeric Jacobian
                 Sim3 up, pe, pi;
                 sim3_exp(u, up);
@@ -434,7 +279,7 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
             Sim3 inv;
             sim3_inverse(est, inv);
             double v[SO_NSYS];
-            SO_UNROLL for (int j = 0; j < SO_NSYS; ++j) v[j] = 0.0;
+            ORBM_UNROLL for (int j = 0; j < SO_NSYS; ++j) v[j] = 0.0;
             for (int i = tid; i < n; i += NT) {
                 if (!kept[i]) continue;
                 const PairC c = pair(i);
@@ -448,10 +293,10 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
             double currentChi = v[35];
             const double iniChi = currentChi;
             double bb[7];                                               // (H stays packed in v: the lower triangle is all the LDLT reads)
-            SO_UNROLL for (int r = 0; r < 7; ++r) bb[r] = v[28 + r];
+            ORBM_UNROLL for (int r = 0; r < 7; ++r) bb[r] = v[28 + r];
             if (iteration == 0) {                                       // computeLambdaInit, tau = 1e-5
                 double maxDiagonal = 0.;
-                SO_UNROLL for (int j = 0; j < 7; ++j) { const double f = fabs(v[j * (j + 1) / 2 + j]); maxDiagonal = (f < maxDiagonal) ? maxDiagonal : f; }
+                ORBM_UNROLL for (int j = 0; j < 7; ++j) { const double f = fabs(v[j * (j + 1) / 2 + j]); maxDiagonal = (f < maxDiagonal) ? maxDiagonal : f; }
                 lambda = 1e-5 * maxDiagonal;
                 ni = 2;
                 lmBad = 0;
@@ -460,10 +305,10 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
             int qmax = 0;
             do {
                 double Hl[49], x[7] = {0, 0, 0, 0, 0, 0, 0};
-                SO_UNROLL for (int r = 0; r < 7; ++r)
-                    SO_UNROLL for (int c = 0; c < 7; ++c) Hl[7 * r + c] = c <= r ? v[r * (r + 1) / 2 + c] : 0.0;
-                SO_UNROLL for (int j = 0; j < 7; ++j) Hl[8 * j] += lambda;
-                const bool ok2 = ldlt_solve<7>(Hl, bb, x);
+                ORBM_UNROLL for (int r = 0; r < 7; ++r)
+                    ORBM_UNROLL for (int c = 0; c < 7; ++c) Hl[7 * r + c] = c <= r ? v[r * (r + 1) / 2 + c] : 0.0;
+                ORBM_UNROLL for (int j = 0; j < 7; ++j) Hl[8 * j] += lambda;
+                const bool ok2 = ldlt_solve<7, LdltZeroDiagonal::AsEigen>(Hl, bb, x);
                 if (d.fix_scale) x[6] = 0;                              // oplusImpl writes into the solver's x
                 Sim3 up, trial;
                 sim3_exp(x, up);
@@ -473,7 +318,7 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
                 if (!ok2) tempChi = 1.7976931348623157e308;
                 rho = (currentChi - tempChi);
                 double scale = 0.;
-                SO_UNROLL for (int j = 0; j < 7; ++j) scale += x[j] * (lambda * x[j] + bb[j]);
+                ORBM_UNROLL for (int j = 0; j < 7; ++j) scale += x[j] * (lambda * x[j] + bb[j]);
                 scale += 1e-3;
                 rho /= scale;
                 if (rho > 0 && isfinite(tempChi)) {
@@ -552,8 +397,7 @@ int orbm_optimize_sim3(const orbm_sim3_opt_problem *problems, int P, const float
         if (q.n == 0) continue;
         if (!q.X1w || !q.X2w || !q.obs1 || !q.obs2 || !q.octave1 || !q.octave2 || !q.Tcw1 || !q.Tcw2 || !inv_level_sigma2 || nlevels < 1 || !kept)
             ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-        for (int i = 0; i < q.n; ++i)
-            if (q.octave1[i] < 0 || q.octave1[i] >= nlevels || q.octave2[i] < 0 || q.octave2[i] >= nlevels) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
+        if (!octaves_in_range(q, nlevels)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
         total += (size_t)q.n;
     }
     for (int p = 0; p < P; ++p) {               // what a problem without a correspondence returns (:1595 with nothing optimised)
@@ -578,23 +422,16 @@ int orbm_optimize_sim3(const orbm_sim3_opt_problem *problems, int P, const float
         d.n = q.n; d.fix_scale = q.fix_scale ? 1 : 0; d.th2 = q.th2; d.s12 = q.s12;
         memcpy(d.R12, q.R12, sizeof(d.R12)); memcpy(d.t12, q.t12, sizeof(d.t12));
         if (q.n == 0) continue;
+        stage_two_keyframes(sc, q, d);
         const size_t n = (size_t)q.n;
-        d.o_X1w = (unsigned)sc.in(q.X1w, sizeof(float) * 3 * n); d.o_X2w = (unsigned)sc.in(q.X2w, sizeof(float) * 3 * n);
         d.o_obs1 = (unsigned)sc.in(q.obs1, sizeof(float) * 2 * n); d.o_obs2 = (unsigned)sc.in(q.obs2, sizeof(float) * 2 * n);
-        d.o_oct1 = (unsigned)sc.in(q.octave1, sizeof(int32_t) * n); d.o_oct2 = (unsigned)sc.in(q.octave2, sizeof(int32_t) * n);
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) { d.R1[3 * r + c] = q.Tcw1[4 * r + c]; d.R2[3 * r + c] = q.Tcw2[4 * r + c]; }
-            d.t1[r] = q.Tcw1[4 * r + 3]; d.t2[r] = q.Tcw2[4 * r + 3];
-        }
-        d.cam1[0] = q.fx1; d.cam1[1] = q.fy1; d.cam1[2] = q.cx1; d.cam1[3] = q.cy1;
-        d.cam2[0] = q.fx2; d.cam2[1] = q.fy2; d.cam2[2] = q.cx2; d.cam2[3] = q.cy2;
     }
     for (int p = 0; p < P; ++p)
         if (dev[p].n > SO_LDS_PAIRS) dev[p].o_pair = (unsigned)sc.scratch(sizeof(PairC) * (size_t)(dev[p].n - SO_LDS_PAIRS));
     const size_t o_res = sc.out(sizeof(orbm_sim3_opt_result) * (size_t)P);
     for (int p = 0; p < P; ++p)
         if (dev[p].n) dev[p].o_kept = (unsigned)sc.out((size_t)dev[p].n);
-    if (sc.w.used > 0xffffffffu) ORBX_FAIL(ORBX_ERR_CAPACITY, "the call's arrays exceed 4 GiB");
+    if (!sc.offsets_fit_32_bits()) ORBX_FAIL(ORBX_ERR_CAPACITY, "the call's arrays exceed 4 GiB");
     if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
     hipLaunchKernelGGL(k_sim3_optimize<SO_NT>, dim3((unsigned)P), dim3(SO_NT), 0, sc.stream(), sc.d<const Sim3OptDev>(o_dev), sc.d<char>(0),
                        sc.d<const float>(o_sg), sc.d<orbm_sim3_opt_result>(o_res));

@@ -1,18 +1,16 @@
 """ctypes wrapper of tests/create_points_oracle.c, the CPU restatement of the per-pair arithmetic of
 LocalMapping::CreateNewMapPoints, and the loop over the neighbours around it and the oracle's literal SearchForTriangulation
-(test infrastructure: never part of the product).  The C file is compiled on first use into a per-user cache directory, as
-tests/pose_only_oracle.py builds its file.
+(test infrastructure: never part of the product).  The C file is compiled on first use into a per-user cache directory
+(tests/c_oracle.py).
 
 No OpenCV exists for this project to run, so the restated cv::SVD (JacobiSVDImpl_<float>) is unpinned like the other OpenCV
 primitives; tests/test_cpu_create_points.py checks it from first principles against numpy in float64."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import c_oracle
 import oracle
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -32,17 +30,7 @@ RESULT_DTYPE = np.dtype([("status", "i4"), ("from_svd", "i4"), ("sweeps", "i4"),
 def lib():
     global _LIB
     if _LIB is None:
-        src = open(_SRC, "rb").read()
-        tag = hashlib.sha256(src).hexdigest()[:16]
-        d = os.path.join(tempfile.gettempdir(), f"orbslam_create_points_oracle_{os.getuid()}")
-        os.makedirs(d, exist_ok=True)
-        so = os.path.join(d, f"create_points_oracle_{tag}.so")
-        if not os.path.exists(so):
-            tmp = so + f".{os.getpid()}.tmp"
-            subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-std=c99", "-shared", "-fPIC", "-o", tmp,
-                                   _SRC, "-lm"])
-            os.replace(tmp, so)
-        L = C.CDLL(so)
+        L = C.CDLL(c_oracle.build(_SRC))
         vp = C.c_void_p
         L.cpo_pairs.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_float, vp]
         L.cpo_pairs.restype = None

@@ -4,7 +4,8 @@
  * VertexSE3Expmap, N unary EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose edges with Huber kernels,
  * BlockSolver_6_3 over LinearSolverDense, OptimizationAlgorithmLevenberg, 4 rounds x 10 iterations with the inlier / outlier
  * reclassification between rounds.  Plain C99, double throughout (float where the reference has float).  Each function names the
- * reference lines it follows (Thirdparty/g2o/g2o/...); the few Eigen routines involved are restated and named where used.
+ * reference lines it follows (Thirdparty/g2o/g2o/...); the few Eigen routines involved are restated and named where used, those the
+ * OptimizeSim3 restatement needs too in tests/g2o_restated.h.
  * tests/pose_only_oracle.py compiles this file and wraps it with ctypes; the device kernel (orbm_pose.hip) is checked against it.
  *
  * Sums over edges run in edge order (= keypoint order: SparseOptimizer::sortVectorContainers sorts _activeEdges by id,
@@ -13,6 +14,8 @@
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
+
+#include "g2o_restated.h"
 
 typedef struct { double q[4]; double t[3]; } po_se3;   /* q = x y z w (Eigen's coeffs() order) */
 
@@ -46,32 +49,8 @@ static void normalize_rotation(double q[4])
     q_normalize(q);
 }
 
-/* Quaterniond(const Matrix3d&) (Eigen quaternionbase_assign_substitute_pair), R row major */
-void po_quat_from_matrix(const double R[9], double q[4])
-{
-#define M(i, j) R[3 * (i) + (j)]
-    double t = M(0, 0) + M(1, 1) + M(2, 2);
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (M(2, 1) - M(1, 2)) * t;
-        q[1] = (M(0, 2) - M(2, 0)) * t;
-        q[2] = (M(1, 0) - M(0, 1)) * t;
-    } else {
-        int i = 0;
-        if (M(1, 1) > M(0, 0)) i = 1;
-        if (M(2, 2) > M(i, i)) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(M(i, i) - M(j, j) - M(k, k) + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (M(k, j) - M(j, k)) * t;
-        q[j] = (M(j, i) + M(i, j)) * t;
-        q[k] = (M(k, i) + M(i, k)) * t;
-    }
-#undef M
-}
+/* Quaterniond(const Matrix3d&), R row major (tests/g2o_restated.h, as the quaternion product and rotation below) */
+void po_quat_from_matrix(const double R[9], double q[4]) { quat_from_matrix(R, q); }
 
 /* QuaternionBase::toRotationMatrix (Eigen), R row major */
 void po_quat_to_matrix(const double q[4], double R[9])
@@ -84,24 +63,6 @@ void po_quat_to_matrix(const double q[4], double R[9])
     R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
     R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
     R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
-/* Quaternion * Vector3d (Eigen _transformVector): uv = vec x v; uv += uv; v + w uv + vec x uv */
-static void q_rotate(const double q[4], const double v[3], double o[3])
-{
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    for (int i = 0; i < 3; ++i) o[i] = v[i] + q[3] * uv[i] + c[i];
-}
-
-/* Quaternion product a * b (Eigen quat_product) */
-static void q_mul(const double a[4], const double b[4], double o[4])
-{
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
 }
 
 /* SE3Quat::map (se3quat.h): r * xyz + t */
@@ -174,63 +135,12 @@ void po_to_cv(const po_se3 *s, float T[16])
     T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
 }
 
-/* Eigen::LDLT<MatrixXd> (ldlt_inplace, Eigen 3.3: diagonal pivoting on the lower triangle) of the n x n (n <= 6) row-major A, then
- * solve(b) and isPositive() (linear_solver_dense.h:104-110).  Returns isPositive(); x is written only then. */
+/* LinearSolverDense's LDLT of the n x n (n <= 6) row-major A (A is not changed); x = 0 where the diagonal has no entry to pivot on */
 int po_ldlt_solve(const double *A, const double *b, int n, double *x)
 {
     double m[36];
-    int tr[6];
     memcpy(m, A, sizeof(double) * n * n);
-#define L(i, j) m[6 * 0 + (i) * n + (j)]
-    enum { ZERO = 0, POS = 1, NEG = 2, INDEF = 3 };
-    int sign = ZERO, found_zero = 0;
-    double temp[6];
-    for (int k = 0; k < n; ++k) {
-        int big = k;                                   /* diagonal().tail(n-k).cwiseAbs().maxCoeff(&index) */
-        for (int j = k + 1; j < n; ++j)
-            if (fabs(L(j, j)) > fabs(L(big, big))) big = j;
-        tr[k] = big;
-        if (k != big) {
-            for (int j = 0; j < k; ++j) { const double s = L(k, j); L(k, j) = L(big, j); L(big, j) = s; }
-            for (int i = big + 1; i < n; ++i) { const double s = L(i, k); L(i, k) = L(i, big); L(i, big) = s; }
-            { const double s = L(k, k); L(k, k) = L(big, big); L(big, big) = s; }
-            for (int i = k + 1; i < big; ++i) { const double s = L(i, k); L(i, k) = L(big, i); L(big, i) = s; }
-        }
-        const int rs = n - k - 1;
-        if (k > 0) {
-            for (int j = 0; j < k; ++j) temp[j] = L(j, j) * L(k, j);
-            double s = 0;
-            for (int j = 0; j < k; ++j) s = (j == 0) ? L(k, 0) * temp[0] : s + L(k, j) * temp[j];
-            L(k, k) -= s;
-            for (int i = k + 1; i < n; ++i) {
-                double a = 0;
-                for (int j = 0; j < k; ++j) a = (j == 0) ? L(i, 0) * temp[0] : a + L(i, j) * temp[j];
-                L(i, k) -= a;
-            }
-        }
-        const double akk = L(k, k);
-        const int valid = fabs(akk) > 0.0;
-        if (k == 0 && !valid) { for (int j = 0; j < n; ++j) x[j] = 0.0; return 1; }   /* zero diagonal: ZeroSign, isPositive(); D^-1 = 0 */
-        if (rs > 0 && valid)
-            for (int i = k + 1; i < n; ++i) L(i, k) /= akk;
-        if (!valid) found_zero = 1;
-        if (sign == POS) { if (akk < 0) sign = INDEF; }
-        else if (sign == NEG) { if (akk > 0) sign = INDEF; }
-        else if (sign == ZERO) { if (akk > 0) sign = POS; else if (akk < 0) sign = NEG; }
-    }
-    (void)found_zero;
-    if (!(sign == POS || sign == ZERO)) return 0;
-    /* LDLT::solve: x = P b; L^-1; D^-1 (|d| > DBL_MIN, else 0); L^-T; P^T */
-    double y[6];
-    memcpy(y, b, sizeof(double) * n);
-    for (int k = 0; k < n; ++k) if (tr[k] != k) { const double s = y[k]; y[k] = y[tr[k]]; y[tr[k]] = s; }
-    for (int i = 0; i < n; ++i) for (int j = 0; j < i; ++j) y[i] -= L(i, j) * y[j];
-    for (int i = 0; i < n; ++i) y[i] = (fabs(L(i, i)) > DBL_MIN) ? y[i] / L(i, i) : 0.0;
-    for (int i = n - 1; i >= 0; --i) for (int j = i + 1; j < n; ++j) y[i] -= L(j, i) * y[j];
-    for (int k = n - 1; k >= 0; --k) if (tr[k] != k) { const double s = y[k]; y[k] = y[tr[k]]; y[tr[k]] = s; }
-    memcpy(x, y, sizeof(double) * n);
-#undef L
-    return 1;
+    return ldlt_solve(m, b, n, LDLT_RETURN_ZERO, x);
 }
 
 /* ---------------------------------------------------------------- the edges (types_six_dof_expmap.h:196-260, .cpp:266-364) */

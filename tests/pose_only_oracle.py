@@ -1,12 +1,11 @@
 """ctypes wrapper of tests/pose_only_oracle.c, the CPU restatement of Optimizer::PoseOptimization (test infrastructure: never part
-of the product).  The C file is compiled on first use into a per-user cache directory, as tests/test_cxx_host.py builds its helper."""
+of the product).  The C file is compiled on first use into a per-user cache directory (tests/c_oracle.py)."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
+
+import c_oracle
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "pose_only_oracle.c")
@@ -36,17 +35,7 @@ EDGE_BYTES = EDGE_DTYPE.itemsize
 def lib():
     global _LIB
     if _LIB is None:
-        src = open(_SRC, "rb").read()
-        tag = hashlib.sha256(src).hexdigest()[:16]
-        d = os.path.join(tempfile.gettempdir(), f"orbslam_pose_oracle_{os.getuid()}")
-        os.makedirs(d, exist_ok=True)
-        so = os.path.join(d, f"pose_only_oracle_{tag}.so")
-        if not os.path.exists(so):
-            tmp = so + f".{os.getpid()}.tmp"
-            subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-std=c99", "-shared", "-fPIC", "-o", tmp,
-                                   _SRC, "-lm"])
-            os.replace(tmp, so)
-        L = C.CDLL(so)
+        L = C.CDLL(c_oracle.build(_SRC, [os.path.join(_HERE, "g2o_restated.h")]))
         vp = C.c_void_p
         L.po_pose_optimization.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats), vp]
         L.po_pose_optimization.restype = C.c_int

@@ -16,6 +16,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "g2o_restated.h"              /* Eigen: Quaterniond(Matrix3d), quaternion product, quaternion * vector, LDLT */
+
 typedef struct { double q[4], t[3], s; } s3x_sim3;   /* q = x y z w */
 
 typedef struct {                                      /* = orbm_sim3_opt_result */
@@ -36,53 +38,6 @@ static double jig(double v)
 static double p_sin(double x) { return jig(sin(x)); }
 static double p_cos(double x) { return jig(cos(x)); }
 static double p_exp(double x) { return jig(exp(x)); }
-
-/* ---- Eigen: Quaterniond(Matrix3d), quaternion product, quaternion * vector */
-static void quat_from_matrix(const double R[9], double q[4])
-{
-#define M(i, j) R[3 * (i) + (j)]
-    double t = M(0, 0) + M(1, 1) + M(2, 2);
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (M(2, 1) - M(1, 2)) * t;
-        q[1] = (M(0, 2) - M(2, 0)) * t;
-        q[2] = (M(1, 0) - M(0, 1)) * t;
-    } else {
-        int i = 0;
-        if (M(1, 1) > M(0, 0)) i = 1;
-        if (M(2, 2) > M(i, i)) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(M(i, i) - M(j, j) - M(k, k) + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (M(k, j) - M(j, k)) * t;
-        q[j] = (M(j, i) + M(i, j)) * t;
-        q[k] = (M(k, i) + M(i, k)) * t;
-    }
-#undef M
-}
-
-static void q_mul(const double a[4], const double b[4], double o[4])
-{
-    double r[4];
-    r[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    r[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    r[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    r[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-    memcpy(o, r, sizeof(r));
-}
-
-static void q_rotate(const double q[4], const double v[3], double o[3])
-{
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    double r[3];
-    for (int i = 0; i < 3; ++i) r[i] = v[i] + q[3] * uv[i] + c[i];
-    memcpy(o, r, sizeof(r));
-}
 
 /* ---- sim3.h */
 void s3x_from_rts(const float R[9], const float t[3], float s, s3x_sim3 *o)      /* :64-67 behind Converter::toMatrix3d / toVector3d */
@@ -167,63 +122,9 @@ void s3x_map(const s3x_sim3 *a, const double X[3], double o[3])                 
     for (int k = 0; k < 3; ++k) o[k] = a->s * r[k] + a->t[k];
 }
 
-/* ---- Eigen::LDLT of an N x N matrix + solve; returns isPositive() (x is left as it is when not) */
-#define N7 7
-static int ldlt_solve7(double m[N7 * N7], const double b[N7], double x[N7])
-{
-    int tr[N7], sign = 0;   /* 0 ZeroSign, 1 PositiveSemiDef, 2 NegativeSemiDef, 3 Indefinite */
-    double temp[N7];
-#define L(i, j) m[N7 * (i) + (j)]
-    for (int k = 0; k < N7; ++k) {
-        int big = k;
-        double bv = fabs(L(k, k));
-        for (int j = k + 1; j < N7; ++j) {
-            const double f = fabs(L(j, j));
-            if (f > bv) { big = j; bv = f; }
-        }
-        tr[k] = big;
-        if (big != k) {
-            const int c = big;
-            for (int j = 0; j < k; ++j) { const double s = L(k, j); L(k, j) = L(c, j); L(c, j) = s; }
-            for (int i = c + 1; i < N7; ++i) { const double s = L(i, k); L(i, k) = L(i, c); L(i, c) = s; }
-            { const double s = L(k, k); L(k, k) = L(c, c); L(c, c) = s; }
-            for (int i = k + 1; i < c; ++i) { const double s = L(i, k); L(i, k) = L(c, i); L(c, i) = s; }
-        }
-        if (k > 0) {
-            for (int j = 0; j < k; ++j) temp[j] = L(j, j) * L(k, j);
-            double s = L(k, 0) * temp[0];
-            for (int j = 1; j < k; ++j) s = s + L(k, j) * temp[j];
-            L(k, k) -= s;
-            for (int i = k + 1; i < N7; ++i) {
-                double a = L(i, 0) * temp[0];
-                for (int j = 1; j < k; ++j) a = a + L(i, j) * temp[j];
-                L(i, k) -= a;
-            }
-        }
-        const double akk = L(k, k);
-        const int valid = fabs(akk) > 0.0;
-        if (k == 0 && !valid) {         /* "the entire diagonal is zero": ZeroSign, identity transpositions, the matrix as it is -- also */
-            for (int j = 0; j < N7; ++j) tr[j] = j;                        /* for a NaN matrix, whose solve below then gives NaN */
-            break;
-        }
-        if (valid)
-            for (int i = k + 1; i < N7; ++i) L(i, k) /= akk;
-        if (sign == 1) { if (akk < 0) sign = 3; }
-        else if (sign == 2) { if (akk > 0) sign = 3; }
-        else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = 2; }
-    }
-    if (!(sign == 1 || sign == 0)) return 0;
-    double y[N7];
-    for (int i = 0; i < N7; ++i) y[i] = b[i];
-    for (int k = 0; k < N7; ++k) if (tr[k] != k) { const double s = y[k]; y[k] = y[tr[k]]; y[tr[k]] = s; }
-    for (int i = 0; i < N7; ++i) for (int j = 0; j < i; ++j) y[i] -= L(i, j) * y[j];
-    for (int i = 0; i < N7; ++i) y[i] = (fabs(L(i, i)) > 2.2250738585072014e-308) ? y[i] / L(i, i) : 0.0;
-    for (int i = N7 - 1; i >= 0; --i) for (int j = i + 1; j < N7; ++j) y[i] -= L(j, i) * y[j];
-    for (int k = N7 - 1; k >= 0; --k) if (tr[k] != k) { const double s = y[k]; y[k] = y[tr[k]]; y[tr[k]] = s; }
-    for (int i = 0; i < N7; ++i) x[i] = y[i];
-#undef L
-    return 1;
-}
+/* LinearSolverDense's LDLT of a 7 x 7 matrix, in place, Eigen's way where the diagonal has no entry to pivot on (x is left as it is
+ * when not isPositive()) */
+static int ldlt_solve7(double m[49], const double b[7], double x[7]) { return ldlt_solve(m, b, 7, LDLT_AS_EIGEN, x); }
 int s3x_ldlt7(const double *H, const double *b, double *x) { double m[49]; memcpy(m, H, sizeof(m)); return ldlt_solve7(m, b, x); }
 
 /* ---- the edges */

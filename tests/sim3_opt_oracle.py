@@ -1,13 +1,12 @@
 """ctypes wrapper of tests/sim3_opt_oracle.c, the CPU restatement of Optimizer::OptimizeSim3 (src/Optimizer.cc:1564-1624) on g2o's code
-paths (test infrastructure: never part of the product).  The C file is compiled on first use into a per-user cache directory, as
-tests/sim3_oracle.py builds its file."""
+paths (test infrastructure: never part of the product).  The C file is compiled on first use into a per-user cache directory
+(tests/c_oracle.py)."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
+
+import c_oracle
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "sim3_opt_oracle.c")
@@ -34,24 +33,10 @@ class Trace(C.Structure):       # s3x_trace
                 ("min_abs_rho", C.c_double), ("hit_limit", C.c_int32 * 2)]
 
 
-def build(flags=("-O2",)):
-    """the shared object of the restatement built with `flags` (always -ffp-contract=off -fno-fast-math)"""
-    src = open(_SRC, "rb").read()
-    tag = hashlib.sha256(src + " ".join(flags).encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), f"orbslam_sim3_opt_oracle_{os.getuid()}")
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, f"sim3_opt_oracle_{tag}.so")
-    if not os.path.exists(so):
-        tmp = so + f".{os.getpid()}.tmp"
-        subprocess.check_call(["gcc", *flags, "-ffp-contract=off", "-fno-fast-math", "-std=c99", "-D_GNU_SOURCE", "-shared", "-fPIC", "-o", tmp,
-                               _SRC, "-lm"])
-        os.replace(tmp, so)
-    return so
-
-
 def lib(flags=("-O2",)):
+    """the restatement built with `flags` (always -ffp-contract=off -fno-fast-math)"""
     if flags not in _LIBS:
-        L = C.CDLL(build(flags))
+        L = C.CDLL(c_oracle.build(_SRC, [os.path.join(_HERE, "g2o_restated.h")], (*flags, "-D_GNU_SOURCE")))
         vp = C.c_void_p
         L.s3x_set_ulp.argtypes = [C.c_uint64]; L.s3x_set_ulp.restype = None
         L.s3x_from_rts.argtypes = [vp, vp, C.c_float, vp]; L.s3x_from_rts.restype = None

@@ -1,16 +1,15 @@
 """ctypes wrapper of tests/sim3_oracle.c, the CPU restatement of Sim3Solver (src/Sim3Solver.cc): the constructor's data
 preparation, ComputeSim3, CheckInliers, SetRansacParameters and the fold of iterate (test infrastructure: never part of the product).
-The C file is compiled on first use into a per-user cache directory, as tests/create_points_oracle.py builds its file.
+The C file is compiled on first use into a per-user cache directory (tests/c_oracle.py).
 
 No OpenCV exists for this project to run, so the restated cv::eigen (JacobiImpl_<float>) and cv::Rodrigues are unpinned like the
 other OpenCV primitives; tests/test_cpu_sim3.py checks them from first principles against numpy in float64."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
+
+import c_oracle
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "sim3_oracle.c")
@@ -22,23 +21,10 @@ class Fold(C.Structure):        # s3o_fold
                 ("best", C.c_int32)]
 
 
-def build(flags=("-O2",)):
-    """the shared object of the restatement built with `flags` (always -ffp-contract=off -fno-fast-math)"""
-    src = open(_SRC, "rb").read()
-    tag = hashlib.sha256(src + " ".join(flags).encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), f"orbslam_sim3_oracle_{os.getuid()}")
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, f"sim3_oracle_{tag}.so")
-    if not os.path.exists(so):
-        tmp = so + f".{os.getpid()}.tmp"
-        subprocess.check_call(["gcc", *flags, "-ffp-contract=off", "-fno-fast-math", "-std=c99", "-shared", "-fPIC", "-o", tmp, _SRC, "-lm"])
-        os.replace(tmp, so)
-    return so
-
-
 def lib(flags=("-O2",)):
+    """the restatement built with `flags` (always -ffp-contract=off -fno-fast-math)"""
     if flags not in _LIBS:
-        L = C.CDLL(build(flags))
+        L = C.CDLL(c_oracle.build(_SRC, flags=flags))
         vp = C.c_void_p
         L.s3o_eigen4.argtypes = [vp, vp, vp]; L.s3o_eigen4.restype = C.c_int
         L.s3o_rodrigues.argtypes = [vp, vp]; L.s3o_rodrigues.restype = None
