@@ -1,12 +1,13 @@
-// orbm_internal.h -- pieces shared by the matcher translation units (orbm_match.hip,
-// orbm_search.hip): the Frame grid constants, the keypoint / query records of the
-// windowed searches and small host / device helpers.
+// orbm_internal.h -- pieces shared by the matcher translation units (orbm_match.hip, orbm_search.hip, orbm_triang.hip,
+// orbm_pose.hip, orbm_sim3.hip, orbm_sim3opt.hip): the Frame grid constants, the keypoint / query records of the windowed
+// searches, the resident frame (struct orbm_frame), the per-call workspace and small host / device helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 
+#include <atomic>
 #include <vector>
 
 #include "../../include/orbslam_hip.h"
@@ -26,12 +27,75 @@ struct WinQuery { float u, v, r, xr; int min_level, max_level; };
 // Sorted keypoint record of the windowed searches: position sp in the array = rank in GetFeaturesInArea order.
 struct SeqKp { float x, y, uright; int octave; };
 struct GridParams { float min_x, min_y, inv_w, inv_h; };
+struct FrameHdr { int n, ns, min_octave, max_octave; };     // what k_frame_build leaves in front of a resident frame's block
 static_assert(sizeof(WinQuery) == sizeof(orbm_window_query), "query layout");
 
 __device__ __forceinline__ int popc256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
 {
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
            __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
+// cv::Mat gemm of one row of a 3 x 3 float matrix with a vector, plus t: the float row sum, then the sum with t in double.
+__device__ __forceinline__ float gemm_row(const float *R, int r, float b0, float b1, float b2, float t)
+{
+    return (float)((double)(R[3 * r] * b0 + R[3 * r + 1] * b1 + R[3 * r + 2] * b2) + (double)t);
+}
+
+// ---- cv::Mat float arithmetic of the pose handling in front of the projection loops, on the host (a handful of operations
+// per call; -ffp-contract=off keeps them unfused).  OpenCV 3.4 semantics restated (gemm's 3 x 3 special case: float row
+// sum left to right, then float(double(sum) * alpha + double(c) * beta); scaling by a FLOAT factor with a + 0.0f).
+inline void pose_parts(const float *T16, float *R, float *t)
+{
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R[3 * r + c] = T16[4 * r + c]; t[r] = T16[4 * r + 3]; }
+}
+inline void gemm3(const float *A, const float *b, double alpha, const float *c, double beta, float *d)
+{
+    float out[3];
+    for (int k = 0; k < 3; ++k) {
+        const float t = A[3 * k] * b[0] + A[3 * k + 1] * b[1] + A[3 * k + 2] * b[2];
+        out[k] = (float)((double)t * alpha + (double)(c ? c[k] : 0.0f) * beta);
+    }
+    d[0] = out[0]; d[1] = out[1]; d[2] = out[2];
+}
+inline void transpose3(const float *A, float *At)
+{
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) At[3 * r + c] = A[3 * c + r];
+}
+inline void scale_mat(const float *A, int n, double s, float *out)
+{
+    const float a = (float)s, b = (float)0.0;
+    for (int i = 0; i < n; ++i) out[i] = A[i] * a + b;
+}
+inline void neg_Rt_t(const float *R, const float *t, float *out)   // -R.t() * t  (ORBmatcher.cc:1542, :1679, :504)
+{
+    float Rt[9];
+    transpose3(R, Rt);
+    gemm3(Rt, t, -1.0, nullptr, 0.0, out);
+}
+
+// The co-iteration of two FeatureVectors (ORBmatcher.cc:384-456, :745-828, :881-891 / :1004-1012), given as their ascending node
+// ids: visit(a, b) for every node both hold (nodes1[a] == nodes2[b]); otherwise lower_bound on the other map.
+template <class F>
+inline void for_each_common_node(const int32_t *nodes1, int nn1, const int32_t *nodes2, int nn2, F visit)
+{
+    for (int a = 0, b = 0; a < nn1 && b < nn2;) {
+        if (nodes1[a] == nodes2[b]) {
+            visit(a, b);
+            ++a; ++b;
+        } else if (nodes1[a] < nodes2[b]) {
+            while (a < nn1 && nodes1[a] < nodes2[b]) ++a;
+        } else {
+            while (b < nn2 && nodes2[b] < nodes1[a]) ++b;
+        }
+    }
+}
+// every feature index of a FeatureVector (off, items; nn nodes) names one of n features: 0, else -1
+inline int bow_check_items(const int32_t *off, const int32_t *items, int nn, int n)
+{
+    for (int k = 0; k < (nn ? off[nn] : 0); ++k)
+        if (items[k] < 0 || items[k] >= n) return -1;
+    return 0;
 }
 
 // ---- the rotation-consistency check of every ORBmatcher search, one definition each for the device and the host code
@@ -201,11 +265,6 @@ inline void stage_two_keyframes(StagedCall &sc, const Problem &q, Dev &d)
     d.cam2[0] = q.fx2; d.cam2[1] = q.fy2; d.cam2[2] = q.cx2; d.cam2[3] = q.cy2;
 }
 
-// What another translation unit (orbm_pose.hip) reads of a resident frame: the sorted keypoint records and the permutation in
-// HBM (perm[sorted position] = keypoint index, all n positions), the keypoint count and the octave range.
-struct FrameDeviceView { const SeqKp *kp; const int *perm; int n, min_octave, max_octave; };
-void frame_device_view(const orbm_frame *f, FrameDeviceView &v);
-
 // Work a caller appends to a whole-loop projection search, on the search's stream, behind the resolver and in front of the call's
 // host wait (orbm_pose.hip: the pose solve of the tracking functions).  The driver (run_sequential, orbm_search.hip) asks the chain
 // for its arrays while it lays the workspace out -- inputs inside the staged block (they travel with the call's one upload),
@@ -244,3 +303,21 @@ int search_by_projection_points_chain(const orbm_frame *cur, const orbm_view *vi
                                       orbm_window_query *queries_out, SearchChain *chain);
 
 } // namespace orbm_detail
+
+// A frame resident in HBM: the sorted keypoint records, descriptors, angles, the permutation and the cell table of
+// k_frame_build in ONE device block (recycled through a pool: a frame per image must not cost a hipMalloc), plus a host
+// copy of the permutation (the per-call occupancy masks are given by keypoint index and staged in sorted order).
+// Read-only after creation: any number of searches, from any thread, may use it at once.
+struct orbm_frame {
+    int n = 0, ns = 0, cap = 0, has_uright = 0;
+    int nstereo = 0;                                        // keypoints with a right coordinate >= 0; -1: not known on the host (device arrays)
+    int min_octave = 0, max_octave = -1;                    // over the keypoints (empty frame: 0, -1)
+    float min_x = 0, min_y = 0, max_x = 0, max_y = 0;       // the bounds the SEARCHES use (cell range of a window, image tests)
+    orbm_detail::GridParams gp = {0.f, 0.f, 0.f, 0.f};      // ... with the cell pitch the grid was built with
+    char *block = nullptr;
+    std::atomic<int> *refs = nullptr;                       // handles sharing the block (orbm_frame_alias)
+    orbm_detail::SeqKp *kp = nullptr; uint4 *desc = nullptr; float *angle = nullptr; int *perm = nullptr, *cell_off = nullptr;
+    orbm_detail::FrameHdr *hdr = nullptr;
+    std::vector<int> perm_host;                             // [n]: keypoint index at sorted position (the first ns: inside the grid)
+    std::vector<int> inv_host;                              // [n]: sorted position of keypoint index
+};

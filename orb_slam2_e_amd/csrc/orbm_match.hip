@@ -484,68 +484,6 @@ __global__ __launch_bounds__(MT) void k_match_cands(const uint4 *__restrict__ A,
     best_o[i] = best; second_o[i] = second; idx_o[i] = idx;
 }
 
-// SearchForTriangulation inner loop (ORBmatcher.cc:892-990) + CheckDistEpipolarLine
-// (:341-358): every query over its BoW-node candidate list (16 lanes per query, see the kernel).
-// `dist>bestDist` is non-strict in the reference, so a later candidate with an equal
-// distance replaces the earlier one; vbMatched2 is never set there, so queries are
-// independent.
-struct TriParams { float F12[9]; float ex, ey; int only_stereo; };
-// 16 lanes per query, four queries per wave: the candidates of a query (its BoW node's members in frame 2, ~30) are taken 16 at a
-// time.  The reference keeps the LAST candidate among those of smallest distance that pass the gates (`dist > bestDist` is
-// non-strict, and the gates do not depend on bestDist), i.e. the minimum of dist << 16 | (0xffff - position in the list).
-// (One lane per query walking its list alone was a 68-us chain of dependent loads for 2,000 queries on 32 waves.)
-__global__ __launch_bounds__(MT) void k_match_triang(const orbx_keypoint *__restrict__ kps1, const uint4 *__restrict__ A, int nA,
-                                                     const orbx_keypoint *__restrict__ kps2, const uint4 *__restrict__ B,
-                                                     const int *__restrict__ off, const int *__restrict__ cidx,
-                                                     const uint8_t *__restrict__ hasmp1, const uint8_t *__restrict__ hasmp2,
-                                                     const uint8_t *__restrict__ stereo1, const uint8_t *__restrict__ stereo2,
-                                                     TriParams tp, const float *__restrict__ scale2, const float *__restrict__ sigma2,
-                                                     int *__restrict__ match12, int *__restrict__ bestdist)
-{
-    const int i = (blockIdx.x * MT + threadIdx.x) >> 4, sub = threadIdx.x & 15;
-    if (i >= nA) return;                       // (whole 16-lane groups leave together)
-    unsigned key = 0xffffffffu;
-    int k0 = 0;
-    if (!hasmp1[i] && !(tp.only_stereo && !stereo1[i])) {
-        const uint4 a0 = A[2 * i], a1 = A[2 * i + 1];
-        const orbx_keypoint kp1 = kps1[i];
-        // epipolar line in the second image l = x1' F12 = [a b c]
-        const float a = kp1.x * tp.F12[0] + kp1.y * tp.F12[3] + tp.F12[6];
-        const float b = kp1.x * tp.F12[1] + kp1.y * tp.F12[4] + tp.F12[7];
-        const float c = kp1.x * tp.F12[2] + kp1.y * tp.F12[5] + tp.F12[8];
-        const float den = a * a + b * b;
-        const bool st1 = stereo1[i] != 0;
-        k0 = off[i];
-        const int k1 = off[i + 1];
-        for (int k = k0 + sub; k < k1; k += 16) {
-            const int j = cidx[k];
-            if (hasmp2[j]) continue;
-            const bool st2 = stereo2[j] != 0;
-            if (tp.only_stereo && !st2) continue;
-            const int dist = popc256(a0, a1, B[2 * j], B[2 * j + 1]);
-            if (dist > 45) continue;           // TH_LOW
-            const orbx_keypoint kp2 = kps2[j];
-            if (!st1 && !st2) {
-                const float distex = tp.ex - kp2.x, distey = tp.ey - kp2.y;
-                if (distex * distex + distey * distey < 100 * scale2[kp2.octave]) continue;
-            }
-            const float num = a * kp2.x + b * kp2.y + c;
-            if (den == 0) continue;
-            const float dsqr = num * num / den;
-            if ((double)dsqr < 3.84 * (double)sigma2[kp2.octave]) {
-                const unsigned k2 = ((unsigned)dist << 16) | (0xffffu - (unsigned)min(k - k0, 0xffff));
-                key = k2 < key ? k2 : key;
-            }
-        }
-    }
-    key = orbx::row_min_u32(key);
-    if (sub == 0) {
-        const bool hit = key != 0xffffffffu;
-        match12[i] = hit ? cidx[k0 + (int)(0xffffu - (key & 0xffffu))] : -1;
-        bestdist[i] = hit ? (int)(key >> 16) : 45;
-    }
-}
-
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:305-370), one wave per map
 // point: N x N Hamming matrix in LDS, per-row median (element int(0.5*(N-1)) of the
 // sorted row) by bisection on the value, arg-min with first-wins through a
@@ -962,100 +900,6 @@ int orbm_bow_transform_batch_dev(orbm_vocabulary *v, const uint8_t *desc_dev, co
                           word_id_dev, node_id_dev);
     ORBX_HIP(hipGetLastError());
     return ORBX_OK;
-}
-
-int orbm_match_triangulation(const orbx_keypoint *kps1, const uint8_t *desc1, int n1, const orbx_keypoint *kps2,
-                             const uint8_t *desc2, int n2, const int32_t *cand_off, const int32_t *cand_idx,
-                             const uint8_t *has_mappoint1, const uint8_t *has_mappoint2, const uint8_t *stereo1,
-                             const uint8_t *stereo2, int only_stereo, const float *F12, float ex, float ey,
-                             const float *scale_factors2, const float *level_sigma2, int nlevels, int32_t *match12,
-                             int32_t *best_dist)
-{
-    if (n1 < 0 || n2 < 0 || nlevels < 1 || (n1 && (!kps1 || !desc1 || !has_mappoint1 || !stereo1 || !match12 || !best_dist)) ||
-        !cand_off || !F12 || !scale_factors2 || !level_sigma2)
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    ORBX_NEED_DEVICE();
-    if (n1 == 0) return ORBX_OK;
-    const int nc = cand_off[n1];
-    if (nc < 0 || (nc && (!cand_idx || !kps2 || !desc2 || !has_mappoint2 || !stereo2))) ORBX_FAIL(ORBX_ERR_ARG, "bad candidate lists");
-    for (int k = 0; k < nc; ++k)
-        if (cand_idx[k] < 0 || cand_idx[k] >= n2) ORBX_FAIL(ORBX_ERR_ARG, "candidate index out of range");
-    for (int i = 0; i < n1; ++i)
-        if (cand_off[i] > cand_off[i + 1] || cand_off[i] < 0) ORBX_FAIL(ORBX_ERR_ARG, "candidate offsets not monotone");
-    for (int i = 0; i < n1; ++i)
-        if (cand_off[i + 1] - cand_off[i] > 65535) ORBX_FAIL(ORBX_ERR_CAPACITY, "more than 65,535 candidates for one keypoint (the tie rule's position field)");
-    for (int j = 0; j < n2; ++j)
-        if (kps2[j].octave < 0 || kps2[j].octave >= nlevels) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
-    StagedCall sc;
-    const size_t o_k1 = sc.in(kps1, sizeof(orbx_keypoint) * n1), o_a = sc.in(desc1, (size_t)32 * n1),
-                 o_k2 = sc.in(kps2, sizeof(orbx_keypoint) * (size_t)n2), o_b = sc.in(desc2, (size_t)32 * n2),
-                 o_off = sc.in(cand_off, sizeof(int) * (n1 + 1)), o_ci = sc.in(cand_idx, sizeof(int) * (size_t)nc),
-                 o_m1 = sc.in(has_mappoint1, n1), o_m2 = sc.in(has_mappoint2, n2), o_s1 = sc.in(stereo1, n1), o_s2 = sc.in(stereo2, n2),
-                 o_sc = sc.in(scale_factors2, sizeof(float) * nlevels), o_sg = sc.in(level_sigma2, sizeof(float) * nlevels),
-                 o_o = sc.out(sizeof(int) * 2 * (size_t)n1);
-    if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
-    TriParams tp;
-    for (int i = 0; i < 9; ++i) tp.F12[i] = F12[i];
-    tp.ex = ex; tp.ey = ey; tp.only_stereo = only_stereo ? 1 : 0;
-    int *ob = sc.d<int>(o_o);
-    hipLaunchKernelGGL(k_match_triang, dim3((unsigned)(((size_t)n1 * 16 + MT - 1) / MT)), dim3(MT), 0, sc.stream(), sc.d<const orbx_keypoint>(o_k1),
-                       sc.d<const uint4>(o_a), n1, sc.d<const orbx_keypoint>(o_k2), sc.d<const uint4>(o_b), sc.d<const int>(o_off),
-                       sc.d<const int>(o_ci), sc.d<const uint8_t>(o_m1), sc.d<const uint8_t>(o_m2), sc.d<const uint8_t>(o_s1),
-                       sc.d<const uint8_t>(o_s2), tp, sc.d<const float>(o_sc), sc.d<const float>(o_sg), ob, ob + n1);
-    ORBX_HIP(hipGetLastError());
-    if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
-    memcpy(match12, sc.r<int>(o_o), sizeof(int) * n1);
-    memcpy(best_dist, sc.r<int>(o_o) + n1, sizeof(int) * n1);
-    return ORBX_OK;
-}
-
-// The whole ORBmatcher::SearchForTriangulation (ORBmatcher.cc:858-1024) in one call: the FeatureVector co-iteration (:881-891,
-// :1004-1012: equal node ids -> every keypoint of the node in KF1 scans the node's members of KF2, in member order), the gated loop
-// on the device (orbm_match_triangulation), the rotation histogram, ComputeThreeMaxima and the rejection (:992-1012).  A
-// FeatureVector = (nodes ascending, off, items), as for orbm_search_by_bow.  match12[n1] = index in KF2 or -1; the pair list
-// vMatchedPairs is its non-negative entries in index order (:1014-1021).
-int orbm_search_for_triangulation(const orbx_keypoint *kps1, const uint8_t *desc1, int n1, const int32_t *nodes1, const int32_t *off1,
-                                  const int32_t *items1, int nn1, const uint8_t *has_mappoint1, const uint8_t *stereo1,
-                                  const orbx_keypoint *kps2, const uint8_t *desc2, int n2, const int32_t *nodes2, const int32_t *off2,
-                                  const int32_t *items2, int nn2, const uint8_t *has_mappoint2, const uint8_t *stereo2, int only_stereo,
-                                  const float *F12, float ex, float ey, const float *scale_factors2, const float *level_sigma2, int nlevels,
-                                  int check_orientation, int32_t *match12, int *nmatches)
-{
-    if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !nmatches || (n1 && !match12) || (nn1 && (!nodes1 || !off1 || !items1)) ||
-        (nn2 && (!nodes2 || !off2 || !items2)))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    *nmatches = 0;
-    if (n1 == 0) return ORBX_OK;
-    for (int a = 0; a < nn1; ++a)
-        for (int k = off1[a]; k < off1[a + 1]; ++k)
-            if (items1[k] < 0 || items1[k] >= n1) ORBX_FAIL(ORBX_ERR_ARG, "feature index out of range");
-    for (int b = 0; b < nn2; ++b)
-        for (int k = off2[b]; k < off2[b + 1]; ++k)
-            if (items2[k] < 0 || items2[k] >= n2) ORBX_FAIL(ORBX_ERR_ARG, "feature index out of range");
-    std::vector<int32_t> cnt(n1, 0), start2(n1, 0), cand_off((size_t)n1 + 1, 0);
-    for (int a = 0, b = 0; a < nn1 && b < nn2;) {
-        if (nodes1[a] == nodes2[b]) {
-            for (int k = off1[a]; k < off1[a + 1]; ++k) { cnt[items1[k]] = off2[b + 1] - off2[b]; start2[items1[k]] = off2[b]; }
-            ++a; ++b;
-        } else if (nodes1[a] < nodes2[b]) {
-            while (a < nn1 && nodes1[a] < nodes2[b]) ++a;     // lower_bound on the other map (:1004-1011)
-        } else {
-            while (b < nn2 && nodes2[b] < nodes1[a]) ++b;
-        }
-    }
-    for (int i = 0; i < n1; ++i) {
-        if ((long long)cand_off[i] + cnt[i] > 0x7fffffffll) ORBX_FAIL(ORBX_ERR_CAPACITY, "candidate lists exceed 2^31 entries");
-        cand_off[i + 1] = cand_off[i] + cnt[i];
-    }
-    std::vector<int32_t> cand((size_t)std::max(cand_off[n1], 1));
-    for (int i = 0; i < n1; ++i)
-        if (cnt[i]) memcpy(&cand[cand_off[i]], items2 + start2[i], sizeof(int32_t) * (size_t)cnt[i]);
-    std::vector<int32_t> best((size_t)n1);
-    const int rc = orbm_match_triangulation(kps1, desc1, n1, kps2, desc2, n2, cand_off.data(), cand.data(), has_mappoint1, has_mappoint2,
-                                            stereo1, stereo2, only_stereo, F12, ex, ey, scale_factors2, level_sigma2, nlevels, match12, best.data());
-    if (rc != ORBX_OK) return rc;
-    return triangulation_rotation_check(match12, n1, check_orientation,
-                                        [&](int i) { return kps1[i].angle - kps2[match12[i]].angle; }, nmatches);     // :994
 }
 
 int orbm_hamming_matrix(const uint8_t *A, int nA, const uint8_t *B, int nB, uint16_t *out)

@@ -545,7 +545,7 @@ std::atomic<int> g_last_track_waits{0};    // host waits of the last tracking ca
 // into the pinned result block behind the search's.
 struct PoseChain : SearchChain {
     // set by the caller
-    FrameDeviceView fv;
+    const orbm_frame *fr = nullptr;
     PoseCam pc;
     const float *Tcw = nullptr;
     const orbm_points *pts = nullptr;
@@ -562,33 +562,33 @@ struct PoseChain : SearchChain {
     size_t o_t = 0, o_off = 0, o_pp = 0, o_bh = 0, o_bp = 0, o_bt = 0, r_t = 0, r_g = 0, r_s = 0, r_k = 0, r_o = 0, x_g = 0;
     void carve_inputs(Workspace &w) override
     {
-        const size_t n = fv.n ? (size_t)fv.n : 1, m = pts->n ? (size_t)pts->n : 1;
+        const size_t n = fr->n ? (size_t)fr->n : 1, m = pts->n ? (size_t)pts->n : 1;
         o_t = w.carve(sizeof(float) * 16); o_off = w.carve(2 * sizeof(int32_t)); o_pp = w.carve(sizeof(float) * 3 * m);
         o_bh = w.carve(base_has ? n : 1); o_bp = w.carve(base_has ? sizeof(float) * 3 * n : 1); o_bt = w.carve(base_has && base_takes ? n : 1);
     }
     void fill_inputs(Workspace &w) override
     {
-        const int32_t off[2] = {0, fv.n};
+        const int32_t off[2] = {0, fr->n};
         memcpy(w.h<char>(o_t), Tcw, sizeof(float) * 16);
         memcpy(w.h<char>(o_off), off, sizeof(off));
         if (pts->n) memcpy(w.h<char>(o_pp), pts->pos, sizeof(float) * 3 * (size_t)pts->n);
-        if (base_has && fv.n) {
-            memcpy(w.h<char>(o_bh), base_has, (size_t)fv.n);
-            memcpy(w.h<char>(o_bp), base_pos, sizeof(float) * 3 * (size_t)fv.n);
-            if (base_takes) memcpy(w.h<char>(o_bt), base_takes, (size_t)fv.n);
+        if (base_has && fr->n) {
+            memcpy(w.h<char>(o_bh), base_has, (size_t)fr->n);
+            memcpy(w.h<char>(o_bp), base_pos, sizeof(float) * 3 * (size_t)fr->n);
+            if (base_takes) memcpy(w.h<char>(o_bt), base_takes, (size_t)fr->n);
         }
     }
     void carve_results(Workspace &w) override
     {
         r_t = w.carve(sizeof(float) * 16); r_g = w.carve(sizeof(int32_t)); r_s = w.carve(sizeof(orbm_pose_stats));
-        r_k = w.carve(4 * sizeof(int32_t)); r_o = w.carve(fv.n ? (size_t)fv.n : 1);
-        x_g = w.carve(sizeof(float4) * (size_t)(fv.n ? fv.n : 1));      // device scratch (behind the results: never read back)
+        r_k = w.carve(4 * sizeof(int32_t)); r_o = w.carve(fr->n ? (size_t)fr->n : 1);
+        x_g = w.carve(sizeof(float4) * (size_t)(fr->n ? fr->n : 1));      // device scratch (behind the results: never read back)
     }
     template <typename T> static T *res(const Ctx &c, size_t off) { return reinterpret_cast<T *>(c.w->pin + (off - c.o_res)); }
     int launch(const Ctx &c) override
     {
         const Workspace &w = *c.w;
-        PoseSrc src = {nullptr, nullptr, fv.kp, fv.perm, nullptr, nullptr, w.d<int>(o_off), w.d<float>(o_t),
+        PoseSrc src = {nullptr, nullptr, fr->kp, fr->perm, nullptr, nullptr, w.d<int>(o_off), w.d<float>(o_t),
                        c.match_kp, w.d<float>(o_pp), c.qtakes, base_has ? w.d<uint8_t>(o_bh) : nullptr, w.d<float>(o_bp),
                        base_has && base_takes ? w.d<uint8_t>(o_bt) : nullptr, w.d<float4>(x_g), c.flags, c.nq, c.gen, c.check_overflow ? 1 : 0,
                        c.check_converged ? 1 : 0, min_matches};
@@ -608,7 +608,7 @@ struct PoseChain : SearchChain {
         memcpy(Tcw_out, res<float>(c, r_t), sizeof(float) * 16);
         if (stats) memcpy(stats, res<orbm_pose_stats>(c, r_s), sizeof(orbm_pose_stats));
         const uint8_t *o = res<uint8_t>(c, r_o);
-        for (int j = 0; j < fv.n; ++j)
+        for (int j = 0; j < fr->n; ++j)
             if (match_kp[j] >= 0 || (base_has && base_has[j])) outlier[j] = o[j];
     }
 };
@@ -617,9 +617,9 @@ struct PoseChain : SearchChain {
 int track_prepare(const orbm_frame *cur, const orbm_view *view, const orbm_pose_camera *cam, PoseChain &ch)
 {
     if (make_cam(cam, ch.pc)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    frame_device_view(cur, ch.fv);
-    if (ch.fv.n > POSE_MAXN) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 8,192 keypoints in one pose problem");
-    if (ch.fv.min_octave < 0 || ch.fv.max_octave >= cam->nlevels || ch.fv.max_octave >= view->nlevels)
+    ch.fr = cur;
+    if (ch.fr->n > POSE_MAXN) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 8,192 keypoints in one pose problem");
+    if (ch.fr->min_octave < 0 || ch.fr->max_octave >= cam->nlevels || ch.fr->max_octave >= view->nlevels)
         ORBX_FAIL(ORBX_ERR_ARG, "keypoint octave outside the view's or the pose camera's levels");
     return ORBX_OK;
 }
@@ -646,19 +646,17 @@ int orbm_frame_pose_optimization(const orbm_frame *frame, const uint8_t *has_mp,
     PoseCam pc;
     if (!frame || !Tcw_in || !Tcw_out || !ngood || make_cam(cam, pc)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     ORBX_NEED_DEVICE();
-    FrameDeviceView fv;
-    frame_device_view(frame, fv);
-    const int n = fv.n;
+    const int n = frame->n;
     if (n && (!has_mp || !mp_pos || !outlier)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     if (n > POSE_MAXN) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 8,192 keypoints in one pose problem");
-    if (fv.min_octave < 0 || fv.max_octave >= cam->nlevels) ORBX_FAIL(ORBX_ERR_ARG, "keypoint octave outside mvInvLevelSigma2");
+    if (frame->min_octave < 0 || frame->max_octave >= cam->nlevels) ORBX_FAIL(ORBX_ERR_ARG, "keypoint octave outside mvInvLevelSigma2");
     const int32_t off[2] = {0, n};
     StagedCall sc;
     const size_t o_h = sc.in(has_mp, (size_t)n), o_p = sc.in(mp_pos, sizeof(float) * 3 * (size_t)n), o_o = sc.in(off, sizeof(off)),
                  o_t = sc.in(Tcw_in, sizeof(float) * 16);
     const size_t r_t = sc.out(sizeof(float) * 16), r_g = sc.out(sizeof(int32_t)), r_s = sc.out(sizeof(orbm_pose_stats)), r_o = sc.out((size_t)n);
     if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
-    PoseSrc src = {nullptr, nullptr, fv.kp, fv.perm, sc.d<uint8_t>(o_h), sc.d<float>(o_p), sc.d<int>(o_o), sc.d<float>(o_t)};
+    PoseSrc src = {nullptr, nullptr, frame->kp, frame->perm, sc.d<uint8_t>(o_h), sc.d<float>(o_p), sc.d<int>(o_o), sc.d<float>(o_t)};
     PoseOut po = {sc.d<float>(r_t), sc.d<uint8_t>(r_o), sc.d<int32_t>(r_g), sc.d<orbm_pose_stats>(r_s)};
     hipLaunchKernelGGL(k_pose_optimization<1>, dim3(1), dim3(PT), 0, sc.stream(), src, pc, po);
     ORBX_HIP(hipGetLastError());
@@ -713,7 +711,7 @@ int orbm_track_with_motion_model(const orbm_frame *cur, const orbm_view *view, c
     PoseChain ch;
     const int rc0 = track_prepare(cur, view, cam, ch);
     if (rc0 != ORBX_OK) return rc0;
-    if (ch.fv.n && (!match_kp || !outlier)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (ch.fr->n && (!match_kp || !outlier)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     memset(result, 0, sizeof(*result));
     memcpy(Tcw_out, Tcw, sizeof(float) * 16);
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -747,7 +745,7 @@ int orbm_track_local_map(const orbm_frame *cur, const orbm_view *view, const orb
     PoseChain ch;
     const int rc0 = track_prepare(cur, view, cam, ch);
     if (rc0 != ORBX_OK) return rc0;
-    const int n = ch.fv.n;
+    const int n = ch.fr->n;
     if (n && (!match_kp || !outlier)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     memset(result, 0, sizeof(*result));
     memcpy(Tcw_out, Tcw, sizeof(float) * 16);
