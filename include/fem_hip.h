@@ -146,6 +146,54 @@ int fem_trial_setup(fem_model *m, const float *u0, const int32_t *ids, int nids,
                     const int32_t *derived, int nder);
 int fem_trial_energy(fem_model *m, const double *points, float *a_out, float *sE, float *nsE);
 
+/* Optimizer::PoseOptimizationNR's non-linear optimisation (src/Optimizer.cc:733-809) on the device, ONE launch per call: the four
+ * rounds of initializeOptimization(0) + optimize(10), every Levenberg iteration and trial of
+ * OptimizationAlgorithmLevenberg::solve (core/optimization_algorithm_levenberg.cpp:63-241) with the hook :159-199 inside the kernel
+ * (bit for bit fem_trial_energy's sE / nsE for the same estimates), the BlockSolver_6_3 Schur step, the inlier / outlier pass
+ * after each round and the write-back.  The caller keeps the walk over MapPoint* / KeyFrame* (:515-709) and flattens it:
+ *   Tcw[16]             pFrame->mTcw (vertex 0), kf_Tcw[nkf][16] the fixed keyframes' poses, row-major 4 x 4
+ *   points[npoints][3]  GetWorldPos() of the point vertices, in vpMapPoints order (= the model's npoints of fem_trial_setup)
+ *   per edge, in vpEdges order -- grouped by point, points ascending, a point's frame edge first as :619-709 creates them:
+ *   e_point, e_cam (-1: the frame, else a keyframe index), e_obs[2], e_inv_sigma2, e_cam_k[4] = fx fy cx cy
+ * Limits (ORBX_ERR_UNSUPPORTED, nothing is launched; PoseOptimizationNR_fem with fem_trial_energy per trial remains the path
+ * beyond them): npoints + derived nodes <= 1,365 (Ksize <= 8,190), nedges <= 65,536, nkf <= 1,024.  ORBX_ERR_ARG: a null
+ * pointer, a negative size, an edge's point or camera index out of range, edges not grouped by ascending point, a model that is
+ * not a single mesh with fem_trial_setup done for the same npoints.  The graph is checked before the model.  npoints < 3
+ * (:711-714) returns ngood = 0, the input pose and points, outlier = 0, without a launch and without looking at the model. */
+typedef struct {
+    int32_t npoints, nkf, nedges, reserved;
+    const float *Tcw, *kf_Tcw, *points;
+    const int32_t *e_point, *e_cam;
+    const float *e_obs, *e_inv_sigma2, *e_cam_k;
+} orbm_pose_nr_graph;
+typedef struct {
+    float Tcw[16];       /* what SetPose receives (Converter::toCvMat of the estimate) */
+    float *points_out;   /* [npoints][3]: what SetWorldPos receives */
+    uint8_t *outlier;    /* [npoints]: pFrame->mvbOutlier[idx] */
+    int32_t ngood, reserved;   /* nInitialCorrespondences - nBad (:833) */
+} orbm_pose_nr_result;
+/* One Levenberg trial, the fields of orbslam_hip::PoseOptimizationNR_fem::Trial */
+typedef struct { float sE, nsE; double tempChi, currentChi, rho, lambda; int32_t qmax, accepted; } orbm_pose_nr_trial;
+/* Optional.  The caller sets trial_log / trial_capacity (may be NULL / 0) and points (double [npoints][3], may be NULL) before
+ * the call; ntrials counts every trial, of which the first trial_capacity are written (trial_overflow = 1 if there were more);
+ * results[nresults]: OptimizationAlgorithm::SolverResult per iteration (1 OK, 2 Terminate). */
+typedef struct {
+    int32_t rounds, iterations[4], trials[4], nresults, results[40];
+    int32_t trial_capacity, ntrials, trial_overflow, reserved;
+    orbm_pose_nr_trial *trial_log;
+    double q[4], t[3];   /* the final estimate of vertex 0 (x y z w) */
+    double *points;      /* the final point estimates */
+} orbm_pose_nr_stats;
+/* One upload, one launch on the model's stream, one host wait. */
+int orbm_pose_optimization_nr(fem_model *m, const orbm_pose_nr_graph *g, orbm_pose_nr_result *out, orbm_pose_nr_stats *stats);
+/* `batch` independent problems (relocalisation candidates, many cameras) in one launch, one workgroup each, on a stream of the
+ * library's own (never the legacy stream); models[k] belongs to graphs[k].  The launch does not wait on the models' own streams, so
+ * each model must be idle: no fem_* call on it in flight on another thread, and no asynchronous one (fem_cg_iterate) pending --
+ * every other call that changes a model (fem_assemble, fem_dirichlet_*, fem_trial_setup, fem_trial_energy) has waited for its
+ * stream before it returned.  stats: NULL or [batch].  A problem's results are byte for byte those of its single call. */
+int orbm_pose_optimization_nr_batch(fem_model *const *models, const orbm_pose_nr_graph *graphs, int batch, orbm_pose_nr_result *out,
+                                    orbm_pose_nr_stats *stats);
+
 /* Jacobi-preconditioned conjugate gradients, double vectors on the float matrix:
  * K x = b per mesh, x0 = 0.  Runs until `iters` iterations, or earlier when every
  * mesh has ||r|| <= tol*||b|| (checked every 25 iterations; tol <= 0 disables).

@@ -1142,6 +1142,63 @@ private:
     int mNBad = 0, mMaxTrialsAfterFailure = 10;                                                     // :50
 };
 
+// Optimizer::PoseOptimizationNR (src/Optimizer.cc:478-834) with the bundle itself on the device: Compute() is
+// PoseOptimizationNR_fem::Compute (fea2.Compute(1)'s numeric half and the hook's state parked on the device); operator() runs
+// :733-809 -- the four rounds of optimize(10), g2o's Levenberg trials with the hook, the Schur step, the inlier / outlier passes,
+// the write-back -- as ONE launch of orbm_pose_optimization_nr on the graph the caller has flattened from its walk over
+// MapPoint* / KeyFrame* (:515-709; integration/Optimizer_pose_nr_hip.cc).  Tcw = pFrame->mTcw (replaced by what SetPose receives),
+// points = GetWorldPos() of vpMapPoints (replaced by what SetWorldPos receives), outlier = mvbOutlier by point.  Returns
+// nInitialCorrespondences - nBad, or -1 on a library error (status() has the code: ORBX_ERR_UNSUPPORTED beyond the kernel's limits,
+// where PoseOptimizationNR_fem with g2o's own loop remains the path).
+class PoseOptimizationNR {
+public:
+    struct Graph {
+        std::vector<float> kfTcw;                 // [nkf][16]
+        std::vector<int32_t> ePoint, eCam;        // per edge, in vpEdges order; eCam -1 = the frame
+        std::vector<float> eObs, eInvSigma2, eCamK;   // [ne][2], [ne], [ne][4] = fx fy cx cy
+    };
+
+    explicit PoseOptimizationNR(int nElType) : fea2(3500, 0.495f, 0.5f, 0.577350269f, nElType) {}
+
+    bool Compute(const std::vector<float> &topXYZ, const std::vector<int32_t> &faces, int nVertices,
+                 const std::vector<int32_t> &derived = std::vector<int32_t>())
+    {
+        if (!fea2.Compute(topXYZ, faces)) return false;
+        mStatus = fem_trial_setup(fea2.model(), fea2.u0.data(), fea2.vDir.data(), (int)fea2.vDir.size(), 100000000.0f, nVertices,
+                                  derived.empty() ? nullptr : derived.data(), (int)derived.size() / 4);
+        return mStatus == ORBX_OK;
+    }
+
+    int operator()(const Graph &g, float Tcw[16], std::vector<float> &points, std::vector<uint8_t> &outlier,
+                   orbm_pose_nr_stats *stats = nullptr)
+    {
+        const size_t ne = g.ePoint.size();
+        if (points.size() % 3 || g.kfTcw.size() % 16 || g.eCam.size() != ne || g.eObs.size() != 2 * ne || g.eInvSigma2.size() != ne ||
+            g.eCamK.size() != 4 * ne) { mStatus = ORBX_ERR_ARG; return -1; }
+        orbm_pose_nr_graph c;
+        std::memset(&c, 0, sizeof(c));
+        c.npoints = (int32_t)(points.size() / 3); c.nkf = (int32_t)(g.kfTcw.size() / 16); c.nedges = (int32_t)ne;
+        c.Tcw = Tcw; c.kf_Tcw = g.kfTcw.data(); c.points = points.data(); c.e_point = g.ePoint.data(); c.e_cam = g.eCam.data();
+        c.e_obs = g.eObs.data(); c.e_inv_sigma2 = g.eInvSigma2.data(); c.e_cam_k = g.eCamK.data();
+        std::vector<float> pointsOut(points.size());
+        outlier.assign(points.size() / 3, 0);
+        orbm_pose_nr_result r;
+        std::memset(&r, 0, sizeof(r));
+        r.points_out = pointsOut.data(); r.outlier = outlier.data();
+        mStatus = orbm_pose_optimization_nr(fea2.model(), &c, &r, stats);
+        if (mStatus != ORBX_OK) return -1;
+        std::memcpy(Tcw, r.Tcw, sizeof(r.Tcw));
+        points.swap(pointsOut);
+        return r.ngood;
+    }
+
+    FEA2 fea2;
+    int status() const { return mStatus == ORBX_OK ? fea2.status() : mStatus; }
+
+private:
+    int mStatus = ORBX_OK;
+};
+
 // Optimizer::PoseOptimization(Frame *pFrame) (src/Optimizer.cc:264-476) on the flattened frame: one call of
 // orbm_pose_optimization (host arrays) or orbm_frame_pose_optimization (the frame's resident handle).  kpsUn = mvKeysUn,
 // uright = mvuRight (empty: monocular), hasMp[i] = mvpMapPoints[i] != NULL, mpPos[3 i ..] = its GetWorldPos(), Tcw = mTcw

@@ -31,8 +31,11 @@
 
 #include "../../include/fem_hip.h"
 #include "common.h"
+#include "fem_internal.h"
 
 namespace {
+
+using namespace fem_detail;   // the row sum and the block sum of the energy (shared with orbm_pose_nr.hip)
 
 constexpr int RPB = 256; // rows per block in the CG vector kernels
 constexpr int LPR = 8;   // lanes per row in the SpMV
@@ -375,28 +378,7 @@ __global__ __launch_bounds__(256) void k_fem_eliminate(float *__restrict__ vals,
     }
 }
 
-// f = K*a in float, ascending column order per row (= the dense row sum of MultiplyMatricesEigen with exact zeros skipped, and the
-// oracle's left-to-right sum, bit for bit).  16 lanes per row: they fetch 16 entries of the row side by side -- value, column,
-// a[column] -- and lane 0 of the group adds the 16 products IN ORDER, the products handed down the group one lane per step
-// (DPP row_shl:1).  The order of the additions is the reference's; only the memory round trips run side by side.  (One thread
-// walking its row alone waited for memory at every entry: 34 us for 3,756 rows of ~117 entries, most of an LM trial.)
-// Entries past the row's end contribute +0.0f, which leaves a float sum that started at +0.0f unchanged (it can never be -0.0f).
-__device__ __forceinline__ float fem_row_sum16(const float *__restrict__ v, const int *__restrict__ lcol, const float *__restrict__ am,
-                                               int k0, int k1, int sub)
-{
-    float s = 0.0f;
-    for (int kb = k0; kb < k1; kb += 16) {
-        const int k = kb + sub;
-        float p = 0.0f;
-        if (k < k1) p = v[k] * am[lcol[k]];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            s += p;                                                                                   // lane 0: + product j of the chunk
-            p = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x101, 0xf, 0xf, true));   // row_shl:1
-        }
-    }
-    return s;   // valid in lane 0 of the 16-lane group
-}
+// (fem_row_sum16, the row sum of f = K*a: fem_internal.h)
 __global__ __launch_bounds__(256) void k_fem_matvec(const float *__restrict__ vals, const int *__restrict__ lcol,
                                                     const int *__restrict__ rowptr, size_t nnz, int ndof, const float *__restrict__ a,
                                                     float *__restrict__ f)
@@ -413,30 +395,7 @@ __global__ __launch_bounds__(256) void k_fem_matvec(const float *__restrict__ va
 // (K is positive definite after the Dirichlet elimination, so p.Ap > 0 for p != 0).  The oracle's CG has the same guard.
 __device__ __forceinline__ double cg_ratio(double num, double den) { return den > 0.0 ? num / den : 0.0; }
 
-// Sum over the wave, the same value in every lane, in a fixed order: four DPP row_shr steps leave each row of 16 lanes' total in its
-// last lane, the four row totals are read into scalars and added row 0 .. 3.  No LDS round trips: the xor butterfly through
-// ds_bpermute (12 of them per f64 sum, each step waiting for the last) was 2 us of the 5 the coarse correction added per iteration.
-template <int N> __device__ __forceinline__ double dpp_shr_f64(double v)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)b, 0x110 + N, 0xf, 0xf, true);         // row_shr:N, 0 from beyond the row
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), 0x110 + N, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int l)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-    v += dpp_shr_f64<1>(v);
-    v += dpp_shr_f64<2>(v);
-    v += dpp_shr_f64<4>(v);
-    v += dpp_shr_f64<8>(v);
-    return ((readlane_f64(v, 15) + readlane_f64(v, 31)) + readlane_f64(v, 47)) + readlane_f64(v, 63);
-}
+// (wave_sum_f64 and the block_sum built on it: fem_internal.h)
 // The same sum, bit for bit, of a v that is +0.0 in every lane but 0 and 8 of each row (k_fem_spmv's p.Ap terms: one lane in eight): the
 // four steps above reduce to  row total = (v[8] + v[0]) + 0.0  -- every other term of the scan adds a +0.0, which changes nothing but
 // the sign of a -0.0, and the one `+ 0.0` left does the same (x + (-x) rounds to +0.0, so no case tells the two apart).
@@ -446,18 +405,6 @@ __device__ __forceinline__ double wave_sum_f64_lanes08(double v)
     v += 0.0;
     return ((readlane_f64(v, 8) + readlane_f64(v, 24)) + readlane_f64(v, 40)) + readlane_f64(v, 56);
 }
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-    v = wave_sum_f64(v);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    double t = 0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-    return t;
-}
-
 // Sum of n per-workgroup partials in a fixed order, the same value in every lane: lane l
 // adds part[l], part[l+64], ... and wave_sum_f64 joins the 64 lane sums.  (A serial
 // loop over the partials was 5 of the 8 us of k_fem_cg_update on one 6.6k-dof mesh.)
@@ -480,10 +427,10 @@ __global__ __launch_bounds__(256) void k_fem_energy(const float *__restrict__ a,
     for (int i = threadIdx.x; i < nrows; i += 256) s += (double)a[row0 + i] * (double)f[row0 + i];
     s = block_sum(s, sh);
     if (threadIdx.x == 0) {
-        float e = (float)s;
-        if (e < 0.0f) e = -e;
+        float e, ne;
+        strain_energy_of(s, nrows, e, ne);
         if (sE) sE[mesh] = e;
-        if (nsE) nsE[mesh] = e / (float)(nrows / 3);
+        if (nsE) nsE[mesh] = ne;
     }
 }
 
@@ -547,37 +494,9 @@ __global__ __launch_bounds__(TRIAL_T) void k_fem_trial_a_fused(const double *__r
                                                                int nder, int sequential, float *__restrict__ top, const float *__restrict__ u0,
                                                                float *__restrict__ a, const int *__restrict__ ids, int nids, float klarge)
 {
-    const int mesh = blockIdx.x, nTop = npoints + nder, ndof = 6 * nTop, tid = threadIdx.x;
-    float *t = top + (size_t)mesh * nTop * 3;
-    const double *p = points + (size_t)mesh * npoints * 3;
-    for (int i = tid; i < 3 * npoints; i += TRIAL_T) t[i] = (float)p[i];
-    __syncthreads();
-    if (nder) {
-        if (sequential) {
-            if (tid == 0)
-                for (int d = 0; d < nder; ++d) {
-                    const int *e = derived + 4 * d;
-                    for (int k = 0; k < 3; ++k)
-                        t[3 * (npoints + d) + k] = e[0] == 2 ? (t[3 * e[1] + k] + t[3 * e[2] + k]) / 2
-                                                             : (t[3 * e[1] + k] + t[3 * e[2] + k] + t[3 * e[3] + k]) / 3;
-                }
-        } else {
-            for (int i = tid; i < 3 * nder; i += TRIAL_T) {
-                const int d = i / 3, k = i - 3 * d;
-                const int *e = derived + 4 * d;
-                t[3 * (npoints + d) + k] = e[0] == 2 ? (t[3 * e[1] + k] + t[3 * e[2] + k]) / 2
-                                                     : (t[3 * e[1] + k] + t[3 * e[2] + k] + t[3 * e[3] + k]) / 3;
-            }
-        }
-        __syncthreads();
-    }
-    float *am = a + (size_t)mesh * ndof;
-    for (int i = tid; i < ndof; i += TRIAL_T) {
-        const float u = u0[i];
-        am[i] = (i < 3 * nTop ? t[i] : u) - u;
-    }
-    __syncthreads();
-    for (int q = tid; q < nids * 3; q += TRIAL_T) am[3 * (ids[q / 3] - 1) + q % 3] = 1 / klarge;
+    const int mesh = blockIdx.x, nTop = npoints + nder, ndof = 6 * nTop;
+    trial_displacement(points + (size_t)mesh * npoints * 3, npoints, derived, nder, sequential, top + (size_t)mesh * nTop * 3, u0,
+                       a + (size_t)mesh * ndof, ids, nids, klarge, threadIdx.x, TRIAL_T);
 }
 // (2) k_fem_matvec_energy: f = K a as k_fem_matvec (16 lanes per row, the additions in ascending column order), and the workgroup that finishes LAST
 // (a counter per mesh, which it resets) runs k_fem_energy's reduction -- the same 256 threads, strides and summation order, so
@@ -606,10 +525,10 @@ __global__ __launch_bounds__(256) void k_fem_matvec_energy(const float *__restri
     for (int i = threadIdx.x; i < ndof; i += 256) s += (double)am[i] * (double)__builtin_nontemporal_load(fm + i);
     s = block_sum(s, sh);
     if (threadIdx.x == 0) {
-        float e = (float)s;
-        if (e < 0.0f) e = -e;
+        float e, ne;
+        strain_energy_of(s, ndof, e, ne);
         if (sE) sE[mesh] = e;
-        if (nsE) nsE[mesh] = e / (float)(ndof / 3);
+        if (nsE) nsE[mesh] = ne;
         done[mesh] = 0;                   // ready for the next trial
     }
 }
@@ -3678,6 +3597,15 @@ int fem_trial_setup(fem_model *m, const float *u0, const int32_t *ids, int nids,
     }
     m->trial_ready = true;
     return ORBX_OK;
+}
+
+extern "C++" bool fem_detail::trial_view(const fem_model *m, TrialView *v)
+{
+    if (!m || !m->trial_ready || m->segmented() || m->nmesh != 1) return false;
+    v->vals = m->d_vals; v->u0 = m->d_tr_u0; v->lcol = m->d_lcol; v->rowptr = m->d_rowptr; v->derived = m->d_tr_derived; v->ids = m->d_tr_ids;
+    v->ndof = m->ndof; v->npoints = m->tr_npoints; v->nder = m->tr_nder; v->nids = m->tr_nids; v->sequential = m->tr_seq;
+    v->klarge = m->tr_klarge; v->stream = m->stream;
+    return true;
 }
 
 int fem_trial_energy(fem_model *m, const double *points, float *a_out, float *sE, float *nsE)

@@ -203,6 +203,7 @@ struct StagedCall {
     std::vector<In> ins;
     size_t staged = 0, res_off = 0, res_bytes = 0;
     int waits = 0;                  // host waits (stream synchronisations) of this call so far
+    hipStream_t on = nullptr;       // set before upload(): run on this stream (a fem_model's) instead of the workspace's own
     StagedCall() : w(*lease.w) { w.used = 0; }
     size_t in(const void *src, size_t bytes)
     {
@@ -221,20 +222,22 @@ struct StagedCall {
         return o;
     }
     bool offsets_fit_32_bits() const { return w.used <= 0xffffffffu; }  // for calls whose device records hold offsets as unsigned
-    hipStream_t stream() const { return w.st; }
+    hipStream_t stream() const { return on ? on : w.st; }
     template <typename T> T *d(size_t off) const { return reinterpret_cast<T *>(w.dev + off); }
     template <typename T> const T *r(size_t off) const { return reinterpret_cast<const T *>(w.pin + (off - res_off)); }
     int upload() // after the last in / scratch / out
     {
+        const char *dev_before = w.dev;
         if (w.reserve(w.used, staged > res_bytes ? staged : res_bytes)) return -1;
+        if (on && w.dev != dev_before && hipStreamSynchronize(w.st) != hipSuccess) return -1;   // a grown arena is zeroed on the workspace's stream
         for (const In &i : ins) memcpy(w.pin + i.off, i.src, i.bytes);
-        return orbx::stage_in(w.dev, w.pin, staged, w.st) != hipSuccess ? -1 : 0;
+        return orbx::stage_in(w.dev, w.pin, staged, stream()) != hipSuccess ? -1 : 0;
     }
     int download()
     {
-        if (orbx::stage_out(w.pin, w.dev + res_off, res_bytes, w.st) != hipSuccess) return -1;
+        if (orbx::stage_out(w.pin, w.dev + res_off, res_bytes, stream()) != hipSuccess) return -1;
         ++waits;
-        return hipStreamSynchronize(w.st) == hipSuccess ? 0 : -1;
+        return hipStreamSynchronize(stream()) == hipSuccess ? 0 : -1;
     }
 };
 
