@@ -242,7 +242,9 @@ int orbm_search_fuse(const orbm_window_query *queries, const uint8_t *qdesc, int
  * match_kp[j] = query whose point ends in slot j, -1 = slot untouched, -2 = slot set to
  * NULL by the rotation check; match_q[i] = keypoint chosen by query i when it was accepted
  * (before the rotation check) or -1; *nmatches as the reference counts it.
- * Limits: at most 8192 keypoints inside the grid, 65536 queries. */
+ * Limits: at most 8192 keypoints inside the grid, 65536 queries.  A keypoint octave outside 0..15 in the searched frame is
+ * ORBX_ERR_ARG ("octave out of range") here, in orbm_search_window, orbm_search_for_initialization, their resident-frame
+ * forms and the whole-function entries: a candidate entry holds the octave in four bits. */
 int orbm_search_projection(const orbm_window_query *queries, const uint8_t *qdesc, const float *qangle, const uint8_t *qtakes,
                            int nq, const orbx_keypoint *kps, const uint8_t *desc, int n, const uint8_t *occupied,
                            const float *uright, float min_x, float min_y, float max_x, float max_y, int th_accept, float nnratio,

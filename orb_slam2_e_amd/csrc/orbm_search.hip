@@ -1802,6 +1802,15 @@ void form_cam_common(FormCam &c, const orbm_view *v, const orbm_frame *f, int fo
 }
 
 bool bad_view(const orbm_view *v) { return !v || !v->scale_factors || v->nlevels < 1 || v->nlevels > 16; }
+// A candidate entry holds its keypoint's octave in four bits (k_win_wave, entry_level; k_win_best packs it the same way): a frame
+// with an octave outside 0..15 cannot be searched.
+bool bad_octaves(const orbx_keypoint *kps, int n)
+{
+    for (int j = 0; j < n; ++j)
+        if (kps[j].octave < 0 || kps[j].octave > 15) return true;
+    return false;
+}
+bool bad_octaves(const orbm_frame *f) { return f->n && (f->min_octave < 0 || f->max_octave > 15); }
 bool bad_points(const orbm_points *p, bool need_range, bool need_normal, bool need_octave, int nlevels)
 {
     if (!p || p->n < 0 || p->n > 65536) return true;
@@ -2095,6 +2104,7 @@ int orbm_search_window(const orbm_window_query *queries, const uint8_t *qdesc, i
     if (nq < 0 || n < 0 || n > 65535 || (nq && (!queries || !qdesc || !best || !best_level || !second || !second_level || !idx)) ||
         (n && (!kps || !desc)) || !(max_x > min_x) || !(max_y > min_y))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(kps, n)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     if (nq == 0) return ORBX_OK;
     SortedFrame sf;
@@ -2108,6 +2118,7 @@ int orbm_frame_search_window(const orbm_frame *frame, const orbm_window_query *q
 {
     if (!frame || nq < 0 || (nq && (!queries || !qdesc || !best || !best_level || !second || !second_level || !idx)))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(frame)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     if (nq == 0) return ORBX_OK;
     FrameSrc fs(frame);
@@ -2224,6 +2235,7 @@ int orbm_search_projection(const orbm_window_query *queries, const uint8_t *qdes
     if (nq < 0 || n < 0 || n > 65535 || (nq && (!queries || !qdesc || !match_q)) || (n && (!kps || !desc || !match_kp)) || !nmatches ||
         (check_orientation && nq && !qangle) || !(max_x > min_x) || !(max_y > min_y))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(kps, n)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     SortedFrame sf;
     sort_frame(kps, desc, n, nullptr, uright, min_x, min_y, max_x, max_y, sf);
@@ -2242,6 +2254,7 @@ int orbm_frame_search_projection(const orbm_frame *frame, const orbm_window_quer
 {
     if (!frame || nq < 0 || (nq && (!queries || !qdesc || !match_q)) || (frame->n && !match_kp) || !nmatches || (check_orientation && nq && !qangle))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(frame)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     FrameSrc fs(frame);
     SeqSearch r;
@@ -2260,6 +2273,7 @@ int orbm_search_for_initialization(const orbx_keypoint *kps1, const uint8_t *des
     if (n1 < 0 || n2 < 0 || n2 > 65535 || (n1 && (!kps1 || !desc1 || !prev_matched || !matches12)) || (n2 && (!kps2 || !desc2)) ||
         !nmatches || !(max_x > min_x) || !(max_y > min_y))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(kps2, n2)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     SortedFrame sf;
     sort_frame(kps2, desc2, n2, nullptr, nullptr, min_x, min_y, max_x, max_y, sf);
@@ -2273,6 +2287,7 @@ int orbm_frame_search_for_initialization(const orbm_frame *frame2, const orbx_ke
 {
     if (!frame2 || n1 < 0 || (frame2->n && !kps2) || (n1 && (!kps1 || !desc1 || !prev_matched || !matches12)) || !nmatches)
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(frame2)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     FrameSrc fs(frame2);
     return search_init_core(fs, frame2->n, kps2, kps1, desc1, n1, prev_matched, window_size, nnratio, check_orientation, matches12, nmatches);
@@ -2418,6 +2433,7 @@ int orbm_detail::search_by_projection_points_chain(const orbm_frame *cur, const 
     if (!cur || bad_view(view) || !Tcw || bad_points(points, true, true, false, view->nlevels) || !nmatches || (points->n && !match_q) ||
         (cur->n && !match_kp))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(cur)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     PointsPrefix px;
     px.pts = points; px.scale = view->scale_factors; px.frustum = true; px.proj_host = projected_out;
@@ -2448,6 +2464,7 @@ int orbm_detail::search_by_projection_last_chain(const orbm_frame *cur, const or
     if (!cur || bad_view(view) || !Tcw || !Tlw || bad_points(last, false, false, true, view->nlevels) || !nmatches ||
         (last->n && !match_q) || (cur->n && !match_kp) || (check_orientation && last->n && !last->angle))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(cur)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     PointsPrefix px;
     px.pts = last; px.scale = view->scale_factors;
@@ -2486,6 +2503,7 @@ int orbm_search_by_projection_keyframe(const orbm_frame *cur, const orbm_view *v
     if (!cur || bad_view(view) || !Tcw || bad_points(kf, true, false, false, view->nlevels) || !nmatches || (kf->n && !match_q) ||
         (cur->n && !match_kp) || (check_orientation && kf->n && !kf->angle))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(cur)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     PointsPrefix px;
     px.pts = kf; px.scale = view->scale_factors;
@@ -2508,6 +2526,7 @@ int orbm_search_by_projection_sim3(const orbm_frame *kf, const orbm_view *view, 
     if (!kf || bad_view(view) || !Scw || bad_points(points, true, true, false, view->nlevels) || !nmatches || (points->n && !match_q) ||
         (kf->n && !match_kp))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(kf)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     PointsPrefix px;
     px.pts = points; px.scale = view->scale_factors;
@@ -2540,6 +2559,7 @@ int orbm_search_by_sim3(const orbm_frame *kf1, const orbm_frame *kf2, const orbm
         bad_points(points2, true, false, false, view->nlevels) || !nfound || points1->n != kf1->n || points2->n != kf2->n ||
         (kf1->n && !match12))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bad_octaves(kf1) || bad_octaves(kf2)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     const int n1 = kf1->n, n2 = kf2->n;
     for (int i = 0; i < n1; ++i) { match12[i] = -1; if (vnMatch1) vnMatch1[i] = -1; }
