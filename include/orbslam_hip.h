@@ -33,7 +33,8 @@ enum {
 const char *orbx_last_error(void);
 /* ABI version of this header (major*100+minor).  136 (additions only): the pose-only optimisation (orbm_pose_*).  Added since
  * without a new number (additions only): orbm_create_new_map_points, orbm_debug_last_create_points_waits; orbm_sim3_hypotheses,
- * orbm_debug_last_sim3_waits; orbm_optimize_sim3, orbm_debug_last_sim3_opt_waits. */
+ * orbm_debug_last_sim3_waits; orbm_optimize_sim3, orbm_debug_last_sim3_opt_waits; orbm_map_create / _destroy / _size,
+ * orbm_search_by_projection_map_poses, orbm_frame_search_by_projection_map_poses, orbm_debug_last_map_poses_waits. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -596,6 +597,43 @@ int orbm_optimize_sim3(const orbm_sim3_opt_problem *problems, int P, const float
 /* Host waits (stream synchronisations) of the last orbm_optimize_sim3 call of this process: 1 when it launched, 0 when it returned
  * before the launch. */
 int orbm_debug_last_sim3_opt_waits(void);
+
+/* ------------------------------------------- the whole-map relocalisation search under P poses in one call
+ * PnPsolver::iterate(Frame&, .., Map*) (src/PnPsolver.cc:267-646) calls SearchByProjection(F, pMap, Rcw, tcw, ..) over and over
+ * with the same frame and the same map: after every refined RANSAC hypothesis (:355-398) and, in its second stage (:419-634), for
+ * up to five recorded poses walked twice.  Nothing couples those searches -- the search writes no state another search reads -- so
+ * all poses of a stage run in ONE launch, with one upload and one host wait.
+ *
+ * orbm_map is a snapshot of what pMap->GetAllMapPoints() returned: the five arrays of orbm_search_by_projection_map
+ * (mp_min_dist / mp_max_dist = GetMinDistanceInvariance() / GetMaxDistanceInvariance(), 32-byte descriptors), copied to HBM once.
+ * Opaque and immutable like orbm_frame: no slots, no updates, no link to orbm_points; it may be searched from several threads at
+ * once.  m = 0 is legal.  One Tracking::Relocalization() makes one snapshot and uses it for every candidate keyframe. */
+typedef struct orbm_map orbm_map;
+int orbm_map_create(const float *mp_pos, const float *mp_normal, const float *mp_min_dist, const float *mp_max_dist,
+                    const uint8_t *mp_desc, int m, orbm_map **out);
+int orbm_map_destroy(orbm_map *map);
+int orbm_map_size(const orbm_map *map, int *m);
+
+/* Rcw [P][9] row-major, tcw [P][3].  Row p of every output is what orbm_frame_search_by_projection_map returns for pose p, bit for
+ * bit: matched_mp [P][n] (the last map point wins), nmatches [P] (acceptances, not occupied slots), proj [P][m][4] or NULL (u, v,
+ * viewCos, level; level -1 where culled).  A pose's rows do not depend on the other poses of the call or on their order.
+ * has_mappoint [n] by keypoint index, or NULL: no keypoint holds a map point.
+ *   P = 0, m = 0 or n = 0   ORBX_OK, rows preset (-1 / 0), nothing is launched
+ *   P > 16                  ORBX_ERR_UNSUPPORTED (the second stage makes at most 10 searches)
+ *   ORBX_ERR_ARG            a NULL array that is needed, P < 0, nlevels outside 1 .. 16, a keypoint octave outside 0 .. 15
+ * Every refusal happens before any device work and writes nothing.  The host-array form uploads frame and map with the call. */
+int orbm_frame_search_by_projection_map_poses(const orbm_frame *frame, const uint8_t *has_mappoint, const orbm_map *map,
+                                              const double *Rcw, const double *tcw, int P, const orbm_camera *cam,
+                                              const float *scale_factors, int nlevels, float th, float nnratio, int th_reloc,
+                                              int32_t *matched_mp, int32_t *nmatches, float *proj);
+int orbm_search_by_projection_map_poses(const orbx_keypoint *kps, const uint8_t *desc, int n, const uint8_t *has_mappoint,
+                                        const float *mp_pos, const float *mp_normal, const float *mp_min_dist,
+                                        const float *mp_max_dist, const uint8_t *mp_desc, int m, const double *Rcw,
+                                        const double *tcw, int P, const orbm_camera *cam, const float *scale_factors, int nlevels,
+                                        float th, float nnratio, int th_reloc, int32_t *matched_mp, int32_t *nmatches, float *proj);
+/* Host waits (stream synchronisations) of the last ..._map_poses call of this process: 1 when it launched, 0 when it returned
+ * before the launch. */
+int orbm_debug_last_map_poses_waits(void);
 
 /* ------------------------------------------- the SearchByProjection forms and SearchBySim3 as WHOLE functions
  * Projection prefix, candidate search, in-loop assignment, acceptance and rotation check in one call, nothing in between

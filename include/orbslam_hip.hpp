@@ -814,6 +814,67 @@ public:
         return mStatus == ORBX_OK ? nm : 0;
     }
 
+    // What pMap->GetAllMapPoints() returned, flat and resident in HBM (orbm_map): made once per Tracking::Relocalization(), read by
+    // the searches of every candidate keyframe's PnPsolver::iterate.  Immutable; holds no reference to the arrays it was made from.
+    // Movable, not copyable; any number of searches may read it at once.
+    class MapSnapshot {
+    public:
+        MapSnapshot() = default;
+        MapSnapshot(const float *mpPos, const float *mpNormal, const float *mpMinDistance, const float *mpMaxDistance,
+                    const uint8_t *mpDescriptors, int nMapPoints)
+        {
+            mStatus = orbm_map_create(mpPos, mpNormal, mpMinDistance, mpMaxDistance, mpDescriptors, nMapPoints, &mH);
+            if (mStatus == ORBX_OK) orbm_map_size(mH, &N); else mH = nullptr;
+        }
+        MapSnapshot(MapSnapshot &&o) noexcept : N(o.N), mH(o.mH), mStatus(o.mStatus) { o.mH = nullptr; }
+        MapSnapshot &operator=(MapSnapshot &&o) noexcept { if (this != &o) { reset(); mH = o.mH; N = o.N; mStatus = o.mStatus; o.mH = nullptr; } return *this; }
+        MapSnapshot(const MapSnapshot &) = delete;
+        MapSnapshot &operator=(const MapSnapshot &) = delete;
+        ~MapSnapshot() { reset(); }
+        void reset() { if (mH) orbm_map_destroy(mH); mH = nullptr; }
+        const orbm_map *handle() const { return mH; }
+        int status() const { return mStatus; }
+        int N = 0;
+    private:
+        orbm_map *mH = nullptr;
+        int mStatus = ORBX_OK;
+    };
+    struct MapPose { double Rcw[9], tcw[3]; };      // row-major Rcw
+
+    // The search above under every pose of `poses` (at most 16) in ONE launch (orbm_frame_search_by_projection_map_poses):
+    // vMatchedMPs[p] and nmatches[p] are what the single-pose search returns for poses[p].  False (and empty rows) on failure.
+    bool SearchByProjection(const ResidentFrame &F, const std::vector<uint8_t> &hasMapPoint, const MapSnapshot &map,
+                            const std::vector<MapPose> &poses, const orbm_camera &cam, const std::vector<float> &scaleFactors, float th,
+                            std::vector<std::vector<int32_t>> &vMatchedMPs, std::vector<int> &nmatches)
+    {
+        const int P = (int)poses.size(), n = F.N;
+        std::vector<double> R((size_t)9 * P + 1), t((size_t)3 * P + 1);
+        for (int p = 0; p < P; ++p) {
+            std::copy(poses[p].Rcw, poses[p].Rcw + 9, R.begin() + 9 * p);
+            std::copy(poses[p].tcw, poses[p].tcw + 3, t.begin() + 3 * p);
+        }
+        std::vector<int32_t> rows((size_t)P * n + 1, -1), nm((size_t)P + 1, 0);
+        mStatus = orbm_frame_search_by_projection_map_poses(F.handle(), hasMapPoint.empty() ? nullptr : hasMapPoint.data(), map.handle(), R.data(),
+                                                            t.data(), P, &cam, scaleFactors.data(), (int)scaleFactors.size(), th, mfNNratio,
+                                                            TH_RELOC, rows.data(), nm.data(), nullptr);
+        vMatchedMPs.clear(); nmatches.clear();
+        if (mStatus != ORBX_OK) return false;
+        for (int p = 0; p < P; ++p) {
+            vMatchedMPs.emplace_back(rows.begin() + (size_t)p * n, rows.begin() + (size_t)(p + 1) * n);
+            nmatches.push_back(nm[p]);
+        }
+        return true;
+    }
+    // ... on a frame given as host arrays: its grid is built for this call (a Frame that is searched again keeps a ResidentFrame)
+    bool SearchByProjection(const FrameView &F, const std::vector<uint8_t> &hasMapPoint, const MapSnapshot &map,
+                            const std::vector<MapPose> &poses, const orbm_camera &cam, const std::vector<float> &scaleFactors, float th,
+                            std::vector<std::vector<int32_t>> &vMatchedMPs, std::vector<int> &nmatches)
+    {
+        const ResidentFrame R(F);
+        if (R.status() != ORBX_OK) { mStatus = R.status(); vMatchedMPs.clear(); nmatches.clear(); return false; }
+        return SearchByProjection(R, hasMapPoint, map, poses, cam, scaleFactors, th, vMatchedMPs, nmatches);
+    }
+
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:305-370) for many map points at once: the observed descriptors of
     // point i are rows off[i] .. off[i+1) of desc; best[i] = the row (within the point) with the least median distance.
     static int ComputeDistinctiveDescriptors(const uint8_t *desc, const std::vector<int32_t> &off, std::vector<int32_t> &best)

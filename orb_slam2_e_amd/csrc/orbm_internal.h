@@ -324,3 +324,11 @@ struct orbm_frame {
     std::vector<int> perm_host;                             // [n]: keypoint index at sorted position (the first ns: inside the grid)
     std::vector<int> inv_host;                              // [n]: sorted position of keypoint index
 };
+
+// The map as the whole-map search reads it (orbm_map_create): descriptors, positions, normals and the two distance bounds of m
+// map points in ONE device block.  Read-only after creation.
+struct orbm_map {
+    int m = 0;
+    char *block = nullptr;
+    uint4 *desc = nullptr; float *pos = nullptr, *nrm = nullptr, *mind = nullptr, *maxd = nullptr;
+};

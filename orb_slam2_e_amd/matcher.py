@@ -409,6 +409,48 @@ class ORBmatcher:
                                                           _p(matched), C.byref(nm), _p(proj)))
         return matched[:frame.n], nm.value, proj
 
+    # ---------------------------------------------------------------- the whole-map search under P poses in one call
+    def SearchByProjectionMapPoses(self, kps, desc, has_mp, mp_pos, mp_normal, mp_min_dist, mp_max_dist, mp_desc, Rcw, tcw, cam,
+                                   scale_factors, th=1.0, want_proj=True):
+        """SearchByProjection(Frame&, Map*, Rcw, tcw, ...) (ORBmatcher.cc:134-222) under P poses in one launch
+        (orbm_search_by_projection_map_poses): Rcw[P, 3, 3], tcw[P, 3]; frame and map travel with the call.
+        Returns (vMatchedMPs[P, n] as indices or -1, nmatches[P], proj[P, m, 4] or None): row p = SearchByProjectionMap at pose p."""
+        kps = np.ascontiguousarray(kps); d = np.ascontiguousarray(desc, np.uint8)
+        hm = np.ascontiguousarray(has_mp, np.uint8) if has_mp is not None else None
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        pos, nrm, mn, mx = f32(mp_pos), f32(mp_normal), f32(mp_min_dist), f32(mp_max_dist)
+        md = np.ascontiguousarray(mp_desc, np.uint8)
+        R, t, P = _poses(Rcw, tcw)
+        cam = np.ascontiguousarray(cam, self.CAM_DTYPE).reshape(1)
+        sc = f32(scale_factors)
+        n, m = len(kps), len(pos)
+        matched = np.zeros((P, n), np.int32); nm = np.zeros(P, np.int32)
+        proj = np.zeros((P, m, 4), np.float32) if want_proj else None
+        check(self._L.orbm_search_by_projection_map_poses(_p(kps), _p(d), n, _p(hm) if hm is not None else None, _p(pos), _p(nrm), _p(mn),
+                                                          _p(mx), _p(md), m, _p(R), _p(t), P, _p(cam), _p(sc), len(sc), th, self.mfNNratio,
+                                                          self.TH_RELOC, _p(matched), _p(nm), _p(proj) if want_proj else None))
+        return matched, nm, proj
+
+    def frame_search_by_projection_map_poses(self, frame, has_mp, snapshot, Rcw, tcw, cam, scale_factors, th=1.0, want_proj=True):
+        """The same on a resident frame and a MapSnapshot (orbm_frame_search_by_projection_map_poses): the call uploads
+        has_mp, the poses and the scale factors only."""
+        hm = np.ascontiguousarray(has_mp, np.uint8) if has_mp is not None else None
+        R, t, P = _poses(Rcw, tcw)
+        cam = np.ascontiguousarray(cam, self.CAM_DTYPE).reshape(1)
+        sc = np.ascontiguousarray(scale_factors, np.float32)
+        n, m = frame.n, snapshot.m
+        matched = np.zeros((P, n), np.int32); nm = np.zeros(P, np.int32)
+        proj = np.zeros((P, m, 4), np.float32) if want_proj else None
+        check(self._L.orbm_frame_search_by_projection_map_poses(frame._h, _p(hm) if hm is not None else None, snapshot._h, _p(R), _p(t), P,
+                                                                _p(cam), _p(sc), len(sc), th, self.mfNNratio, self.TH_RELOC, _p(matched),
+                                                                _p(nm), _p(proj) if want_proj else None))
+        return matched, nm, proj
+
+    @staticmethod
+    def last_map_poses_waits():
+        """orbm_debug_last_map_poses_waits: host waits of the last ..._map_poses call of this process (1 when it launched)."""
+        return lib().orbm_debug_last_map_poses_waits()
+
     def frame_search_by_bow(self, frame1, fv1, valid1, frame2, fv2, valid2=None, kf_kf=False):
         """SearchByBoW on two resident frames (orbm_frame_search_by_bow): fv = feature_vector_arrays(...) of each side.
         Returns (match12, match21, nmatches)."""
@@ -562,6 +604,14 @@ class ORBmatcher:
         return out + (q12[:n1], q21[:n2]) if want_queries else out
 
 
+def _poses(Rcw, tcw):
+    """Rcw[P, 3, 3] (or [P, 9]), tcw[P, 3] as the flat double arrays of the ..._map_poses entries."""
+    R = np.ascontiguousarray(Rcw, np.float64).reshape(-1, 9); t = np.ascontiguousarray(tcw, np.float64).reshape(-1, 3)
+    if len(R) != len(t):
+        raise ValueError("Rcw and tcw differ in the number of poses")
+    return R, t, len(R)
+
+
 class TrackResult(C.Structure):
     """orbm_track_result"""
     _fields_ = [("tracked", C.c_int32), ("search_used", C.c_int32), ("nsearch", C.c_int32), ("ngood", C.c_int32), ("nmatches", C.c_int32),
@@ -679,6 +729,32 @@ class Frame:
     def close(self):
         if getattr(self, "_h", None):
             self._L.orbm_frame_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class MapSnapshot:
+    """orbm_map: what pMap->GetAllMapPoints() returned, flat and resident in HBM (immutable; made once per relocalisation).
+    mp_min_dist / mp_max_dist are the GetMinDistanceInvariance() / GetMaxDistanceInvariance() values."""
+
+    def __init__(self, mp_pos, mp_normal, mp_min_dist, mp_max_dist, mp_desc):
+        self._L = lib()
+        self._h = C.c_void_p()
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        pos, nrm, mn, mx = f32(mp_pos).reshape(-1, 3), f32(mp_normal).reshape(-1, 3), f32(mp_min_dist), f32(mp_max_dist)
+        md = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
+        if not (len(pos) == len(nrm) == len(mn) == len(mx) == len(md)):
+            raise ValueError("the map arrays differ in length")
+        check(self._L.orbm_map_create(_p(pos), _p(nrm), _p(mn), _p(mx), _p(md), len(pos), C.byref(self._h)))
+        m = C.c_int(0)
+        check(self._L.orbm_map_size(self._h, C.byref(m)))
+        self.m = m.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbm_map_destroy(self._h)
             self._h = None
 
     def __del__(self):
