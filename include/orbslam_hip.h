@@ -441,6 +441,40 @@ int orbm_frame_size(const orbm_frame *frame, int *n, int *nsorted);
 /* introspection (tests): the device-built order as orbm_sorted_frame returns it: perm[nsorted], cell_off[64 * 48 + 1] */
 int orbm_frame_layout(const orbm_frame *frame, int32_t *perm, int32_t *cell_off);
 
+/* ---- Frame::UndistortKeyPoints / ComputeImageBounds (src/Frame.cc:419-479) and frames straight from the extractor.
+ * The camera as the launch files give it: mK (fx, fy, cx, cy) and mDistCoef (k1, k2, p1, p2, k3; k3 = 0 when the file has four
+ * entries).  A keypoint goes through cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK) as OpenCV 3.4 evaluates it for
+ * CV_32FC2 points (double arithmetic, five iterations; restated in csrc/orbm_undistort.h, parity unpinned); k1 == 0 means no
+ * undistortion at all, whatever the other coefficients are (the reference tests k1 only).  Near the border of a wide-angle image
+ * the five iterations diverge: such results are huge or not finite, as the reference's are, and lie outside the grid.
+ * Every entry refuses (ORBX_ERR_ARG) a camera with a non-finite field or with fx == 0 or fy == 0. */
+typedef struct orbm_distortion { float fx, fy, cx, cy, k1, k2, p1, p2, k3; } orbm_distortion;
+
+/* Frame::ComputeImageBounds: bounds[4] = mnMinX, mnMinY, mnMaxX, mnMaxY (k1 == 0: 0, 0, width, height).  Host only, no device needed. */
+int orbm_image_bounds(const orbm_distortion *cam, int width, int height, float *bounds);
+
+/* n points on the device, one launch, one wait; xy / xy_un [n][2], may alias; n = 0 ok */
+int orbm_undistort_points(const orbm_distortion *cam, const float *xy, int n, float *xy_un);
+
+/* As orbm_frame_from_extractor, with the undistortion done inside the frame build: the keypoints never leave the device.  Without a
+ * host uright array the call does not read the keypoint count back first (one host wait); with one it does (two).
+ * cam NULL or cam->k1 == 0: exactly orbm_frame_from_extractor with xy_undistorted = NULL. */
+int orbm_frame_from_extractor_cam(orbx_extractor *ex, int frame, const orbm_distortion *cam, const float *uright, int uright_from_stereo,
+                                  float min_x, float min_y, float max_x, float max_y, orbm_frame **out);
+
+/* Frames first .. first + count - 1 of the extractor's last batch -> out[0 .. count - 1]: ONE launch (a workgroup per frame), one
+ * copy of every header and permutation, one host wait.  out[i] equals the single call for frame first + i.  Right coordinates come
+ * from the last orbx_stereo_match (uright_from_stereo) or not at all.  All or nothing: on any failure no handle is left and out
+ * is not written.  count = 0: ORBX_OK, nothing launched. */
+int orbm_frames_from_extractor(orbx_extractor *ex, int first, int count, const orbm_distortion *cam, int uright_from_stereo,
+                               float min_x, float min_y, float max_x, float max_y, orbm_frame **out);
+
+/* mvKeysUn coordinates of a handle by keypoint index, xy[n][2] (what the searches use) */
+int orbm_frame_keypoints_un(const orbm_frame *frame, float *xy);
+
+/* host waits (stream synchronisations) of the last frame-making call of this process */
+int orbm_debug_last_frame_build_waits(void);
+
 /* The host-array searches above, on a resident frame (same results; `skip` / `occupied` by keypoint index as there). */
 int orbm_frame_search_window(const orbm_frame *frame, const orbm_window_query *queries, const uint8_t *qdesc, int nq, const uint8_t *skip,
                              int init_dist, int32_t *best, int32_t *best_level, int32_t *second, int32_t *second_level, int32_t *idx);

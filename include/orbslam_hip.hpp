@@ -433,6 +433,21 @@ public:
     // ---- resident frames and the projection searches as whole functions ----------------------------------------------------
     // A Frame / KeyFrame kept in HBM between searches (orbm_frame): Frame::AssignFeaturesToGrid runs once, on the device.
     // Holds no reference to the arrays it was made from.  Movable, not copyable; any number of searches may read it at once.
+    // mK and mDistCoef of a launch file (k3 = 0 when it has four coefficients).  k1 == 0: no undistortion (Frame.cc:421-425).
+    struct Distortion {
+        float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f, k1 = 0.f, k2 = 0.f, p1 = 0.f, p2 = 0.f, k3 = 0.f;
+        orbm_distortion c() const { return orbm_distortion{fx, fy, cx, cy, k1, k2, p1, p2, k3}; }
+    };
+    // Frame::ComputeImageBounds (Frame.cc:451-479), on the host; returns the status
+    static int ImageBounds(const Distortion &cam, int width, int height, float &mnMinX, float &mnMinY, float &mnMaxX, float &mnMaxY)
+    {
+        const orbm_distortion c = cam.c();
+        float b[4];
+        const int rc = orbm_image_bounds(&c, width, height, b);
+        if (rc == ORBX_OK) { mnMinX = b[0]; mnMinY = b[1]; mnMaxX = b[2]; mnMaxY = b[3]; }
+        return rc;
+    }
+
     class ResidentFrame {
     public:
         ResidentFrame() = default;
@@ -444,6 +459,40 @@ public:
         {
             mStatus = orbm_frame_from_extractor(ex.handle(), 0, xyUndistorted, uRight, uRightFromStereo, mnMinX, mnMinY, mnMaxX, mnMaxY, &mH);
             sync();
+        }
+        // ... with Frame::UndistortKeyPoints done inside the frame build: the keypoints never leave the device
+        ResidentFrame(ORBextractor &ex, const Distortion &cam, const float *uRight, bool uRightFromStereo, float mnMinX, float mnMinY,
+                      float mnMaxX, float mnMaxY)
+        {
+            const orbm_distortion c = cam.c();
+            mStatus = orbm_frame_from_extractor_cam(ex.handle(), 0, &c, uRight, uRightFromStereo, mnMinX, mnMinY, mnMaxX, mnMaxY, &mH);
+            sync();
+        }
+        // frames first .. first + count - 1 of the extractor's last batch in ONE launch (orbm_frames_from_extractor); all or nothing:
+        // an empty vector and *status (when given) say why.  cam null: the coordinates as the extractor left them.
+        static std::vector<ResidentFrame> FromBatch(ORBextractor &ex, int first, int count, const Distortion *cam, bool uRightFromStereo,
+                                                    float mnMinX, float mnMinY, float mnMaxX, float mnMaxY, int *status = nullptr)
+        {
+            std::vector<orbm_frame *> h((size_t)(count > 0 ? count : 1), nullptr);
+            orbm_distortion c = orbm_distortion();
+            if (cam) c = cam->c();
+            const int rc = orbm_frames_from_extractor(ex.handle(), first, count, cam ? &c : nullptr, uRightFromStereo, mnMinX, mnMinY, mnMaxX,
+                                                      mnMaxY, h.data());
+            if (status) *status = rc;
+            std::vector<ResidentFrame> out;
+            for (int i = 0; rc == ORBX_OK && i < count; ++i) {
+                out.emplace_back();
+                out.back().mH = h[i];
+                out.back().sync();
+            }
+            return out;
+        }
+        // mvKeysUn coordinates by keypoint index (x0, y0, x1, ...): what the searches use
+        std::vector<float> KeysUn() const
+        {
+            std::vector<float> xy((size_t)2 * (size_t)N);
+            if (mH && orbm_frame_keypoints_un(mH, xy.data()) != ORBX_OK) xy.clear();
+            return xy;
         }
         ResidentFrame(ResidentFrame &&o) noexcept : mH(o.mH), N(o.N), mStatus(o.mStatus) { o.mH = nullptr; }
         ResidentFrame &operator=(ResidentFrame &&o) noexcept { if (this != &o) { reset(); mH = o.mH; N = o.N; mStatus = o.mStatus; o.mH = nullptr; } return *this; }

@@ -42,6 +42,52 @@ inline HipFramePtr HipFrameFromExtractor(orbx_extractor *ex, const std::vector<c
     return rc == ORBX_OK ? HipFrameAdopt(f) : HipFramePtr();
 }
 
+// mK and mDistCoef (4 or 5 entries; Tracking.cc reads k3 only when the settings file has it) as the library takes them
+inline orbm_distortion HipDistortion(const cv::Mat &mK, const cv::Mat &mDistCoef)
+{
+    orbm_distortion c;
+    c.fx = mK.at<float>(0, 0); c.fy = mK.at<float>(1, 1); c.cx = mK.at<float>(0, 2); c.cy = mK.at<float>(1, 2);
+    c.k1 = mDistCoef.at<float>(0); c.k2 = mDistCoef.at<float>(1); c.p1 = mDistCoef.at<float>(2); c.p2 = mDistCoef.at<float>(3);
+    c.k3 = mDistCoef.total() > 4 ? mDistCoef.at<float>(4) : 0.0f;
+    return c;
+}
+
+// Frame::ComputeImageBounds (src/Frame.cc:451-479) without cv::undistortPoints: false = the library refused the camera
+inline bool HipImageBounds(const cv::Mat &mK, const cv::Mat &mDistCoef, int cols, int rows, float &mnMinX, float &mnMinY, float &mnMaxX,
+                           float &mnMaxY)
+{
+    const orbm_distortion c = HipDistortion(mK, mDistCoef);
+    float b[4];
+    if (orbm_image_bounds(&c, cols, rows, b) != ORBX_OK) return false;
+    mnMinX = b[0]; mnMinY = b[1]; mnMaxX = b[2]; mnMaxY = b[3];
+    return true;
+}
+
+// The same end of a Frame constructor with Frame::UndistortKeyPoints (src/Frame.cc:419-449) done inside the frame build: called IN
+// PLACE of UndistortKeyPoints (after ExtractORB and, in the stereo constructor, ComputeStereoMatches), it makes the handle from the
+// extractor's device results and mK / mDistCoef, and fills mvKeysUn from the handle -- the undistortion becomes a download of what the
+// searches use.  No keypoint coordinate travels to the device.
+inline HipFramePtr HipFrameFromExtractor(orbx_extractor *ex, const cv::Mat &mK, const cv::Mat &mDistCoef, const std::vector<cv::KeyPoint> &mvKeys,
+                                         std::vector<cv::KeyPoint> &mvKeysUn, const std::vector<float> &mvuRight, bool stereoOnDevice,
+                                         float mnMinX, float mnMinY, float mnMaxX, float mnMaxY)
+{
+    const orbm_distortion c = HipDistortion(mK, mDistCoef);
+    bool anyRight = false;
+    for (size_t i = 0; i < mvuRight.size() && !anyRight; ++i) anyRight = mvuRight[i] >= 0;
+    orbm_frame *f = nullptr;
+    if (orbm_frame_from_extractor_cam(ex, 0, &c, (!stereoOnDevice && anyRight) ? mvuRight.data() : nullptr, stereoOnDevice ? 1 : 0, mnMinX,
+                                      mnMinY, mnMaxX, mnMaxY, &f) != ORBX_OK)
+        return HipFramePtr();
+    HipFramePtr frame = HipFrameAdopt(f);
+    int n = 0;
+    std::vector<float> xy(2 * mvKeys.size());
+    if (orbm_frame_size(f, &n, nullptr) != ORBX_OK || (size_t)n != mvKeys.size() || orbm_frame_keypoints_un(f, xy.data()) != ORBX_OK)
+        return HipFramePtr();
+    mvKeysUn = mvKeys;
+    for (size_t i = 0; i < mvKeysUn.size(); ++i) { mvKeysUn[i].pt.x = xy[2 * i]; mvKeysUn[i].pt.y = xy[2 * i + 1]; }
+    return frame;
+}
+
 // KeyFrame::KeyFrame(Frame &F, ...): the Frame's grid, the KeyFrame's int-valued bounds (include/KeyFrame.h:201-204)
 inline HipFramePtr HipFrameForKeyFrame(const HipFramePtr &frame, int mnMinX, int mnMinY, int mnMaxX, int mnMaxY)
 {

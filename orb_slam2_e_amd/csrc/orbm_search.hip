@@ -38,6 +38,7 @@
 
 #include "common.h"
 #include "orbm_internal.h"
+#include "orbm_undistort.h"
 #include "orbx_internal.h"
 #include "orbx_math.h"
 
@@ -1170,12 +1171,33 @@ __global__ __launch_bounds__(MT) void k_rotation(const int *__restrict__ acc_sp,
 constexpr int FB_T = 1024, FB_MAXN = SEQ_MAXN, FB_NC = FRAME_GRID_COLS * FRAME_GRID_ROWS;
 constexpr size_t FB_LDS = sizeof(int) * (2 * (size_t)FB_NC + 2) + (size_t)FB_MAXN * (2 + 2 + 1 + 1);
 
-__global__ __launch_bounds__(FB_T) void k_frame_build(const orbx_keypoint *__restrict__ kps, const uint4 *__restrict__ desc_raw,
-                                                      const float2 *__restrict__ xy_un, const float *__restrict__ uright_raw,
-                                                      const int *__restrict__ n_dev, int n_host, GridParams gp, SeqKp *__restrict__ kp,
-                                                      uint4 *__restrict__ desc, float *__restrict__ angle, int *__restrict__ perm,
-                                                      int *__restrict__ cell_off, FrameHdr *__restrict__ hdr)
+// What k_frame_build reads of one frame: where the keypoints are (n on the device or from the host, never more than n_max) and the
+// arrays of the block it fills.  res_hdr / res_perm: a second copy of the header and the permutation, in the launch's result block
+// (the batch form: ONE copy brings every frame's pair to the host), or null.
+struct FrameJob {
+    const orbx_keypoint *kps; const uint4 *desc_raw; const float2 *xy_un; const float *uright_raw; const int *n_dev;
+    int n_host, n_max;
+    SeqKp *kp; uint4 *desc; float *angle; int *perm; int *cell_off; FrameHdr *hdr;
+    FrameHdr *res_hdr; int *res_perm;
+};
+
+// One workgroup per frame.  BATCH: frame blockIdx.x of `table` (in the call's staged block); otherwise `one`, from the kernel's own
+// arguments (chosen when compiled: a pointer that may be either makes every access of the record a per-lane flat load).  cam: the
+// keypoint coordinates go through Frame::UndistortKeyPoints (undistort_point; cam.k1 == 0: they stay) unless xy_un replaces them.
+template <bool BATCH>
+__global__ __launch_bounds__(FB_T) void k_frame_build(FrameJob one, const FrameJob *__restrict__ table, GridParams gp, orbm_distortion cam)
 {
+    const FrameJob J = BATCH ? table[blockIdx.x] : one;
+    const orbx_keypoint *__restrict__ kps = J.kps;
+    const uint4 *__restrict__ desc_raw = J.desc_raw;
+    const float2 *__restrict__ xy_un = J.xy_un;
+    const float *__restrict__ uright_raw = J.uright_raw;
+    const int *__restrict__ n_dev = J.n_dev;
+    SeqKp *__restrict__ kp = J.kp;
+    uint4 *__restrict__ desc = J.desc;
+    float *__restrict__ angle = J.angle;
+    int *__restrict__ perm = J.perm, *__restrict__ cell_off = J.cell_off, *__restrict__ res_perm = J.res_perm;
+    FrameHdr *hdr = J.hdr, *res_hdr = J.res_hdr;
     extern __shared__ __align__(16) unsigned char fb_sm[];
     int *s_off = reinterpret_cast<int *>(fb_sm);                 // [FB_NC + 1] histogram, then exclusive scan
     int *s_run = s_off + FB_NC + 1;                              // [FB_NC + 1] keypoints of the cell placed so far (last entry: scan carry)
@@ -1183,13 +1205,15 @@ __global__ __launch_bounds__(FB_T) void k_frame_build(const orbx_keypoint *__res
     unsigned short *s_pos = s_cell + FB_MAXN;                    // [n] sorted position
     unsigned char *s_low = reinterpret_cast<unsigned char *>(s_pos + FB_MAXN), *s_tot = s_low + FB_MAXN;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = min(n_dev ? *n_dev : n_host, FB_MAXN);
+    const int n = min(min(n_dev ? *n_dev : J.n_host, J.n_max), FB_MAXN);
     __shared__ int s_omin, s_omax;     // octave range of the keypoints (the searches index per-level tables with it)
     if (tid == 0) { s_omin = INT_MAX; s_omax = INT_MIN; }
     for (int c = tid; c <= FB_NC; c += FB_T) { s_off[c] = 0; s_run[c] = 0; }
     __syncthreads();
     for (int j = tid; j < n; j += FB_T) {
-        const float x = xy_un ? xy_un[j].x : kps[j].x, y = xy_un ? xy_un[j].y : kps[j].y;
+        float x, y;
+        if (xy_un) { x = xy_un[j].x; y = xy_un[j].y; }
+        else undistort_point(cam, kps[j].x, kps[j].y, &x, &y);
         const int px = orbx_f2i_x86(roundf((x - gp.min_x) * gp.inv_w)), py = orbx_f2i_x86(roundf((y - gp.min_y) * gp.inv_h));   // NaN: outside
         const bool in = !(px < 0 || px >= FRAME_GRID_COLS || py < 0 || py >= FRAME_GRID_ROWS);
         const int c = in ? px * FRAME_GRID_ROWS + py : FB_NC;   // FB_NC: outside the grid -- kept behind the sorted part, in index order
@@ -1248,18 +1272,39 @@ __global__ __launch_bounds__(FB_T) void k_frame_build(const orbx_keypoint *__res
     int omin = INT_MAX, omax = INT_MIN;
     for (int j = tid; j < n; j += FB_T) {
         const int sp = s_pos[j];
+        // every load in front of the first store (the pointers come from a table: the compiler cannot tell them apart, and a
+        // load behind a store would wait for its own round trip)
         const orbx_keypoint k = kps[j];
+        const uint4 d0 = desc_raw[2 * j], d1 = desc_raw[2 * j + 1];
+        const float ur = uright_raw ? uright_raw[j] : -1.0f;
+        const float2 c = xy_un ? xy_un[j] : make_float2(k.x, k.y);
         omin = min(omin, k.octave); omax = max(omax, k.octave);
         SeqKp o;
-        o.x = xy_un ? xy_un[j].x : k.x; o.y = xy_un ? xy_un[j].y : k.y;
-        o.uright = uright_raw ? uright_raw[j] : -1.0f;
+        if (xy_un) { o.x = c.x; o.y = c.y; }
+        else undistort_point(cam, k.x, k.y, &o.x, &o.y);        // (a pure function of the keypoint: the bits of the first pass)
+        o.uright = ur;
         o.octave = k.octave;
         kp[sp] = o; angle[sp] = k.angle; perm[sp] = j;
-        desc[2 * sp] = desc_raw[2 * j]; desc[2 * sp + 1] = desc_raw[2 * j + 1];
+        if (res_perm) res_perm[sp] = j;
+        desc[2 * sp] = d0; desc[2 * sp + 1] = d1;
     }
     if (omin <= omax) { atomicMin(&s_omin, omin); atomicMax(&s_omax, omax); }
     __syncthreads();
-    if (tid == 0) { hdr->n = n; hdr->ns = s_off[FB_NC]; hdr->min_octave = s_omin; hdr->max_octave = s_omax; }
+    if (tid == 0) {
+        const FrameHdr h = {n, s_off[FB_NC], s_omin, s_omax};
+        *hdr = h;
+        if (res_hdr) *res_hdr = h;
+    }
+}
+
+// Frame::UndistortKeyPoints on n points, one thread each (orbm_undistort_points)
+__global__ __launch_bounds__(MT) void k_undistort_points(orbm_distortion cam, const float2 *__restrict__ xy, int n, float2 *__restrict__ xy_un)
+{
+    const int i = blockIdx.x * MT + threadIdx.x;
+    if (i >= n) return;
+    float2 o;
+    undistort_point(cam, xy[i].x, xy[i].y, &o.x, &o.y);
+    xy_un[i] = o;
 }
 
 // The projection prefixes of the remaining SearchByProjection forms and of SearchBySim3, one thread per list entry, in the
@@ -1467,32 +1512,34 @@ void frame_release(orbm_frame *f)
     delete f;
 }
 
-// k_frame_build on `st` from device-resident inputs, then the header and the permutation back to the host (one small
-// block through the pinned arena of the leased workspace `w`, whose first pin_need bytes must be free for it).
-int frame_build(orbm_frame *f, Workspace &w, const orbx_keypoint *d_kps, const uint4 *d_desc, const float2 *d_xy, const float *d_ur,
-                const int *d_n, int n_host, int n_bound)
+std::atomic<int> g_last_frame_build_waits{0};    // host waits of the last frame-making call (orbm_debug_last_frame_build_waits)
+
+int frame_build_prepare()
 {
     static std::atomic<bool> attr_set{false};
     if (!attr_set.load(std::memory_order_acquire)) {
-        ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_frame_build), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS));
+        ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_frame_build<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS));
+        ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_frame_build<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS));
         attr_set.store(true, std::memory_order_release);
     }
-    hipStream_t st = w.st;
-    hipLaunchKernelGGL(k_frame_build, dim3(1), dim3(FB_T), FB_LDS, st, d_kps, d_desc, d_xy, d_ur, d_n, n_host, f->gp, f->kp, f->desc,
-                       f->angle, f->perm, f->cell_off, f->hdr);
-    ORBX_HIP(hipGetLastError());
-    // results: hdr (256-byte slot) + perm[n_bound], staged out through the arena's tail
-    const size_t bytes = (256 + sizeof(int) * (size_t)n_bound + 15) & ~(size_t)15;
-    char *pin = w.pin + w.pin_cap - ((bytes + 255) & ~(size_t)255);
-    ORBX_HIP(hipMemcpyAsync(pin, f->hdr, sizeof(FrameHdr), hipMemcpyDeviceToHost, st));
-    ORBX_HIP(hipMemcpyAsync(pin + 256, f->perm, sizeof(int) * (size_t)n_bound, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(hipStreamSynchronize(st));
+    return ORBX_OK;
+}
+
+FrameJob frame_job(const orbm_frame *f, const orbx_keypoint *d_kps, const uint4 *d_desc, const float2 *d_xy, const float *d_ur, const int *d_n,
+                   int n_host, int n_bound)
+{
+    return {d_kps, d_desc, d_xy, d_ur, d_n, n_host, n_bound, f->kp, f->desc, f->angle, f->perm, f->cell_off, f->hdr, nullptr, nullptr};
+}
+
+// What the host keeps of a built frame: the header and the permutation as they came back (hdr, perm[n_bound])
+int frame_adopt(orbm_frame *f, const void *hdr, const int *perm, int n_bound)
+{
     FrameHdr h;
-    memcpy(&h, pin, sizeof(h));
+    memcpy(&h, hdr, sizeof(h));
     f->n = h.n; f->ns = h.ns;
     f->min_octave = h.n ? h.min_octave : 0; f->max_octave = h.n ? h.max_octave : -1;
     if (h.n < 0 || h.n > n_bound || h.ns < 0 || h.ns > h.n) ORBX_FAIL(ORBX_ERR_HIP, "frame header out of range");
-    f->perm_host.assign(reinterpret_cast<const int *>(pin + 256), reinterpret_cast<const int *>(pin + 256) + h.n);
+    f->perm_host.assign(perm, perm + h.n);
     f->inv_host.assign((size_t)h.n, 0);
     for (int sp = 0; sp < h.n; ++sp) {
         const int j = f->perm_host[sp];
@@ -1500,6 +1547,27 @@ int frame_build(orbm_frame *f, Workspace &w, const orbx_keypoint *d_kps, const u
         f->inv_host[j] = sp;
     }
     return ORBX_OK;
+}
+
+// k_frame_build on `st` from device-resident inputs, then the header and the permutation back to the host (one small
+// block through the pinned arena of the leased workspace `w`, whose first pin_need bytes must be free for it).
+// cam: Frame::UndistortKeyPoints inside the build (null: the coordinates as they are, or d_xy).
+int frame_build(orbm_frame *f, Workspace &w, const orbx_keypoint *d_kps, const uint4 *d_desc, const float2 *d_xy, const float *d_ur,
+                const int *d_n, int n_host, int n_bound, const orbm_distortion *cam = nullptr)
+{
+    if (const int rc = frame_build_prepare()) return rc;
+    hipStream_t st = w.st;
+    hipLaunchKernelGGL(k_frame_build<false>, dim3(1), dim3(FB_T), FB_LDS, st, frame_job(f, d_kps, d_desc, d_xy, d_ur, d_n, n_host, n_bound),
+                       (const FrameJob *)nullptr, f->gp, cam ? *cam : orbm_distortion{});
+    ORBX_HIP(hipGetLastError());
+    // results: hdr (256-byte slot) + perm[n_bound], staged out through the arena's tail
+    const size_t bytes = (256 + sizeof(int) * (size_t)n_bound + 15) & ~(size_t)15;
+    char *pin = w.pin + w.pin_cap - ((bytes + 255) & ~(size_t)255);
+    ORBX_HIP(hipMemcpyAsync(pin, f->hdr, sizeof(FrameHdr), hipMemcpyDeviceToHost, st));
+    ORBX_HIP(hipMemcpyAsync(pin + 256, f->perm, sizeof(int) * (size_t)n_bound, hipMemcpyDeviceToHost, st));
+    ORBX_HIP(hipStreamSynchronize(st));
+    g_last_frame_build_waits.fetch_add(1, std::memory_order_relaxed);      // counted where the stream is waited for
+    return frame_adopt(f, pin, reinterpret_cast<const int *>(pin + 256), n_bound);
 }
 
 // The frame of a call: sorted on the host and staged with the call's inputs (the host-array entry points), or resident.
@@ -2181,6 +2249,7 @@ int orbm_frame_create(const orbx_keypoint *kps, const uint8_t *desc, int n, cons
     if (!out || n < 0 || (n && (!kps || !desc)) || !(max_x > min_x) || !(max_y > min_y)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     if (n > FB_MAXN) ORBX_FAIL(ORBX_ERR_CAPACITY, "more than 8,192 keypoints in a resident frame");
     ORBX_NEED_DEVICE();
+    g_last_frame_build_waits.store(0, std::memory_order_relaxed);
     orbm_frame *f = new orbm_frame();
     f->min_x = min_x; f->min_y = min_y; f->max_x = max_x; f->max_y = max_y; f->has_uright = uright ? 1 : 0;
     for (int i = 0; uright && i < n; ++i) f->nstereo += uright[i] >= 0;
@@ -2206,20 +2275,32 @@ int orbm_frame_create(const orbx_keypoint *kps, const uint8_t *desc, int n, cons
     return ORBX_OK;
 }
 
-int orbm_frame_from_extractor(orbx_extractor *ex, int frame, const float *xy_undistorted, const float *uright, int uright_from_stereo,
-                              float min_x, float min_y, float max_x, float max_y, orbm_frame **out)
+// A frame of the extractor's last batch with empty arrays and the grid of the given bounds (null: allocation failed)
+static orbm_frame *frame_for_extractor(const orbx_extractor *ex, int has_uright, float min_x, float min_y, float max_x, float max_y)
+{
+    orbm_frame *f = new orbm_frame();
+    f->min_x = min_x; f->min_y = min_y; f->max_x = max_x; f->max_y = max_y; f->has_uright = has_uright;
+    f->nstereo = f->has_uright ? -1 : 0;
+    f->gp = {min_x, min_y, (float)FRAME_GRID_COLS / (max_x - min_x), (float)FRAME_GRID_ROWS / (max_y - min_y)};
+    if (frame_alloc(f, ex->kcap)) { frame_release(f); return nullptr; }
+    return f;
+}
+
+// orbm_frame_from_extractor / orbm_frame_from_extractor_cam: the coordinates from the host (xy_undistorted), through the camera
+// inside the build (cam), or as the extractor left them (both null)
+static int frame_from_extractor(orbx_extractor *ex, int frame, const float *xy_undistorted, const orbm_distortion *cam, const float *uright,
+                                int uright_from_stereo, float min_x, float min_y, float max_x, float max_y, orbm_frame **out)
 {
     if (!out || !ex || frame < 0 || frame >= ex->last_batch || !(max_x > min_x) || !(max_y > min_y) || (uright && uright_from_stereo))
         ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (cam && !distortion_ok(*cam)) ORBX_FAIL(ORBX_ERR_ARG, "camera with a non-finite field or a zero focal length");
     if (ex->kcap > FB_MAXN) ORBX_FAIL(ORBX_ERR_CAPACITY, "more than 8,192 keypoints in a resident frame");
     if (uright_from_stereo && (!ex->d_uright || !ex->st_valid || frame >= ex->st_batch)) ORBX_FAIL(ORBX_ERR_ARG, "no stereo results");
     ORBX_NEED_DEVICE();
+    g_last_frame_build_waits.store(0, std::memory_order_relaxed);
     const int cap = ex->kcap;
-    orbm_frame *f = new orbm_frame();
-    f->min_x = min_x; f->min_y = min_y; f->max_x = max_x; f->max_y = max_y; f->has_uright = (uright || uright_from_stereo) ? 1 : 0;
-    f->nstereo = f->has_uright ? -1 : 0;
-    f->gp = {min_x, min_y, (float)FRAME_GRID_COLS / (max_x - min_x), (float)FRAME_GRID_ROWS / (max_y - min_y)};
-    if (frame_alloc(f, cap)) { frame_release(f); ORBX_FAIL(ORBX_ERR_HIP, "frame allocation failed"); }
+    orbm_frame *f = frame_for_extractor(ex, (uright || uright_from_stereo) ? 1 : 0, min_x, min_y, max_x, max_y);
+    if (!f) ORBX_FAIL(ORBX_ERR_HIP, "frame allocation failed");
     WorkspaceLease lease;
     Workspace &w = *lease.w;
     w.used = 0;
@@ -2235,6 +2316,7 @@ int orbm_frame_from_extractor(orbx_extractor *ex, int frame, const float *xy_und
     int rc = ORBX_OK;
     if (xy_undistorted || uright) {
         if (hipMemcpyAsync(&n_known, d_n, sizeof(int), hipMemcpyDeviceToHost, w.st) != hipSuccess || hipStreamSynchronize(w.st) != hipSuccess) rc = ORBX_ERR_HIP;
+        g_last_frame_build_waits.fetch_add(1, std::memory_order_relaxed);
         if (rc == ORBX_OK && (n_known < 0 || n_known > cap)) rc = ORBX_ERR_HIP;
         if (rc == ORBX_OK) {
             if (xy_undistorted) memcpy(w.h<char>(o_xy), xy_undistorted, sizeof(float) * 2 * (size_t)n_known);
@@ -2245,10 +2327,122 @@ int orbm_frame_from_extractor(orbx_extractor *ex, int frame, const float *xy_und
     if (rc == ORBX_OK)
         rc = frame_build(f, w, ex->d_kps + (size_t)frame * cap, reinterpret_cast<const uint4 *>(d_desc),
                          xy_undistorted ? w.d<float2>(o_xy) : nullptr,
-                         uright ? w.d<float>(o_u) : (uright_from_stereo ? ex->d_uright + (size_t)frame * cap : nullptr), d_n, 0, cap);
+                         uright ? w.d<float>(o_u) : (uright_from_stereo ? ex->d_uright + (size_t)frame * cap : nullptr), d_n, 0, cap, cam);
     (void)producer;      // frame_build has waited for the stream: nothing of this call still reads the extractor's buffers
     if (rc != ORBX_OK) { frame_release(f); if (rc == ORBX_ERR_HIP) ORBX_FAIL(ORBX_ERR_HIP, "building the frame failed"); return rc; }
     *out = f;
+    return ORBX_OK;
+}
+
+int orbm_frame_from_extractor(orbx_extractor *ex, int frame, const float *xy_undistorted, const float *uright, int uright_from_stereo,
+                              float min_x, float min_y, float max_x, float max_y, orbm_frame **out)
+{
+    return frame_from_extractor(ex, frame, xy_undistorted, nullptr, uright, uright_from_stereo, min_x, min_y, max_x, max_y, out);
+}
+
+int orbm_frame_from_extractor_cam(orbx_extractor *ex, int frame, const orbm_distortion *cam, const float *uright, int uright_from_stereo,
+                                  float min_x, float min_y, float max_x, float max_y, orbm_frame **out)
+{
+    return frame_from_extractor(ex, frame, nullptr, cam, uright, uright_from_stereo, min_x, min_y, max_x, max_y, out);
+}
+
+int orbm_frames_from_extractor(orbx_extractor *ex, int first, int count, const orbm_distortion *cam, int uright_from_stereo, float min_x,
+                               float min_y, float max_x, float max_y, orbm_frame **out)
+{
+    if (!out || !ex || first < 0 || count < 0 || count > ex->last_batch || first > ex->last_batch - count || !(max_x > min_x) || !(max_y > min_y))
+        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (cam && !distortion_ok(*cam)) ORBX_FAIL(ORBX_ERR_ARG, "camera with a non-finite field or a zero focal length");
+    if (ex->kcap > FB_MAXN) ORBX_FAIL(ORBX_ERR_CAPACITY, "more than 8,192 keypoints in a resident frame");
+    if (uright_from_stereo && (!ex->d_uright || !ex->st_valid || first + count > ex->st_batch)) ORBX_FAIL(ORBX_ERR_ARG, "no stereo results");
+    ORBX_NEED_DEVICE();
+    g_last_frame_build_waits.store(0, std::memory_order_relaxed);
+    if (count == 0) return ORBX_OK;
+    const int cap = ex->kcap;
+    std::vector<orbm_frame *> fs((size_t)count, nullptr);
+    auto fail = [&](int rc, const char *what) {       // all or nothing
+        for (orbm_frame *f : fs)
+            if (f) frame_release(f);
+        ORBX_FAIL(rc, what);
+    };
+    for (int i = 0; i < count; ++i)
+        if (!(fs[i] = frame_for_extractor(ex, uright_from_stereo ? 1 : 0, min_x, min_y, max_x, max_y))) return fail(ORBX_ERR_HIP, "frame allocation failed");
+    if (frame_build_prepare() != ORBX_OK) return fail(ORBX_ERR_HIP, "building the frames failed");
+    // staged: the table of the frames; result block: a 256-byte header slot and perm[cap] per frame
+    WorkspaceLease lease;
+    Workspace &w = *lease.w;
+    w.used = 0;
+    const size_t slot = (256 + sizeof(int) * (size_t)cap + 255) & ~(size_t)255;
+    const size_t o_tab = w.carve(sizeof(FrameJob) * (size_t)count), staged = w.used, o_res = w.carve(slot * (size_t)count), res_bytes = w.used - o_res;
+    const size_t total = w.used;
+    if (w.reserve(total, std::max(staged, res_bytes))) return fail(ORBX_ERR_HIP, "workspace allocation failed");
+    FrameJob *tab = w.h<FrameJob>(o_tab);
+    for (int i = 0; i < count; ++i) {
+        const size_t fr = (size_t)(first + i);
+        tab[i] = frame_job(fs[i], ex->d_kps + fr * cap, reinterpret_cast<const uint4 *>(ex->d_desc + fr * cap * 32), nullptr,
+                           uright_from_stereo ? ex->d_uright + fr * cap : nullptr, ex->d_counts + fr, 0, cap);
+        tab[i].res_hdr = reinterpret_cast<FrameHdr *>(w.dev + o_res + slot * i);
+        tab[i].res_perm = reinterpret_cast<int *>(w.dev + o_res + slot * i + 256);
+    }
+    const hipStream_t st = w.st;
+    orbx_extractor *producer = orbx_detail::order_after_producer(ex->d_desc + (size_t)first * cap * 32, st);
+    bool ok = orbx::stage_in(w.dev, w.pin, staged, st) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_frame_build<true>, dim3(count), dim3(FB_T), FB_LDS, st, tab[0], (const FrameJob *)w.d<FrameJob>(o_tab), fs[0]->gp,
+                           cam ? *cam : orbm_distortion{});
+        ok = hipGetLastError() == hipSuccess && orbx::stage_out(w.pin, w.dev + o_res, res_bytes, st) == hipSuccess;
+    }
+    ok = hipStreamSynchronize(st) == hipSuccess && ok;     // (waited for in any case: nothing of this call still reads the extractor's buffers)
+    g_last_frame_build_waits.store(1, std::memory_order_relaxed);
+    (void)producer;
+    if (!ok) return fail(ORBX_ERR_HIP, "building the frames failed");
+    for (int i = 0; i < count; ++i) {
+        const char *r = w.pin + slot * i;
+        if (frame_adopt(fs[i], r, reinterpret_cast<const int *>(r + 256), cap) != ORBX_OK) return fail(ORBX_ERR_HIP, "frame header out of range");
+    }
+    for (int i = 0; i < count; ++i) out[i] = fs[i];
+    return ORBX_OK;
+}
+
+int orbm_frame_keypoints_un(const orbm_frame *f, float *xy)
+{
+    if (!f || (f->n && !xy)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (f->n == 0) return ORBX_OK;
+    ORBX_NEED_DEVICE();
+    std::vector<SeqKp> kp((size_t)f->n);
+    WorkspaceLease lease;
+    const hipStream_t st = lease.w->own_stream();
+    if (!st) ORBX_FAIL(ORBX_ERR_HIP, "hipStreamCreate failed");
+    ORBX_HIP(hipMemcpyAsync(kp.data(), f->kp, sizeof(SeqKp) * (size_t)f->n, hipMemcpyDeviceToHost, st));
+    ORBX_HIP(hipStreamSynchronize(st));
+    for (int sp = 0; sp < f->n; ++sp) { xy[2 * f->perm_host[sp]] = kp[sp].x; xy[2 * f->perm_host[sp] + 1] = kp[sp].y; }
+    return ORBX_OK;
+}
+
+int orbm_debug_last_frame_build_waits(void) { return g_last_frame_build_waits.load(std::memory_order_relaxed); }
+
+int orbm_image_bounds(const orbm_distortion *cam, int width, int height, float *bounds)
+{
+    if (!cam || !bounds || width <= 0 || height <= 0 || !distortion_ok(*cam)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    float x[4], y[4];       // (0, 0), (w, 0), (0, h), (w, h): Frame::ComputeImageBounds (src/Frame.cc:451-479)
+    for (int i = 0; i < 4; ++i) undistort_point(*cam, (i & 1) ? (float)width : 0.0f, (i & 2) ? (float)height : 0.0f, &x[i], &y[i]);
+    bounds[0] = std::min(x[0], x[2]); bounds[1] = std::min(y[0], y[1]);
+    bounds[2] = std::max(x[1], x[3]); bounds[3] = std::max(y[2], y[3]);
+    return ORBX_OK;
+}
+
+int orbm_undistort_points(const orbm_distortion *cam, const float *xy, int n, float *xy_un)
+{
+    if (!cam || n < 0 || (n && (!xy || !xy_un)) || !distortion_ok(*cam)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    ORBX_NEED_DEVICE();
+    if (n == 0) return ORBX_OK;
+    StagedCall sc;
+    const size_t o_in = sc.in(xy, sizeof(float) * 2 * (size_t)n), o_out = sc.out(sizeof(float) * 2 * (size_t)n);
+    if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
+    hipLaunchKernelGGL(k_undistort_points, dim3((n + MT - 1) / MT), dim3(MT), 0, sc.stream(), *cam, (const float2 *)sc.d<float2>(o_in), n,
+                       sc.d<float2>(o_out));
+    ORBX_HIP(hipGetLastError());
+    if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
+    memcpy(xy_un, sc.r<float>(o_out), sizeof(float) * 2 * (size_t)n);
     return ORBX_OK;
 }
 

@@ -688,6 +688,29 @@ class View:
         self.c = _CView(fx, fy, cx, cy, mb, mbf, log_scale_factor, len(self._sc), _p(self._sc))
 
 
+class Distortion(C.Structure):
+    """orbm_distortion: mK (fx, fy, cx, cy) and mDistCoef (k1, k2, p1, p2, k3) of a launch file.  k1 == 0: no undistortion."""
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+    def __init__(self, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+        super().__init__(fx, fy, cx, cy, k1, k2, p1, p2, k3)
+
+
+def image_bounds(camera, width, height):
+    """Frame::ComputeImageBounds: (mnMinX, mnMinY, mnMaxX, mnMaxY) as float32 (host only)."""
+    b = np.zeros(4, np.float32)
+    check(lib().orbm_image_bounds(C.byref(camera), int(width), int(height), _p(b)))
+    return tuple(b)
+
+
+def undistort_points(camera, xy):
+    """Frame::UndistortKeyPoints on an (n, 2) float32 array, on the device."""
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    out = np.zeros_like(xy)
+    check(lib().orbm_undistort_points(C.byref(camera), _p(xy) if len(xy) else None, len(xy), _p(out) if len(xy) else None))
+    return out
+
+
 class Frame:
     """orbm_frame: a Frame / KeyFrame resident in HBM (grid built once, on the device)."""
 
@@ -706,14 +729,42 @@ class Frame:
         self.n, self.ns = n.value, ns.value
 
     @classmethod
-    def from_extractor(cls, ex, frame=0, bounds=(0.0, 0.0, 640.0, 480.0), xy_undistorted=None, uright=None, uright_from_stereo=False):
+    def from_extractor(cls, ex, frame=0, bounds=(0.0, 0.0, 640.0, 480.0), xy_undistorted=None, uright=None, uright_from_stereo=False,
+                       camera=None):
+        """camera (a Distortion): Frame::UndistortKeyPoints runs inside the frame build (orbm_frame_from_extractor_cam); it and
+        xy_undistorted exclude each other."""
         L = lib()
         h = C.c_void_p()
         xy = np.ascontiguousarray(xy_undistorted, np.float32) if xy_undistorted is not None else None
         ur = np.ascontiguousarray(uright, np.float32) if uright is not None else None
-        check(L.orbm_frame_from_extractor(ex._h, int(frame), _p(xy) if xy is not None else None, _p(ur) if ur is not None else None,
-                                          int(bool(uright_from_stereo)), *[float(b) for b in bounds], C.byref(h)))
+        if camera is not None:
+            if xy is not None:
+                raise ValueError("camera and xy_undistorted exclude each other")
+            check(L.orbm_frame_from_extractor_cam(ex._h, int(frame), C.byref(camera), _p(ur) if ur is not None else None,
+                                                  int(bool(uright_from_stereo)), *[float(b) for b in bounds], C.byref(h)))
+        else:
+            check(L.orbm_frame_from_extractor(ex._h, int(frame), _p(xy) if xy is not None else None, _p(ur) if ur is not None else None,
+                                              int(bool(uright_from_stereo)), *[float(b) for b in bounds], C.byref(h)))
         return cls(bounds=bounds, _handle=h)
+
+    @classmethod
+    def batch_from_extractor(cls, ex, first, count, bounds=(0.0, 0.0, 640.0, 480.0), camera=None, uright_from_stereo=False):
+        """orbm_frames_from_extractor: frames first .. first + count - 1 of the extractor's last batch in ONE launch; a list of Frames."""
+        hs = (C.c_void_p * max(int(count), 1))()
+        check(lib().orbm_frames_from_extractor(ex._h, int(first), int(count), C.byref(camera) if camera is not None else None,
+                                               int(bool(uright_from_stereo)), *[float(b) for b in bounds], hs))
+        return [cls(bounds=bounds, _handle=C.c_void_p(hs[i])) for i in range(int(count))]
+
+    @staticmethod
+    def last_build_waits():
+        """orbm_debug_last_frame_build_waits: host waits of the last frame-making call of this process."""
+        return lib().orbm_debug_last_frame_build_waits()
+
+    def keypoints_un(self):
+        """orbm_frame_keypoints_un: the mvKeysUn coordinates by keypoint index, (n, 2) float32 (what the searches use)."""
+        xy = np.zeros((self.n, 2), np.float32)
+        check(self._L.orbm_frame_keypoints_un(self._h, _p(xy) if self.n else None))
+        return xy
 
     def alias(self, bounds):
         """orbm_frame_alias: the same device data searched with other bounds (a KeyFrame's int-valued mnMinX .. mnMaxY)."""
