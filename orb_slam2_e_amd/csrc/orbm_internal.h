@@ -1,6 +1,8 @@
-// orbm_internal.h -- pieces shared by the matcher translation units (orbm_match.hip, orbm_search.hip, orbm_triang.hip,
-// orbm_pose.hip, orbm_sim3.hip, orbm_sim3opt.hip): the Frame grid constants, the keypoint / query records of the windowed
-// searches, the resident frame (struct orbm_frame), the per-call workspace and small host / device helpers.
+// orbm_internal.h -- pieces shared by the matcher translation units (orbm_match.hip, orbm_frame.hip, orbm_window.hip,
+// orbm_search.hip, orbm_triang.hip, orbm_pose.hip, orbm_pose_nr.hip, orbm_sim3.hip, orbm_sim3opt.hip): the Frame grid constants,
+// the keypoint / query records of the windowed searches, the resident frame (struct orbm_frame) and the map snapshot (struct
+// orbm_map), the per-call workspace and small host / device helpers.  What only orbm_frame.hip, orbm_window.hip and
+// orbm_search.hip share among themselves is in orbm_search_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,10 +21,6 @@ namespace orbm_detail {
 constexpr int MT = 256; // threads per block of the small helper kernels
 constexpr int FRAME_GRID_ROWS = 48, FRAME_GRID_COLS = 64; // include/Frame.h:37-38
 
-// order = grid cell << 16 | keypoint index: ascending order = the order in which
-// Frame::GetFeaturesInArea (src/Frame.cc:342-395) lists its result (column-major cells,
-// insertion order inside a cell); 0xffffffff = not in the grid / skipped.
-struct WinKp { float x, y, uright; int octave; unsigned order; };
 struct WinQuery { float u, v, r, xr; int min_level, max_level; };
 // Sorted keypoint record of the windowed searches: position sp in the array = rank in GetFeaturesInArea order.
 struct SeqKp { float x, y, uright; int octave; };
@@ -150,21 +148,6 @@ inline int triangulation_rotation_check(int32_t *match12, int n1, int check_orie
     for (int i = 0; i < n1; ++i) nm += match12[i] >= 0;
     *nmatches = nm;
     return ORBX_OK;
-}
-
-// Frame::AssignFeaturesToGrid / PosInGrid (src/Frame.cc:245-260,397-407), on the host: n float ops.
-inline void build_winkp(const orbx_keypoint *kps, int n, const uint8_t *skip, const float *uright, float min_x, float min_y,
-                        float max_x, float max_y, std::vector<WinKp> &wk)
-{
-    const float invW = (float)FRAME_GRID_COLS / (max_x - min_x), invH = (float)FRAME_GRID_ROWS / (max_y - min_y);
-    wk.resize(n ? n : 1);
-    for (int j = 0; j < n; ++j) {
-        const int px = orbx_f2i_x86(roundf((kps[j].x - min_x) * invW)), py = orbx_f2i_x86(roundf((kps[j].y - min_y) * invH));
-        const bool in = !(px < 0 || px >= FRAME_GRID_COLS || py < 0 || py >= FRAME_GRID_ROWS);
-        wk[j].x = kps[j].x; wk[j].y = kps[j].y; wk[j].octave = kps[j].octave;
-        wk[j].uright = uright ? uright[j] : -1.0f;
-        wk[j].order = (in && !(skip && skip[j])) ? ((unsigned)(px * FRAME_GRID_ROWS + py) << 16) | (unsigned)j : 0xffffffffu;
-    }
 }
 
 // Per-call scratch without per-call hipMalloc: a pool of workspaces (device arena, pinned

@@ -28,17 +28,19 @@
 //      (:1802-1843) and rejects the matches outside the three main bins.
 // The host never waits in the middle of a call (run_sequential over a SeqSearch: seq_layout, seq_stage, seq_lists, seq_resolve,
 // seq_collect): the entry buffer is sized per query and the flags that ask for a repeat come back with the results.
+// The frames these loops search are made in orbm_frame.hip; the window searches whose queries do not depend on each other, the
+// whole-map search among them, are in orbm_window.hip.  The three units share orbm_search_internal.h: a frame comes through
+// FrameSrc / FrameView, and SearchBySim3 (below) runs its two directions on the other unit's launch_win_best.
 #include <limits.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <atomic>
-#include <mutex>
 #include <vector>
 
 #include "common.h"
 #include "orbm_internal.h"
-#include "orbm_undistort.h"
+#include "orbm_search_internal.h"
 #include "orbx_internal.h"
 #include "orbx_math.h"
 
@@ -46,25 +48,11 @@ using namespace orbm_detail;
 
 namespace {
 
-constexpr int SEQ_MAXN = 8192;     // keypoints per frame the resolver's LDS state holds
 enum { ACCEPT_BEST = 0, ACCEPT_RATIO_SAME_LEVEL = 1, ACCEPT_RATIO = 2 };
 
 
 constexpr int TOPK = 8; // best candidates per query kept sorted for the resolver
 
-
-// Minimum over the wave, in every lane: a butterfly inside each row of 16 lanes on the DPP path (no LDS crossbar round trips),
-// then the four row results through scalar registers.  All 64 lanes must be active.
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
-{
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xf, 0xf, false));    // quad_perm [1, 0, 3, 2]
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xf, 0xf, false));    // quad_perm [2, 3, 0, 1]
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xf, 0xf, false));   // row_half_mirror
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xf, 0xf, false));   // row_mirror
-    const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 0), b = (unsigned)__builtin_amdgcn_readlane((int)v, 16),
-                   c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
-    return min(min(a, b), min(c, d));
-}
 
 // The TOPK entries of a list with the smallest (distance, position) keys, in that
 // order -- all the sequential resolver normally needs.  Run by the wave that has just written the list
@@ -734,123 +722,6 @@ __global__ __launch_bounds__(RES_T) void k_resolve_init_par(const unsigned *__re
     if (tid == 0) host_nm[0] = s_nm - removed;
 }
 
-// Window search without coupling between queries = Frame::GetFeaturesInArea (src/Frame.cc:342-395)
-// fused with the best / second-best-with-levels loop of SearchByProjection (ORBmatcher.cc:69-118).
-// One wave per query walks the window's runs of the sorted keypoint array as k_win_wave does; every
-// lane keeps the two smallest keys dist << 16 | position-in-visiting-order of its candidates (strict
-// '<', first wins = smallest key; bestDist2 = second smallest), two wave reductions pick the winners.
-// Outputs: best / second distance (init_dist when absent), their octaves (-1), arg-best as a
-// keypoint index (-1).
-// The walk and the selection are device functions (win_best_walk, win_best_select): k_map_search_poses runs the same two on the
-// items of its queue.
-struct WinBest { unsigned k1, k2, e1, e2; };        // the two smallest keys of a lane and their entries e = octave << 16 | sorted position
-struct WinPick { int best, second, blevel, slevel, sp; };   // distances (init_dist when absent), octaves (-1), arg-best as a sorted position (-1)
-
-__device__ __forceinline__ WinBest win_best_walk(const WinQuery &w, const uint4 *__restrict__ a, int lane, const SeqKp *__restrict__ kp,
-                                                 const uint4 *__restrict__ B, const int *__restrict__ cell_off,
-                                                 const uint8_t *__restrict__ occ, const GridParams &gp, int has_uright, int init_dist,
-                                                 const float *__restrict__ inv_sigma2, int fuse_gate)
-{
-    unsigned k1 = 0xffffffffu, k2 = 0xffffffffu, e1 = 0, e2 = 0; // e = octave << 16 | sorted position
-    int c = 0;
-    const int nMinCellX = (int)fmaxf(0.f, floorf((w.u - gp.min_x - w.r) * gp.inv_w));
-    const int nMaxCellX = (int)fminf((float)FRAME_GRID_COLS - 1, ceilf((w.u - gp.min_x + w.r) * gp.inv_w));
-    const int nMinCellY = (int)fmaxf(0.f, floorf((w.v - gp.min_y - w.r) * gp.inv_h));
-    const int nMaxCellY = (int)fminf((float)FRAME_GRID_ROWS - 1, ceilf((w.v - gp.min_y + w.r) * gp.inv_h));
-    const bool none = !(w.r >= 0.f) || nMinCellX >= FRAME_GRID_COLS || nMaxCellX < 0 || nMinCellY >= FRAME_GRID_ROWS || nMaxCellY < 0;
-    if (!none) {
-        const bool check_levels = (w.min_level > 0) || (w.max_level >= 0);
-        const uint4 a0 = a[0], a1 = a[1];
-        const unsigned long long lt = (1ull << lane) - 1ull;
-        for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-            const int r0 = cell_off[ix * FRAME_GRID_ROWS + nMinCellY], r1 = cell_off[ix * FRAME_GRID_ROWS + nMaxCellY + 1];
-            for (int kb = r0; kb < r1; kb += 64) {
-                const int k = kb + lane;
-                bool ok = k < r1;
-                SeqKp p = {0.f, 0.f, 0.f, 0};
-                if (ok) p = kp[k];
-                if (occ && ok) ok = occ[k] == 0;
-                if (check_levels) ok = ok && !(p.octave < w.min_level) && !(w.max_level >= 0 && p.octave > w.max_level);
-                const float distx = p.x - w.u, disty = p.y - w.v;
-                ok = ok && fabsf(distx) < w.r && fabsf(disty) < w.r;
-                bool use = ok; // in the visiting order (position) every keypoint of the window counts; `use`: it is scored
-                if (fuse_gate == 0) {
-                    if (has_uright && p.uright > 0) ok = ok && !(fabsf(w.xr - p.uright) > w.r);
-                    use = ok;
-                } else if (ok && inv_sigma2) { // reprojection-error gate of ORBmatcher::Fuse (:1109-1132)
-                    const float ex = w.u - p.x, ey = w.v - p.y;
-                    if (has_uright && p.uright >= 0) {
-                        const float er = w.xr - p.uright;
-                        const float e2 = ex * ex + ey * ey + er * er;
-                        use = !((double)(e2 * inv_sigma2[p.octave]) > 7.8);
-                    } else {
-                        const float e2 = ex * ex + ey * ey;
-                        use = !((double)(e2 * inv_sigma2[p.octave]) > 5.99);
-                    }
-                }
-                const unsigned long long bal = __ballot(ok);
-                if (use) {
-                    const int dist = popc256(a0, a1, B[2 * k], B[2 * k + 1]);
-                    if (dist < init_dist) { // dist<bestDist / dist<bestDist2 can only fire below the initial value
-                        const unsigned key = ((unsigned)dist << 16) | (unsigned)(c + __popcll(bal & lt));
-                        const unsigned en = ((unsigned)p.octave << 16) | (unsigned)k;
-                        if (key < k1) { k2 = k1; e2 = e1; k1 = key; e1 = en; }
-                        else if (key < k2) { k2 = key; e2 = en; }
-                    }
-                }
-                c += __popcll(bal);
-            }
-        }
-    }
-    return {k1, k2, e1, e2};
-}
-
-// smallest key of the wave, then the smallest of what is left (keys are unique); the same result in every lane
-__device__ __forceinline__ WinPick win_best_select(const WinBest &t, int init_dist)
-{
-    const unsigned g1 = wave_min_u32(t.k1);
-    const bool own1 = g1 != 0xffffffffu && t.k1 == g1;
-    const unsigned long long b1 = __ballot(own1);
-    const unsigned c2 = own1 ? t.k2 : t.k1;
-    const unsigned g2 = wave_min_u32(c2);
-    const unsigned long long b2 = __ballot(g2 != 0xffffffffu && c2 == g2);
-    const unsigned w1 = b1 ? (unsigned)__shfl((int)t.e1, __ffsll((long long)b1) - 1) : 0u;
-    const unsigned w2 = b2 ? (unsigned)__shfl((int)(own1 ? t.e2 : t.e1), __ffsll((long long)b2) - 1) : 0u;
-    WinPick o;
-    o.best = b1 ? (int)(g1 >> 16) : init_dist;
-    o.sp = b1 ? (int)(w1 & 0xffffu) : -1;
-    o.blevel = b1 ? (int)(w1 >> 16) : -1;
-    o.second = b2 ? (int)(g2 >> 16) : init_dist;
-    o.slevel = b2 ? (int)(w2 >> 16) : -1;
-    return o;
-}
-
-__global__ __launch_bounds__(MT) void k_win_best(const WinQuery *__restrict__ q, const uint4 *__restrict__ A, int nq,
-                                                 const SeqKp *__restrict__ kp, const uint4 *__restrict__ B,
-                                                 const int *__restrict__ cell_off, const int *__restrict__ perm, const uint8_t *__restrict__ occ, GridParams gp,
-                                                 int has_uright, int init_dist, const float *__restrict__ inv_sigma2, int fuse_gate,
-                                                 int *__restrict__ best_o, int *__restrict__ bl_o, int *__restrict__ second_o,
-                                                 int *__restrict__ sl_o, int *__restrict__ idx_o)
-{
-    const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * (MT / 64) + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (i >= nq) return;
-    const WinQuery w = q[i];
-    const WinPick o = win_best_select(win_best_walk(w, A + 2 * i, lane, kp, B, cell_off, occ, gp, has_uright, init_dist, inv_sigma2, fuse_gate),
-                                      init_dist);
-    if (lane == 0) {
-        best_o[i] = o.best;
-        idx_o[i] = o.sp >= 0 ? perm[o.sp] : -1;
-        bl_o[i] = o.blevel;
-        second_o[i] = o.second;
-        sl_o[i] = o.slevel;
-    }
-}
-
-// The fork's whole-map relocalisation search (ORBmatcher.cc:134-222): isInFrustum
-// (:262-330) + ComputeDistance (:224-260) per map point in the reference's mixed
-// float / double arithmetic (fixed op order, no contraction), producing the
-// GetFeaturesInArea query of :162-163; k_win_best does the search; then the
-// TH_RELOC / same-level ratio acceptance (:205-216) with "last map point wins".
 // The upload of a call's staged inputs (orbx::stage_in: pinned host memory read by the compute queue) folded into the call's first
 // kernel: blocks [0, nblocks) of the launch copy 16 bytes per thread, the others do the kernel's own work and read THEIR inputs --
 // which nothing else needs on the device -- straight from the pinned block.  One launch less per call.
@@ -865,66 +736,6 @@ __device__ __forceinline__ bool stage_block(const StageJob &job)
 inline StageJob stage_job(void *dev, const void *pin, size_t bytes)
 {
     return {static_cast<const uint4 *>(pin), static_cast<uint4 *>(dev), bytes / 16, (int)((bytes / 16 + MT - 1) / MT)};
-}
-
-struct MapIntr { float fx, fy, cx, cy; int bminx, bmaxx, bminy, bmaxy; float th; int nlevels; };    // what all poses of a call share
-struct MapCam { MapIntr in; double R[9], t[3]; };
-
-// isInFrustum + ComputeDistance + the level and window of one map point under one pose (R, t): the one copy of this arithmetic,
-// called by k_map_frustum and k_map_search_poses.  True when the point survives; w and out are written either way.
-__device__ __forceinline__ bool map_frustum_point(float ptX, float ptY, float ptZ, float nX, float nY, float nZ, float minDistance,
-                                                  float maxDistance, const double *__restrict__ R, const double *__restrict__ t,
-                                                  const MapIntr &cam, const float *__restrict__ scale, WinQuery &w, float (&out)[4])
-{
-    w = {0.f, 0.f, -1.f, 0.f, 0, -1}; // r < 0: no candidates
-    out[0] = 0.f; out[1] = 0.f; out[2] = 0.f; out[3] = -1.f;
-    const float PcX = (float)(R[0] * ptX + R[1] * ptY + R[2] * ptZ + t[0]);
-    const float PcY = (float)(R[3] * ptX + R[4] * ptY + R[5] * ptZ + t[1]);
-    const float PcZ = (float)(R[6] * ptX + R[7] * ptY + R[8] * ptZ + t[2]);
-    bool ok = !(PcZ < 0.0f);
-    const float invz = (float)(1.0 / (double)PcZ);
-    const float u = cam.fx * PcX * invz + cam.cx;
-    const float v = cam.fy * PcY * invz + cam.cy;
-    ok = ok && !(u < (float)cam.bminx || u > (float)cam.bmaxx) && !(v < (float)cam.bminy || v > (float)cam.bmaxy);
-    // ComputeDistance: PO = Pt - (-R^T) t, norm in double
-    double PO[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double rtt = ((-1) * R[a]) * t[0] + ((-1) * R[3 + a]) * t[1] + ((-1) * R[6 + a]) * t[2];
-        PO[a] = (double)(a == 0 ? ptX : a == 1 ? ptY : ptZ) - rtt;
-    }
-    const double normSum = PO[0] * PO[0] + PO[1] * PO[1] + PO[2] * PO[2];
-    const float dist = (float)sqrt(normSum);
-    ok = ok && !((double)dist < (0.9 * (double)minDistance) || (double)dist > ((double)maxDistance / 0.9));
-    float viewCos = (float)(PO[0] * nX + PO[1] * nY + PO[2] * nZ);
-    viewCos = viewCos / dist;
-    ok = ok && !(viewCos < 0.5f);
-    const float ratio = dist / minDistance;
-    int level = 0;
-    while (level < cam.nlevels && scale[level] < ratio) ++level; // lower_bound(mvScaleFactors, ratio)
-    if (level >= cam.nlevels) level = cam.nlevels - 1;
-    if (ok) {
-        float r = (double)viewCos > 0.998 ? 3.0f : 4.5f; // RadiusByViewingCos
-        if ((double)cam.th != 1.0) r *= cam.th;
-        w.u = u; w.v = v; w.r = r * scale[level]; w.min_level = level - 1; w.max_level = level;
-        out[0] = u; out[1] = v; out[2] = viewCos; out[3] = (float)level;
-    }
-    return ok;
-}
-
-__global__ __launch_bounds__(MT) void k_map_frustum(const float *__restrict__ pos, const float *__restrict__ nrm,
-                                                    const float *__restrict__ mind, const float *__restrict__ maxd, int m,
-                                                    MapCam cam, const float *__restrict__ scale, WinQuery *__restrict__ q,
-                                                    float *__restrict__ proj)
-{
-    const int i = blockIdx.x * MT + threadIdx.x;
-    if (i >= m) return;
-    WinQuery w;
-    float out[4];
-    map_frustum_point(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], mind[i], maxd[i], cam.R, cam.t,
-                      cam.in, scale, w, out);
-    q[i] = w;
-    if (proj) { proj[4 * i] = out[0]; proj[4 * i + 1] = out[1]; proj[4 * i + 2] = out[2]; proj[4 * i + 3] = out[3]; }
 }
 
 // Batch projection of map points into a Frame / KeyFrame, in the reference's float / double order, op by op:
@@ -1005,99 +816,6 @@ __global__ __launch_bounds__(MT) void k_project_points(const uint8_t *__restrict
     if (q) q[i] = w;
 }
 
-// TH_RELOC and the same-level ratio test (:205-216) on what the window search returned for one map point
-__device__ __forceinline__ bool reloc_accepts(int best, int bidx, int second, int blevel, int slevel, int th_reloc, float nnratio)
-{
-    return bidx >= 0 && best <= th_reloc && !(blevel == slevel && (float)best > nnratio * (float)second);
-}
-
-__global__ __launch_bounds__(MT) void k_reloc_accept(const int *__restrict__ best, const int *__restrict__ bidx,
-                                                     const int *__restrict__ second, const int *__restrict__ blevel,
-                                                     const int *__restrict__ slevel, int m, int th_reloc, float nnratio,
-                                                     int *__restrict__ matched, int *__restrict__ nmatches)
-{
-    const int i = blockIdx.x * MT + threadIdx.x;
-    const bool acc = i < m && reloc_accepts(best[i], bidx[i], second[i], blevel[i], slevel[i], th_reloc, nnratio);
-    if (acc) atomicMax(&matched[bidx[i]], i); // vMatchedMPs[bestIdx] = pMP: the last map point wins
-    const unsigned long long b = __ballot(acc);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(nmatches, __popcll(b));
-}
-
-// The whole-map search under P poses in ONE launch (PnPsolver::iterate's second stage, src/PnPsolver.cc:419-634, calls the search
-// above once per recorded pose over the same frame and the same map).  A workgroup of MPP_T threads (16 waves) owns MPP_TILE map
-// points.  Phase 1: thread (point, pose) of the first MPP_TILE * MPP_MAXP threads does the frustum arithmetic of its pair and
-// appends a survivor with its window to a queue in LDS (ballot + popcount per wave, one LDS atomic per wave; MPP_TILE * MPP_MAXP
-// entries: it cannot overflow).  Phase 2, behind a barrier: the sixteen waves take the items in turn, one wave per item:
-// win_best_walk with the map point's descriptor as the query, win_best_select, reloc_accepts, and lane 0's atomicMax into the
-// pose's row of `matched` (the last map point wins, whatever the order).  The acceptances of a pose are counted in LDS and leave
-// the workgroup as one atomicAdd per pose.  No query and no best / second array goes through HBM; every loop is bounded by the
-// queue length or the window's runs, and no workgroup waits for another.
-// A window walk is a chain of dependent loads (cell table -> keypoints -> descriptors) tens of microseconds long, so what decides
-// the kernel's time is how many walks a wave does one after the other: 16 points x 16 waves keeps that at P / 4 (a quarter of the
-// map survives a pose) with m / 16 workgroups in flight; 64 points x 4 waves made it 4 P with m / 64.
-constexpr int MPP_T = 1024, MPP_TILE = 16, MPP_MAXP = 16;
-struct MapPose { double R[9], t[3]; };
-struct MapItem { float u, v, r; unsigned key; };      // key = point in the tile | pose << 4 | level << 8
-
-__global__ __launch_bounds__(MPP_T) void k_map_search_poses(const float *__restrict__ pos, const float *__restrict__ nrm,
-                                                            const float *__restrict__ mind, const float *__restrict__ maxd,
-                                                            const uint4 *__restrict__ mdesc, int m, const MapPose *__restrict__ poses, int P,
-                                                            MapIntr cam, const float *__restrict__ scale, const SeqKp *__restrict__ kp,
-                                                            const uint4 *__restrict__ B, const int *__restrict__ cell_off,
-                                                            const int *__restrict__ perm, const uint8_t *__restrict__ occ, GridParams gp, int n,
-                                                            int th_reloc, float nnratio, int *__restrict__ matched,
-                                                            int *__restrict__ nmatches, float *__restrict__ proj)
-{
-    __shared__ MapItem s_item[MPP_TILE * MPP_MAXP];
-    __shared__ int s_nitems, s_nm[MPP_MAXP];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int i0 = blockIdx.x * MPP_TILE;
-    if (threadIdx.x == 0) s_nitems = 0;
-    if (threadIdx.x < MPP_MAXP) s_nm[threadIdx.x] = 0;
-    __syncthreads();
-    if (threadIdx.x < MPP_TILE * MPP_MAXP) {       // (whole waves)
-        const int l = threadIdx.x % MPP_TILE, p = threadIdx.x / MPP_TILE, i = i0 + l;
-        bool ok = false;
-        WinQuery w;
-        if (i < m && p < P) {
-            float out[4];
-            const MapPose &ps = poses[p];
-            ok = map_frustum_point(pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2], nrm[3 * (size_t)i], nrm[3 * (size_t)i + 1],
-                                   nrm[3 * (size_t)i + 2], mind[i], maxd[i], ps.R, ps.t, cam, scale, w, out);
-            if (proj) *reinterpret_cast<float4 *>(proj + 4 * ((size_t)p * m + i)) = make_float4(out[0], out[1], out[2], out[3]);
-        }
-        const unsigned long long bal = __ballot(ok);
-        if (bal) {          // (wave-uniform)
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&s_nitems, __popcll(bal));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (ok) s_item[base + __popcll(bal & ((1ull << lane) - 1ull))] = {w.u, w.v, w.r, (unsigned)l | ((unsigned)p << 4) | ((unsigned)w.max_level << 8)};
-        }
-    }
-    __syncthreads();
-    const int nitems = s_nitems;        // <= MPP_TILE * P
-    for (int it = wave; it < nitems; it += MPP_T / 64) {
-        const MapItem e = s_item[it];
-        const unsigned key = (unsigned)__builtin_amdgcn_readfirstlane((int)e.key);
-        const int i = i0 + (int)(key & 15u), p = (int)((key >> 4) & 15u), level = (int)(key >> 8);
-        WinQuery w;
-        w.u = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(e.u)));
-        w.v = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(e.v)));
-        w.r = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(e.r)));
-        w.xr = 0.f; w.min_level = level - 1; w.max_level = level;
-        const WinPick o = win_best_select(win_best_walk(w, mdesc + 2 * (size_t)i, lane, kp, B, cell_off, occ, gp, 0, INT_MAX, nullptr, 0), INT_MAX);
-        if (lane == 0) {
-            const int bidx = o.sp >= 0 ? perm[o.sp] : -1;
-            if (reloc_accepts(o.best, bidx, o.second, o.blevel, o.slevel, th_reloc, nnratio)) {
-                atomicMax(&matched[(size_t)p * n + bidx], i);
-                atomicAdd(&s_nm[p], 1);
-            }
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < P && s_nm[threadIdx.x]) atomicAdd(&nmatches[threadIdx.x], s_nm[threadIdx.x]);
-}
-
 // Rotation histogram + ComputeThreeMaxima (:1802-1843) + rejection, and the translation of
 // sorted positions back to keypoint indices.  One block.
 // MODE 0: match_kp[perm[sp]] = query (or -1 untouched / -2 cleared), match_q[i] = keypoint.
@@ -1154,157 +872,6 @@ __global__ __launch_bounds__(MT) void k_rotation(const int *__restrict__ acc_sp,
     }
     __syncthreads();
     if (tid == 0) *nmatches -= removed;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// A frame resident in HBM (orbm_frame): Frame::AssignFeaturesToGrid (src/Frame.cc:245-260, PosInGrid :397-407) on the device.
-// ONE workgroup lays the keypoints out in (cell, index) order -- the order Frame::GetFeaturesInArea visits a window in --
-//   1. cell of every keypoint (the reference's float arithmetic), cell histogram in LDS;
-//   2. exclusive scan of the histogram = cell_off;
-//   3. rank of a keypoint inside its cell = keypoints of the same cell with a smaller index: per 64-keypoint chunk the
-//      lanes compare cells pairwise (all waves), then one wave walks the chunks in order with a running count per cell;
-//   4. gather: position, level, right coordinate, angle, descriptor, permutation.
-// Keypoints outside the grid (Frame::PosInGrid false: no window search ever returns them) follow the sorted part at positions
-// ns .. n-1 in index order: the searches over explicit candidate lists (SearchByBoW) address features by index, grid or not.
-// Keypoints come as cv::KeyPoint records (mvKeysUn; or the extractor's device results, optionally with the undistorted
-// coordinates beside them), n from the host or from the extractor's count array.
-constexpr int FB_T = 1024, FB_MAXN = SEQ_MAXN, FB_NC = FRAME_GRID_COLS * FRAME_GRID_ROWS;
-constexpr size_t FB_LDS = sizeof(int) * (2 * (size_t)FB_NC + 2) + (size_t)FB_MAXN * (2 + 2 + 1 + 1);
-
-// What k_frame_build reads of one frame: where the keypoints are (n on the device or from the host, never more than n_max) and the
-// arrays of the block it fills.  res_hdr / res_perm: a second copy of the header and the permutation, in the launch's result block
-// (the batch form: ONE copy brings every frame's pair to the host), or null.
-struct FrameJob {
-    const orbx_keypoint *kps; const uint4 *desc_raw; const float2 *xy_un; const float *uright_raw; const int *n_dev;
-    int n_host, n_max;
-    SeqKp *kp; uint4 *desc; float *angle; int *perm; int *cell_off; FrameHdr *hdr;
-    FrameHdr *res_hdr; int *res_perm;
-};
-
-// One workgroup per frame.  BATCH: frame blockIdx.x of `table` (in the call's staged block); otherwise `one`, from the kernel's own
-// arguments (chosen when compiled: a pointer that may be either makes every access of the record a per-lane flat load).  cam: the
-// keypoint coordinates go through Frame::UndistortKeyPoints (undistort_point; cam.k1 == 0: they stay) unless xy_un replaces them.
-template <bool BATCH>
-__global__ __launch_bounds__(FB_T) void k_frame_build(FrameJob one, const FrameJob *__restrict__ table, GridParams gp, orbm_distortion cam)
-{
-    const FrameJob J = BATCH ? table[blockIdx.x] : one;
-    const orbx_keypoint *__restrict__ kps = J.kps;
-    const uint4 *__restrict__ desc_raw = J.desc_raw;
-    const float2 *__restrict__ xy_un = J.xy_un;
-    const float *__restrict__ uright_raw = J.uright_raw;
-    const int *__restrict__ n_dev = J.n_dev;
-    SeqKp *__restrict__ kp = J.kp;
-    uint4 *__restrict__ desc = J.desc;
-    float *__restrict__ angle = J.angle;
-    int *__restrict__ perm = J.perm, *__restrict__ cell_off = J.cell_off, *__restrict__ res_perm = J.res_perm;
-    FrameHdr *hdr = J.hdr, *res_hdr = J.res_hdr;
-    extern __shared__ __align__(16) unsigned char fb_sm[];
-    int *s_off = reinterpret_cast<int *>(fb_sm);                 // [FB_NC + 1] histogram, then exclusive scan
-    int *s_run = s_off + FB_NC + 1;                              // [FB_NC + 1] keypoints of the cell placed so far (last entry: scan carry)
-    unsigned short *s_cell = reinterpret_cast<unsigned short *>(s_run + FB_NC + 1);   // [n] cell or 0xffff
-    unsigned short *s_pos = s_cell + FB_MAXN;                    // [n] sorted position
-    unsigned char *s_low = reinterpret_cast<unsigned char *>(s_pos + FB_MAXN), *s_tot = s_low + FB_MAXN;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = min(min(n_dev ? *n_dev : J.n_host, J.n_max), FB_MAXN);
-    __shared__ int s_omin, s_omax;     // octave range of the keypoints (the searches index per-level tables with it)
-    if (tid == 0) { s_omin = INT_MAX; s_omax = INT_MIN; }
-    for (int c = tid; c <= FB_NC; c += FB_T) { s_off[c] = 0; s_run[c] = 0; }
-    __syncthreads();
-    for (int j = tid; j < n; j += FB_T) {
-        float x, y;
-        if (xy_un) { x = xy_un[j].x; y = xy_un[j].y; }
-        else undistort_point(cam, kps[j].x, kps[j].y, &x, &y);
-        const int px = orbx_f2i_x86(roundf((x - gp.min_x) * gp.inv_w)), py = orbx_f2i_x86(roundf((y - gp.min_y) * gp.inv_h));   // NaN: outside
-        const bool in = !(px < 0 || px >= FRAME_GRID_COLS || py < 0 || py >= FRAME_GRID_ROWS);
-        const int c = in ? px * FRAME_GRID_ROWS + py : FB_NC;   // FB_NC: outside the grid -- kept behind the sorted part, in index order
-        s_cell[j] = (unsigned short)c;
-        if (in) atomicAdd(&s_off[c], 1);
-    }
-    __syncthreads();
-    {   // exclusive scan of FB_NC counts: 3 per thread, wave scan, wave totals through s_run's spare slots
-        constexpr int PER = FB_NC / FB_T;
-        static_assert(FB_NC % FB_T == 0, "cells per thread");
-        int v[PER], sum = 0;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) { v[k] = s_off[tid * PER + k]; sum += v[k]; }
-        const int inc = orbx::wave_incl_scan(sum);
-        __shared__ int wsum[FB_T / 64];
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int base = 0;
-        for (int w = 0; w < wave; ++w) base += wsum[w];
-        int run = base + inc - sum;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) { s_off[tid * PER + k] = run; run += v[k]; }
-        if (tid == FB_T - 1) s_off[FB_NC] = run;
-    }
-    __syncthreads();
-    for (int c = tid; c <= FB_NC; c += FB_T) cell_off[c] = s_off[c];
-    // rank inside the chunk: lanes of one cell, in lane order
-    const int nchunk = (n + 63) / 64;
-    for (int ch = wave; ch < nchunk; ch += FB_T / 64) {
-        const int j = ch * 64 + lane;
-        const int c = j < n ? (int)s_cell[j] : 0xffff;
-        int low = 0, tot = 0;
-#pragma unroll 8
-        for (int l = 0; l < 64; ++l) {
-            const int cl = __shfl(c, l);
-            const int same = cl == c;
-            tot += same;
-            low += same && l < lane;
-        }
-        if (j < n) { s_low[j] = (unsigned char)low; s_tot[j] = (unsigned char)(tot - 1); }   // (tot - 1 <= 63 fits a byte)
-    }
-    __syncthreads();
-    if (wave == 0) {        // chunks in index order: the running count of a cell is what the earlier chunks put there
-        for (int ch = 0; ch < nchunk; ++ch) {
-            const int j = ch * 64 + lane;
-            const int c = j < n ? (int)s_cell[j] : 0xffff;
-            int base = 0;
-            if (c != 0xffff) base = s_run[c];
-            if (c != 0xffff) {
-                s_pos[j] = (unsigned short)(s_off[c] + base + s_low[j]);
-                if (s_low[j] == s_tot[j]) s_run[c] = base + s_tot[j] + 1;    // the cell's last lane of the chunk
-            }
-        }
-    }
-    __syncthreads();
-    int omin = INT_MAX, omax = INT_MIN;
-    for (int j = tid; j < n; j += FB_T) {
-        const int sp = s_pos[j];
-        // every load in front of the first store (the pointers come from a table: the compiler cannot tell them apart, and a
-        // load behind a store would wait for its own round trip)
-        const orbx_keypoint k = kps[j];
-        const uint4 d0 = desc_raw[2 * j], d1 = desc_raw[2 * j + 1];
-        const float ur = uright_raw ? uright_raw[j] : -1.0f;
-        const float2 c = xy_un ? xy_un[j] : make_float2(k.x, k.y);
-        omin = min(omin, k.octave); omax = max(omax, k.octave);
-        SeqKp o;
-        if (xy_un) { o.x = c.x; o.y = c.y; }
-        else undistort_point(cam, k.x, k.y, &o.x, &o.y);        // (a pure function of the keypoint: the bits of the first pass)
-        o.uright = ur;
-        o.octave = k.octave;
-        kp[sp] = o; angle[sp] = k.angle; perm[sp] = j;
-        if (res_perm) res_perm[sp] = j;
-        desc[2 * sp] = d0; desc[2 * sp + 1] = d1;
-    }
-    if (omin <= omax) { atomicMin(&s_omin, omin); atomicMax(&s_omax, omax); }
-    __syncthreads();
-    if (tid == 0) {
-        const FrameHdr h = {n, s_off[FB_NC], s_omin, s_omax};
-        *hdr = h;
-        if (res_hdr) *res_hdr = h;
-    }
-}
-
-// Frame::UndistortKeyPoints on n points, one thread each (orbm_undistort_points)
-__global__ __launch_bounds__(MT) void k_undistort_points(orbm_distortion cam, const float2 *__restrict__ xy, int n, float2 *__restrict__ xy_un)
-{
-    const int i = blockIdx.x * MT + threadIdx.x;
-    if (i >= n) return;
-    float2 o;
-    undistort_point(cam, xy[i].x, xy[i].y, &o.x, &o.y);
-    xy_un[i] = o;
 }
 
 // The projection prefixes of the remaining SearchByProjection forms and of SearchBySim3, one thread per list entry, in the
@@ -1414,203 +981,6 @@ __global__ __launch_bounds__(MT) void k_sim3_agree(const int *__restrict__ best1
 
 std::atomic<int> g_last_iterations{0};    // iterations of the last k_resolve_par (-1: it gave up and k_resolve ran)
 std::atomic<int> g_force_sequential{0};   // orbm_debug_force_sequential_resolver: tests run both resolvers
-
-struct SortedFrame {
-    std::vector<SeqKp> kp;
-    std::vector<int> cell_off; // [COLS*ROWS + 1] runs of the sorted array per grid cell (col * ROWS + row)
-    GridParams gp = {0.f, 0.f, 0.f, 0.f};
-    std::vector<int> perm;
-    std::vector<float> angle;
-    std::vector<uint8_t> desc;
-};
-
-// Keypoints in the grid (and not excluded by `skip`), ordered by (cell, index).
-void sort_frame(const orbx_keypoint *kps, const uint8_t *desc, int n, const uint8_t *skip, const float *uright, float min_x,
-                float min_y, float max_x, float max_y, SortedFrame &sf)
-{
-    std::vector<WinKp> wk;
-    build_winkp(kps, n, skip, uright, min_x, min_y, max_x, max_y, wk);
-    // counting sort by grid cell; inside a cell ascending keypoint index (= insertion order, Frame.cc:245-260)
-    sf.gp = {min_x, min_y, (float)FRAME_GRID_COLS / (max_x - min_x), (float)FRAME_GRID_ROWS / (max_y - min_y)}; // Frame.cc:95-96
-    sf.cell_off.assign(FRAME_GRID_COLS * FRAME_GRID_ROWS + 1, 0);
-    for (int j = 0; j < n; ++j)
-        if (wk[j].order != 0xffffffffu) sf.cell_off[(wk[j].order >> 16) + 1]++;
-    for (int c = 0; c < FRAME_GRID_COLS * FRAME_GRID_ROWS; ++c) sf.cell_off[c + 1] += sf.cell_off[c];
-    const size_t ns = (size_t)sf.cell_off[FRAME_GRID_COLS * FRAME_GRID_ROWS];
-    std::vector<unsigned> order(ns ? ns : 1);
-    {
-        std::vector<int> fill(sf.cell_off.begin(), sf.cell_off.end() - 1);
-        for (int j = 0; j < n; ++j)
-            if (wk[j].order != 0xffffffffu) order[fill[wk[j].order >> 16]++] = wk[j].order;
-    }
-    sf.kp.resize(ns ? ns : 1); sf.perm.resize(ns ? ns : 1); sf.angle.resize(ns ? ns : 1); sf.desc.resize(32 * (ns ? ns : 1));
-    for (size_t s = 0; s < ns; ++s) {
-        const int j = (int)(order[s] & 0xffffu);
-        sf.kp[s] = {wk[j].x, wk[j].y, wk[j].uright, wk[j].octave};
-        sf.perm[s] = j;
-        sf.angle[s] = kps[j].angle;
-        memcpy(&sf.desc[32 * s], desc + 32 * (size_t)j, 32);
-    }
-    sf.kp.resize(ns); sf.perm.resize(ns); sf.angle.resize(ns); sf.desc.resize(32 * ns);
-}
-
-// What the search kernels read of a frame, wherever it lives.
-struct FrameView {
-    const SeqKp *kp; const uint4 *desc; const float *angle; const int *perm; const int *cell_off;
-    GridParams gp;
-};
-
-std::mutex g_frame_mu;
-std::vector<std::pair<int, char *>> g_frame_pool;     // (capacity, block) of destroyed frames
-
-size_t frame_block_bytes(int cap)
-{
-    return 256 + ((sizeof(SeqKp) + 32 + 4 + 4) * (size_t)cap + 255) / 256 * 256 + sizeof(int) * (FB_NC + 1);
-}
-
-void frame_pointers(orbm_frame *f)
-{
-    const int cap = f->cap;
-    char *p = f->block;
-    f->hdr = reinterpret_cast<FrameHdr *>(p); p += 256;
-    f->desc = reinterpret_cast<uint4 *>(p); p += (size_t)32 * cap;
-    f->kp = reinterpret_cast<SeqKp *>(p); p += sizeof(SeqKp) * (size_t)cap;
-    f->angle = reinterpret_cast<float *>(p); p += sizeof(float) * (size_t)cap;
-    f->perm = reinterpret_cast<int *>(p);
-    f->cell_off = reinterpret_cast<int *>(f->block + frame_block_bytes(cap) - sizeof(int) * (FB_NC + 1));
-}
-
-int frame_alloc(orbm_frame *f, int n)
-{
-    const int cap = std::max(2048, (n + 1023) / 1024 * 1024);
-    {
-        std::lock_guard<std::mutex> lk(g_frame_mu);
-        for (size_t i = 0; i < g_frame_pool.size(); ++i)
-            if (g_frame_pool[i].first == cap) {
-                f->block = g_frame_pool[i].second;
-                g_frame_pool.erase(g_frame_pool.begin() + (long)i);
-                break;
-            }
-    }
-    if (!f->block && hipMalloc((void **)&f->block, frame_block_bytes(cap)) != hipSuccess) { f->block = nullptr; return -1; }
-    f->cap = cap;
-    f->refs = new std::atomic<int>(1);
-    frame_pointers(f);
-    return 0;
-}
-
-void frame_release(orbm_frame *f)
-{
-    if (f->block && f->refs && f->refs->fetch_sub(1) == 1) {      // the last handle on the block
-        delete f->refs;
-        {
-            std::lock_guard<std::mutex> lk(g_frame_mu);
-            if (g_frame_pool.size() < 64) { g_frame_pool.emplace_back(f->cap, f->block); f->block = nullptr; }
-        }
-        if (f->block) (void)hipFree(f->block);
-    }
-    delete f;
-}
-
-std::atomic<int> g_last_frame_build_waits{0};    // host waits of the last frame-making call (orbm_debug_last_frame_build_waits)
-
-int frame_build_prepare()
-{
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set.load(std::memory_order_acquire)) {
-        ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_frame_build<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS));
-        ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_frame_build<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS));
-        attr_set.store(true, std::memory_order_release);
-    }
-    return ORBX_OK;
-}
-
-FrameJob frame_job(const orbm_frame *f, const orbx_keypoint *d_kps, const uint4 *d_desc, const float2 *d_xy, const float *d_ur, const int *d_n,
-                   int n_host, int n_bound)
-{
-    return {d_kps, d_desc, d_xy, d_ur, d_n, n_host, n_bound, f->kp, f->desc, f->angle, f->perm, f->cell_off, f->hdr, nullptr, nullptr};
-}
-
-// What the host keeps of a built frame: the header and the permutation as they came back (hdr, perm[n_bound])
-int frame_adopt(orbm_frame *f, const void *hdr, const int *perm, int n_bound)
-{
-    FrameHdr h;
-    memcpy(&h, hdr, sizeof(h));
-    f->n = h.n; f->ns = h.ns;
-    f->min_octave = h.n ? h.min_octave : 0; f->max_octave = h.n ? h.max_octave : -1;
-    if (h.n < 0 || h.n > n_bound || h.ns < 0 || h.ns > h.n) ORBX_FAIL(ORBX_ERR_HIP, "frame header out of range");
-    f->perm_host.assign(perm, perm + h.n);
-    f->inv_host.assign((size_t)h.n, 0);
-    for (int sp = 0; sp < h.n; ++sp) {
-        const int j = f->perm_host[sp];
-        if (j < 0 || j >= h.n) ORBX_FAIL(ORBX_ERR_HIP, "frame permutation out of range");
-        f->inv_host[j] = sp;
-    }
-    return ORBX_OK;
-}
-
-// k_frame_build on `st` from device-resident inputs, then the header and the permutation back to the host (one small
-// block through the pinned arena of the leased workspace `w`, whose first pin_need bytes must be free for it).
-// cam: Frame::UndistortKeyPoints inside the build (null: the coordinates as they are, or d_xy).
-int frame_build(orbm_frame *f, Workspace &w, const orbx_keypoint *d_kps, const uint4 *d_desc, const float2 *d_xy, const float *d_ur,
-                const int *d_n, int n_host, int n_bound, const orbm_distortion *cam = nullptr)
-{
-    if (const int rc = frame_build_prepare()) return rc;
-    hipStream_t st = w.st;
-    hipLaunchKernelGGL(k_frame_build<false>, dim3(1), dim3(FB_T), FB_LDS, st, frame_job(f, d_kps, d_desc, d_xy, d_ur, d_n, n_host, n_bound),
-                       (const FrameJob *)nullptr, f->gp, cam ? *cam : orbm_distortion{});
-    ORBX_HIP(hipGetLastError());
-    // results: hdr (256-byte slot) + perm[n_bound], staged out through the arena's tail
-    const size_t bytes = (256 + sizeof(int) * (size_t)n_bound + 15) & ~(size_t)15;
-    char *pin = w.pin + w.pin_cap - ((bytes + 255) & ~(size_t)255);
-    ORBX_HIP(hipMemcpyAsync(pin, f->hdr, sizeof(FrameHdr), hipMemcpyDeviceToHost, st));
-    ORBX_HIP(hipMemcpyAsync(pin + 256, f->perm, sizeof(int) * (size_t)n_bound, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(hipStreamSynchronize(st));
-    g_last_frame_build_waits.fetch_add(1, std::memory_order_relaxed);      // counted where the stream is waited for
-    return frame_adopt(f, pin, reinterpret_cast<const int *>(pin + 256), n_bound);
-}
-
-// The frame of a call: sorted on the host and staged with the call's inputs (the host-array entry points), or resident.
-struct FrameSrc {
-    const SortedFrame *host = nullptr;
-    const orbm_frame *res = nullptr;
-    size_t o_k = 0, o_b = 0, o_kang = 0, o_perm = 0, o_cell = 0;
-    bool all_positions = false;     // resident frame addressed by explicit candidate lists: the positions behind the grid's count too
-    explicit FrameSrc(const SortedFrame &sf) : host(&sf) {}
-    explicit FrameSrc(const orbm_frame *f, bool all = false) : res(f), all_positions(all) {}
-    int ns() const { return host ? (int)host->perm.size() : (all_positions ? res->n : res->ns); }
-    const int *perm() const { return host ? host->perm.data() : res->perm_host.data(); }
-    GridParams gp() const { return host ? host->gp : res->gp; }
-    void carve(Workspace &w)
-    {
-        if (!host) return;
-        const size_t m = ns() ? (size_t)ns() : 1;
-        o_k = w.carve(sizeof(SeqKp) * m); o_b = w.carve(32 * m); o_kang = w.carve(sizeof(float) * m); o_perm = w.carve(sizeof(int) * m);
-        o_cell = w.carve(sizeof(int) * (FRAME_GRID_COLS * FRAME_GRID_ROWS + 1));
-    }
-    void fill(Workspace &w) const
-    {
-        if (!host) return;
-        const size_t m = (size_t)ns();
-        if (!host->kp.empty()) memcpy(w.h<char>(o_k), host->kp.data(), sizeof(SeqKp) * m);
-        if (!host->cell_off.empty()) memcpy(w.h<char>(o_cell), host->cell_off.data(), sizeof(int) * host->cell_off.size());
-        memcpy(w.h<char>(o_b), host->desc.data(), 32 * m);
-        memcpy(w.h<char>(o_kang), host->angle.data(), sizeof(float) * m);
-        memcpy(w.h<char>(o_perm), host->perm.data(), sizeof(int) * m);
-    }
-    FrameView view(const Workspace &w) const
-    {
-        if (host) return {w.d<SeqKp>(o_k), w.d<uint4>(o_b), w.d<float>(o_kang), w.d<int>(o_perm), w.d<int>(o_cell), host->gp};
-        return {res->kp, res->desc, res->angle, res->perm, res->cell_off, res->gp};
-    }
-    // occupancy by keypoint index -> by sorted position
-    void fill_occ(uint8_t *dst, const uint8_t *occupied) const
-    {
-        const int m = ns();
-        const int *pm = perm();
-        for (int s = 0; s < m; ++s) dst[s] = occupied[pm[s]];
-    }
-};
 
 // A list of map points as the whole-function searches take it (orbm_points), staged with a call, and the prefix kernel that
 // turns it into window queries on the device.
@@ -1985,15 +1355,6 @@ void form_cam_common(FormCam &c, const orbm_view *v, const orbm_frame *f, int fo
 }
 
 bool bad_view(const orbm_view *v) { return !v || !v->scale_factors || v->nlevels < 1 || v->nlevels > 16; }
-// A candidate entry holds its keypoint's octave in four bits (k_win_wave, entry_level; k_win_best packs it the same way): a frame
-// with an octave outside 0..15 cannot be searched.
-bool bad_octaves(const orbx_keypoint *kps, int n)
-{
-    for (int j = 0; j < n; ++j)
-        if (kps[j].octave < 0 || kps[j].octave > 15) return true;
-    return false;
-}
-bool bad_octaves(const orbm_frame *f) { return f->n && (f->min_octave < 0 || f->max_octave > 15); }
 bool bad_points(const orbm_points *p, bool need_range, bool need_normal, bool need_octave, int nlevels)
 {
     if (!p || p->n < 0 || p->n > 65536) return true;
@@ -2009,189 +1370,17 @@ bool bad_points(const orbm_points *p, bool need_range, bool need_normal, bool ne
     return false;
 }
 
-// One window search without coupling (k_win_best) for device-resident queries: returns into ob[5][nq] (best, best level, second,
-// second level, idx).
-void launch_win_best(hipStream_t st, const WinQuery *dq, const uint4 *da, int nq, const FrameView &fv, const uint8_t *docc, int has_uright,
-                     int init_dist, const float *inv_sigma2, int fuse_gate, int *ob)
+// orbm_search_projection on a frame from either source: the caller's windows, the loop of SearchByProjection (:69-130)
+int search_projection_core(FrameSrc &fs, int n, int has_uright, const orbm_window_query *queries, const uint8_t *qdesc, const float *qangle,
+                           const uint8_t *qtakes, int nq, const uint8_t *occupied, int th_accept, float nnratio, int ratio_same_level,
+                           int check_orientation, int32_t *match_kp, int32_t *match_q, int *nmatches)
 {
-    hipLaunchKernelGGL(k_win_best, dim3((nq + MT / 64 - 1) / (MT / 64)), dim3(MT), 0, st, dq, da, nq, fv.kp, fv.desc, fv.cell_off, fv.perm, docc,
-                       fv.gp, has_uright, init_dist, inv_sigma2, fuse_gate, ob, ob + nq, ob + 2 * nq, ob + 3 * nq, ob + 4 * nq);
-}
-
-int search_window_core(FrameSrc &fs, const orbm_window_query *queries, const uint8_t *qdesc, int nq, const uint8_t *skip, int has_uright,
-                       int init_dist, const float *inv_level_sigma2, int nlevels, int fuse_gate, int32_t *best, int32_t *best_level,
-                       int32_t *second, int32_t *second_level, int32_t *idx)
-{
-    const int ns = fs.ns();
-    WorkspaceLease lease;
-    Workspace &w = *lease.w;
-    w.used = 0;
-    const size_t o_q = w.carve(sizeof(WinQuery) * nq), o_a = w.carve((size_t)32 * nq);
-    fs.carve(w);
-    const size_t o_occ = w.carve(skip && ns ? (size_t)ns : 1), o_sg = w.carve(inv_level_sigma2 ? sizeof(float) * nlevels : 1);
-    const size_t staged = w.used;
-    const size_t o_res = w.carve(sizeof(int) * 5 * (size_t)nq);
-    if (w.reserve(w.used, std::max(staged, sizeof(int) * 5 * (size_t)nq + 16))) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
-    memcpy(w.h<char>(o_q), queries, sizeof(WinQuery) * nq);
-    memcpy(w.h<char>(o_a), qdesc, (size_t)32 * nq);
-    fs.fill(w);
-    if (skip && ns) fs.fill_occ(w.h<uint8_t>(o_occ), skip);
-    if (inv_level_sigma2) memcpy(w.h<char>(o_sg), inv_level_sigma2, sizeof(float) * nlevels);
-    ORBX_HIP(orbx::stage_in(w.dev, w.pin, staged, w.st));
-    int *ob = w.d<int>(o_res);
-    launch_win_best(w.st, w.d<WinQuery>(o_q), w.d<uint4>(o_a), nq, fs.view(w), skip && ns ? w.d<uint8_t>(o_occ) : nullptr, has_uright, init_dist,
-                    inv_level_sigma2 ? w.d<float>(o_sg) : nullptr, fuse_gate, ob);
-    ORBX_HIP(hipGetLastError());
-    ORBX_HIP(orbx::stage_out(w.pin, ob, (sizeof(int) * 5 * (size_t)nq + 15) & ~(size_t)15, w.st));
-    ORBX_HIP(hipStreamSynchronize(w.st));
-    const int *r = w.h<int>(0);
-    if (best) memcpy(best, r, sizeof(int) * nq);
-    if (best_level) memcpy(best_level, r + nq, sizeof(int) * nq);
-    if (second) memcpy(second, r + 2 * nq, sizeof(int) * nq);
-    if (second_level) memcpy(second_level, r + 3 * nq, sizeof(int) * nq);
-    if (idx) memcpy(idx, r + 4 * nq, sizeof(int) * nq);
-    return ORBX_OK;
-}
-
-MapIntr map_intrinsics(const orbm_camera *cam, float th, int nlevels)
-{
-    return {cam->fx, cam->fy, cam->cx, cam->cy, cam->min_x, cam->max_x, cam->min_y, cam->max_y, th, nlevels};
-}
-
-int search_map_core(FrameSrc &fs, int n, const uint8_t *has_mappoint, const float *mp_pos, const float *mp_normal, const float *mp_min_dist,
-                    const float *mp_max_dist, const uint8_t *mp_desc, int m, const double *Rcw, const double *tcw, const orbm_camera *cam,
-                    const float *scale_factors, int nlevels, float th, float nnratio, int th_reloc, int32_t *matched_mp, int *nmatches,
-                    float *proj)
-{
-    const int ns = fs.ns();
-    WorkspaceLease lease;
-    Workspace &w = *lease.w;
-    w.used = 0;
-    const size_t o_pos = w.carve(sizeof(float) * 3 * m), o_nrm = w.carve(sizeof(float) * 3 * m), o_min = w.carve(sizeof(float) * m),
-                 o_max = w.carve(sizeof(float) * m), o_md = w.carve((size_t)32 * m);
-    fs.carve(w);
-    const size_t o_occ = w.carve(has_mappoint && ns ? (size_t)ns : 1), o_sc = w.carve(sizeof(float) * nlevels);
-    const size_t staged = w.used;
-    const size_t o_q = w.carve(sizeof(WinQuery) * m), o_o = w.carve(sizeof(int) * 5 * (size_t)m);
-    const size_t o_res = w.used;
-    const size_t o_mk = w.carve(sizeof(int) * n), o_nm = w.carve(sizeof(int)), o_proj = w.carve(sizeof(float) * 4 * m);
-    const size_t res_bytes = w.used - o_res;
-    if (w.reserve(w.used, std::max(staged, res_bytes))) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
-    memcpy(w.h<char>(o_pos), mp_pos, sizeof(float) * 3 * m); memcpy(w.h<char>(o_nrm), mp_normal, sizeof(float) * 3 * m);
-    memcpy(w.h<char>(o_min), mp_min_dist, sizeof(float) * m); memcpy(w.h<char>(o_max), mp_max_dist, sizeof(float) * m);
-    memcpy(w.h<char>(o_md), mp_desc, (size_t)32 * m);
-    fs.fill(w);
-    if (has_mappoint && ns) fs.fill_occ(w.h<uint8_t>(o_occ), has_mappoint);
-    memcpy(w.h<char>(o_sc), scale_factors, sizeof(float) * nlevels);
-    hipStream_t st = w.st;
-    ORBX_HIP(orbx::stage_in(w.dev, w.pin, staged, st));
-    ORBX_HIP(hipMemsetAsync(w.d<char>(o_mk), 0xff, sizeof(int) * n, st));
-    ORBX_HIP(hipMemsetAsync(w.d<char>(o_nm), 0, sizeof(int), st));
-    MapCam mc;
-    mc.in = map_intrinsics(cam, th, nlevels);
-    for (int i = 0; i < 9; ++i) mc.R[i] = Rcw[i];
-    for (int i = 0; i < 3; ++i) mc.t[i] = tcw[i];
-    int *ob = w.d<int>(o_o);
-    const dim3 g((m + MT - 1) / MT);
-    hipLaunchKernelGGL(k_map_frustum, g, dim3(MT), 0, st, (const float *)w.d<float>(o_pos), (const float *)w.d<float>(o_nrm),
-                       (const float *)w.d<float>(o_min), (const float *)w.d<float>(o_max), m, mc, (const float *)w.d<float>(o_sc),
-                       w.d<WinQuery>(o_q), w.d<float>(o_proj));
-    launch_win_best(st, w.d<WinQuery>(o_q), w.d<uint4>(o_md), m, fs.view(w), has_mappoint && ns ? w.d<uint8_t>(o_occ) : nullptr, 0, INT_MAX,
-                    nullptr, 0, ob);
-    hipLaunchKernelGGL(k_reloc_accept, g, dim3(MT), 0, st, (const int *)ob, (const int *)(ob + 4 * m), (const int *)(ob + 2 * m),
-                       (const int *)(ob + m), (const int *)(ob + 3 * m), m, th_reloc, nnratio, w.d<int>(o_mk), w.d<int>(o_nm));
-    ORBX_HIP(hipGetLastError());
-    ORBX_HIP(orbx::stage_out(w.pin, w.dev + o_res, res_bytes, st));
-    ORBX_HIP(hipStreamSynchronize(st));
-    memcpy(matched_mp, w.pin + (o_mk - o_res), sizeof(int) * n);
-    if (nmatches) memcpy(nmatches, w.pin + (o_nm - o_res), sizeof(int));
-    if (proj) memcpy(proj, w.pin + (o_proj - o_res), sizeof(float) * 4 * m);
-    return ORBX_OK;
-}
-
-std::atomic<int> g_last_map_poses_waits{0};    // host waits of the last ..._map_poses call of this process
-
-// The map of a ..._map_poses call: the caller's host arrays, staged with the call, or a snapshot's device block.
-struct MapSrc {
-    const float *pos, *nrm, *mind, *maxd;
-    const uint8_t *desc;
-    const orbm_map *snap;
-    int m;
-};
-
-// One upload (the map and the frame only where they are host arrays; has_mappoint by sorted position, the poses, the scale
-// factors), the presets, k_map_search_poses, one result block, one wait.
-int search_map_poses_core(FrameSrc &fs, int n, const uint8_t *has_mappoint, const MapSrc &map, const double *Rcw, const double *tcw, int P,
-                          const orbm_camera *cam, const float *scale_factors, int nlevels, float th, float nnratio, int th_reloc,
-                          int32_t *matched_mp, int32_t *nmatches, float *proj)
-{
-    const int ns = fs.ns(), m = map.m;
-    WorkspaceLease lease;
-    Workspace &w = *lease.w;
-    w.used = 0;
-    size_t o_pos = 0, o_nrm = 0, o_min = 0, o_max = 0, o_md = 0;
-    if (!map.snap) {
-        o_pos = w.carve(sizeof(float) * 3 * m); o_nrm = w.carve(sizeof(float) * 3 * m); o_min = w.carve(sizeof(float) * m);
-        o_max = w.carve(sizeof(float) * m); o_md = w.carve((size_t)32 * m);
-    }
-    fs.carve(w);
-    const size_t o_occ = w.carve(has_mappoint && ns ? (size_t)ns : 1), o_pose = w.carve(sizeof(MapPose) * P), o_sc = w.carve(sizeof(float) * nlevels);
-    const size_t staged = w.used;
-    const size_t o_res = w.used;
-    const size_t o_mk = w.carve(sizeof(int) * (size_t)P * n), o_nm = w.carve(sizeof(int) * P),
-                 o_proj = w.carve(proj ? sizeof(float) * 4 * (size_t)P * m : 1);
-    const size_t res_bytes = w.used - o_res;
-    if (w.reserve(w.used, std::max(staged, res_bytes))) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
-    if (!map.snap) {
-        memcpy(w.h<char>(o_pos), map.pos, sizeof(float) * 3 * m); memcpy(w.h<char>(o_nrm), map.nrm, sizeof(float) * 3 * m);
-        memcpy(w.h<char>(o_min), map.mind, sizeof(float) * m); memcpy(w.h<char>(o_max), map.maxd, sizeof(float) * m);
-        memcpy(w.h<char>(o_md), map.desc, (size_t)32 * m);
-    }
-    fs.fill(w);
-    if (has_mappoint && ns) fs.fill_occ(w.h<uint8_t>(o_occ), has_mappoint);
-    MapPose *hp = w.h<MapPose>(o_pose);
-    for (int p = 0; p < P; ++p) {
-        for (int k = 0; k < 9; ++k) hp[p].R[k] = Rcw[9 * p + k];
-        for (int k = 0; k < 3; ++k) hp[p].t[k] = tcw[3 * p + k];
-    }
-    memcpy(w.h<char>(o_sc), scale_factors, sizeof(float) * nlevels);
-    hipStream_t st = w.st;
-    ORBX_HIP(orbx::stage_in(w.dev, w.pin, staged, st));
-    ORBX_HIP(hipMemsetAsync(w.d<char>(o_mk), 0xff, sizeof(int) * (size_t)P * n, st));
-    ORBX_HIP(hipMemsetAsync(w.d<char>(o_nm), 0, sizeof(int) * P, st));
-    const FrameView fv = fs.view(w);
-    const float *d_pos = map.snap ? map.snap->pos : w.d<float>(o_pos), *d_nrm = map.snap ? map.snap->nrm : w.d<float>(o_nrm);
-    const float *d_min = map.snap ? map.snap->mind : w.d<float>(o_min), *d_max = map.snap ? map.snap->maxd : w.d<float>(o_max);
-    const uint4 *d_md = map.snap ? map.snap->desc : w.d<uint4>(o_md);
-    hipLaunchKernelGGL(k_map_search_poses, dim3((m + MPP_TILE - 1) / MPP_TILE), dim3(MPP_T), 0, st, d_pos, d_nrm, d_min, d_max, d_md, m,
-                       (const MapPose *)w.d<MapPose>(o_pose), P, map_intrinsics(cam, th, nlevels), (const float *)w.d<float>(o_sc), fv.kp,
-                       fv.desc, fv.cell_off, fv.perm, has_mappoint && ns ? (const uint8_t *)w.d<uint8_t>(o_occ) : nullptr, fv.gp, n, th_reloc,
-                       nnratio, w.d<int>(o_mk), w.d<int>(o_nm), proj ? w.d<float>(o_proj) : nullptr);
-    ORBX_HIP(hipGetLastError());
-    ORBX_HIP(orbx::stage_out(w.pin, w.dev + o_res, res_bytes, st));
-    ORBX_HIP(hipStreamSynchronize(st));
-    g_last_map_poses_waits.store(1, std::memory_order_relaxed);    // counted where the stream is waited for
-    memcpy(matched_mp, w.pin + (o_mk - o_res), sizeof(int) * (size_t)P * n);
-    memcpy(nmatches, w.pin + (o_nm - o_res), sizeof(int) * P);
-    if (proj) memcpy(proj, w.pin + (o_proj - o_res), sizeof(float) * 4 * (size_t)P * m);
-    return ORBX_OK;
-}
-
-// What both ..._map_poses entries refuse and preset once their own arguments are checked; *go = there is something to launch.
-int map_poses_begin(int n, int m, const double *Rcw, const double *tcw, int P, const orbm_camera *cam, const float *scale_factors,
-                    int nlevels, int32_t *matched_mp, int32_t *nmatches, bool octaves_bad, bool *go)
-{
-    *go = false;
-    if (P < 0 || nlevels < 1 || nlevels > 16 || !cam || !scale_factors || (P && (!Rcw || !tcw || !nmatches || (n && !matched_mp))))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    if (P > MPP_MAXP) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 16 poses in one call");
-    if (octaves_bad) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
-    ORBX_NEED_DEVICE();
-    g_last_map_poses_waits.store(0, std::memory_order_relaxed);
-    for (size_t j = 0; j < (size_t)P * n; ++j) matched_mp[j] = -1;
-    for (int p = 0; p < P; ++p) nmatches[p] = 0;
-    *go = P && n && m;
-    return ORBX_OK;
+    SeqSearch r;
+    r.queries = reinterpret_cast<const WinQuery *>(queries); r.q.desc = qdesc; r.q.angle = qangle; r.qtakes = qtakes; r.nq = nq;
+    r.fs = &fs; r.n = n; r.occupied = occupied; r.has_uright = has_uright;
+    r.th = th_accept; r.nnratio = nnratio; r.accept_mode = ratio_same_level ? ACCEPT_RATIO_SAME_LEVEL : ACCEPT_BEST; r.check = check_orientation;
+    r.match_kp = match_kp; r.match_q = match_q; r.nmatches = nmatches;
+    return run_sequential(r);
 }
 
 int search_init_core(FrameSrc &fs, int n2, const orbx_keypoint *kps2, const orbx_keypoint *kps1, const uint8_t *desc1, int n1, float *prev_matched, int window_size,
@@ -2227,426 +1416,6 @@ int orbm_debug_force_sequential_resolver(int on)
 
 int orbm_debug_last_resolver_iterations(void) { return g_last_iterations.load(std::memory_order_relaxed); }
 
-int orbm_sorted_frame(const orbx_keypoint *kps, int n, const uint8_t *skip, const float *uright, float min_x, float min_y,
-                      float max_x, float max_y, int32_t *perm, int32_t *cell_off, int32_t *nsorted)
-{
-    if (n < 0 || (n && !kps) || !nsorted || !(max_x > min_x) || !(max_y > min_y)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    if (n > 65535) ORBX_FAIL(ORBX_ERR_CAPACITY, "more than 65,535 keypoints per frame");
-    SortedFrame sf;
-    std::vector<uint8_t> nodesc((size_t)32 * (n ? n : 1), 0);
-    sort_frame(kps, nodesc.data(), n, skip, uright, min_x, min_y, max_x, max_y, sf);
-    *nsorted = (int)sf.perm.size();
-    if (perm) memcpy(perm, sf.perm.data(), sizeof(int) * sf.perm.size());
-    if (cell_off) memcpy(cell_off, sf.cell_off.data(), sizeof(int) * sf.cell_off.size());
-    return ORBX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ resident frames
-
-int orbm_frame_create(const orbx_keypoint *kps, const uint8_t *desc, int n, const float *uright, float min_x, float min_y, float max_x,
-                      float max_y, orbm_frame **out)
-{
-    if (!out || n < 0 || (n && (!kps || !desc)) || !(max_x > min_x) || !(max_y > min_y)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    if (n > FB_MAXN) ORBX_FAIL(ORBX_ERR_CAPACITY, "more than 8,192 keypoints in a resident frame");
-    ORBX_NEED_DEVICE();
-    g_last_frame_build_waits.store(0, std::memory_order_relaxed);
-    orbm_frame *f = new orbm_frame();
-    f->min_x = min_x; f->min_y = min_y; f->max_x = max_x; f->max_y = max_y; f->has_uright = uright ? 1 : 0;
-    for (int i = 0; uright && i < n; ++i) f->nstereo += uright[i] >= 0;
-    f->gp = {min_x, min_y, (float)FRAME_GRID_COLS / (max_x - min_x), (float)FRAME_GRID_ROWS / (max_y - min_y)};
-    if (frame_alloc(f, n)) { frame_release(f); ORBX_FAIL(ORBX_ERR_HIP, "frame allocation failed"); }
-    WorkspaceLease lease;
-    Workspace &w = *lease.w;
-    w.used = 0;
-    const size_t m = n ? (size_t)n : 1;
-    const size_t o_k = w.carve(sizeof(orbx_keypoint) * m), o_d = w.carve(32 * m), o_u = w.carve(sizeof(float) * m);
-    const size_t staged = w.used;
-    if (w.reserve(staged, staged + sizeof(int) * m + 1024)) { frame_release(f); ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed"); }
-    if (n) {
-        memcpy(w.h<char>(o_k), kps, sizeof(orbx_keypoint) * m);
-        memcpy(w.h<char>(o_d), desc, 32 * m);
-        if (uright) memcpy(w.h<char>(o_u), uright, sizeof(float) * m);
-    }
-    int rc = orbx::stage_in(w.dev, w.pin, staged, w.st) == hipSuccess ? ORBX_OK : ORBX_ERR_HIP;
-    if (rc == ORBX_OK)
-        rc = frame_build(f, w, w.d<orbx_keypoint>(o_k), w.d<uint4>(o_d), nullptr, uright ? w.d<float>(o_u) : nullptr, nullptr, n, n ? n : 1);
-    if (rc != ORBX_OK) { frame_release(f); return rc; }
-    *out = f;
-    return ORBX_OK;
-}
-
-// A frame of the extractor's last batch with empty arrays and the grid of the given bounds (null: allocation failed)
-static orbm_frame *frame_for_extractor(const orbx_extractor *ex, int has_uright, float min_x, float min_y, float max_x, float max_y)
-{
-    orbm_frame *f = new orbm_frame();
-    f->min_x = min_x; f->min_y = min_y; f->max_x = max_x; f->max_y = max_y; f->has_uright = has_uright;
-    f->nstereo = f->has_uright ? -1 : 0;
-    f->gp = {min_x, min_y, (float)FRAME_GRID_COLS / (max_x - min_x), (float)FRAME_GRID_ROWS / (max_y - min_y)};
-    if (frame_alloc(f, ex->kcap)) { frame_release(f); return nullptr; }
-    return f;
-}
-
-// orbm_frame_from_extractor / orbm_frame_from_extractor_cam: the coordinates from the host (xy_undistorted), through the camera
-// inside the build (cam), or as the extractor left them (both null)
-static int frame_from_extractor(orbx_extractor *ex, int frame, const float *xy_undistorted, const orbm_distortion *cam, const float *uright,
-                                int uright_from_stereo, float min_x, float min_y, float max_x, float max_y, orbm_frame **out)
-{
-    if (!out || !ex || frame < 0 || frame >= ex->last_batch || !(max_x > min_x) || !(max_y > min_y) || (uright && uright_from_stereo))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    if (cam && !distortion_ok(*cam)) ORBX_FAIL(ORBX_ERR_ARG, "camera with a non-finite field or a zero focal length");
-    if (ex->kcap > FB_MAXN) ORBX_FAIL(ORBX_ERR_CAPACITY, "more than 8,192 keypoints in a resident frame");
-    if (uright_from_stereo && (!ex->d_uright || !ex->st_valid || frame >= ex->st_batch)) ORBX_FAIL(ORBX_ERR_ARG, "no stereo results");
-    ORBX_NEED_DEVICE();
-    g_last_frame_build_waits.store(0, std::memory_order_relaxed);
-    const int cap = ex->kcap;
-    orbm_frame *f = frame_for_extractor(ex, (uright || uright_from_stereo) ? 1 : 0, min_x, min_y, max_x, max_y);
-    if (!f) ORBX_FAIL(ORBX_ERR_HIP, "frame allocation failed");
-    WorkspaceLease lease;
-    Workspace &w = *lease.w;
-    w.used = 0;
-    const size_t o_xy = w.carve(xy_undistorted ? sizeof(float) * 2 * (size_t)cap : 1), o_u = w.carve(uright ? sizeof(float) * (size_t)cap : 1);
-    const size_t staged = w.used;
-    if (w.reserve(staged, staged + sizeof(int) * (size_t)cap + 1024)) { frame_release(f); ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed"); }
-    // the caller's arrays hold n entries, n = the frame's count: known here only after the extraction has finished -- it has, for
-    // the caller to hold undistorted coordinates -- so read it back first in that case
-    int n_known = -1;
-    const int *d_n = ex->d_counts + frame;
-    const uint8_t *d_desc = ex->d_desc + (size_t)frame * cap * 32;
-    orbx_extractor *producer = orbx_detail::order_after_producer(d_desc, w.st);
-    int rc = ORBX_OK;
-    if (xy_undistorted || uright) {
-        if (hipMemcpyAsync(&n_known, d_n, sizeof(int), hipMemcpyDeviceToHost, w.st) != hipSuccess || hipStreamSynchronize(w.st) != hipSuccess) rc = ORBX_ERR_HIP;
-        g_last_frame_build_waits.fetch_add(1, std::memory_order_relaxed);
-        if (rc == ORBX_OK && (n_known < 0 || n_known > cap)) rc = ORBX_ERR_HIP;
-        if (rc == ORBX_OK) {
-            if (xy_undistorted) memcpy(w.h<char>(o_xy), xy_undistorted, sizeof(float) * 2 * (size_t)n_known);
-            if (uright) memcpy(w.h<char>(o_u), uright, sizeof(float) * (size_t)n_known);
-            if (orbx::stage_in(w.dev, w.pin, staged, w.st) != hipSuccess) rc = ORBX_ERR_HIP;
-        }
-    }
-    if (rc == ORBX_OK)
-        rc = frame_build(f, w, ex->d_kps + (size_t)frame * cap, reinterpret_cast<const uint4 *>(d_desc),
-                         xy_undistorted ? w.d<float2>(o_xy) : nullptr,
-                         uright ? w.d<float>(o_u) : (uright_from_stereo ? ex->d_uright + (size_t)frame * cap : nullptr), d_n, 0, cap, cam);
-    (void)producer;      // frame_build has waited for the stream: nothing of this call still reads the extractor's buffers
-    if (rc != ORBX_OK) { frame_release(f); if (rc == ORBX_ERR_HIP) ORBX_FAIL(ORBX_ERR_HIP, "building the frame failed"); return rc; }
-    *out = f;
-    return ORBX_OK;
-}
-
-int orbm_frame_from_extractor(orbx_extractor *ex, int frame, const float *xy_undistorted, const float *uright, int uright_from_stereo,
-                              float min_x, float min_y, float max_x, float max_y, orbm_frame **out)
-{
-    return frame_from_extractor(ex, frame, xy_undistorted, nullptr, uright, uright_from_stereo, min_x, min_y, max_x, max_y, out);
-}
-
-int orbm_frame_from_extractor_cam(orbx_extractor *ex, int frame, const orbm_distortion *cam, const float *uright, int uright_from_stereo,
-                                  float min_x, float min_y, float max_x, float max_y, orbm_frame **out)
-{
-    return frame_from_extractor(ex, frame, nullptr, cam, uright, uright_from_stereo, min_x, min_y, max_x, max_y, out);
-}
-
-int orbm_frames_from_extractor(orbx_extractor *ex, int first, int count, const orbm_distortion *cam, int uright_from_stereo, float min_x,
-                               float min_y, float max_x, float max_y, orbm_frame **out)
-{
-    if (!out || !ex || first < 0 || count < 0 || count > ex->last_batch || first > ex->last_batch - count || !(max_x > min_x) || !(max_y > min_y))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    if (cam && !distortion_ok(*cam)) ORBX_FAIL(ORBX_ERR_ARG, "camera with a non-finite field or a zero focal length");
-    if (ex->kcap > FB_MAXN) ORBX_FAIL(ORBX_ERR_CAPACITY, "more than 8,192 keypoints in a resident frame");
-    if (uright_from_stereo && (!ex->d_uright || !ex->st_valid || first + count > ex->st_batch)) ORBX_FAIL(ORBX_ERR_ARG, "no stereo results");
-    ORBX_NEED_DEVICE();
-    g_last_frame_build_waits.store(0, std::memory_order_relaxed);
-    if (count == 0) return ORBX_OK;
-    const int cap = ex->kcap;
-    std::vector<orbm_frame *> fs((size_t)count, nullptr);
-    auto fail = [&](int rc, const char *what) {       // all or nothing
-        for (orbm_frame *f : fs)
-            if (f) frame_release(f);
-        ORBX_FAIL(rc, what);
-    };
-    for (int i = 0; i < count; ++i)
-        if (!(fs[i] = frame_for_extractor(ex, uright_from_stereo ? 1 : 0, min_x, min_y, max_x, max_y))) return fail(ORBX_ERR_HIP, "frame allocation failed");
-    if (frame_build_prepare() != ORBX_OK) return fail(ORBX_ERR_HIP, "building the frames failed");
-    // staged: the table of the frames; result block: a 256-byte header slot and perm[cap] per frame
-    WorkspaceLease lease;
-    Workspace &w = *lease.w;
-    w.used = 0;
-    const size_t slot = (256 + sizeof(int) * (size_t)cap + 255) & ~(size_t)255;
-    const size_t o_tab = w.carve(sizeof(FrameJob) * (size_t)count), staged = w.used, o_res = w.carve(slot * (size_t)count), res_bytes = w.used - o_res;
-    const size_t total = w.used;
-    if (w.reserve(total, std::max(staged, res_bytes))) return fail(ORBX_ERR_HIP, "workspace allocation failed");
-    FrameJob *tab = w.h<FrameJob>(o_tab);
-    for (int i = 0; i < count; ++i) {
-        const size_t fr = (size_t)(first + i);
-        tab[i] = frame_job(fs[i], ex->d_kps + fr * cap, reinterpret_cast<const uint4 *>(ex->d_desc + fr * cap * 32), nullptr,
-                           uright_from_stereo ? ex->d_uright + fr * cap : nullptr, ex->d_counts + fr, 0, cap);
-        tab[i].res_hdr = reinterpret_cast<FrameHdr *>(w.dev + o_res + slot * i);
-        tab[i].res_perm = reinterpret_cast<int *>(w.dev + o_res + slot * i + 256);
-    }
-    const hipStream_t st = w.st;
-    orbx_extractor *producer = orbx_detail::order_after_producer(ex->d_desc + (size_t)first * cap * 32, st);
-    bool ok = orbx::stage_in(w.dev, w.pin, staged, st) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(k_frame_build<true>, dim3(count), dim3(FB_T), FB_LDS, st, tab[0], (const FrameJob *)w.d<FrameJob>(o_tab), fs[0]->gp,
-                           cam ? *cam : orbm_distortion{});
-        ok = hipGetLastError() == hipSuccess && orbx::stage_out(w.pin, w.dev + o_res, res_bytes, st) == hipSuccess;
-    }
-    ok = hipStreamSynchronize(st) == hipSuccess && ok;     // (waited for in any case: nothing of this call still reads the extractor's buffers)
-    g_last_frame_build_waits.store(1, std::memory_order_relaxed);
-    (void)producer;
-    if (!ok) return fail(ORBX_ERR_HIP, "building the frames failed");
-    for (int i = 0; i < count; ++i) {
-        const char *r = w.pin + slot * i;
-        if (frame_adopt(fs[i], r, reinterpret_cast<const int *>(r + 256), cap) != ORBX_OK) return fail(ORBX_ERR_HIP, "frame header out of range");
-    }
-    for (int i = 0; i < count; ++i) out[i] = fs[i];
-    return ORBX_OK;
-}
-
-int orbm_frame_keypoints_un(const orbm_frame *f, float *xy)
-{
-    if (!f || (f->n && !xy)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    if (f->n == 0) return ORBX_OK;
-    ORBX_NEED_DEVICE();
-    std::vector<SeqKp> kp((size_t)f->n);
-    WorkspaceLease lease;
-    const hipStream_t st = lease.w->own_stream();
-    if (!st) ORBX_FAIL(ORBX_ERR_HIP, "hipStreamCreate failed");
-    ORBX_HIP(hipMemcpyAsync(kp.data(), f->kp, sizeof(SeqKp) * (size_t)f->n, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(hipStreamSynchronize(st));
-    for (int sp = 0; sp < f->n; ++sp) { xy[2 * f->perm_host[sp]] = kp[sp].x; xy[2 * f->perm_host[sp] + 1] = kp[sp].y; }
-    return ORBX_OK;
-}
-
-int orbm_debug_last_frame_build_waits(void) { return g_last_frame_build_waits.load(std::memory_order_relaxed); }
-
-int orbm_image_bounds(const orbm_distortion *cam, int width, int height, float *bounds)
-{
-    if (!cam || !bounds || width <= 0 || height <= 0 || !distortion_ok(*cam)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    float x[4], y[4];       // (0, 0), (w, 0), (0, h), (w, h): Frame::ComputeImageBounds (src/Frame.cc:451-479)
-    for (int i = 0; i < 4; ++i) undistort_point(*cam, (i & 1) ? (float)width : 0.0f, (i & 2) ? (float)height : 0.0f, &x[i], &y[i]);
-    bounds[0] = std::min(x[0], x[2]); bounds[1] = std::min(y[0], y[1]);
-    bounds[2] = std::max(x[1], x[3]); bounds[3] = std::max(y[2], y[3]);
-    return ORBX_OK;
-}
-
-int orbm_undistort_points(const orbm_distortion *cam, const float *xy, int n, float *xy_un)
-{
-    if (!cam || n < 0 || (n && (!xy || !xy_un)) || !distortion_ok(*cam)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    ORBX_NEED_DEVICE();
-    if (n == 0) return ORBX_OK;
-    StagedCall sc;
-    const size_t o_in = sc.in(xy, sizeof(float) * 2 * (size_t)n), o_out = sc.out(sizeof(float) * 2 * (size_t)n);
-    if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
-    hipLaunchKernelGGL(k_undistort_points, dim3((n + MT - 1) / MT), dim3(MT), 0, sc.stream(), *cam, (const float2 *)sc.d<float2>(o_in), n,
-                       sc.d<float2>(o_out));
-    ORBX_HIP(hipGetLastError());
-    if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
-    memcpy(xy_un, sc.r<float>(o_out), sizeof(float) * 2 * (size_t)n);
-    return ORBX_OK;
-}
-
-int orbm_frame_destroy(orbm_frame *f)
-{
-    if (!f) return ORBX_OK;
-    frame_release(f);
-    return ORBX_OK;
-}
-
-int orbm_frame_alias(const orbm_frame *src, float min_x, float min_y, float max_x, float max_y, orbm_frame **out)
-{
-    if (!src || !out || !(max_x > min_x) || !(max_y > min_y)) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    orbm_frame *f = new orbm_frame();
-    f->n = src->n; f->ns = src->ns; f->cap = src->cap; f->has_uright = src->has_uright; f->nstereo = src->nstereo;
-    f->min_octave = src->min_octave; f->max_octave = src->max_octave;
-    f->min_x = min_x; f->min_y = min_y; f->max_x = max_x; f->max_y = max_y;
-    f->gp = {min_x, min_y, src->gp.inv_w, src->gp.inv_h};        // KeyFrame: int bounds, the Frame's mfGridElement*Inv (KeyFrame.cc:36,44)
-    f->block = src->block; f->refs = src->refs;
-    f->refs->fetch_add(1);
-    frame_pointers(f);
-    f->perm_host = src->perm_host; f->inv_host = src->inv_host;
-    *out = f;
-    return ORBX_OK;
-}
-
-int orbm_frame_size(const orbm_frame *f, int *n, int *nsorted)
-{
-    if (!f) ORBX_FAIL(ORBX_ERR_ARG, "null frame");
-    if (n) *n = f->n;
-    if (nsorted) *nsorted = f->ns;
-    return ORBX_OK;
-}
-
-int orbm_frame_layout(const orbm_frame *f, int32_t *perm, int32_t *cell_off)
-{
-    if (!f) ORBX_FAIL(ORBX_ERR_ARG, "null frame");
-    if (perm) memcpy(perm, f->perm_host.data(), sizeof(int) * (size_t)f->ns);
-    if (cell_off) {   // (debug accessor; on a leased stream like every other call)
-        WorkspaceLease lease;
-        const hipStream_t st = lease.w->own_stream();
-        if (!st) ORBX_FAIL(ORBX_ERR_HIP, "hipStreamCreate failed");
-        ORBX_HIP(hipMemcpyAsync(cell_off, f->cell_off, sizeof(int) * (FB_NC + 1), hipMemcpyDeviceToHost, st));
-        ORBX_HIP(hipStreamSynchronize(st));
-    }
-    return ORBX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ window searches
-
-int orbm_search_window(const orbm_window_query *queries, const uint8_t *qdesc, int nq, const orbx_keypoint *kps,
-                       const uint8_t *desc, int n, const uint8_t *skip, const float *uright, float min_x, float min_y,
-                       float max_x, float max_y, int init_dist, int32_t *best, int32_t *best_level, int32_t *second,
-                       int32_t *second_level, int32_t *idx)
-{
-    if (nq < 0 || n < 0 || n > 65535 || (nq && (!queries || !qdesc || !best || !best_level || !second || !second_level || !idx)) ||
-        (n && (!kps || !desc)) || !(max_x > min_x) || !(max_y > min_y))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    if (bad_octaves(kps, n)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
-    ORBX_NEED_DEVICE();
-    if (nq == 0) return ORBX_OK;
-    SortedFrame sf;
-    sort_frame(kps, desc, n, nullptr, uright, min_x, min_y, max_x, max_y, sf);
-    FrameSrc fs(sf);
-    return search_window_core(fs, queries, qdesc, nq, skip, uright ? 1 : 0, init_dist, nullptr, 0, 0, best, best_level, second, second_level, idx);
-}
-
-int orbm_frame_search_window(const orbm_frame *frame, const orbm_window_query *queries, const uint8_t *qdesc, int nq, const uint8_t *skip,
-                             int init_dist, int32_t *best, int32_t *best_level, int32_t *second, int32_t *second_level, int32_t *idx)
-{
-    if (!frame || nq < 0 || (nq && (!queries || !qdesc || !best || !best_level || !second || !second_level || !idx)))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    if (bad_octaves(frame)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
-    ORBX_NEED_DEVICE();
-    if (nq == 0) return ORBX_OK;
-    FrameSrc fs(frame);
-    return search_window_core(fs, queries, qdesc, nq, skip, frame->has_uright, init_dist, nullptr, 0, 0, best, best_level, second, second_level, idx);
-}
-
-int orbm_search_by_projection_map(const orbx_keypoint *kps, const uint8_t *desc, int n, const uint8_t *has_mappoint,
-                                  const float *mp_pos, const float *mp_normal, const float *mp_min_dist,
-                                  const float *mp_max_dist, const uint8_t *mp_desc, int m, const double *Rcw,
-                                  const double *tcw, const orbm_camera *cam, const float *scale_factors, int nlevels,
-                                  float th, float nnratio, int th_reloc, int32_t *matched_mp, int *nmatches, float *proj)
-{
-    if (n < 0 || m < 0 || n > 65535 || nlevels < 1 || nlevels > 64 || !cam || !Rcw || !tcw || !scale_factors || !matched_mp ||
-        (n && (!kps || !desc)) || (m && (!mp_pos || !mp_normal || !mp_min_dist || !mp_max_dist || !mp_desc)) ||
-        !(cam->grid_max_x > cam->grid_min_x) || !(cam->grid_max_y > cam->grid_min_y))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    ORBX_NEED_DEVICE();
-    for (int j = 0; j < n; ++j) matched_mp[j] = -1;
-    if (nmatches) *nmatches = 0;
-    if (n == 0 || m == 0) return ORBX_OK;
-    SortedFrame sf;
-    sort_frame(kps, desc, n, nullptr, nullptr, cam->grid_min_x, cam->grid_min_y, cam->grid_max_x, cam->grid_max_y, sf);
-    FrameSrc fs(sf);
-    return search_map_core(fs, n, has_mappoint, mp_pos, mp_normal, mp_min_dist, mp_max_dist, mp_desc, m, Rcw, tcw, cam, scale_factors, nlevels,
-                           th, nnratio, th_reloc, matched_mp, nmatches, proj);
-}
-
-int orbm_frame_search_by_projection_map(const orbm_frame *frame, const uint8_t *has_mappoint, const float *mp_pos, const float *mp_normal,
-                                        const float *mp_min_dist, const float *mp_max_dist, const uint8_t *mp_desc, int m, const double *Rcw,
-                                        const double *tcw, const orbm_camera *cam, const float *scale_factors, int nlevels, float th,
-                                        float nnratio, int th_reloc, int32_t *matched_mp, int *nmatches, float *proj)
-{
-    if (!frame || m < 0 || nlevels < 1 || nlevels > 64 || !cam || !Rcw || !tcw || !scale_factors || !matched_mp ||
-        (m && (!mp_pos || !mp_normal || !mp_min_dist || !mp_max_dist || !mp_desc)))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    ORBX_NEED_DEVICE();
-    const int n = frame->n;
-    for (int j = 0; j < n; ++j) matched_mp[j] = -1;
-    if (nmatches) *nmatches = 0;
-    if (n == 0 || m == 0) return ORBX_OK;
-    FrameSrc fs(frame);
-    return search_map_core(fs, n, has_mappoint, mp_pos, mp_normal, mp_min_dist, mp_max_dist, mp_desc, m, Rcw, tcw, cam, scale_factors, nlevels,
-                           th, nnratio, th_reloc, matched_mp, nmatches, proj);
-}
-
-// ------------------------------------------------------------------------------------------------ the map as a snapshot
-
-int orbm_map_create(const float *mp_pos, const float *mp_normal, const float *mp_min_dist, const float *mp_max_dist, const uint8_t *mp_desc,
-                    int m, orbm_map **out)
-{
-    if (!out || m < 0 || (m && (!mp_pos || !mp_normal || !mp_min_dist || !mp_max_dist || !mp_desc))) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    ORBX_NEED_DEVICE();
-    orbm_map *mp = new orbm_map();
-    mp->m = m;
-    if (m) {
-        // one block: descriptors, positions, normals, the two distances (each part a multiple of 16 bytes behind a 256-byte boundary)
-        const size_t b_desc = (size_t)32 * m, b_3 = (sizeof(float) * 3 * m + 255) & ~(size_t)255, b_1 = (sizeof(float) * m + 255) & ~(size_t)255;
-        if (hipMalloc((void **)&mp->block, ((b_desc + 255) & ~(size_t)255) + 2 * b_3 + 2 * b_1) != hipSuccess) { delete mp; ORBX_FAIL(ORBX_ERR_HIP, "map allocation failed"); }
-        char *p = mp->block;
-        mp->desc = reinterpret_cast<uint4 *>(p); p += (b_desc + 255) & ~(size_t)255;
-        mp->pos = reinterpret_cast<float *>(p); p += b_3;
-        mp->nrm = reinterpret_cast<float *>(p); p += b_3;
-        mp->mind = reinterpret_cast<float *>(p); p += b_1;
-        mp->maxd = reinterpret_cast<float *>(p);
-        WorkspaceLease lease;
-        const hipStream_t st = lease.w->own_stream();
-        bool ok = st != nullptr;
-        ok = ok && hipMemcpyAsync(mp->desc, mp_desc, b_desc, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && hipMemcpyAsync(mp->pos, mp_pos, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && hipMemcpyAsync(mp->nrm, mp_normal, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && hipMemcpyAsync(mp->mind, mp_min_dist, sizeof(float) * m, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && hipMemcpyAsync(mp->maxd, mp_max_dist, sizeof(float) * m, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && hipStreamSynchronize(st) == hipSuccess;
-        if (!ok) { (void)hipFree(mp->block); delete mp; ORBX_FAIL(ORBX_ERR_HIP, "map upload failed"); }
-    }
-    *out = mp;
-    return ORBX_OK;
-}
-
-int orbm_map_destroy(orbm_map *map)
-{
-    if (!map) return ORBX_OK;
-    if (map->block) (void)hipFree(map->block);
-    delete map;
-    return ORBX_OK;
-}
-
-int orbm_map_size(const orbm_map *map, int *m)
-{
-    if (!map || !m) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    *m = map->m;
-    return ORBX_OK;
-}
-
-int orbm_search_by_projection_map_poses(const orbx_keypoint *kps, const uint8_t *desc, int n, const uint8_t *has_mappoint,
-                                        const float *mp_pos, const float *mp_normal, const float *mp_min_dist, const float *mp_max_dist,
-                                        const uint8_t *mp_desc, int m, const double *Rcw, const double *tcw, int P, const orbm_camera *cam,
-                                        const float *scale_factors, int nlevels, float th, float nnratio, int th_reloc,
-                                        int32_t *matched_mp, int32_t *nmatches, float *proj)
-{
-    if (n < 0 || m < 0 || n > 65535 || (n && (!kps || !desc)) || (m && (!mp_pos || !mp_normal || !mp_min_dist || !mp_max_dist || !mp_desc)) ||
-        (cam && (!(cam->grid_max_x > cam->grid_min_x) || !(cam->grid_max_y > cam->grid_min_y))))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    bool go;
-    if (const int rc = map_poses_begin(n, m, Rcw, tcw, P, cam, scale_factors, nlevels, matched_mp, nmatches, bad_octaves(kps, n), &go)) return rc;
-    if (!go) return ORBX_OK;
-    SortedFrame sf;
-    sort_frame(kps, desc, n, nullptr, nullptr, cam->grid_min_x, cam->grid_min_y, cam->grid_max_x, cam->grid_max_y, sf);
-    FrameSrc fs(sf);
-    const MapSrc map = {mp_pos, mp_normal, mp_min_dist, mp_max_dist, mp_desc, nullptr, m};
-    return search_map_poses_core(fs, n, has_mappoint, map, Rcw, tcw, P, cam, scale_factors, nlevels, th, nnratio, th_reloc, matched_mp, nmatches,
-                                 proj);
-}
-
-int orbm_frame_search_by_projection_map_poses(const orbm_frame *frame, const uint8_t *has_mappoint, const orbm_map *map, const double *Rcw,
-                                              const double *tcw, int P, const orbm_camera *cam, const float *scale_factors, int nlevels,
-                                              float th, float nnratio, int th_reloc, int32_t *matched_mp, int32_t *nmatches, float *proj)
-{
-    if (!frame || !map) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    bool go;
-    if (const int rc = map_poses_begin(frame->n, map->m, Rcw, tcw, P, cam, scale_factors, nlevels, matched_mp, nmatches, bad_octaves(frame), &go))
-        return rc;
-    if (!go) return ORBX_OK;
-    FrameSrc fs(frame);
-    const MapSrc src = {nullptr, nullptr, nullptr, nullptr, nullptr, map, map->m};
-    return search_map_poses_core(fs, frame->n, has_mappoint, src, Rcw, tcw, P, cam, scale_factors, nlevels, th, nnratio, th_reloc, matched_mp,
-                                 nmatches, proj);
-}
-
-int orbm_debug_last_map_poses_waits(void) { return g_last_map_poses_waits.load(std::memory_order_relaxed); }
-
 int orbm_project_points(int mode, const float *mp_pos, const float *mp_normal, const float *mp_min_distance,
                         const float *mp_max_distance, int m, const float *Rcw, const float *tcw, const float *Ow,
                         const orbm_camera *cam, float mbf, float viewing_cos_limit, float log_scale_factor,
@@ -2681,35 +1450,6 @@ int orbm_project_points(int mode, const float *mp_pos, const float *mp_normal, c
     return ORBX_OK;
 }
 
-int orbm_search_fuse(const orbm_window_query *queries, const uint8_t *qdesc, int nq, const orbx_keypoint *kps, const uint8_t *desc,
-                     int n, const float *uright, const float *inv_level_sigma2, int nlevels, float min_x, float min_y, float max_x,
-                     float max_y, int32_t *best, int32_t *idx)
-{
-    if (nq < 0 || n < 0 || n > 65535 || (nq && (!queries || !qdesc || !best || !idx)) || (n && (!kps || !desc)) ||
-        (inv_level_sigma2 && (nlevels < 1 || nlevels > 64)) || !(max_x > min_x) || !(max_y > min_y))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    for (int j = 0; j < n && inv_level_sigma2; ++j)
-        if (kps[j].octave < 0 || kps[j].octave >= nlevels) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
-    ORBX_NEED_DEVICE();
-    if (nq == 0) return ORBX_OK;
-    SortedFrame sf;
-    sort_frame(kps, desc, n, nullptr, uright, min_x, min_y, max_x, max_y, sf);
-    if (!uright) for (SeqKp &k : sf.kp) k.uright = -1.0f;
-    FrameSrc fs(sf);
-    return search_window_core(fs, queries, qdesc, nq, nullptr, uright ? 1 : 0, 256, inv_level_sigma2, nlevels, 1, best, nullptr, nullptr, nullptr, idx);
-}
-
-int orbm_frame_search_fuse(const orbm_frame *frame, const orbm_window_query *queries, const uint8_t *qdesc, int nq,
-                           const float *inv_level_sigma2, int nlevels, int32_t *best, int32_t *idx)
-{
-    if (!frame || nq < 0 || (nq && (!queries || !qdesc || !best || !idx)) || (inv_level_sigma2 && (nlevels < 1 || nlevels > 16)))
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
-    ORBX_NEED_DEVICE();
-    if (nq == 0) return ORBX_OK;
-    FrameSrc fs(frame);
-    return search_window_core(fs, queries, qdesc, nq, nullptr, frame->has_uright, 256, inv_level_sigma2, nlevels, 1, best, nullptr, nullptr, nullptr, idx);
-}
-
 int orbm_search_projection(const orbm_window_query *queries, const uint8_t *qdesc, const float *qangle, const uint8_t *qtakes,
                            int nq, const orbx_keypoint *kps, const uint8_t *desc, int n, const uint8_t *occupied,
                            const float *uright, float min_x, float min_y, float max_x, float max_y, int th_accept, float nnratio,
@@ -2723,12 +1463,8 @@ int orbm_search_projection(const orbm_window_query *queries, const uint8_t *qdes
     SortedFrame sf;
     sort_frame(kps, desc, n, nullptr, uright, min_x, min_y, max_x, max_y, sf);
     FrameSrc fs(sf);
-    SeqSearch r;
-    r.queries = reinterpret_cast<const WinQuery *>(queries); r.q.desc = qdesc; r.q.angle = qangle; r.qtakes = qtakes; r.nq = nq;
-    r.fs = &fs; r.n = n; r.occupied = occupied; r.has_uright = uright ? 1 : 0;
-    r.th = th_accept; r.nnratio = nnratio; r.accept_mode = ratio_same_level ? ACCEPT_RATIO_SAME_LEVEL : ACCEPT_BEST; r.check = check_orientation;
-    r.match_kp = match_kp; r.match_q = match_q; r.nmatches = nmatches;
-    return run_sequential(r);
+    return search_projection_core(fs, n, uright ? 1 : 0, queries, qdesc, qangle, qtakes, nq, occupied, th_accept, nnratio, ratio_same_level,
+                                  check_orientation, match_kp, match_q, nmatches);
 }
 
 int orbm_frame_search_projection(const orbm_frame *frame, const orbm_window_query *queries, const uint8_t *qdesc, const float *qangle,
@@ -2740,12 +1476,8 @@ int orbm_frame_search_projection(const orbm_frame *frame, const orbm_window_quer
     if (bad_octaves(frame)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
     ORBX_NEED_DEVICE();
     FrameSrc fs(frame);
-    SeqSearch r;
-    r.queries = reinterpret_cast<const WinQuery *>(queries); r.q.desc = qdesc; r.q.angle = qangle; r.qtakes = qtakes; r.nq = nq;
-    r.fs = &fs; r.n = frame->n; r.occupied = occupied; r.has_uright = frame->has_uright;
-    r.th = th_accept; r.nnratio = nnratio; r.accept_mode = ratio_same_level ? ACCEPT_RATIO_SAME_LEVEL : ACCEPT_BEST; r.check = check_orientation;
-    r.match_kp = match_kp; r.match_q = match_q; r.nmatches = nmatches;
-    return run_sequential(r);
+    return search_projection_core(fs, frame->n, frame->has_uright, queries, qdesc, qangle, qtakes, nq, occupied, th_accept, nnratio,
+                                  ratio_same_level, check_orientation, match_kp, match_q, nmatches);
 }
 
 int orbm_search_for_initialization(const orbx_keypoint *kps1, const uint8_t *desc1, int n1, const orbx_keypoint *kps2,

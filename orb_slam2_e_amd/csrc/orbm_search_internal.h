@@ -1,0 +1,121 @@
+// orbm_search_internal.h -- what the three units of the windowed searches share and nothing else:
+//   orbm_frame.hip   makes frames: sorted on the host for one call (sort_frame) or resident in HBM (k_frame_build);
+//   orbm_window.hip  searches them with independent queries (k_win_best, k_map_search_poses);
+//   orbm_search.hip  searches them with the reference's coupled loops (run_sequential), and SearchBySim3 through launch_win_best.
+// A frame reaches a search as a FrameSrc and its kernels as a FrameView.  What only one unit uses stays in that unit; what the
+// other matcher units need as well is in orbm_internal.h.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <initializer_list>
+#include <vector>
+
+#include "orbm_internal.h"
+
+namespace orbm_detail {
+
+constexpr int SEQ_MAXN = 8192;     // keypoints per frame the resolver's LDS state holds, and a resident frame at most
+
+// Minimum over the wave, in every lane: a butterfly inside each row of 16 lanes on the DPP path (no LDS crossbar round trips),
+// then the four row results through scalar registers.  All 64 lanes must be active.
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
+{
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xf, 0xf, false));    // quad_perm [1, 0, 3, 2]
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xf, 0xf, false));    // quad_perm [2, 3, 0, 1]
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xf, 0xf, false));   // row_half_mirror
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xf, 0xf, false));   // row_mirror
+    const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 0), b = (unsigned)__builtin_amdgcn_readlane((int)v, 16),
+                   c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
+    return min(min(a, b), min(c, d));
+}
+
+struct SortedFrame {
+    std::vector<SeqKp> kp;
+    std::vector<int> cell_off; // [COLS*ROWS + 1] runs of the sorted array per grid cell (col * ROWS + row)
+    GridParams gp = {0.f, 0.f, 0.f, 0.f};
+    std::vector<int> perm;
+    std::vector<float> angle;
+    std::vector<uint8_t> desc;
+};
+
+// Keypoints in the grid (and not excluded by `skip`), ordered by (cell, index).  (orbm_frame.hip)
+void sort_frame(const orbx_keypoint *kps, const uint8_t *desc, int n, const uint8_t *skip, const float *uright, float min_x,
+                float min_y, float max_x, float max_y, SortedFrame &sf);
+
+// What the search kernels read of a frame, wherever it lives.
+struct FrameView {
+    const SeqKp *kp; const uint4 *desc; const float *angle; const int *perm; const int *cell_off;
+    GridParams gp;
+};
+
+// The frame of a call: sorted on the host and staged with the call's inputs (the host-array entry points), or resident.
+struct FrameSrc {
+    const SortedFrame *host = nullptr;
+    const orbm_frame *res = nullptr;
+    size_t o_k = 0, o_b = 0, o_kang = 0, o_perm = 0, o_cell = 0;
+    bool all_positions = false;     // resident frame addressed by explicit candidate lists: the positions behind the grid's count too
+    explicit FrameSrc(const SortedFrame &sf) : host(&sf) {}
+    explicit FrameSrc(const orbm_frame *f, bool all = false) : res(f), all_positions(all) {}
+    int ns() const { return host ? (int)host->perm.size() : (all_positions ? res->n : res->ns); }
+    const int *perm() const { return host ? host->perm.data() : res->perm_host.data(); }
+    void carve(Workspace &w)
+    {
+        if (!host) return;
+        const size_t m = ns() ? (size_t)ns() : 1;
+        o_k = w.carve(sizeof(SeqKp) * m); o_b = w.carve(32 * m); o_kang = w.carve(sizeof(float) * m); o_perm = w.carve(sizeof(int) * m);
+        o_cell = w.carve(sizeof(int) * (FRAME_GRID_COLS * FRAME_GRID_ROWS + 1));
+    }
+    void fill(Workspace &w) const
+    {
+        if (!host) return;
+        const size_t m = (size_t)ns();
+        if (!host->kp.empty()) memcpy(w.h<char>(o_k), host->kp.data(), sizeof(SeqKp) * m);
+        if (!host->cell_off.empty()) memcpy(w.h<char>(o_cell), host->cell_off.data(), sizeof(int) * host->cell_off.size());
+        memcpy(w.h<char>(o_b), host->desc.data(), 32 * m);
+        memcpy(w.h<char>(o_kang), host->angle.data(), sizeof(float) * m);
+        memcpy(w.h<char>(o_perm), host->perm.data(), sizeof(int) * m);
+    }
+    FrameView view(const Workspace &w) const
+    {
+        if (host) return {w.d<SeqKp>(o_k), w.d<uint4>(o_b), w.d<float>(o_kang), w.d<int>(o_perm), w.d<int>(o_cell), host->gp};
+        return {res->kp, res->desc, res->angle, res->perm, res->cell_off, res->gp};
+    }
+    // occupancy by keypoint index -> by sorted position
+    void fill_occ(uint8_t *dst, const uint8_t *occupied) const
+    {
+        const int m = ns();
+        const int *pm = perm();
+        for (int s = 0; s < m; ++s) dst[s] = occupied[pm[s]];
+    }
+};
+
+// A candidate entry holds its keypoint's octave in four bits (k_win_wave, entry_level; k_win_best packs it the same way): a frame
+// with an octave outside 0..15 cannot be searched.
+inline bool bad_octaves(const orbx_keypoint *kps, int n)
+{
+    for (int j = 0; j < n; ++j)
+        if (kps[j].octave < 0 || kps[j].octave > 15) return true;
+    return false;
+}
+inline bool bad_octaves(const orbm_frame *f) { return f->n && (f->min_octave < 0 || f->max_octave > 15); }
+
+// One window search without coupling (k_win_best, orbm_window.hip) for device-resident queries: returns into ob[5][nq] (best, best
+// level, second, second level, idx).
+void launch_win_best(hipStream_t st, const WinQuery *dq, const uint4 *da, int nq, const FrameView &fv, const uint8_t *docc, int has_uright,
+                     int init_dist, const float *inv_sigma2, int fuse_gate, int *ob);
+
+// Copies outside a call's staged traffic (a resident frame's arrays for an accessor, a snapshot's upload), all in one direction: on
+// the own stream of a leased workspace, like every other call, waited for once.
+struct CopyJob { void *dst; const void *src; size_t bytes; };
+inline int copy_and_wait(std::initializer_list<CopyJob> jobs, hipMemcpyKind kind)
+{
+    WorkspaceLease lease;
+    const hipStream_t st = lease.w->own_stream();
+    if (!st) ORBX_FAIL(ORBX_ERR_HIP, "hipStreamCreate failed");
+    for (const CopyJob &j : jobs) ORBX_HIP(hipMemcpyAsync(j.dst, j.src, j.bytes, kind, st));
+    ORBX_HIP(hipStreamSynchronize(st));
+    return ORBX_OK;
+}
+
+} // namespace orbm_detail
