@@ -500,6 +500,29 @@ int orbm_frame_search_by_bow(const orbm_frame *frame1, const int32_t *nodes1, co
                              const int32_t *items2, int nn2, const uint8_t *valid2, int th, int strict_th, float nnratio,
                              int check_orientation, int32_t *match12, int32_t *match21, int *nmatches);
 
+/* K searches of orbm_frame_search_by_bow in one call: the loop over the candidate keyframes that opens Tracking::Relocalization
+ * (src/Tracking.cc:1768-1795: frame2 = the current frame in every pair, valid2 = NULL) and LoopClosing::ComputeSim3
+ * (src/LoopClosing.cc:252-280: frame1 = the current keyframe in every pair).  A pair's fields are that function's arguments, and
+ * pair k's match12, match21 and nmatches[k] are exactly what it returns for the pair alone, the -1 presets included.  Frames are
+ * only read: the same frame may stand in any number of pairs, on either side.
+ * K = 0 .. 64 (more: ORBX_ERR_UNSUPPORTED; K = 0: ORBX_OK, nothing is launched).  Every pair is checked as the single call
+ * checks it, and a pair that fails fails the whole call (ORBX_ERR_ARG, ORBX_ERR_CAPACITY) before anything is launched or written.
+ * One lease, one staged upload, one launch per phase (list fill; one resolver workgroup per pair) and ONE host wait for all pairs
+ * that have a query; a pair without one (no common node, no valid query, an empty frame) keeps its -1 rows and takes no part.  A
+ * pair whose fixed point does not settle is repeated alone on the sequential resolver, at one more wait each; the others'
+ * results stand.  Under orbm_debug_force_sequential_resolver(1) every pair with a query takes that path.  Re-entrant. */
+typedef struct orbm_bow_pair {
+    const orbm_frame *frame1; const int32_t *nodes1, *off1, *items1; int32_t nn1; const uint8_t *valid1;   /* [frame1->n] */
+    const orbm_frame *frame2; const int32_t *nodes2, *off2, *items2; int32_t nn2; const uint8_t *valid2;   /* [frame2->n] or NULL (Frame form) */
+    int32_t *match12;   /* out, [frame1->n] */
+    int32_t *match21;   /* out, [frame2->n], may be NULL */
+} orbm_bow_pair;
+int orbm_frame_search_by_bow_pairs(const orbm_bow_pair *pairs, int K, int th, int strict_th, float nnratio, int check_orientation,
+                                   int32_t *nmatches /* [K] */);
+/* Host waits (stream synchronisations) of the last orbm_frame_search_by_bow_pairs of this process: 0 when no pair had a query, 1
+ * on the common path, one more for every pair that was repeated on the sequential resolver. */
+int orbm_debug_last_bow_pairs_waits(void);
+
 /* orbm_search_for_triangulation on two resident keyframes: a keypoint is "stereo" where the frame's right coordinate is >= 0
  * (mvuRight, as given to orbm_frame_create / taken from ComputeStereoMatches); the call uploads the feature-vector lists and the two
  * "owns a MapPoint" masks, and the rotation histogram runs on angle differences formed on the device.  Positions are the frames'

@@ -700,6 +700,37 @@ public:
         return mStatus == ORBX_OK ? nm : 0;
     }
 
+    // One side of a batched SearchByBoW: a resident frame, its flat FeatureVector and its "owns a good MapPoint" mask
+    // (valid == nullptr on the second side: SearchByBoW(KeyFrame*, Frame&, ...), every feature of the frame is a candidate).
+    struct BoWSide {
+        const ResidentFrame *frame; const FeatureVector *fv; const std::vector<uint8_t> *valid;
+    };
+    // SearchByBoW for K (first, second) pairs in ONE call (orbm_frame_search_by_bow_pairs; at most 64): the loop over the candidate
+    // keyframes of Tracking::Relocalization (Tracking.cc:1768-1795: second = the current frame in every pair, bKeyFrames = false)
+    // and of LoopClosing::ComputeSim3 (LoopClosing.cc:252-280: first = the current keyframe in every pair, bKeyFrames = true: both
+    // masks, bestDist1 < TH_LOW).  vvnMatches12[k] / vnMatches[k] = what the single call returns for pair k.  Returns the status.
+    int SearchByBoW(const std::vector<std::pair<BoWSide, BoWSide>> &vPairs, bool bKeyFrames, std::vector<std::vector<int32_t>> &vvnMatches12,
+                    std::vector<int32_t> &vnMatches)
+    {
+        const size_t K = vPairs.size();
+        std::vector<orbm_bow_pair> p(K);
+        vvnMatches12.resize(K);
+        vnMatches.assign(K > 0 ? K : 1, 0);
+        for (size_t k = 0; k < K; ++k) {
+            const BoWSide &a = vPairs[k].first, &b = vPairs[k].second;
+            vvnMatches12[k].assign(a.frame->N > 0 ? a.frame->N : 1, -1);
+            p[k].frame1 = a.frame->handle(); p[k].nodes1 = a.fv->nodes.data(); p[k].off1 = a.fv->off.data(); p[k].items1 = a.fv->items.data();
+            p[k].nn1 = (int32_t)a.fv->nodes.size(); p[k].valid1 = a.valid->data();
+            p[k].frame2 = b.frame->handle(); p[k].nodes2 = b.fv->nodes.data(); p[k].off2 = b.fv->off.data(); p[k].items2 = b.fv->items.data();
+            p[k].nn2 = (int32_t)b.fv->nodes.size(); p[k].valid2 = bKeyFrames && b.valid ? b.valid->data() : nullptr;
+            p[k].match12 = vvnMatches12[k].data(); p[k].match21 = nullptr;
+        }
+        mStatus = orbm_frame_search_by_bow_pairs(p.data(), (int)K, TH_LOW, bKeyFrames ? 1 : 0, mfNNratio, mbCheckOrientation, vnMatches.data());
+        for (size_t k = 0; k < K; ++k) vvnMatches12[k].resize(vPairs[k].first.frame->N);
+        vnMatches.resize(K);
+        return mStatus;
+    }
+
     // SearchForTriangulation on two resident keyframes (stereo = the frame's right coordinate >= 0): the lists and the two
     // "owns a MapPoint" masks are all that travels.
     int SearchForTriangulation(const ResidentFrame &KF1, const FeatureVector &fv1, const std::vector<uint8_t> &hasMP1,

@@ -24,6 +24,8 @@
 //      Queries whose candidate sets cannot meet are independent of each other: the BoW searches hand
 //      k_resolve one SEGMENT per vocabulary node (a feature belongs to one node, ORBmatcher.cc:384-456),
 //      one workgroup per segment, so the nodes resolve side by side instead of one after the other;
+//      whole SEARCHES that share nothing -- SearchByBoW against every candidate keyframe -- run as one call
+//      (orbm_frame_search_by_bow_pairs: k_list_fill_pairs, then k_resolve_par_pairs with one fixed-point workgroup per search);
 //   4. k_rotation builds the 30-bin rotation histogram, ORBmatcher::ComputeThreeMaxima
 //      (:1802-1843) and rejects the matches outside the three main bins.
 // The host never waits in the middle of a call (run_sequential over a SeqSearch: seq_layout, seq_stage, seq_lists, seq_resolve,
@@ -195,14 +197,13 @@ __global__ __launch_bounds__(MT) void k_win_wave(const WinQuery *__restrict__ q,
 // cand[cbeg[i] .. cbeg[i] + off[i+1] - off[i]): the queries of one node share one copy of the node's member list.
 // qmap (queries taken from a resident frame): query i is the feature at sorted position qmap[i] of that frame -- A and qang_src are the
 // frame's arrays, and the query's angle is set down in qang_dst[i] for the rotation check.
-__global__ __launch_bounds__(MT) void k_list_fill(const uint4 *__restrict__ A, int nq, const uint4 *__restrict__ B,
-                                                  const int *__restrict__ off, const int *__restrict__ cbeg,
-                                                  const int *__restrict__ cand, unsigned *__restrict__ ent,
-                                                  unsigned *__restrict__ top, const int *__restrict__ qmap,
-                                                  const float *__restrict__ qang_src, float *__restrict__ qang_dst)
+// list_fill_query is the wave's work, shared by k_list_fill (one search) and k_list_fill_pairs (a batch of searches).  Its pointers
+// are not __restrict__ on purpose: k_list_fill's own parameters carry the qualifier, and with it here as well that kernel's register
+// allocation moved.
+__device__ __forceinline__ void list_fill_query(int i, int lane, const uint4 *A, const uint4 *B, const int *off, const int *cbeg,
+                                                const int *cand, unsigned *ent, unsigned *top, const int *qmap,
+                                                const float *qang_src, float *qang_dst)
 {
-    const int i = blockIdx.x * (MT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= nq) return;
     const int qi = qmap ? qmap[i] : i;
     if (qmap && lane == 0) qang_dst[i] = qang_src[qi];
     const uint4 a0 = A[2 * qi], a1 = A[2 * qi + 1];
@@ -214,6 +215,41 @@ __global__ __launch_bounds__(MT) void k_list_fill(const uint4 *__restrict__ A, i
     }
     __threadfence_block();
     wave_topk(ent, off[i], off[i + 1] - off[i], lane, top + (size_t)i * TOPK);
+}
+__global__ __launch_bounds__(MT) void k_list_fill(const uint4 *__restrict__ A, int nq, const uint4 *__restrict__ B,
+                                                  const int *__restrict__ off, const int *__restrict__ cbeg,
+                                                  const int *__restrict__ cand, unsigned *__restrict__ ent,
+                                                  unsigned *__restrict__ top, const int *__restrict__ qmap,
+                                                  const float *__restrict__ qang_src, float *__restrict__ qang_dst)
+{
+    const int i = blockIdx.x * (MT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= nq) return;
+    list_fill_query(i, lane, A, B, off, cbeg, cand, ent, top, qmap, qang_src, qang_dst);
+}
+
+// One search of a batch of BoW searches over resident frames (orbm_frame_search_by_bow_pairs), as its two kernels read it: the
+// two frames' arrays, the search's lists, short lists and angles in the call's workspace, its working copies of the results and
+// its rows of the result block in pinned host memory.
+struct BowPairDev {
+    const uint4 *A, *B;                         // descriptors of frame1 / frame2 by sorted position
+    const float *qang_src, *kangle;             // angles of frame1 / frame2 by sorted position
+    const int *perm;                            // frame2: keypoint index at sorted position
+    const int *qmap, *off, *cbeg, *cand;        // query -> sorted position in frame1; the lists (off[nq + 1] counts from 0)
+    unsigned *ent, *top;                        // the search's entries and short lists
+    float *qang;                                // [nq] the queries' angles, set down by the list kernel
+    int *match_q, *match_kp, *dev_nm;           // device working copies: [nq], [n], [4]
+    int *host_q, *host_kp, *host_nm;            // pinned: [nq], [n], [4]
+    int nq, ns, n, reserved;                    // queries; positions of frame2 (= its keypoints: addressed by index); keypoints of frame2
+};
+
+// k_list_fill for all searches of a batch: blockIdx.y = the search, one wave per query; the grid's first dimension is sized for the
+// batch's largest nq, and a wave beyond its search's nq leaves before any work.
+__global__ __launch_bounds__(MT) void k_list_fill_pairs(const BowPairDev *__restrict__ recs)
+{
+    const BowPairDev &p = recs[blockIdx.y];
+    const int i = blockIdx.x * (MT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= p.nq) return;
+    list_fill_query(i, lane, p.A, p.B, p.off, p.cbeg, p.cand, p.ent, p.top, p.qmap, p.qang_src, p.qang);
 }
 
 // Exclusive scan of cnt[0..n) into off[0..n], one block (n is a few thousand).
@@ -471,21 +507,25 @@ __device__ __forceinline__ void for_each_query(int tid, int nq, F f)
         if (tid + r * RES_T < nq) f(tid + r * RES_T, r);
     for (int i = tid + RES_QREG * RES_T; i < nq; i += RES_T) f(i, -1);
 }
-__global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restrict__ ent, const unsigned *__restrict__ top,
-                                                       const int *__restrict__ lbeg, const int *__restrict__ lend, int nq, int ns,
-                                                       const uint8_t *__restrict__ takes, int th, float nnratio, int accept_mode,
-                                                       const float *__restrict__ qangle, const float *__restrict__ kangle,
-                                                       const int *__restrict__ perm, int check, int *__restrict__ match_q,
-                                                       int *__restrict__ match_kp, int n, const int *__restrict__ flags, int gen,
-                                                       int *__restrict__ host_q, int *__restrict__ host_kp, int *__restrict__ host_nm,
-                                                       int *__restrict__ dev_nm)
+// The kernel's body is resolve_par: ONE workgroup's work on ONE search, whose whole state -- the claim tables, permutation and
+// angles in the dynamic LDS `sm` (4 * ns ints), the histogram, the counts and the "changed" word in static LDS -- belongs to the
+// workgroup that runs it.  k_resolve_par runs it on a call's search; k_resolve_par_pairs on the search its workgroup index selects.
+// ALL_TAKE: every query's match blocks its slot (the BoW searches): there is no `takes` array to read.
+template <bool ALL_TAKE>
+__device__ __forceinline__ void resolve_par(int *__restrict__ sm, const unsigned *__restrict__ ent, const unsigned *__restrict__ top,
+                                            const int *__restrict__ lbeg, const int *__restrict__ lend, int nq, int ns,
+                                            const uint8_t *__restrict__ takes, int th, float nnratio, int accept_mode,
+                                            const float *__restrict__ qangle, const float *__restrict__ kangle,
+                                            const int *__restrict__ perm, int check, int *__restrict__ match_q,
+                                            int *__restrict__ match_kp, int n, const int *__restrict__ flags, int gen,
+                                            int *__restrict__ host_q, int *__restrict__ host_kp, int *__restrict__ host_nm,
+                                            int *__restrict__ dev_nm)
 {
     // dev_nm: the device copy of the count ([0]) and of the "fixed point reached" word ([2]) for work chained behind this kernel
     // (SearchChain), which must not wait for the host to read them; flags[1] of the same block is only read here.
     // host_*: the call's result block in PINNED HOST memory.  The kernel's last phase writes the results there itself (posted
     // writes over PCIe, each element once): a device-to-host copy behind the kernel cost the call its 5 us plus ~9 us of
     // hand-over between the compute queue and the copy engine.  match_q / match_kp stay the device-side working copies.
-    extern __shared__ __align__(16) int sm[];
     int *f_cur = sm, *f_nxt = sm + ns;     // first[s] of the last / of this iteration (INT_MAX: nobody takes s)
     int *s_perm = sm + 2 * ns;             // what the tail gathers by sorted position sits in LDS before the iterations end:
     float *s_kang = reinterpret_cast<float *>(sm + 3 * ns);   // the kernel is one workgroup of dependent round trips
@@ -504,7 +544,7 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
         br[r] = er[r] = 0; tkr[r] = 1; qar[r] = 0.f;
 #pragma unroll
         for (int k = 0; k < TOPK; ++k) tpr[r][k] = 0xffffffffu;
-        if (i < nq) { load_top(top, i, tpr[r]); br[r] = lbeg[i]; er[r] = lend[i]; tkr[r] = takes[i]; qar[r] = qangle[i]; }
+        if (i < nq) { load_top(top, i, tpr[r]); br[r] = lbeg[i]; er[r] = lend[i]; tkr[r] = ALL_TAKE ? 1 : (int)takes[i]; qar[r] = qangle[i]; }
     }
     for (int j = tid; j < ns; j += RES_T) { f_cur[j] = INT_MAX; f_nxt[j] = INT_MAX; s_perm[j] = perm[j]; s_kang[j] = kangle[j]; }
     for (int j = tid; j < n; j += RES_T) match_kp[j] = -1;
@@ -532,7 +572,7 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
             unsigned tpg[TOPK];
             if (r < 0) load_top(top, i, tpg);
             const int sel = r >= 0 ? select(i, tpr[r], br[r], er[r], f_cur) : select(i, tpg, lbeg[i], lend[i], f_cur);
-            const int prev = r >= 0 ? selr[r] : match_q[i], tk = r >= 0 ? tkr[r] : (int)takes[i];
+            const int prev = r >= 0 ? selr[r] : match_q[i], tk = r >= 0 ? tkr[r] : (ALL_TAKE ? 1 : (int)takes[i]);
             const int claim = sel >= 0 && tk ? sel : -1, was = prev >= 0 && tk ? prev : -1;
             changed |= claim != was || prev == -2;
             if (r >= 0) selr[r] = sel; else match_q[i] = sel;
@@ -588,6 +628,29 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
     __syncthreads();
     for (int j = tid; j < n; j += RES_T) host_kp[j] = match_kp[j];
     if (tid == 0) { host_nm[0] = s_nm - removed; dev_nm[0] = s_nm - removed; }
+}
+__global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restrict__ ent, const unsigned *__restrict__ top,
+                                                       const int *__restrict__ lbeg, const int *__restrict__ lend, int nq, int ns,
+                                                       const uint8_t *__restrict__ takes, int th, float nnratio, int accept_mode,
+                                                       const float *__restrict__ qangle, const float *__restrict__ kangle,
+                                                       const int *__restrict__ perm, int check, int *__restrict__ match_q,
+                                                       int *__restrict__ match_kp, int n, const int *__restrict__ flags, int gen,
+                                                       int *__restrict__ host_q, int *__restrict__ host_kp, int *__restrict__ host_nm,
+                                                       int *__restrict__ dev_nm)
+{
+    extern __shared__ __align__(16) int sm[];
+    resolve_par<false>(sm, ent, top, lbeg, lend, nq, ns, takes, th, nnratio, accept_mode, qangle, kangle, perm, check, match_q, match_kp, n,
+                       flags, gen, host_q, host_kp, host_nm, dev_nm);
+}
+// One 1024-thread workgroup PER SEARCH of a batch of BoW searches: workgroup b resolves the search of record b, on its own LDS
+// (the launch asks for the dynamic LDS of the batch's largest ns; a workgroup lays out its own ns).  Workgroups never wait for
+// each other; one whose chains exceed RES_MAXIT says so in ITS result row and touches no other.
+__global__ __launch_bounds__(RES_T) void k_resolve_par_pairs(const BowPairDev *__restrict__ recs, int th, float nnratio, int check, int gen)
+{
+    extern __shared__ __align__(16) int sm[];
+    const BowPairDev &p = recs[blockIdx.x];
+    resolve_par<true>(sm, p.ent, p.top, p.off, p.off + 1, p.nq, p.ns, nullptr, th, nnratio, ACCEPT_RATIO, p.qang, p.kangle, p.perm, check,
+                      p.match_q, p.match_kp, p.n, p.dev_nm, gen, p.host_q, p.host_kp, p.host_nm, p.dev_nm);
 }
 
 // SearchForInitialization's loop (ORBmatcher.cc:626-696) as a parallel fixed point.  What couples its queries is
@@ -981,6 +1044,7 @@ __global__ __launch_bounds__(MT) void k_sim3_agree(const int *__restrict__ best1
 
 std::atomic<int> g_last_iterations{0};    // iterations of the last k_resolve_par (-1: it gave up and k_resolve ran)
 std::atomic<int> g_force_sequential{0};   // orbm_debug_force_sequential_resolver: tests run both resolvers
+std::atomic<int> g_last_bow_pairs_waits{0};   // host waits of the last orbm_frame_search_by_bow_pairs
 
 // A list of map points as the whole-function searches take it (orbm_points), staged with a call, and the prefix kernel that
 // turns it into window queries on the device.
@@ -1060,6 +1124,8 @@ struct SeqSearch {
     int *nmatches = nullptr;
     WinQuery *queries_out = nullptr;
     SearchChain *chain = nullptr;           // work appended behind the resolver, in front of the wait (mode 0 on a prefix, one segment)
+    bool sequential = false;                // start on the sequential resolver (a search whose fixed point is known not to settle)
+    int *waits = nullptr;                   // optional: counts the call's host waits
     bool windows() const { return queries || prefix; }
 };
 
@@ -1275,7 +1341,7 @@ void seq_collect(const SeqSearch &r, const Workspace &w, const SeqLayout &L, con
     if (L.tp_bytes) memcpy(r.prefix->proj_host, L.tp_pin, sizeof(orbm_projected_point) * (size_t)nq);
 }
 
-// The LDS limits of the four resolvers (the largest request each can make; the fixed-point kernels also have static LDS), raised
+// The LDS limits of the five resolvers (the largest request each can make; the fixed-point kernels also have static LDS), raised
 // once per process whichever thread calls first.  A failure stays and fails every call.
 int resolver_lds_limits()
 {
@@ -1284,6 +1350,7 @@ int resolver_lds_limits()
         if (!e) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (!e) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_par), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
         if (!e) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_init_par), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+        if (!e) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_par_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
         return e;
     }();
     ORBX_HIP(err);
@@ -1310,7 +1377,7 @@ int run_sequential(const SeqSearch &r)
     p.win_stride = r.mode == 1 ? 1024 : 256;
     p.ent_need = r.lists.off ? (size_t)r.lists.off[nq] : (size_t)nq * p.win_stride;
     p.init_c = ns ? std::min(7, (144 * 1024 / 4) / ns - 3) : 7;
-    p.sequential = g_force_sequential.load(std::memory_order_relaxed) != 0 || (r.mode == 1 && p.init_c < 2);
+    p.sequential = r.sequential || g_force_sequential.load(std::memory_order_relaxed) != 0 || (r.mode == 1 && p.init_c < 2);
 
     WorkspaceLease lease;
     Workspace &w = *lease.w;
@@ -1331,6 +1398,7 @@ int run_sequential(const SeqSearch &r)
         }
         ORBX_HIP(hipStreamSynchronize(w.st));
         if (r.chain) r.chain->waits++;
+        if (r.waits) ++*r.waits;
         if (ns) {
             if (r.windows() && !p.exact && *L.res<int>(w, L.o_nm + sizeof(int)) == p.gen) { p.exact = true; continue; }
             if (!p.sequential) {
@@ -1552,6 +1620,127 @@ void bow_lists(const int32_t *nodes1, const int32_t *off1, const int32_t *items1
     });
 }
 
+// The arguments of one BoW search over two resident frames, as orbm_frame_search_by_bow and every pair of
+// orbm_frame_search_by_bow_pairs are checked.
+int bow_frames_check(const orbm_frame *frame1, const int32_t *nodes1, const int32_t *off1, const int32_t *items1, int nn1, const uint8_t *valid1,
+                     const orbm_frame *frame2, const int32_t *nodes2, const int32_t *off2, const int32_t *items2, int nn2, const int32_t *match12)
+{
+    if (!frame1 || !frame2 || nn1 < 0 || nn2 < 0 || (frame1->n && (!match12 || !valid1)) || (nn1 && (!nodes1 || !off1 || !items1)) ||
+        (nn2 && (!nodes2 || !off2 || !items2)))
+        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (bow_check_items(off1, items1, nn1, frame1->n) || bow_check_items(off2, items2, nn2, frame2->n)) ORBX_FAIL(ORBX_ERR_ARG, "feature index out of range");
+    return ORBX_OK;
+}
+
+// The match rows from a search's results: every accepted query blocks its candidate, so slot mq[i] still names i unless rejected.
+void bow_rows(const BowLists &L, const int32_t *mq, const int32_t *mk, int32_t *match12, int32_t *match21)
+{
+    for (size_t i = 0; i < L.qidx.size(); ++i)
+        if (mq[i] >= 0 && mk[mq[i]] == (int32_t)i) { match12[L.qidx[i]] = mq[i]; if (match21) match21[mq[i]] = L.qidx[i]; }
+}
+
+// One search over two resident frames whose lists hold a query, by run_sequential (rows preset by the caller).
+int bow_frames_run(const orbm_frame *frame1, const orbm_frame *frame2, const BowLists &L, int th, int strict_th, float nnratio,
+                   int check_orientation, bool sequential, int32_t *match12, int32_t *match21, int *nmatches, int *waits = nullptr)
+{
+    const int nq = (int)L.qidx.size(), n2 = frame2->n;
+    std::vector<int32_t> qsrc(nq), mk(n2), mq(nq);
+    for (int i = 0; i < nq; ++i) qsrc[i] = frame1->inv_host[L.qidx[i]];
+    FrameSrc fs(frame2, true);
+    SeqSearch r;
+    r.lists = L.lists(); r.q.frame = frame1; r.q.pos = qsrc.data(); r.nq = nq;
+    r.fs = &fs; r.n = n2;
+    r.th = strict_th ? th - 1 : th; r.nnratio = nnratio; r.accept_mode = ACCEPT_RATIO; r.check = check_orientation;
+    r.match_kp = mk.data(); r.match_q = mq.data(); r.nmatches = nmatches; r.sequential = sequential; r.waits = waits;
+    const int rc = run_sequential(r);
+    if (rc != ORBX_OK) return rc;
+    bow_rows(L, mq.data(), mk.data(), match12, match21);
+    return ORBX_OK;
+}
+
+// ---- orbm_frame_search_by_bow_pairs: K searches, one lease, one staged upload, one launch per phase, one host wait.
+// The workspace of the batch: every search that has a query ("active") gets its regions behind each other.
+struct BowBatchSlot {
+    int pair = 0;                       // index in the caller's array
+    BowLists L;
+    std::vector<int32_t> qsrc;
+    size_t o_qmap = 0, o_off = 0, o_cbeg = 0, o_cand = 0;       // staged
+    size_t o_top = 0, o_qang = 0, o_mq = 0, o_mk = 0, o_nm = 0; // device only
+    size_t o_hq = 0, o_hk = 0, o_hnm = 0;                       // result block (pinned: offset - o_res)
+    size_t ent0 = 0;
+};
+
+int bow_pairs_launch(const orbm_bow_pair *pairs, std::vector<BowBatchSlot> &act, int th, int strict_th, float nnratio, int check_orientation,
+                     int32_t *nmatches, std::vector<int> &unsettled, int &iterations, int &waits)
+{
+    WorkspaceLease lease;
+    Workspace &w = *lease.w;
+    if (const int rc = resolver_lds_limits()) return rc;
+    w.used = 0;
+    size_t nent = 0;
+    int max_nq = 0, max_ns = 0;
+    for (BowBatchSlot &s : act) {
+        const size_t nq = s.L.qidx.size(), nc = s.L.cand.size();
+        s.o_qmap = w.carve(sizeof(int) * nq); s.o_off = w.carve(sizeof(int) * (nq + 1)); s.o_cbeg = w.carve(sizeof(int) * nq);
+        s.o_cand = w.carve(sizeof(int) * (nc ? nc : 1));
+        s.ent0 = nent; nent += ((size_t)s.L.cand_off[nq] + 63) & ~(size_t)63;
+        max_nq = std::max(max_nq, (int)nq); max_ns = std::max(max_ns, pairs[s.pair].frame2->n);
+    }
+    const size_t o_rec = w.carve(sizeof(BowPairDev) * act.size());
+    const size_t staged = w.used;
+    for (BowBatchSlot &s : act) {
+        const size_t nq = s.L.qidx.size(), n2 = (size_t)pairs[s.pair].frame2->n;
+        s.o_top = w.carve(sizeof(unsigned) * TOPK * nq); s.o_qang = w.carve(sizeof(float) * nq);
+        s.o_mq = w.carve(sizeof(int) * nq); s.o_mk = w.carve(sizeof(int) * n2); s.o_nm = w.carve(4 * sizeof(int));
+    }
+    const size_t o_res = w.used;
+    for (BowBatchSlot &s : act) {
+        const size_t nq = s.L.qidx.size(), n2 = (size_t)pairs[s.pair].frame2->n;
+        s.o_hq = w.carve(sizeof(int) * nq); s.o_hk = w.carve(sizeof(int) * n2); s.o_hnm = w.carve(4 * sizeof(int));
+    }
+    const size_t res_bytes = w.used - o_res;
+    if (w.reserve(o_res + res_bytes, std::max(staged, res_bytes))) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
+    if (w.reserve_entries(nent)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
+    const int gen = (int)(w.gen = (w.gen % 0x7ffffffe) + 1);
+    BowPairDev *rec = w.h<BowPairDev>(o_rec);
+    for (size_t a = 0; a < act.size(); ++a) {
+        const BowBatchSlot &s = act[a];
+        const orbm_frame *f1 = pairs[s.pair].frame1, *f2 = pairs[s.pair].frame2;
+        const size_t nq = s.L.qidx.size();
+        memcpy(w.h<char>(s.o_qmap), s.qsrc.data(), sizeof(int) * nq);
+        memcpy(w.h<char>(s.o_off), s.L.cand_off.data(), sizeof(int) * (nq + 1));
+        memcpy(w.h<char>(s.o_cbeg), s.L.cand_beg.data(), sizeof(int) * nq);
+        if (!s.L.cand.empty()) memcpy(w.h<char>(s.o_cand), s.L.cand.data(), sizeof(int) * s.L.cand.size());
+        BowPairDev &d = rec[a];
+        d.A = f1->desc; d.B = f2->desc; d.qang_src = f1->angle; d.kangle = f2->angle; d.perm = f2->perm;
+        d.qmap = w.d<int>(s.o_qmap); d.off = w.d<int>(s.o_off); d.cbeg = w.d<int>(s.o_cbeg); d.cand = w.d<int>(s.o_cand);
+        d.ent = w.ent + s.ent0; d.top = w.d<unsigned>(s.o_top); d.qang = w.d<float>(s.o_qang);
+        d.match_q = w.d<int>(s.o_mq); d.match_kp = w.d<int>(s.o_mk); d.dev_nm = w.d<int>(s.o_nm);
+        d.host_q = reinterpret_cast<int *>(w.pin + (s.o_hq - o_res)); d.host_kp = reinterpret_cast<int *>(w.pin + (s.o_hk - o_res));
+        d.host_nm = reinterpret_cast<int *>(w.pin + (s.o_hnm - o_res));
+        d.nq = (int)nq; d.ns = f2->n; d.n = f2->n; d.reserved = 0;
+    }
+    hipStream_t st = w.st;
+    ORBX_HIP(orbx::stage_in(w.dev, w.pin, staged, st));
+    const BowPairDev *drec = w.d<BowPairDev>(o_rec);
+    hipLaunchKernelGGL(k_list_fill_pairs, dim3((max_nq + MT / 64 - 1) / (MT / 64), (unsigned)act.size()), dim3(MT), 0, st, drec);
+    hipLaunchKernelGGL(k_resolve_par_pairs, dim3((unsigned)act.size()), dim3(RES_T), sizeof(int) * 4 * (size_t)max_ns, st, drec,
+                       strict_th ? th - 1 : th, nnratio, check_orientation, gen);
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipStreamSynchronize(st));
+    ++waits;
+    for (const BowBatchSlot &s : act) {
+        const orbm_bow_pair &p = pairs[s.pair];
+        const int *hq = reinterpret_cast<const int *>(w.pin + (s.o_hq - o_res)), *hk = reinterpret_cast<const int *>(w.pin + (s.o_hk - o_res)),
+                  *hnm = reinterpret_cast<const int *>(w.pin + (s.o_hnm - o_res));
+        if (hnm[2] != gen) { unsettled.push_back((int)(&s - act.data())); iterations = -1; continue; }
+        if (iterations >= 0) iterations = std::max(iterations, hnm[3]);
+        bow_rows(s.L, hq, hk, p.match12, p.match21);
+        nmatches[s.pair] = hnm[0];
+    }
+    return ORBX_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1600,33 +1789,77 @@ int orbm_frame_search_by_bow(const orbm_frame *frame1, const int32_t *nodes1, co
                              const int32_t *items2, int nn2, const uint8_t *valid2, int th, int strict_th, float nnratio,
                              int check_orientation, int32_t *match12, int32_t *match21, int *nmatches)
 {
-    if (!frame1 || !frame2 || nn1 < 0 || nn2 < 0 || (frame1->n && (!match12 || !valid1)) || (nn1 && (!nodes1 || !off1 || !items1)) ||
-        (nn2 && (!nodes2 || !off2 || !items2)) || !nmatches)
-        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (!nmatches) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (const int rc = bow_frames_check(frame1, nodes1, off1, items1, nn1, valid1, frame2, nodes2, off2, items2, nn2, match12)) return rc;
     const int n1 = frame1->n, n2 = frame2->n;
-    if (bow_check_items(off1, items1, nn1, n1) || bow_check_items(off2, items2, nn2, n2)) ORBX_FAIL(ORBX_ERR_ARG, "feature index out of range");
     ORBX_NEED_DEVICE();
     for (int i = 0; i < n1; ++i) match12[i] = -1;
     if (match21) for (int j = 0; j < n2; ++j) match21[j] = -1;
     *nmatches = 0;
     BowLists L;
     bow_lists(nodes1, off1, items1, nn1, valid1, nodes2, off2, items2, nn2, valid2, n2, frame2->inv_host.data(), L);
-    const int nq = (int)L.qidx.size();
-    if (nq == 0 || n2 == 0) return ORBX_OK;
-    std::vector<int32_t> qsrc(nq), mk(n2), mq(nq);
-    for (int i = 0; i < nq; ++i) qsrc[i] = frame1->inv_host[L.qidx[i]];
-    FrameSrc fs(frame2, true);
-    SeqSearch r;
-    r.lists = L.lists(); r.q.frame = frame1; r.q.pos = qsrc.data(); r.nq = nq;
-    r.fs = &fs; r.n = n2;
-    r.th = strict_th ? th - 1 : th; r.nnratio = nnratio; r.accept_mode = ACCEPT_RATIO; r.check = check_orientation;
-    r.match_kp = mk.data(); r.match_q = mq.data(); r.nmatches = nmatches;
-    const int rc = run_sequential(r);
-    if (rc != ORBX_OK) return rc;
-    for (int i = 0; i < nq; ++i)
-        if (mq[i] >= 0 && mk[mq[i]] == i) { match12[L.qidx[i]] = mq[i]; if (match21) match21[mq[i]] = L.qidx[i]; }
+    if (L.qidx.empty() || n2 == 0) return ORBX_OK;
+    return bow_frames_run(frame1, frame2, L, th, strict_th, nnratio, check_orientation, false, match12, match21, nmatches);
+}
+
+int orbm_frame_search_by_bow_pairs(const orbm_bow_pair *pairs, int K, int th, int strict_th, float nnratio, int check_orientation,
+                                   int32_t *nmatches)
+{
+    if (K < 0 || (K && (!pairs || !nmatches))) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (K > 64) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "at most 64 pairs per call");
+    for (int k = 0; k < K; ++k) {
+        const orbm_bow_pair &p = pairs[k];
+        if (const int rc = bow_frames_check(p.frame1, p.nodes1, p.off1, p.items1, p.nn1, p.valid1, p.frame2, p.nodes2, p.off2, p.items2, p.nn2,
+                                            p.match12))
+            return rc;
+        if (p.frame2->n > SEQ_MAXN) ORBX_FAIL(ORBX_ERR_CAPACITY, "frame too large for the resolver");
+    }
+    ORBX_NEED_DEVICE();
+    g_last_bow_pairs_waits.store(0, std::memory_order_relaxed);
+    std::vector<BowBatchSlot> act;
+    act.reserve((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        const orbm_bow_pair &p = pairs[k];
+        const int n1 = p.frame1->n, n2 = p.frame2->n;
+        for (int i = 0; i < n1; ++i) p.match12[i] = -1;
+        if (p.match21) for (int j = 0; j < n2; ++j) p.match21[j] = -1;
+        nmatches[k] = 0;
+        act.emplace_back();
+        BowBatchSlot &s = act.back();
+        s.pair = k;
+        bow_lists(p.nodes1, p.off1, p.items1, p.nn1, p.valid1, p.nodes2, p.off2, p.items2, p.nn2, p.valid2, n2, p.frame2->inv_host.data(), s.L);
+        if (s.L.qidx.empty() || n2 == 0) { act.pop_back(); continue; }     // no query: the -1 rows stand, the pair takes no part in the launch
+        s.qsrc.resize(s.L.qidx.size());
+        for (size_t i = 0; i < s.qsrc.size(); ++i) s.qsrc[i] = p.frame1->inv_host[s.L.qidx[i]];
+    }
+    if (act.empty()) return ORBX_OK;
+    int waits = 0;              // (counted here and published once: concurrent calls do not add to each other's count)
+    std::vector<int> again;     // positions in act of the pairs that go through the single-pair path on the sequential resolver
+    if (g_force_sequential.load(std::memory_order_relaxed) != 0) {
+        for (size_t a = 0; a < act.size(); ++a) again.push_back((int)a);
+    } else if (act.size() == 1) {   // a batch of one search IS the single call (its record costs the two kernels a dependent load each)
+        const orbm_bow_pair &p = pairs[act[0].pair];
+        const int rc = bow_frames_run(p.frame1, p.frame2, act[0].L, th, strict_th, nnratio, check_orientation, false, p.match12, p.match21,
+                                      &nmatches[act[0].pair], &waits);
+        g_last_bow_pairs_waits.store(waits, std::memory_order_relaxed);
+        return rc;
+    } else {
+        int iterations = 0;
+        if (const int rc = bow_pairs_launch(pairs, act, th, strict_th, nnratio, check_orientation, nmatches, again, iterations, waits)) return rc;
+        g_last_iterations.store(iterations, std::memory_order_relaxed);
+        g_last_bow_pairs_waits.store(waits, std::memory_order_relaxed);
+    }
+    for (const int a : again) {     // the other pairs' results stand; each of these costs one more wait
+        const orbm_bow_pair &p = pairs[act[a].pair];
+        if (const int rc = bow_frames_run(p.frame1, p.frame2, act[a].L, th, strict_th, nnratio, check_orientation, true, p.match12, p.match21,
+                                          &nmatches[act[a].pair]))
+            return rc;
+        g_last_bow_pairs_waits.store(++waits, std::memory_order_relaxed);
+    }
     return ORBX_OK;
 }
+
+int orbm_debug_last_bow_pairs_waits(void) { return g_last_bow_pairs_waits.load(std::memory_order_relaxed); }
 
 // ------------------------------------------------------- the projection searches as whole functions, on resident frames
 

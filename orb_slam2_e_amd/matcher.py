@@ -464,6 +464,39 @@ class ORBmatcher:
                                                self.mfNNratio, int(self.mbCheckOrientation), _p(m12), _p(m21), C.byref(nm)))
         return m12[:frame1.n], m21[:frame2.n], nm.value
 
+    MAX_BOW_PAIRS = 64
+
+    def frame_search_by_bow_pairs(self, pairs, kf_kf=False):
+        """K searches of frame_search_by_bow in one call (orbm_frame_search_by_bow_pairs): pairs = a sequence of
+        (frame1, fv1, valid1, frame2, fv2, valid2), each as that method takes them (valid2 is used only with kf_kf); a frame may
+        stand in any number of pairs.  Returns a list of (match12, match21, nmatches), one per pair: what the single call gives."""
+        i32 = lambda a: np.ascontiguousarray(a, np.int32)
+        K = len(pairs)
+        arr = (_CBowPair * max(K, 1))()
+        keep, rows = [], []
+        for c, (frame1, fv1, valid1, frame2, fv2, valid2) in zip(arr, pairs):
+            nodes1, off1, it1 = [i32(a) for a in fv1]; nodes2, off2, it2 = [i32(a) for a in fv2]
+            v1 = np.ascontiguousarray(valid1, np.uint8)
+            v2 = np.ascontiguousarray(valid2, np.uint8) if kf_kf else None
+            m12 = np.zeros(max(frame1.n, 1), np.int32); m21 = np.zeros(max(frame2.n, 1), np.int32)
+            keep.append((nodes1, off1, it1, v1, nodes2, off2, it2, v2))
+            rows.append((m12[:frame1.n], m21[:frame2.n]))
+            a = lambda x: _p(x).value if x is not None else None
+            h = lambda f: f._h.value if isinstance(f._h, C.c_void_p) else f._h
+            c.frame1, c.nodes1, c.off1, c.items1, c.nn1, c.valid1 = h(frame1), a(nodes1), a(off1), a(it1), len(nodes1), a(v1)
+            c.frame2, c.nodes2, c.off2, c.items2, c.nn2, c.valid2 = h(frame2), a(nodes2), a(off2), a(it2), len(nodes2), a(v2)
+            c.match12, c.match21 = a(m12), a(m21)
+        nm = np.zeros(max(K, 1), np.int32)
+        check(self._L.orbm_frame_search_by_bow_pairs(arr if K else None, K, self.TH_LOW, int(kf_kf), self.mfNNratio,
+                                                     int(self.mbCheckOrientation), _p(nm)))
+        return [(m12, m21, int(nm[k])) for k, (m12, m21) in enumerate(rows)]
+
+    @staticmethod
+    def last_bow_pairs_waits():
+        """orbm_debug_last_bow_pairs_waits: host waits of the last frame_search_by_bow_pairs call of this process (0: no pair had a
+        query; 1 on the common path; one more per pair repeated on the sequential resolver)."""
+        return lib().orbm_debug_last_bow_pairs_waits()
+
     def frame_search_for_triangulation(self, kf1, fv1, has_mp1, kf2, fv2, has_mp2, F12, ex, ey, scale_factors2, level_sigma2,
                                        bOnlyStereo=False):
         """SearchForTriangulation on two resident keyframes (orbm_frame_search_for_triangulation).
@@ -626,6 +659,13 @@ class _CPoints(C.Structure):
 class _CView(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float),
                 ("log_scale_factor", C.c_float), ("nlevels", C.c_int32), ("scale_factors", C.c_void_p)]
+
+
+class _CBowPair(C.Structure):
+    """orbm_bow_pair"""
+    _fields_ = [("frame1", C.c_void_p), ("nodes1", C.c_void_p), ("off1", C.c_void_p), ("items1", C.c_void_p), ("nn1", C.c_int32),
+                ("valid1", C.c_void_p), ("frame2", C.c_void_p), ("nodes2", C.c_void_p), ("off2", C.c_void_p), ("items2", C.c_void_p),
+                ("nn2", C.c_int32), ("valid2", C.c_void_p), ("match12", C.c_void_p), ("match21", C.c_void_p)]
 
 
 class _CTriangKeyFrame(C.Structure):
