@@ -34,7 +34,8 @@ const char *orbx_last_error(void);
 /* ABI version of this header (major*100+minor).  136 (additions only): the pose-only optimisation (orbm_pose_*).  Added since
  * without a new number (additions only): orbm_create_new_map_points, orbm_debug_last_create_points_waits; orbm_sim3_hypotheses,
  * orbm_debug_last_sim3_waits; orbm_optimize_sim3, orbm_debug_last_sim3_opt_waits; orbm_map_create / _destroy / _size,
- * orbm_search_by_projection_map_poses, orbm_frame_search_by_projection_map_poses, orbm_debug_last_map_poses_waits. */
+ * orbm_search_by_projection_map_poses, orbm_frame_search_by_projection_map_poses, orbm_debug_last_map_poses_waits;
+ * orbm_init_find_models, orbm_init_check_rt, orbm_init_reconstruct_f, orbm_debug_last_init_waits, orbm_debug_init_svd. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -654,6 +655,65 @@ int orbm_optimize_sim3(const orbm_sim3_opt_problem *problems, int P, const float
 /* Host waits (stream synchronisations) of the last orbm_optimize_sim3 call of this process: 1 when it launched, 0 when it returned
  * before the launch. */
 int orbm_debug_last_sim3_opt_waits(void);
+
+/* ------------------------------------------- Initializer: every H / F hypothesis of a monocular initialisation in one call
+ * Initializer::Initialize (src/Initializer.cc:44-121) draws the 8-point sets of all iterations first (:77-97); no hypothesis reads
+ * another's result, and FindHomography (:124-172) / FindFundamental (:175-223) return a fold over the per-hypothesis scores.
+ * orbm_init_find_models evaluates all 2 H hypotheses in ONE launch and runs both folds; orbm_init_check_rt is CheckRT (:798-907)
+ * for up to 8 motions in ONE launch; orbm_init_reconstruct_f is ReconstructF (:470-570) around one orbm_init_check_rt call.
+ * ReconstructH (:572-732) is NOT here: this fork takes it only at RH > 0.99 (:115), the host classes report that case as its
+ * own status and the integration shell runs the reference's own ReconstructH there (its CheckRT calls go one motion at a time).
+ * The OpenCV arithmetic (cv::SVDecomp, cv::invert, the 3 x 3 products) is restated from OpenCV 3.4 and unpinned.
+ *
+ * Shared arguments: keys1 [n1][2] / keys2 [n2][2] = mvKeysUn[i].pt of the reference and the current frame (ALL keypoints: Normalize
+ * sums over every one, :749-795); matches [n][2] = mvMatches12 (index into keys1, index into keys2) in that order.  n <= 8,192
+ * (beyond: ORBX_ERR_UNSUPPORTED); a match index outside its frame: ORBX_ERR_ARG. */
+typedef struct orbm_init_models {
+    float H21[9], F21[9];              /* the winning matrices, row-major (zeros when none won) */
+    float SH, SF;                      /* their scores (0 when none won) */
+    int32_t itH, itF;                  /* the winning iterations; -1 = no hypothesis scored above 0 */
+} orbm_init_models;
+
+typedef struct orbm_init_reconstruction {
+    float R21[9], t21[3];              /* the motion, when found */
+    float parallax[4];                 /* parallax1 .. parallax4 of the four CheckRT calls, (R1,t) (R2,t) (R1,-t) (R2,-t) */
+    int32_t ngood[4];                  /* nGood1 .. nGood4 */
+    int32_t found, best, N, max_good, nsimilar;   /* the return value; the motion the == cascade picked (-1: rejected before);
+                                                     the inlier count N; maxGood; nsimilar */
+} orbm_init_reconstruction;
+
+/* sets [H][8] = mvSets (indices into 0..n-1), sigma = mSigma.  H <= 1,024 (beyond: ORBX_ERR_UNSUPPORTED).  ORBX_ERR_ARG before the
+ * launch: a set index outside [0, n) or repeated within a set, n < 8 with H > 0, sigma <= 0.  H = 0: ORBX_OK, nothing is launched.
+ *   out          the folds of :148-171 / :199-222: the first hypothesis whose score is > every earlier one, starting from 0.  A NaN
+ *                score (a singular H21i inverts to zeros) and a score of exactly 0 never win.
+ *   mask_h / _f  (void *: the words are uint64_t) [(n + 63) / 64]: bit i % 64 of word i / 64 = vbMatchesInliersH / F[i]; bits past n
+ *                are 0.  No H winner: n falses, SH = 0, itH = -1.  No F winner: the reference leaves vbMatchesInliersF EMPTY (:178
+ *                reads N from the size of the output vector) and F21 an empty cv::Mat, and ReconstructF would throw; here itF = -1,
+ *                SF = 0 and the mask is zeros.
+ *   hyp_*        per hypothesis, the H model's H first, then the F model's: matrices [2 H][9], scores [2 H], masks
+ *                [2 H][(n + 63) / 64] uint64_t.  Each may be NULL. */
+int orbm_init_find_models(const float *keys1, int n1, const float *keys2, int n2, const int32_t *matches, int n,
+                          const int32_t *sets, int H, float sigma, orbm_init_models *out, void *mask_h, void *mask_f,
+                          float *hyp_matrices, float *hyp_scores, void *hyp_masks);
+/* CheckRT for M <= 8 motions (beyond: ORBX_ERR_UNSUPPORTED): R [M][9], t [M][3], K 3 x 3 row-major, inliers [n] bytes =
+ * vbMatchesInliers.  M = 0 launches nothing.  Per motion:
+ *   good [M][n1] bytes = vbGood, P3D [M][n1][3] = vP3D (entries the reference never writes are 0; a counted match with
+ *   cosParallax >= 0.9998 has its P3D written and good 0); counted [M][n], cos_parallax [M][n] per match (either may be NULL);
+ *   ngood [M] = the return value; parallax [M] (0 with ngood = 0). */
+int orbm_init_check_rt(const float *keys1, int n1, const float *keys2, int n2, const int32_t *matches, int n,
+                       const uint8_t *inliers, const float *K, const float *R, const float *t, int M, float th2, uint8_t *good,
+                       float *P3D, uint8_t *counted, float *cos_parallax, int32_t *ngood, float *parallax);
+/* ReconstructF(vbMatchesInliers, F21, K, R21, t21, vP3D, vbTriangulated, minParallax, minTriangulated): P3D [n1][3] and
+ * triangulated [n1] are written when out->found, else zeros. */
+int orbm_init_reconstruct_f(const float *keys1, int n1, const float *keys2, int n2, const int32_t *matches, int n,
+                            const uint8_t *inliers, const float *F21, const float *K, float sigma, float min_parallax,
+                            int min_triangulated, orbm_init_reconstruction *out, float *P3D, uint8_t *triangulated);
+/* Host waits (stream synchronisations) of the last orbm_init_* call of this process: 1 when it launched, 0 when it returned
+ * before the launch. */
+int orbm_debug_last_init_waits(void);
+/* Test aid, host only: the library's restatement of cv::SVDecomp (csrc/orbm_svd.h) on one matrix.  shape 0: A 16 x 9 -> vt [9] =
+ * vt.row(8); 1: A 8 x 9 -> vt [9] = vt.row(8) (FULL_UV); 2: A 3 x 3 -> w [3], u [9], vt [9]; 3: A 4 x 4 -> vt [4] = vt.row(3). */
+int orbm_debug_init_svd(int shape, const float *A, float *w, float *u, float *vt);
 
 /* ------------------------------------------- the whole-map relocalisation search under P poses in one call
  * PnPsolver::iterate(Frame&, .., Map*) (src/PnPsolver.cc:267-646) calls SearchByProjection(F, pMap, Rcw, tcw, ..) over and over

@@ -1607,5 +1607,121 @@ inline int OptimizeSim3(const std::vector<Sim3OptProblem> &problems, const std::
     return ORBX_OK;
 }
 
+// Initializer (include/Initializer.h, src/Initializer.cc) over orbm_init_find_models / orbm_init_reconstruct_f.  The constructor takes
+// what the reference's takes of the reference frame -- mvKeysUn[i].pt of every keypoint, K (3 x 3 row-major), sigma and the iteration
+// count -- and Initialize what it takes of the current frame plus a source of draws: a callback int(int lo, int hi) (inclusive, as
+// DUtils::Random::RandomInt after SeedRandOnce(0)), called in the reference's order (:82-97), or pre-drawn sets [iterations][8].
+// FindHomography and FindFundamental are one launch, ReconstructF's four CheckRT calls one more.
+// Two differences to the reference.  ReconstructH (:572-732) is not built: this fork takes it only at RH > 0.99 (:115), and
+// Initialize then returns WANTS_RECONSTRUCT_H with H21() and inliersH() for the caller's own ReconstructH.  When no F hypothesis
+// scores above 0 the reference leaves vbMatchesInliersF empty and F21 an empty cv::Mat, and ReconstructF throws; here that is
+// NO_FUNDAMENTAL.
+class Initializer {
+public:
+    enum Status { NOT_INITIALIZED = 0, INITIALIZED = 1, WANTS_RECONSTRUCT_H = 2, NO_FUNDAMENTAL = 3, FAILED = -1 };   // FAILED: status() has the code
+    typedef int (*DrawFn)(int lo, int hi);
+
+    Initializer(std::vector<float> keys1, const float *K, float sigma = 1.0f, int iterations = 200)
+        : mvKeys1(std::move(keys1)), mSigma(sigma), mMaxIterations(iterations)
+    {
+        memcpy(mK, K, sizeof(mK));
+        memset(&mModels, 0, sizeof(mModels));
+        memset(&mRec, 0, sizeof(mRec));
+    }
+
+    // keys2 [n2][2]; vMatches12 [n1]: index into keys2 or -1.  R21 [9], t21 [3], vP3D [n1][3], vbTriangulated [n1].
+    Status Initialize(const std::vector<float> &keys2, const std::vector<int> &vMatches12, DrawFn draw, float *R21, float *t21,
+                      std::vector<float> &vP3D, std::vector<bool> &vbTriangulated)
+    {
+        return run(keys2, vMatches12, draw, nullptr, R21, t21, vP3D, vbTriangulated);
+    }
+    Status Initialize(const std::vector<float> &keys2, const std::vector<int> &vMatches12, const std::vector<int32_t> &sets, float *R21,
+                      float *t21, std::vector<float> &vP3D, std::vector<bool> &vbTriangulated)
+    {
+        return run(keys2, vMatches12, nullptr, &sets, R21, t21, vP3D, vbTriangulated);
+    }
+
+    int status() const { return mStatus; }                       // the library's code of the last Initialize
+    float RH() const { return mRH; }
+    const orbm_init_models &models() const { return mModels; }
+    const orbm_init_reconstruction &reconstruction() const { return mRec; }
+    const float *H21() const { return mModels.H21; }
+    const float *F21() const { return mModels.F21; }
+    const std::vector<int32_t> &matches12() const { return mvMatches12; }   // mvMatches12, [n][2]
+    const std::vector<int32_t> &sets() const { return mvSets; }             // mvSets, [iterations][8]
+    std::vector<bool> inliersH() const { return unpack(mMaskH); }
+    std::vector<bool> inliersF() const { return unpack(mMaskF); }
+
+private:
+    std::vector<bool> unpack(const std::vector<uint64_t> &mask) const
+    {
+        const size_t n = mvMatches12.size() / 2;
+        std::vector<bool> out(n, false);
+        for (size_t i = 0; i < n && i / 64 < mask.size(); ++i) out[i] = (mask[i / 64] >> (i % 64)) & 1;
+        return out;
+    }
+
+    Status run(const std::vector<float> &keys2, const std::vector<int> &vMatches12, DrawFn draw, const std::vector<int32_t> *sets, float *R21,
+               float *t21, std::vector<float> &vP3D, std::vector<bool> &vbTriangulated)
+    {
+        const int n1 = (int)(mvKeys1.size() / 2), n2 = (int)(keys2.size() / 2);
+        mvMatches12.clear();
+        for (size_t i = 0; i < vMatches12.size(); ++i)
+            if (vMatches12[i] >= 0) { mvMatches12.push_back((int32_t)i); mvMatches12.push_back(vMatches12[i]); }
+        const int N = (int)(mvMatches12.size() / 2), H = mMaxIterations;
+        vP3D.assign((size_t)3 * n1, 0.0f);
+        vbTriangulated.assign((size_t)n1, false);
+        for (int k = 0; k < 9; ++k) R21[k] = 0.0f;
+        for (int k = 0; k < 3; ++k) t21[k] = 0.0f;
+        mRH = std::numeric_limits<float>::quiet_NaN();
+        if (draw) {                                              // :77-97
+            if (N < 8 && H > 0) { mStatus = ORBX_ERR_ARG; return FAILED; }
+            mvSets.assign((size_t)8 * H, 0);
+            std::vector<int32_t> avail;
+            for (int it = 0; it < H; ++it) {
+                avail.resize((size_t)N);
+                for (int i = 0; i < N; ++i) avail[i] = i;
+                for (int j = 0; j < 8; ++j) {
+                    const int randi = draw(0, (int)avail.size() - 1);
+                    mvSets[8 * it + j] = avail[randi];
+                    avail[randi] = avail.back();
+                    avail.pop_back();
+                }
+            }
+        } else {
+            if ((int)(sets->size() / 8) < H) { mStatus = ORBX_ERR_ARG; return FAILED; }
+            mvSets.assign(sets->begin(), sets->begin() + (size_t)8 * H);
+        }
+        const size_t words = (size_t)(N + 63) / 64;
+        mMaskH.assign(words + 1, 0); mMaskF.assign(words + 1, 0);
+        mStatus = orbm_init_find_models(mvKeys1.data(), n1, keys2.data(), n2, mvMatches12.data(), N, mvSets.data(), H, mSigma, &mModels,
+                                        mMaskH.data(), mMaskF.data(), nullptr, nullptr, nullptr);
+        if (mStatus != ORBX_OK) return FAILED;
+        mRH = mModels.SH / (mModels.SH + mModels.SF);            // :112
+        if (mRH > 0.99) return WANTS_RECONSTRUCT_H;              // :115
+        if (mModels.itF < 0) return NO_FUNDAMENTAL;
+        const std::vector<bool> in = inliersF();
+        std::vector<uint8_t> inl(in.size() + 1, 0), tri((size_t)n1 + 1, 0);
+        for (size_t i = 0; i < in.size(); ++i) inl[i] = in[i];
+        mStatus = orbm_init_reconstruct_f(mvKeys1.data(), n1, keys2.data(), n2, mvMatches12.data(), N, inl.data(), mModels.F21, mK, mSigma, 0.95f,
+                                          60, &mRec, vP3D.data(), tri.data());
+        if (mStatus != ORBX_OK) return FAILED;
+        if (!mRec.found) return NOT_INITIALIZED;
+        for (int i = 0; i < n1; ++i) vbTriangulated[i] = tri[i] != 0;
+        memcpy(R21, mRec.R21, sizeof(mRec.R21));
+        memcpy(t21, mRec.t21, sizeof(mRec.t21));
+        return INITIALIZED;
+    }
+
+    std::vector<float> mvKeys1;
+    float mK[9], mSigma;
+    int mMaxIterations, mStatus = ORBX_OK;
+    float mRH = 0.0f;
+    std::vector<int32_t> mvMatches12, mvSets;
+    std::vector<uint64_t> mMaskH, mMaskF;
+    orbm_init_models mModels;
+    orbm_init_reconstruction mRec;
+};
+
 } // namespace orbslam_hip
 #endif // ORBSLAM_HIP_HPP
