@@ -35,7 +35,8 @@ const char *orbx_last_error(void);
  * without a new number (additions only): orbm_create_new_map_points, orbm_debug_last_create_points_waits; orbm_sim3_hypotheses,
  * orbm_debug_last_sim3_waits; orbm_optimize_sim3, orbm_debug_last_sim3_opt_waits; orbm_map_create / _destroy / _size,
  * orbm_search_by_projection_map_poses, orbm_frame_search_by_projection_map_poses, orbm_debug_last_map_poses_waits;
- * orbm_init_find_models, orbm_init_check_rt, orbm_init_reconstruct_f, orbm_debug_last_init_waits, orbm_debug_init_svd. */
+ * orbm_init_find_models, orbm_init_check_rt, orbm_init_reconstruct_f, orbm_debug_last_init_waits, orbm_debug_init_svd;
+ * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -523,6 +524,38 @@ int orbm_frame_search_by_bow_pairs(const orbm_bow_pair *pairs, int K, int th, in
 /* Host waits (stream synchronisations) of the last orbm_frame_search_by_bow_pairs of this process: 0 when no pair had a query, 1
  * on the common path, one more for every pair that was repeated on the sequential resolver. */
 int orbm_debug_last_bow_pairs_waits(void);
+
+/* ORBmatcher::Fuse against K target keyframes in one call: the device half (projection block src/ORBmatcher.cc:1053-1094, gated
+ * candidate loop :1092-1150; sim3 != 0: the Sim3 form, :1212-1277) of the loops LocalMapping::SearchInNeighbors
+ * (src/LocalMapping.cc:550-558) and LoopClosing::SearchAndFuse (src/LoopClosing.cc:587-613) run call by call over ONE list of m
+ * map points.  Row k of best / idx / projected ([K][m]) is exactly what orbm_project_points(sim3 ? ORBM_PROJECT_FUSE_SIM3 :
+ * ORBM_PROJECT_FUSE, ...) followed by orbm_frame_search_fuse(targets[k].frame, ...) return for target k alone, integer for integer
+ * and float bit for float bit; a rejected point has best 256, idx -1 and visible 0.  With sim3 set there is no reprojection gate
+ * (as inv_level_sigma2 = NULL in the single call) and inv_level_sigma2 may be NULL.  One pyramid (scale_factors,
+ * inv_level_sigma2, nlevels, log_scale_factor) and one th serve all targets.
+ * active ([K][m] bytes, or NULL = all ones): active[k][i] == 0 says the caller knows the loop skips this pair (a NULL entry, a bad
+ * point, a point already in keyframe k, a point in spAlreadyFound); its row entries are the presets 256, -1 and the rejected
+ * record (visible 0, level -1), and it does no work on the device.
+ * K = 0 .. 128, m = 0 .. 65,536, K * m <= 4,194,304 (beyond: ORBX_ERR_UNSUPPORTED).  K = 0, m = 0 or no active pair: ORBX_OK,
+ * nothing is launched, 0 waits.  Every target is checked as the single calls check theirs -- a frame, a finite pose, with the
+ * gate on every octave of the frame in [0, nlevels), nlevels 1 .. 16 -- and one that fails fails the whole call (ORBX_ERR_ARG)
+ * before anything is launched or written.  Frames are only read; the same frame may stand in several targets.  A launching call
+ * takes one lease, one staged upload, one launch and ONE host wait.  Re-entrant.
+ * The map update stays with the caller, target by target in list order; MapPoint::Replace recomputes the heir's descriptor, so
+ * the rows of later targets for such entries are refreshed by one more call (orbslam_hip.hpp: ORBmatcher::FuseKeyFrames). */
+typedef struct orbm_fuse_target {
+    const orbm_frame *frame;          /* resident keyframe (mvKeysUn, mvuRight, descriptors, grid) */
+    float Rcw[9], tcw[3], Ow[3];      /* as orbm_project_points takes them; Sim3 form: sRcw / s, t / s, -Rcw' tcw (:1188-1192) */
+    orbm_camera cam;                  /* fx .. cy, image bounds (KeyFrame::IsInImage), grid bounds */
+    float mbf;
+} orbm_fuse_target;
+int orbm_fuse_keyframes(const orbm_fuse_target *targets, int K, int sim3, const float *mp_pos, const float *mp_normal,
+                        const float *mp_min_distance, const float *mp_max_distance, const uint8_t *mp_desc, int m,
+                        const uint8_t *active /* [K][m] or NULL */, float th, float log_scale_factor, const float *scale_factors,
+                        const float *inv_level_sigma2, int nlevels, int32_t *best /* [K][m] */, int32_t *idx /* [K][m] */,
+                        orbm_projected_point *projected /* [K][m] or NULL */);
+/* Host waits (stream synchronisations) of the last orbm_fuse_keyframes of this process: 1 when it launched, else 0. */
+int orbm_debug_last_fuse_keyframes_waits(void);
 
 /* orbm_search_for_triangulation on two resident keyframes: a keypoint is "stereo" where the frame's right coordinate is >= 0
  * (mvuRight, as given to orbm_frame_create / taken from ComputeStereoMatches); the call uploads the feature-vector lists and the two

@@ -402,6 +402,157 @@ public:
         return nFused;
     }
 
+    // The loop `for pKFi in targets: matcher.Fuse(pKFi, vpMapPointMatches)` of LocalMapping::SearchInNeighbors
+    // (LocalMapping.cc:550-558) as a whole: ONE orbm_fuse_keyframes call for all K x m pairs, then fuseReplay target by target
+    // in list order.  MapPoint::Replace ends with ComputeDistinctiveDescriptors on the heir (MapPoint.cc:275), so a list
+    // entry's descriptor can change between two targets: after target k the rows of the LATER targets are computed again, in
+    // one more call, for the entries whose handle a replace named as the heir, that are not bad and whose map.descriptor(H)
+    // differs bytewise from the bytes their rows were computed with.  The result is the sequential loop's; host waits = 1 +
+    // refreshes (LastFuseKeyFramesWaits / LastFuseKeyFramesRefreshes).  One pyramid (targets[0].pose) serves all targets.
+    // `map`: what fuseReplay asks for, answered for the CURRENT target, plus void beginTarget(int k), void endTarget(int k,
+    // report) (report(int i): the caller replaced into list entry i; the plain form has nothing to report), const uint8_t
+    // *descriptor(H) (32 bytes) and, for the mask, bool inTarget(H, int k) (pMP->IsInKeyFrame(target k) now).  The mask is an
+    // optimisation only: the tail tests every skip again at its own time.  Handles must be usable as std::map keys.
+    struct FuseTargetView {
+        const orbm_frame *frame = nullptr;      // the keyframe, resident
+        PoseView pose;                          // Sim3 form: Rcw = sRcw / s, tcw = t / s, Ow = -Rcw' tcw (ORBmatcher.cc:1188-1192)
+    };
+    template <class MapOps>
+    std::vector<int> FuseKeyFrames(const std::vector<FuseTargetView> &targets, const MapPointArrays &mps, float th, MapOps &map)
+    {
+        DeviceFuseCandidates cand{this, &mps, th, false};
+        return fuseKeyFramesWith(cand, targets, mps, false, map);
+    }
+    // The loop of LoopClosing::SearchAndFuse (LoopClosing.cc:587-613) over the Sim3 form: beginTarget(k) takes the
+    // spAlreadyFound snapshot of target k, endTarget(k, report) runs the caller's Replace loop (:604-611) and reports every
+    // list index it replaced into; inTarget(H, k): H is among target k's map points now.
+    template <class MapOps>
+    std::vector<int> FuseKeyFramesSim3(const std::vector<FuseTargetView> &targets, const MapPointArrays &mps, float th, MapOps &map)
+    {
+        DeviceFuseCandidates cand{this, &mps, th, true};
+        return fuseKeyFramesWith(cand, targets, mps, true, map);
+    }
+    int LastFuseKeyFramesWaits() const { return mFuseKeyFramesWaits; }
+    int LastFuseKeyFramesRefreshes() const { return mFuseKeyFramesRefreshes; }
+
+    // The candidate stage of FuseKeyFrames on the device: rows [K][points.size()] for the list entries `points` with the
+    // descriptors `desc` (32 bytes each, in that order) and the mask `active`.  Returns the host waits of the call, -1 on error.
+    struct DeviceFuseCandidates {
+        ORBmatcher *self; const MapPointArrays *mps; float th; bool sim3;
+        int operator()(const FuseTargetView *targets, int K, const std::vector<int> &points, const uint8_t *desc, const uint8_t *active,
+                       int32_t *best, int32_t *idx, orbm_projected_point *proj) const
+        {
+            const int m = (int)points.size();
+            std::vector<orbm_fuse_target> t((size_t)K);
+            for (int k = 0; k < K; ++k) {
+                t[k].frame = targets[k].frame;
+                std::copy(targets[k].pose.Rcw, targets[k].pose.Rcw + 9, t[k].Rcw);
+                std::copy(targets[k].pose.tcw, targets[k].pose.tcw + 3, t[k].tcw);
+                std::copy(targets[k].pose.Ow, targets[k].pose.Ow + 3, t[k].Ow);
+                t[k].cam = targets[k].pose.cam; t[k].mbf = targets[k].pose.mbf;
+            }
+            std::vector<float> pos((size_t)3 * m), nrm((size_t)3 * m), mn(m), mx(m);
+            for (int j = 0; j < m; ++j) {
+                const int i = points[j];
+                std::copy(mps->pos + 3 * i, mps->pos + 3 * i + 3, &pos[(size_t)3 * j]);
+                std::copy(mps->normal + 3 * i, mps->normal + 3 * i + 3, &nrm[(size_t)3 * j]);
+                mn[j] = mps->mfMinDistance[i]; mx[j] = mps->mfMaxDistance[i];
+            }
+            const PoseView &p0 = targets[0].pose;
+            self->mStatus = orbm_fuse_keyframes(t.data(), K, sim3, pos.data(), nrm.data(), mn.data(), mx.data(), desc, m, active, th,
+                                                p0.mfLogScaleFactor, p0.mvScaleFactors, sim3 ? nullptr : p0.mvInvLevelSigma2,
+                                                p0.mnScaleLevels, best, idx, proj);
+            return self->mStatus == ORBX_OK ? orbm_debug_last_fuse_keyframes_waits() : -1;
+        }
+    };
+
+    // FuseKeyFrames / FuseKeyFramesSim3 over any candidate stage (the tests put a stub in the device's place).
+    template <class Candidates, class MapOps>
+    std::vector<int> fuseKeyFramesWith(Candidates &cand, const std::vector<FuseTargetView> &targets, const MapPointArrays &mps, bool sim3,
+                                       MapOps &map)
+    {
+        const int K = (int)targets.size(), m = mps.n;
+        mFuseKeyFramesWaits = 0; mFuseKeyFramesRefreshes = 0;
+        std::vector<int> nFused;
+        if (K == 0) return nFused;
+        typedef decltype(map.at(0)) H;
+        std::vector<uint8_t> desc(mps.descriptors, mps.descriptors + (size_t)32 * m);    // the bytes the rows were computed with
+        // mask from the map state at entry; handle -> list indices (the list holds duplicates and NULL entries)
+        std::vector<uint8_t> active((size_t)K * m, 0);
+        std::map<H, std::vector<int>> where;
+        std::vector<int> all(m);
+        for (int i = 0; i < m; ++i) {
+            all[i] = i;
+            H h = map.at(i);
+            if (map.null(h)) continue;
+            where[h].push_back(i);
+            if (map.isBad(h)) continue;
+            for (int k = 0; k < K; ++k) active[(size_t)k * m + i] = !map.inTarget(h, k);
+        }
+        std::vector<int32_t> best((size_t)K * m, 256), idx((size_t)K * m, -1);
+        std::vector<orbm_projected_point> proj((size_t)K * m);
+        int w = cand(targets.data(), K, all, desc.data(), active.data(), best.data(), idx.data(), proj.data());
+        if (w < 0) return nFused;
+        mFuseKeyFramesWaits += w;
+        std::vector<char> heir(m);
+        for (int k = 0; k < K; ++k) {
+            std::fill(heir.begin(), heir.end(), 0);
+            auto mark = [&](const H &h) {
+                auto it = where.find(h);
+                if (it != where.end()) for (int i : it->second) heir[i] = 1;
+            };
+            auto report = [&](int i) { if (i >= 0 && i < m && !map.null(map.at(i))) mark(map.at(i)); };
+            map.beginTarget(k);
+            FuseHeirLog<MapOps, decltype(mark)> tail{map, mark};
+            const std::vector<orbm_projected_point> prow(proj.begin() + (size_t)k * m, proj.begin() + (size_t)(k + 1) * m);
+            const std::vector<int32_t> brow(best.begin() + (size_t)k * m, best.begin() + (size_t)(k + 1) * m),
+                                       irow(idx.begin() + (size_t)k * m, idx.begin() + (size_t)(k + 1) * m);
+            nFused.push_back(sim3 ? fuseReplaySim3(prow, brow, irow, tail) : fuseReplay(prow, brow, irow, tail));
+            map.endTarget(k, report);
+            std::vector<int> dirty;
+            for (int i = 0; i < m; ++i) {
+                if (!heir[i]) continue;
+                H h = map.at(i);
+                if (map.isBad(h)) continue;
+                const uint8_t *d = map.descriptor(h);
+                if (!std::equal(d, d + 32, &desc[(size_t)32 * i])) { std::copy(d, d + 32, &desc[(size_t)32 * i]); dirty.push_back(i); }
+            }
+            if (dirty.empty() || k + 1 >= K) continue;
+            const int nd = (int)dirty.size(), Kr = K - k - 1;
+            std::vector<uint8_t> d2((size_t)32 * nd), a2((size_t)Kr * nd);
+            std::vector<int32_t> b2((size_t)Kr * nd, 256), i2((size_t)Kr * nd, -1);
+            std::vector<orbm_projected_point> p2((size_t)Kr * nd);
+            for (int j = 0; j < nd; ++j) {
+                std::copy(&desc[(size_t)32 * dirty[j]], &desc[(size_t)32 * dirty[j]] + 32, &d2[(size_t)32 * j]);
+                for (int r = 0; r < Kr; ++r) a2[(size_t)r * nd + j] = active[(size_t)(k + 1 + r) * m + dirty[j]];
+            }
+            w = cand(targets.data() + k + 1, Kr, dirty, d2.data(), a2.data(), b2.data(), i2.data(), p2.data());
+            if (w < 0) return nFused;
+            mFuseKeyFramesWaits += w; ++mFuseKeyFramesRefreshes;
+            for (int r = 0; r < Kr; ++r)
+                for (int j = 0; j < nd; ++j) {
+                    const size_t o = (size_t)(k + 1 + r) * m + dirty[j];
+                    best[o] = b2[(size_t)r * nd + j]; idx[o] = i2[(size_t)r * nd + j]; proj[o] = p2[(size_t)r * nd + j];
+                }
+        }
+        return nFused;
+    }
+    // `map` as the Fuse tails see it, marking the heir of every replace(dead, heir).
+    template <class MapOps, class Mark>
+    struct FuseHeirLog {
+        MapOps &map; Mark &mark;
+        auto at(int i) -> decltype(map.at(i)) { return map.at(i); }
+        template <class H> bool null(const H &h) { return map.null(h); }
+        template <class H> bool isBad(const H &h) { return map.isBad(h); }
+        template <class H> bool isInKeyFrame(const H &h) { return map.isInKeyFrame(h); }
+        template <class H> bool alreadyFound(const H &h) { return map.alreadyFound(h); }
+        auto slotOwner(int idx) -> decltype(map.slotOwner(idx)) { return map.slotOwner(idx); }
+        template <class H> int observations(const H &h) { return map.observations(h); }
+        template <class H> void replace(const H &dead, const H &heir) { map.replace(dead, heir); mark(heir); }
+        template <class H> void add(const H &h, int idx) { map.add(h, idx); }
+        template <class H> void recordReplace(int i, const H &h) { map.recordReplace(i, h); }
+    };
+
     // ORBmatcher::SearchBySim3 (ORBmatcher.cc:1303-1527) over projected points: points12[i1] = map point i1 of KF1 seen
     // in KF2 (window.r < 0: skipped), points21 the other way; levels [l-1, l], <= TH_HIGH, then the agreement check.
     int SearchBySim3(const FrameView &KF1, const FrameView &KF2, const std::vector<ProjectedPoint> &points12,
@@ -969,6 +1120,7 @@ protected:
     float mfNNratio;
     bool mbCheckOrientation;
     int mStatus = ORBX_OK;
+    int mFuseKeyFramesWaits = 0, mFuseKeyFramesRefreshes = 0;      // of the last FuseKeyFrames / FuseKeyFramesSim3
     std::vector<int32_t> mScratch;     // per-entry output of the whole-function searches (not re-entrant per OBJECT; instances are stack-local, as in the reference)
 };
 

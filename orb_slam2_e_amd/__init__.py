@@ -6,7 +6,7 @@ reference's ORBextractor / ORBmatcher / FEA2 interfaces used by tests and bench.
 """
 from ._lib import OrbxError, build, lib  # noqa: F401
 from .extractor import KP_DTYPE, ComputeStereoMatches, ORBextractor, extract_pair, stereo_download_batch, stereo_match_batch  # noqa: F401
-from .matcher import Distortion, Frame, MapSnapshot, ORBmatcher, Points, TriangKeyFrame, View, image_bounds, undistort_points  # noqa: F401
+from .matcher import Distortion, Frame, FuseTarget, MapSnapshot, ORBmatcher, Points, TriangKeyFrame, View, image_bounds, undistort_points  # noqa: F401
 from .pose import PoseCamera, PoseStats, pose_optimization, pose_optimization_batch, pose_optimization_batch_device  # noqa: F401
 from .pose import pose_optimization_nr, pose_optimization_nr_batch  # noqa: F401
 from .sim3 import Sim3OptProblem, Sim3Problem, Sim3Solver, optimize_sim3, sim3_hypotheses  # noqa: F401

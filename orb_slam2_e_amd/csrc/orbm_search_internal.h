@@ -1,8 +1,9 @@
 // orbm_search_internal.h -- what the three units of the windowed searches share and nothing else:
 //   orbm_frame.hip   makes frames: sorted on the host for one call (sort_frame) or resident in HBM (k_frame_build);
-//   orbm_window.hip  searches them with independent queries (k_win_best, k_map_search_poses);
+//   orbm_window.hip  searches them with independent queries (k_win_best, k_map_search_poses, k_fuse_keyframes);
 //   orbm_search.hip  searches them with the reference's coupled loops (run_sequential), and SearchBySim3 through launch_win_best.
-// A frame reaches a search as a FrameSrc and its kernels as a FrameView.  What only one unit uses stays in that unit; what the
+// A frame reaches a search as a FrameSrc and its kernels as a FrameView; the projection of a map point (project_point) exists once,
+// for k_project_points and k_fuse_keyframes.  What only one unit uses stays in that unit; what the
 // other matcher units need as well is in orbm_internal.h.
 #pragma once
 #include <stdint.h>
@@ -28,6 +29,81 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v)
     const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 0), b = (unsigned)__builtin_amdgcn_readlane((int)v, 16),
                    c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
     return min(min(a, b), min(c, d));
+}
+
+// Projection of one map point into a Frame / KeyFrame, in the reference's float / double order, op by op: the one copy of this
+// arithmetic, called by k_project_points (orbm_search.hip) and k_fuse_keyframes (orbm_window.hip).
+//   mode 0  Frame::isInFrustum (src/Frame.cc:284-340) + MapPoint::PredictScale (src/MapPoint.cc:464-480) and the window
+//           of SearchByProjection(Frame&, vector<MapPoint*>&, th) (src/ORBmatcher.cc:62-70, RadiusByViewingCos :332-338)
+//   mode 1  the projection block of ORBmatcher::Fuse(KeyFrame*, vector<MapPoint*>&, th) (:1053-1094)
+//   mode 2  the same block of the Sim3 form (:1212-1250): invz = 1.0 / z in double, no right coordinate
+// cv::Mat arithmetic restated (OpenCV 3.4, CV_32F; parity unpinned like the other OpenCV primitives):
+//   Rcw * P + tcw  : gemm's 3 x 3 special case -- the row sum a0 b0 + a1 b1 + a2 b2 in float, left to right, then
+//                    float(double(sum) + double(t));
+//   cv::norm(PO)   : sqrt of the double sum of squares, left to right, cast to float;
+//   PO.dot(Pn)     : double sum of double products, left to right.
+// std::log / std::ceil on a float argument are the float overloads (using namespace std): logf as glibc >= 2.27 evaluates it,
+// restated in orbx_math.h (orbx_logf_glibc_f32: equal to the library at every positive float, tools/trig/logf_count.c; it differs
+// from the rounded double logarithm at 416,909 floats -- at none of them by enough to move a level at scale factor 1.2).
+struct ProjectCam { float fx, fy, cx, cy, min_x, max_x, min_y, max_y, mbf, cos_limit, log_scale, th; float R[9], t[3], Ow[3]; int nlevels, mode; };
+
+// Point i of the arrays; o and w leave as the rejected record (visible 0, level -1; r < 0: no candidates) unless the point passes
+// every test and valid[i] (valid may be NULL).
+__device__ __forceinline__ void project_point(int i, const uint8_t *__restrict__ valid, const float *__restrict__ pos, const float *__restrict__ nrm,
+                                              const float *__restrict__ mind, const float *__restrict__ maxd, const ProjectCam &cam,
+                                              const float *__restrict__ scale, orbm_projected_point &o, WinQuery &w)
+{
+    o = {0.f, 0.f, 0.f, 0.f, 0.f, -1, 0};
+    w = {0.f, 0.f, -1.f, 0.f, 0, -1}; // r < 0: no candidates
+    const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
+    const float *R = cam.R;
+    const float PcX = (float)((double)(R[0] * P0 + R[1] * P1 + R[2] * P2) + (double)cam.t[0]);
+    const float PcY = (float)((double)(R[3] * P0 + R[4] * P1 + R[5] * P2) + (double)cam.t[1]);
+    const float PcZ = (float)((double)(R[6] * P0 + R[7] * P1 + R[8] * P2) + (double)cam.t[2]);
+    bool ok = !(PcZ < 0.0f) && (!valid || valid[i]);
+    float invz, u, v;
+    if (cam.mode == 0) {
+        invz = 1.0f / PcZ;                                  // Frame.cc:302-304
+        u = cam.fx * PcX * invz + cam.cx;
+        v = cam.fy * PcY * invz + cam.cy;
+        ok = ok && !(u < cam.min_x || u > cam.max_x) && !(v < cam.min_y || v > cam.max_y);
+    } else {
+        invz = cam.mode == 1 ? 1 / PcZ : (float)(1.0 / (double)PcZ);   // ORBmatcher.cc:1060 / :1222
+        const float x = PcX * invz, y = PcY * invz;
+        u = cam.fx * x + cam.cx;
+        v = cam.fy * y + cam.cy;
+        ok = ok && (u >= cam.min_x && u < cam.max_x && v >= cam.min_y && v < cam.max_y); // KeyFrame::IsInImage
+    }
+    const float ur = u - cam.mbf * invz;
+    const float maxDistance = 1.2f * maxd[i], minDistance = 0.8f * mind[i]; // MapPoint.cc:430-440
+    const float PO0 = P0 - cam.Ow[0], PO1 = P1 - cam.Ow[1], PO2 = P2 - cam.Ow[2];
+    const float dist = (float)sqrt((double)PO0 * (double)PO0 + (double)PO1 * (double)PO1 + (double)PO2 * (double)PO2);
+    const double dot = (double)PO0 * (double)nrm[3 * i] + (double)PO1 * (double)nrm[3 * i + 1] + (double)PO2 * (double)nrm[3 * i + 2];
+    float viewCos = 0.f;
+    if (cam.mode == 0) {
+        ok = ok && !((double)dist < 0.9 * (double)minDistance || (double)dist > (double)maxDistance / 0.9);
+        viewCos = (float)(dot / (double)dist);
+        ok = ok && !(viewCos < cam.cos_limit);
+    } else {
+        ok = ok && !(dist < minDistance || dist > maxDistance);
+        ok = ok && !(dot < 0.5 * (double)dist);
+    }
+    // PredictScale: ratio = mfMaxDistance / dist; ceil(log(ratio) / mfLogScaleFactor), clamped
+    const float ratio = maxd[i] / dist;
+    const float lg = orbx_logf_glibc_f32(ratio);        // log(float) = logf under the reference's headers; glibc's logf restated (orbx_math.h)
+    int level = orbx_f2i_x86(ceilf(lg / cam.log_scale));   // ratio +inf: INT_MIN -> level 0, as on x86-64
+    if (level < 0) level = 0; else if (level >= cam.nlevels) level = cam.nlevels - 1;
+    if (ok) {
+        o.u = u; o.v = v; o.ur = ur; o.view_cos = viewCos; o.dist = dist; o.level = level; o.visible = 1;
+        float r;
+        if (cam.mode == 0) {
+            r = (double)viewCos > 0.998 ? 3.0f : 4.5f;      // RadiusByViewingCos
+            if ((double)cam.th != 1.0) r *= cam.th;
+        } else {
+            r = cam.th;
+        }
+        w.u = u; w.v = v; w.r = r * scale[level]; w.xr = ur; w.min_level = level - 1; w.max_level = level;
+    }
 }
 
 struct SortedFrame {

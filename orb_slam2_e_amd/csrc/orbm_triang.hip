@@ -141,7 +141,7 @@ __global__ __launch_bounds__(MT) void k_triang_arrays(const orbx_keypoint *__res
 
 // ------------------------------------------------------------------------------------------------ LocalMapping::CreateNewMapPoints
 // The arithmetic behind a matched pair (src/LocalMapping.cc:338-497) in the reference's float / double order, op by op.  cv::Mat
-// arithmetic as restated above k_project_points, plus (OpenCV 3.4, parity unpinned like the rest):
+// arithmetic as restated above project_point (orbm_search_internal.h), plus (OpenCV 3.4, parity unpinned like the rest):
 //   s * row - row      addWeighted with float weights: a * s + b * -1.0f
 //   v / s              convertTo with a FLOAT scale: v * float(1.0 / double(s))
 //   cv::SVD::compute   JacobiSVDImpl_<float> (modules/core/src/lapack.cpp) on the transposed copy: rotations of the pairs of

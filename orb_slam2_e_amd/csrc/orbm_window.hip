@@ -8,6 +8,8 @@
 //     TH_RELOC / same-level ratio, last map point wins (:205-216)                             k_reloc_accept
 //   that search under every pose PnPsolver::iterate recorded   src/PnPsolver.cc:419-634     k_map_search_poses (..._map_poses),
 //     over the caller's arrays or a snapshot of the map in HBM (orbm_map)
+//   ORBmatcher::Fuse against every target keyframe             src/ORBmatcher.cc:1053-1150  k_fuse_keyframes (orbm_fuse_keyframes):
+//     (LocalMapping.cc:550-558, LoopClosing.cc:587-613)                                       projection + gated walk of all pairs
 // The walk over a window's runs of the sorted keypoint array and the selection of the two best are device functions
 // (win_best_walk, win_best_select) that k_win_best and k_map_search_poses share; the frustum arithmetic of one map point under one
 // pose (map_frustum_point) is shared by k_map_frustum and k_map_search_poses.  A call stages its inputs in the workspace's pinned
@@ -299,6 +301,72 @@ __global__ __launch_bounds__(MPP_T) void k_map_search_poses(const float *__restr
     if ((int)threadIdx.x < P && s_nm[threadIdx.x]) atomicAdd(&nmatches[threadIdx.x], s_nm[threadIdx.x]);
 }
 
+// The device half of ORBmatcher::Fuse (projection block src/ORBmatcher.cc:1053-1094 / :1212-1250, gated candidate loop :1092-1150
+// / :1252-1277) for every (target keyframe k, list entry i) pair in ONE launch: LocalMapping::SearchInNeighbors and
+// LoopClosing::SearchAndFuse call Fuse once per target over the same list.  The grid is (tiles of FK_TILE entries, K): blockIdx.x
+// runs fastest, so the workgroups of one target are dispatched together and its cell table and descriptors stay in L2.  The target
+// record (frame view, pose, camera) is indexed by blockIdx.y alone: lane-uniform, fetched through scalar loads.
+// Phase 1, wave 0: lane l projects entry i0 + l (project_point, the arithmetic k_project_points runs) unless the pair is inactive,
+// writes the projected record, and either the rejected result (256, -1) or an item of the LDS queue (ballot + popcount: one wave
+// fills it, so no atomic).  Phase 2, behind the barrier: the FK_T / 64 waves take the items in turn, one wave per item:
+// win_best_walk with fuse_gate = 1 on target k's frame, win_best_select, lane 0 writes best and idx (through perm).  Most pairs die
+// at the mask or in the projection; the walk is a chain of dependent loads (cell table -> keypoints -> descriptors), so what
+// decides the time is how many walks a wave does one after the other: at most FK_TILE / (FK_T / 64) = 4.  An inactive pair costs
+// one byte read and three preset stores.  Every loop is bounded by the queue length or the window's runs.
+constexpr int FK_T = 1024, FK_TILE = 64;
+struct FuseTarget { const SeqKp *kp; const uint4 *desc; const int *perm; const int *cell_off; GridParams gp; int has_uright, ns; ProjectCam cam; };
+struct FuseItem { float u, v, r, xr; int level, l; };
+
+__global__ __launch_bounds__(FK_T) void k_fuse_keyframes(const FuseTarget *__restrict__ targets, const float *__restrict__ pos,
+                                                         const float *__restrict__ nrm, const float *__restrict__ mind,
+                                                         const float *__restrict__ maxd, const uint4 *__restrict__ mdesc, int m,
+                                                         const uint8_t *__restrict__ active, const float *__restrict__ scale,
+                                                         const float *__restrict__ inv_sigma2, int *__restrict__ best_o, int *__restrict__ idx_o,
+                                                         orbm_projected_point *__restrict__ proj)
+{
+    __shared__ FuseItem s_item[FK_TILE];
+    __shared__ int s_nitems;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int k = blockIdx.y, i0 = blockIdx.x * FK_TILE;
+    const FuseTarget &t = targets[k];
+    const size_t row0 = (size_t)k * m;
+    if (wave == 0) {
+        const int i = i0 + lane;
+        bool ok = false;
+        WinQuery w;
+        if (i < m) {
+            orbm_projected_point o = {0.f, 0.f, 0.f, 0.f, 0.f, -1, 0};
+            if (!active || active[row0 + i]) {
+                project_point(i, nullptr, pos, nrm, mind, maxd, t.cam, scale, o, w);
+                ok = o.visible && t.ns > 0;     // a keyframe without a keypoint in its grid has no candidate
+            }
+            if (proj) proj[row0 + i] = o;
+            if (!ok) { best_o[row0 + i] = 256; idx_o[row0 + i] = -1; }
+        }
+        const unsigned long long bal = __ballot(ok);
+        if (ok) s_item[__popcll(bal & ((1ull << lane) - 1ull))] = {w.u, w.v, w.r, w.xr, w.max_level, lane};
+        if (lane == 0) s_nitems = __popcll(bal);
+    }
+    __syncthreads();
+    const int nitems = s_nitems;        // <= FK_TILE
+    for (int it = wave; it < nitems; it += FK_T / 64) {
+        const FuseItem e = s_item[it];
+        const int level = __builtin_amdgcn_readfirstlane(e.level), i = i0 + __builtin_amdgcn_readfirstlane(e.l);
+        WinQuery w;
+        w.u = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(e.u)));
+        w.v = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(e.v)));
+        w.r = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(e.r)));
+        w.xr = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(e.xr)));
+        w.min_level = level - 1; w.max_level = level;
+        const WinPick o = win_best_select(win_best_walk(w, mdesc + 2 * (size_t)i, lane, t.kp, t.desc, t.cell_off, nullptr, t.gp, t.has_uright, 256,
+                                                        inv_sigma2, 1), 256);
+        if (lane == 0) {
+            best_o[row0 + i] = o.best;
+            idx_o[row0 + i] = o.sp >= 0 ? t.perm[o.sp] : -1;
+        }
+    }
+}
+
 } // namespace
 
 // One window search without coupling (k_win_best) for device-resident queries: returns into ob[5][nq] (best, best level, second,
@@ -353,6 +421,7 @@ MapIntr map_intrinsics(const orbm_camera *cam, float th, int nlevels)
 }
 
 std::atomic<int> g_last_map_poses_waits{0};    // host waits of the last ..._map_poses call of this process
+std::atomic<int> g_last_fuse_keyframes_waits{0};    // host waits of the last orbm_fuse_keyframes call of this process
 
 // The map of a whole-map search: the caller's host arrays, staged with the call, or a snapshot's device block (carve and fill then
 // do nothing), in the manner of FrameSrc.
@@ -644,6 +713,75 @@ int orbm_frame_search_by_projection_map_poses(const orbm_frame *frame, const uin
 }
 
 int orbm_debug_last_map_poses_waits(void) { return g_last_map_poses_waits.load(std::memory_order_relaxed); }
+
+// Fuse against K target keyframes: one lease, one staged upload (the target records, the list, the mask, the pyramid), one launch
+// of k_fuse_keyframes, one result block, one wait.  The kernel writes every pair of the result rows, presets included.
+int orbm_fuse_keyframes(const orbm_fuse_target *targets, int K, int sim3, const float *mp_pos, const float *mp_normal,
+                        const float *mp_min_distance, const float *mp_max_distance, const uint8_t *mp_desc, int m, const uint8_t *active,
+                        float th, float log_scale_factor, const float *scale_factors, const float *inv_level_sigma2, int nlevels,
+                        int32_t *best, int32_t *idx, orbm_projected_point *projected)
+{
+    if (K < 0 || m < 0 || nlevels < 1 || nlevels > 16 || !scale_factors || (!sim3 && !inv_level_sigma2) || (K && !targets) ||
+        (m && (!mp_pos || !mp_normal || !mp_min_distance || !mp_max_distance || !mp_desc)) || (K && m && (!best || !idx)))
+        ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (K > 128 || m > 65536 || (size_t)K * (size_t)m > 4194304) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 128 targets, 65,536 points or 4,194,304 pairs in one call");
+    const float *sigma2 = sim3 ? nullptr : inv_level_sigma2;     // the Sim3 form has no reprojection gate
+    for (int k = 0; k < K; ++k) {
+        const orbm_fuse_target &t = targets[k];
+        if (!t.frame) ORBX_FAIL(ORBX_ERR_ARG, "a target without a frame");
+        bool finite = true;
+        for (int j = 0; j < 9; ++j) finite = finite && isfinite(t.Rcw[j]);
+        for (int j = 0; j < 3; ++j) finite = finite && isfinite(t.tcw[j]) && isfinite(t.Ow[j]);
+        if (!finite) ORBX_FAIL(ORBX_ERR_ARG, "a target pose that is not finite");
+        if (sigma2 && t.frame->n && (t.frame->min_octave < 0 || t.frame->max_octave >= nlevels)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
+    }
+    ORBX_NEED_DEVICE();
+    g_last_fuse_keyframes_waits.store(0, std::memory_order_relaxed);
+    if (K == 0 || m == 0) return ORBX_OK;
+    const size_t pairs = (size_t)K * m;
+    bool any = !active;
+    for (size_t j = 0; j < pairs && !any; ++j) any = active[j] != 0;
+    if (!any) {         // no active pair: the presets, nothing is launched
+        const orbm_projected_point none = {0.f, 0.f, 0.f, 0.f, 0.f, -1, 0};
+        for (size_t j = 0; j < pairs; ++j) { best[j] = 256; idx[j] = -1; if (projected) projected[j] = none; }
+        return ORBX_OK;
+    }
+    std::vector<FuseTarget> tab((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        const orbm_fuse_target &t = targets[k];
+        const orbm_frame *f = t.frame;
+        ProjectCam pc;
+        pc.fx = t.cam.fx; pc.fy = t.cam.fy; pc.cx = t.cam.cx; pc.cy = t.cam.cy;
+        pc.min_x = t.cam.grid_min_x; pc.max_x = t.cam.grid_max_x; pc.min_y = t.cam.grid_min_y; pc.max_y = t.cam.grid_max_y;     // KeyFrame::IsInImage, as orbm_project_points
+        pc.mbf = t.mbf; pc.cos_limit = 0.f; pc.log_scale = log_scale_factor; pc.th = th;
+        for (int j = 0; j < 9; ++j) pc.R[j] = t.Rcw[j];
+        for (int j = 0; j < 3; ++j) { pc.t[j] = t.tcw[j]; pc.Ow[j] = t.Ow[j]; }
+        pc.nlevels = nlevels; pc.mode = sim3 ? ORBM_PROJECT_FUSE_SIM3 : ORBM_PROJECT_FUSE;
+        tab[(size_t)k] = {f->kp, f->desc, f->perm, f->cell_off, f->gp, f->has_uright, f->ns, pc};
+    }
+    StagedCall sc;
+    const size_t o_tab = sc.in(tab.data(), sizeof(FuseTarget) * (size_t)K), o_pos = sc.in(mp_pos, sizeof(float) * 3 * m),
+                 o_nrm = sc.in(mp_normal, sizeof(float) * 3 * m), o_min = sc.in(mp_min_distance, sizeof(float) * m),
+                 o_max = sc.in(mp_max_distance, sizeof(float) * m), o_md = sc.in(mp_desc, (size_t)32 * m), o_act = sc.in(active, active ? pairs : 0),
+                 o_sc = sc.in(scale_factors, sizeof(float) * nlevels), o_sg = sc.in(sigma2, sigma2 ? sizeof(float) * nlevels : 0);
+    const size_t o_best = sc.out(sizeof(int) * pairs), o_idx = sc.out(sizeof(int) * pairs),
+                 o_proj = sc.out(projected ? sizeof(orbm_projected_point) * pairs : 0);
+    if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
+    hipLaunchKernelGGL(k_fuse_keyframes, dim3((m + FK_TILE - 1) / FK_TILE, K), dim3(FK_T), 0, sc.stream(), sc.d<const FuseTarget>(o_tab),
+                       sc.d<const float>(o_pos), sc.d<const float>(o_nrm), sc.d<const float>(o_min), sc.d<const float>(o_max),
+                       sc.d<const uint4>(o_md), m, active ? sc.d<const uint8_t>(o_act) : nullptr, sc.d<const float>(o_sc),
+                       sigma2 ? sc.d<const float>(o_sg) : nullptr, sc.d<int>(o_best), sc.d<int>(o_idx),
+                       projected ? sc.d<orbm_projected_point>(o_proj) : nullptr);
+    ORBX_HIP(hipGetLastError());
+    if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
+    g_last_fuse_keyframes_waits.store(sc.waits, std::memory_order_relaxed);    // counted where the stream is waited for
+    memcpy(best, sc.r<int>(o_best), sizeof(int) * pairs);
+    memcpy(idx, sc.r<int>(o_idx), sizeof(int) * pairs);
+    if (projected) memcpy(projected, sc.r<orbm_projected_point>(o_proj), sizeof(orbm_projected_point) * pairs);
+    return ORBX_OK;
+}
+
+int orbm_debug_last_fuse_keyframes_waits(void) { return g_last_fuse_keyframes_waits.load(std::memory_order_relaxed); }
 
 int orbm_search_fuse(const orbm_window_query *queries, const uint8_t *qdesc, int nq, const orbx_keypoint *kps, const uint8_t *desc,
                      int n, const float *uright, const float *inv_level_sigma2, int nlevels, float min_x, float min_y, float max_x,

@@ -343,6 +343,122 @@ class ORBmatcher:
                 nFused += 1
         return nFused
 
+    MAX_FUSE_TARGETS, MAX_FUSE_POINTS, MAX_FUSE_PAIRS = 128, 65536, 4194304
+
+    def fuse_keyframes_rows(self, targets, mp_pos, mp_normal, mp_min_distance, mp_max_distance, mp_desc, log_scale_factor, scale_factors,
+                            inv_level_sigma2, th, active=None, sim3=False, want_projected=True):
+        """orbm_fuse_keyframes: the device half of ORBmatcher::Fuse (projection + gated candidate loop) for every (target
+        keyframe, list entry) pair in one call.  targets = a sequence of FuseTarget; active = [K][m] bytes or None.  Row k of
+        the results is what project_points + frame_search_fuse return for target k alone.  Returns (best[K, m], idx[K, m],
+        projected[K, m] of PROJ_DTYPE or None)."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        pos, nrm, mn, mx = f32(mp_pos).reshape(-1, 3), f32(mp_normal).reshape(-1, 3), f32(mp_min_distance), f32(mp_max_distance)
+        d = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
+        K, m = len(targets), len(pos)
+        arr = (_CFuseTarget * max(K, 1))(*[t.c for t in targets])
+        sc = f32(scale_factors)
+        sg = f32(inv_level_sigma2) if inv_level_sigma2 is not None else None
+        act = np.ascontiguousarray(active, np.uint8).reshape(K, m) if active is not None else None
+        best = np.zeros((K, m), np.int32); idx = np.zeros((K, m), np.int32)
+        proj = np.zeros((K, m), self.PROJ_DTYPE) if want_projected else None
+        opt = lambda a: _p(a) if a is not None and a.size else None
+        check(self._L.orbm_fuse_keyframes(arr if K else None, K, int(sim3), opt(pos), opt(nrm), opt(mn), opt(mx), opt(d), m, opt(act),
+                                          float(th), float(log_scale_factor), _p(sc), _p(sg) if sg is not None else None, len(sc),
+                                          opt(best), opt(idx), opt(proj) if proj is not None else None))
+        return best, idx, proj
+
+    @staticmethod
+    def last_fuse_keyframes_rows_waits():
+        """orbm_debug_last_fuse_keyframes_waits: host waits of the last orbm_fuse_keyframes of this process (1 when it launched)."""
+        return lib().orbm_debug_last_fuse_keyframes_waits()
+
+    _last_fuse_keyframes = {"waits": 0, "refreshes": 0}
+
+    @staticmethod
+    def last_fuse_keyframes_waits():
+        """Host waits of the last fuse_keyframes (the whole loop) of this process: 1 + its refreshes when the first call launched."""
+        return ORBmatcher._last_fuse_keyframes["waits"]
+
+    @staticmethod
+    def last_fuse_keyframes_refreshes():
+        return ORBmatcher._last_fuse_keyframes["refreshes"]
+
+    def fuse_keyframes(self, targets, vpMapPoints, mp_pos, mp_normal, mp_min_distance, mp_max_distance, mp_desc, log_scale_factor,
+                       scale_factors, inv_level_sigma2, th, map_ops, sim3=False, candidates=None):
+        """The loop `for pKFi in targets: matcher.Fuse(pKFi, vpMapPoints)` of LocalMapping::SearchInNeighbors
+        (LocalMapping.cc:550-558) as a whole, or with sim3=True the loop of LoopClosing::SearchAndFuse (LoopClosing.cc:587-613)
+        over the Sim3 form: one device call for all K x m pairs, then the reference's loop tails (fuse_replay /
+        fuse_replay_sim3) on the host, target by target in list order.  Returns nFused per target.
+
+        MapPoint::Replace ends with ComputeDistinctiveDescriptors on the heir (MapPoint.cc:275), so the descriptor of a list
+        entry can change between two targets: after target k the rows of the LATER targets are computed again, in one more call,
+        for the entries that were reported as an heir, are not bad and whose map_ops.descriptor(h) differs bytewise from the
+        bytes their rows were computed with.  The result is the sequential loop's.
+
+        map_ops: what fuse_replay / fuse_replay_sim3 ask for, answered for the CURRENT target, plus begin_target(k) (the Sim3
+        form takes its spAlreadyFound snapshot here), end_target(k, report) (the Sim3 caller runs its Replace loop of
+        LoopClosing.cc:604-611 here and calls report(i) for every list index i it replaced into), descriptor(h) (32 bytes) and,
+        for the mask, in_target(h, k): IsInKeyFrame(target k) -- in the Sim3 form: h is among target k's map points -- at the
+        time of the call.  The mask is an optimisation only: the tails test every skip again at their own time.
+        candidates (optional): a callable (targets, points, desc, active) -> (best, idx, visible), each [len(targets)][len(points)],
+        standing in for the device; points = list indices, desc = their descriptors, active = [len(targets)][len(points)]."""
+        lst = np.ascontiguousarray(vpMapPoints, np.int32)
+        K, m = len(targets), len(lst)
+        desc = np.array(mp_desc, np.uint8).reshape(m, 32).copy()      # the bytes the rows were computed with
+        stats = {"waits": 0, "refreshes": 0}
+        if candidates is None:
+            f32 = lambda a: np.ascontiguousarray(a, np.float32)
+            pos, nrm, mn, mx = f32(mp_pos).reshape(m, 3), f32(mp_normal).reshape(m, 3), f32(mp_min_distance), f32(mp_max_distance)
+
+            def candidates(tg, points, d, act):
+                b, ix, pr = self.fuse_keyframes_rows(tg, pos[points], nrm[points], mn[points], mx[points], d, log_scale_factor,
+                                                     scale_factors, inv_level_sigma2, th, act, sim3)
+                stats["waits"] += self.last_fuse_keyframes_rows_waits()
+                return b, ix, pr["visible"]
+        else:
+            inner = candidates
+
+            def candidates(tg, points, d, act):
+                stats["waits"] += 1
+                return inner(tg, points, d, act)
+        # mask from the map state at entry; handle -> list indices (the list holds duplicates and NULL entries)
+        active = np.zeros((K, m), np.uint8)
+        where = {}
+        for i, h in enumerate(lst):
+            h = int(h)
+            if h < 0:
+                continue
+            where.setdefault(h, []).append(i)
+            if map_ops.is_bad(h):
+                continue
+            for k in range(K):
+                active[k, i] = not map_ops.in_target(h, k)
+        best, idx, visible = (np.array(a) for a in candidates(list(targets), np.arange(m), desc, active))
+        nFused = []
+        for k in range(K):
+            heirs = set()
+            map_ops.begin_target(k)
+            tail = _HeirLog(map_ops, where, heirs)
+            n = (self.fuse_replay_sim3 if sim3 else self.fuse_replay)(lst, visible[k], best[k], idx[k], tail)
+            map_ops.end_target(k, lambda i: heirs.update(where.get(int(lst[i]), ())))
+            nFused.append(n)
+            dirty = []
+            for i in sorted(heirs):
+                h = int(lst[i])
+                if h < 0 or map_ops.is_bad(h):
+                    continue
+                d = np.frombuffer(bytes(map_ops.descriptor(h)), np.uint8)
+                if not np.array_equal(d, desc[i]):
+                    desc[i] = d
+                    dirty.append(i)
+            if dirty and k + 1 < K:
+                dirty = np.array(dirty, np.int64)
+                b, ix, vis = candidates(list(targets[k + 1:]), dirty, desc[dirty], active[k + 1:][:, dirty])
+                best[k + 1:, dirty], idx[k + 1:, dirty], visible[k + 1:, dirty] = b, ix, vis
+                stats["refreshes"] += 1
+        ORBmatcher._last_fuse_keyframes = stats
+        return nFused
+
     @staticmethod
     def distinctive_descriptors(desc, off):
         """MapPoint::ComputeDistinctiveDescriptors for a batch (MapPoint.cc:305-370)."""
@@ -659,6 +775,47 @@ class _CPoints(C.Structure):
 class _CView(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float),
                 ("log_scale_factor", C.c_float), ("nlevels", C.c_int32), ("scale_factors", C.c_void_p)]
+
+
+class _HeirLog:
+    """map_ops as the Fuse tails see it, noting every list index whose handle a replace(dead, heir) names as the heir."""
+
+    def __init__(self, map_ops, where, heirs):
+        self._ops, self._where, self._heirs = map_ops, where, heirs
+
+    def __getattr__(self, name):
+        return getattr(self._ops, name)
+
+    def replace(self, dead, heir):
+        self._ops.replace(dead, heir)
+        self._heirs.update(self._where.get(int(heir), ()))
+
+
+class _CCamera(C.Structure):
+    """orbm_camera (ORBmatcher.CAM_DTYPE as a ctypes structure)"""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("min_x", C.c_int32), ("max_x", C.c_int32),
+                ("min_y", C.c_int32), ("max_y", C.c_int32), ("grid_min_x", C.c_float), ("grid_min_y", C.c_float), ("grid_max_x", C.c_float),
+                ("grid_max_y", C.c_float)]
+
+
+class _CFuseTarget(C.Structure):
+    """orbm_fuse_target"""
+    _fields_ = [("frame", C.c_void_p), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("cam", _CCamera),
+                ("mbf", C.c_float)]
+
+
+class FuseTarget:
+    """orbm_fuse_target: a resident keyframe with the pose and camera ORBmatcher::Fuse projects with.  Rcw, tcw, Ow as
+    project_points takes them (Sim3 form: sRcw / s, t / s, -Rcw' tcw, ORBmatcher.cc:1188-1192); cam = one CAM_DTYPE record."""
+
+    def __init__(self, frame, Rcw, tcw, Ow, cam, mbf):
+        f32 = lambda a, n: np.ascontiguousarray(a, np.float32).reshape(n)
+        self.frame = frame
+        self.Rcw, self.tcw, self.Ow, self.mbf = f32(Rcw, 9), f32(tcw, 3), f32(Ow, 3), float(mbf)
+        self.cam = np.ascontiguousarray(cam, ORBmatcher.CAM_DTYPE).reshape(1).copy()
+        h = frame._h if frame is not None else None
+        self.c = _CFuseTarget(h.value if isinstance(h, C.c_void_p) else h, (C.c_float * 9)(*self.Rcw.tolist()), (C.c_float * 3)(*self.tcw.tolist()),
+                              (C.c_float * 3)(*self.Ow.tolist()), _CCamera.from_buffer_copy(self.cam.tobytes()), self.mbf)
 
 
 class _CBowPair(C.Structure):
