@@ -943,6 +943,46 @@ int orbm_track_local_map(const orbm_frame *cur, const orbm_view *view, const orb
 /* Host waits (stream synchronisations) of the last orbm_track_* call of this process: 1 on the common path. */
 int orbm_debug_last_track_waits(void);
 
+/* KeyFrameDatabase on the device (src/KeyFrameDatabase.cc:40-309, src/LoopClosing.cc:120-141): the BowVectors of the
+ * added keyframes live in HBM, one row of (word id, value) per keyframe under a SLOT number.  Slots are handed out in ascending
+ * order of add and are not reused before clear, so slot order is the order of the reference's inverted lists.  nwords = the
+ * vocabulary's size.  A row or a query holds 0 .. 8,192 words, ids strictly ascending inside [0, nwords) (a BowVector as
+ * std::map iterates it), values as Frame::ComputeBoW leaves them.  ORBX_ERR_ARG, with the reason in orbx_last_error(), before
+ * anything is launched or written: ids not strictly ascending or outside [0, nwords), n or nq negative or above 8,192, a dead or
+ * out-of-range slot (erase, score), a second erase of a slot, a NULL output.  Arguments are checked first, then the device
+ * (ORBX_ERR_NO_DEVICE); create, clear, size and destroy need none, nor does a query or score call that launches nothing.  A database may be used from several threads (one call at a
+ * time runs; the reference holds a mutex too).
+ *   add      uploads the row (the store grows by itself and keeps what is resident); *slot = its slot.  One host wait.
+ *   erase    marks the slot dead; the row stays where it is until clear (dead rows are never compacted in between).
+ *   clear    forgets every slot (the next add gets slot 0) and keeps the capacity.
+ *   size     *live = keyframes in the database, *slots = slots handed out since the last clear (either may be NULL).
+ *   query    fills common[slots], first[slots], score[slots] for EVERY slot:
+ *              dead slot   common -1, first -1, score +0.0f
+ *              live slot   common = words it shares with the query, first = index INTO THE QUERY of the first shared word (-1:
+ *                          none), score = (float)DBoW2::L1Scoring::score(query, row): the double sum of |vi - wi| - |vi| - |wi|
+ *                          over the shared words in ascending word id, then -sum / 2.0 -- bit for bit (-0.0f when nothing is shared)
+ *            One staged upload (the query), one launch, one host wait.  No live keyframe or nq = 0: the rows are filled as above
+ *            (common 0 / -1) and nothing is launched.  Scores are computed for every sharing keyframe, also those the caller's 0.8
+ *            cut on common drops.
+ *   score    the same score for a list of n <= 8,192 live slots (a slot may repeat): LoopClosing::DetectLoop's minScore loop.  One
+ *            upload, one launch, one wait; n = 0: nothing is launched. */
+typedef struct orbm_kfdb orbm_kfdb;
+int orbm_kfdb_create(int nwords, orbm_kfdb **out);
+int orbm_kfdb_destroy(orbm_kfdb *db);
+int orbm_kfdb_add(orbm_kfdb *db, const int32_t *words, const double *values, int n, int32_t *slot);
+int orbm_kfdb_erase(orbm_kfdb *db, int slot);
+int orbm_kfdb_clear(orbm_kfdb *db);
+int orbm_kfdb_size(const orbm_kfdb *db, int *live, int *slots);
+int orbm_kfdb_query(orbm_kfdb *db, const int32_t *qwords, const double *qvalues, int nq, int32_t *common, int32_t *first, float *score);
+int orbm_kfdb_score(orbm_kfdb *db, const int32_t *qwords, const double *qvalues, int nq, const int32_t *slots, int n, float *score);
+/* Host waits of the last orbm_kfdb_query / orbm_kfdb_score of this process: 1 when it launched, 0 when nothing was launched. */
+int orbm_debug_last_kfdb_waits(void);
+/* How often the store replaced a device pool by a larger one since create (-1: NULL database). */
+int orbm_debug_kfdb_reallocs(const orbm_kfdb *db);
+/* Test aid: at most `blocks` workgroups per orbm_kfdb_query / orbm_kfdb_score launch instead of 2,048 (0: the default again), so that
+ * a few keyframes already make every wave stride over several slots.  Same results.  Process-wide; returns the previous setting. */
+int orbm_debug_kfdb_max_blocks(int blocks);
+
 /* Test aid: on != 0 makes the whole-loop projection searches use the one-wave sequential resolver (k_resolve) instead of the
  * parallel fixed-point resolver (k_resolve_par), which otherwise only takes over when the latter does not converge.  Both
  * give the reference loop's result.  Process-wide; returns the previous setting. */

@@ -1875,5 +1875,190 @@ private:
     orbm_init_reconstruction mRec;
 };
 
+// The host half of a KeyFrameDatabase query (src/KeyFrameDatabase.cc:76-309), stated ONCE for both forms and for any way of naming a
+// keyframe (Key: a slot number in KeyFrameDatabase below, a KeyFrame* in integration/KeyFrameDatabase_hip.cc).  Input: what
+// orbm_kfdb_query leaves per slot -- shared-word count, query index of the first shared word, float L1 score.  The callables:
+//   keyOf(slot) -> Key                     of a live slot
+//   fieldsOf(Key) -> KfdbQueryFields       the three fields of this FORM that persist across queries (loop: mnLoopQuery, mnLoopWords,
+//                                          mLoopScore; relocalisation: mnRelocQuery, mnRelocWords, mRelocScore), by reference
+//   connected(Key) -> bool                 loop form: the key is connected to the query keyframe (never asked in the other form)
+//   neighbours(Key, std::vector<Key> &)    GetBestCovisibilityKeyFrames(10)
+// What it restates: keyframes are met in the order (first shared word, slot); one whose query field already holds this id is
+// counted on and not listed again; a connected one ends with a word count of 1 and is not listed; the largest count among the
+// LISTED ones gives the cut int(max * 0.8f), strict; the survivors' scores are stored, the loop form then drops those below
+// minScore; each remaining one collects the stored scores of its neighbours that this id listed (loop form: and that pass the
+// cut; relocalisation form: whatever they hold, also a score of an earlier query) and names the best of the group, a tie staying
+// with the earlier; groups above 0.75 of the best total (loop form: of at least minScore) are returned once each, in list order.
+struct KfdbQueryFields {
+    long unsigned &query;
+    int &words;
+    float &score;
+};
+
+template <class Key, class KeyOf, class FieldsOf, class Connected, class Neighbours>
+std::vector<Key> KfdbCandidatesFromCounts(bool loopForm, const int32_t *common, const int32_t *first, const float *score, size_t nslots,
+                                          long unsigned id, float minScore, KeyOf keyOf, FieldsOf fieldsOf, Connected connected,
+                                          Neighbours neighbours)
+{
+    struct Entry { Key key; float value; };
+    // the sharing slots by (first, slot): a counting sort over `first` that takes the slots in ascending order (at 20,000 keyframes
+    // nearly every slot shares a word, and a comparison sort of those was most of this function)
+    int maxFirst = -1;
+    for (size_t s = 0; s < nslots; ++s)
+        if (common[s] > 0) maxFirst = std::max(maxFirst, (int)first[s]);
+    std::vector<int> start((size_t)maxFirst + 2, 0), order;
+    for (size_t s = 0; s < nslots; ++s)
+        if (common[s] > 0) ++start[(size_t)first[s] + 1];
+    for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
+    order.resize((size_t)start.back());
+    for (size_t s = 0; s < nslots; ++s)
+        if (common[s] > 0) order[(size_t)start[first[s]]++] = (int)s;
+    std::vector<Entry> listed;
+    for (int s : order) {
+        const Key k = keyOf(s);
+        KfdbQueryFields f = fieldsOf(k);
+        if (f.query == id) { f.words += common[s]; continue; }
+        if (loopForm && connected(k)) { f.words = 1; continue; }     // reset at every meeting, then incremented
+        f.query = id;
+        f.words = common[s];
+        listed.push_back(Entry{k, score[s]});
+    }
+    if (listed.empty()) return std::vector<Key>();
+    int most = 0;
+    for (const Entry &e : listed) most = std::max(most, fieldsOf(e.key).words);
+    const int cut = (int)((float)most * 0.8f);
+    std::vector<Entry> kept;
+    for (const Entry &e : listed) {
+        KfdbQueryFields f = fieldsOf(e.key);
+        if (!(f.words > cut)) continue;
+        f.score = e.value;
+        if (!loopForm || e.value >= minScore) kept.push_back(e);
+    }
+    if (kept.empty()) return std::vector<Key>();
+    float bestTotal = loopForm ? minScore : 0.0f;
+    std::vector<Entry> groups;
+    std::vector<Key> nb;
+    for (const Entry &e : kept) {
+        float total = e.value, top = e.value;
+        Key winner = e.key;
+        nb.clear();
+        neighbours(e.key, nb);
+        for (const Key &n : nb) {
+            KfdbQueryFields g = fieldsOf(n);
+            if (g.query != id || (loopForm && !(g.words > cut))) continue;
+            total += g.score;
+            if (g.score > top) { winner = n; top = g.score; }
+        }
+        groups.push_back(Entry{winner, total});
+        if (total > bestTotal) bestTotal = total;
+    }
+    const float keepAbove = 0.75f * bestTotal;
+    std::vector<Key> out;
+    for (const Entry &g : groups)
+        if (g.value > keepAbove && std::find(out.begin(), out.end(), g.key) == out.end()) out.push_back(g.key);
+    return out;
+}
+
+// KeyFrameDatabase (include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc:40-309) over the device store of orbm_kfdb_*: a
+// keyframe is known by the SLOT add() returns (ascending in the order of add, restarting at 0 after clear()).  Both Detect
+// methods are one orbm_kfdb_query followed by KfdbCandidatesFromCounts over the per-slot fields kept here.
+// bestCovisibles(slot, out) fills GetBestCovisibilityKeyFrames(10) of a slot as slots (a neighbour that was never added has no slot
+// and is left out: no query can have listed it).  mLoopScore / mRelocScore, which the reference leaves uninitialised, start at
+// 0.0f.  A query id of 0 lists nobody, as in the reference (the query fields start at 0).
+class KeyFrameDatabase {
+public:
+    typedef DBoW2::BowVector BowVector;
+    struct Fields {                     // KeyFrame.h:160-165
+        long unsigned mnLoopQuery = 0; int mnLoopWords = 0; float mLoopScore = 0.0f;
+        long unsigned mnRelocQuery = 0; int mnRelocWords = 0; float mRelocScore = 0.0f;
+    };
+
+    explicit KeyFrameDatabase(int nwords) { mStatus = orbm_kfdb_create(nwords, &mDb); }
+    ~KeyFrameDatabase() { if (mDb) orbm_kfdb_destroy(mDb); }
+    KeyFrameDatabase(const KeyFrameDatabase &) = delete;
+    KeyFrameDatabase &operator=(const KeyFrameDatabase &) = delete;
+
+    // -1: the library refused (status())
+    int add(const BowVector &bow)
+    {
+        flatten(bow);
+        int32_t slot = -1;
+        mStatus = orbm_kfdb_add(mDb, mWords.data(), mValues.data(), (int)mWords.size(), &slot);
+        if (mStatus != ORBX_OK) return -1;
+        if ((size_t)slot >= mFields.size()) mFields.resize((size_t)slot + 1);
+        mFields[slot] = Fields();
+        return slot;
+    }
+    void erase(int slot) { mStatus = orbm_kfdb_erase(mDb, slot); }
+    void clear() { mStatus = orbm_kfdb_clear(mDb); mFields.clear(); }
+
+    // LoopClosing::DetectLoop's minScore loop (LoopClosing.cc:126-138) over the live connected slots: one library call.
+    // status() != ORBX_OK afterwards: the library refused and the value is not a score.
+    float MinScore(const BowVector &bow, const std::vector<int32_t> &slots)
+    {
+        float minScore = 1;
+        mStatus = ORBX_OK;
+        if (slots.empty()) return minScore;
+        flatten(bow);
+        mScore.resize(slots.size());
+        mStatus = orbm_kfdb_score(mDb, mWords.data(), mValues.data(), (int)mWords.size(), slots.data(), (int)slots.size(), mScore.data());
+        if (mStatus != ORBX_OK) return minScore;
+        for (size_t i = 0; i < slots.size(); ++i)
+            if (mScore[i] < minScore) minScore = mScore[i];
+        return minScore;
+    }
+
+    template <class BestCovisibles>
+    std::vector<int> DetectLoopCandidates(const BowVector &bow, long unsigned mnId, const std::vector<int> &connectedSlots, float minScore,
+                                          BestCovisibles bestCovisibles)
+    {
+        if (!query(bow)) return std::vector<int>();
+        std::vector<char> connected(mFields.size(), 0);
+        for (int c : connectedSlots)
+            if (c >= 0 && (size_t)c < connected.size()) connected[c] = 1;
+        return KfdbCandidatesFromCounts<int>(
+            true, mCommon.data(), mFirst.data(), mScore.data(), mFields.size(), mnId, minScore, [](int s) { return s; },
+            [this](int s) { Fields &f = mFields[s]; return KfdbQueryFields{f.mnLoopQuery, f.mnLoopWords, f.mLoopScore}; },
+            [&connected](int s) { return connected[s] != 0; }, bestCovisibles);
+    }
+
+    template <class BestCovisibles>
+    std::vector<int> DetectRelocalizationCandidates(const BowVector &bow, long unsigned mnId, BestCovisibles bestCovisibles)
+    {
+        if (!query(bow)) return std::vector<int>();
+        return KfdbCandidatesFromCounts<int>(
+            false, mCommon.data(), mFirst.data(), mScore.data(), mFields.size(), mnId, 0.0f, [](int s) { return s; },
+            [this](int s) { Fields &f = mFields[s]; return KfdbQueryFields{f.mnRelocQuery, f.mnRelocWords, f.mRelocScore}; },
+            [](int) { return false; }, bestCovisibles);
+    }
+
+    const Fields &fields(int slot) const { return mFields[slot]; }
+    int slots() const { return (int)mFields.size(); }
+    orbm_kfdb *handle() const { return mDb; }
+    int status() const { return mStatus; }
+
+private:
+    void flatten(const BowVector &bow)
+    {
+        mWords.clear(); mValues.clear();
+        for (BowVector::const_iterator it = bow.begin(); it != bow.end(); ++it) { mWords.push_back((int32_t)it->first); mValues.push_back(it->second); }
+    }
+    bool query(const BowVector &bow)
+    {
+        flatten(bow);
+        const size_t n = mFields.size();
+        mCommon.assign(n ? n : 1, 0); mFirst.assign(n ? n : 1, -1); mScore.assign(n ? n : 1, 0.0f);
+        mStatus = orbm_kfdb_query(mDb, mWords.data(), mValues.data(), (int)mWords.size(), mCommon.data(), mFirst.data(), mScore.data());
+        return mStatus == ORBX_OK;
+    }
+
+    orbm_kfdb *mDb = nullptr;
+    int mStatus = ORBX_OK;
+    std::vector<Fields> mFields;
+    std::vector<int32_t> mWords, mCommon, mFirst;
+    std::vector<double> mValues;
+    std::vector<float> mScore;
+};
+
 } // namespace orbslam_hip
 #endif // ORBSLAM_HIP_HPP
