@@ -1,5 +1,6 @@
 // orbx_internal.h -- extractor state shared by the translation units that work
-// on an orbx_extractor's device-resident results (orbx_extract.hip, orbx_stereo.hip).
+// on an orbx_extractor's device-resident results (orbx_extract.hip and its stage units, orbx_stereo.hip); what only
+// the extractor's own units share is in orbx_extract_internal.h.
 #ifndef ORBX_INTERNAL_H
 #define ORBX_INTERNAL_H
 
@@ -16,7 +17,7 @@ constexpr int PADX = 32;  // left pad (bytes) of every pyramid row
 constexpr int MAXL = 16;
 constexpr int MIN_BORDER = EDGE - 3; // minBorderX/Y, ORBextractor.cc:773
 constexpr int OCT_T = 256;           // threads of k_octree (large batches)
-constexpr int OCT_TW = 512;          // ... of the wide variant small batches run (orbx_extract_batch): same 2,048 register-resident keys, 4 per thread
+constexpr int OCT_TW = 512;          // ... of the wide variant small batches run (launch_octree): same 2,048 register-resident keys, 4 per thread
 constexpr int OCT_KPT = 8, OCT_KB = 4; // keys a k_octree thread keeps in registers (levels above OCT_KPT x OCT_T candidates: arrays); keys per batch of LDS reads
 constexpr int OCT_MAXN = 2047;       // largest per-level feature quota supported (node state of k_octree in LDS)
 

@@ -15,17 +15,12 @@ def edit(path, pairs):
     open(path, "w").write(s)
 
 hook = ('    static int skipmask = getenv("ORBX_SKIP") ? atoi(getenv("ORBX_SKIP")) : 0; static int ncalls = 0; ++ncalls;\n')
-edit("orb_slam2_e_amd/csrc/orbx_extract.hip", [
-    ("    const int nl = ex->nlevels;\n    orbx::KernelProfiler &pf = ex->prof;\n",
-     "    const int nl = ex->nlevels;\n    orbx::KernelProfiler &pf = ex->prof;\n" + hook + "    const int SK = ncalls < 8 ? 0 : skipmask;\n"),
-    ("            hipLaunchKernelGGL(k_pyr_level0_lin,", "            if (!(SK & 1)) hipLaunchKernelGGL(k_pyr_level0_lin,"),
-    ("            hipLaunchKernelGGL(k_pyr_level0, g,", "            if (!(SK & 1)) hipLaunchKernelGGL(k_pyr_level0, g,"),
-    ("        hipLaunchKernelGGL(k_pyr_resize, g,", "        if (!(SK & 2)) hipLaunchKernelGGL(k_pyr_resize, g,"),
-    ("    pf.start(2, st);\n    if (ex->TS == 52)", "    pf.start(2, st);\n    if (SK & 4) {} else if (ex->TS == 52)"),
-    ("    hipLaunchKernelGGL(k_octree, dim3(nl, batch)", "    if (!(SK & 8)) hipLaunchKernelGGL(k_octree, dim3(nl, batch)"),
-    ("        if (S > 256)\n            hipLaunchKernelGGL(k_blur<true>", "        if (SK & 16) {} else if (S > 256)\n            hipLaunchKernelGGL(k_blur<true>"),
-    ("        hipLaunchKernelGGL(k_describe, dim3(nchunks, batch)", "        if (!(SK & 32)) hipLaunchKernelGGL(k_describe, dim3(nchunks, batch)"),
-])
+# the six launch calls of orbx_extract_batch, one bit each (a skipped stage's profiler bracket goes with it)
+stages = [("launch_level0(ex, d_img, stride, frame_stride, batch, st);", 1), ("launch_pyramid(ex, batch, st);", 2), ("launch_fast(ex, batch, st);", 4),
+          ("launch_octree(ex, batch, st);", 8), ("launch_blur(ex, batch, st);", 16), ("launch_describe(ex, batch, st);", 32)]
+edit("orb_slam2_e_amd/csrc/orbx_extract.hip",
+     [("    " + stages[0][0] + "\n", hook + "    const int SK = ncalls < 8 ? 0 : skipmask;\n    " + stages[0][0] + "\n")] +
+     [("    " + call + "\n", "    if (!(SK & %d)) " % bit + call + "\n") for call, bit in stages])
 edit("orb_slam2_e_amd/csrc/orbm_match.hip", [
     ("                              int th, float nnratio, int *best, int *second, int *idx, int *match12, int *nmatch)\n{\n",
      "                              int th, float nnratio, int *best, int *second, int *idx, int *match12, int *nmatch)\n{\n" + hook +

@@ -1,9 +1,12 @@
 """Development aid: shader-clock time per phase of k_fast_cells / k_describe / k_pyr_resize per workgroup, and how many
 workgroups are resident over a launch (100-MHz wall clock).  Needs a library built with the markers switched on -- never the
 product build:
-    cd orb_slam2_e_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
-        -mllvm -amdgpu-mfma-vgpr-form=1 -DORBX_PHASE_TIMING -c orbx_extract.hip -o /tmp/x.o && \
-        hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib_ph.so /tmp/x.o orbx_stereo.o orbm_match.o orbm_search.o fem.o
+    cd orb_slam2_e_amd/csrc && make && mkdir -p /tmp/ph && \
+        for u in extract pyramid fast octree blur describe; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off \
+            -fno-fast-math -mllvm -amdgpu-mfma-vgpr-form=1 -DORBX_PHASE_TIMING -c orbx_$u.hip -o /tmp/ph/orbx_$u.o || break; done && \
+        hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib_ph.so /tmp/ph/orbx_*.o orbx_stereo.o orbm_*.o fem.o
+(the FAST, describe, pyramid and octree units each hold their own quarter of the records, and orbx_extract.hip puts the four
+together in orbx_debug_phases: all six extractor units are built with the flag)
 On the GPU box: cp orb_slam2_e_amd/lib_ph.so orb_slam2_e_amd/liborbslam_hip.so && PYTHONPATH=. python3 tools/phase_timing.py
 (the markers cost a few per cent and a register or two: compare kernels with tools/trace_ab.sh, not with this build)."""
 import ctypes as C, sys
