@@ -182,8 +182,14 @@ int orbx_profile_read(orbx_extractor *ex, int max_kinds, const char **names, dou
 /* -------------------------------------------------------------------- matcher
  * Data plane of ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:37-111).            */
 
+/* Counts that become the y dimension of a launch grid.  The device's limit is hipDeviceProp_t::maxGridSize[1]; the library
+ * relies on no more than 65,535 there, the smallest value a HIP platform reports: orbm_match_batch_dev (npairs) and orbm_bow_transform_batch_dev (nsets) refuse a
+ * larger count with ORBX_ERR_UNSUPPORTED before anything is queued; orbm_hamming_matrix takes any nA (its kernel strides
+ * over the rows). */
+#define ORBM_MAX_GRID_Y 65535
+
 /* ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:1848-1864) for all pairs:
- * out[nA][nB] uint16.  Host pointers; runs on the device. */
+ * out[nA][nB] uint16.  Host pointers; runs on the device.  Any nA, nB >= 0 whose product fits the device. */
 int orbm_hamming_matrix(const uint8_t *A, int nA, const uint8_t *B, int nB, uint16_t *out);
 
 /* Best / second-best / arg-best per query row over all of B, first index wins
@@ -379,7 +385,8 @@ int orbm_distinctive_descriptors(const uint8_t *desc, const int32_t *off, int m,
  * level L - levelsup (the FeatureVector key) and the word weight; BowVector /
  * FeatureVector (std::map insertions, addWeight in feature order, L1 normalise)
  * stay on the host.  The batch form reads descriptor sets resident in HBM
- * (orbx_result_dev layout) and leaves its outputs there. */
+ * (orbx_result_dev layout) and leaves its outputs there; a count outside [0, cap] is clamped, rows past a set's count are
+ * not written, and nsets is at most ORBM_MAX_GRID_Y = 65,535 (more: ORBX_ERR_UNSUPPORTED, nothing queued). */
 typedef struct orbm_vocabulary orbm_vocabulary;
 int orbm_vocab_create(const int32_t *child_off, const int32_t *child_ids, const uint8_t *node_desc, const int32_t *node_word,
                       const double *node_weight, int nnodes, int L, orbm_vocabulary **out);
@@ -397,7 +404,8 @@ int orbm_match_filter(int nA, const int32_t *best, const int32_t *second, const 
 /* Batched device form used by the frames/s pipeline: descriptor sets
  * desc_dev[nsets][cap][32] with counts_dev[nsets]; pair p matches set qa[p]
  * (queries) against set qb[p].  Outputs (device): best/second/idx/match12
- * [npairs][cap] int32, nmatch[npairs].  Asynchronous on `stream`.  When the sets come straight from
+ * [npairs][cap] int32, nmatch[npairs]; npairs is at most ORBM_MAX_GRID_Y = 65,535 (more: ORBX_ERR_UNSUPPORTED, nothing
+ * queued, nmatch not cleared).  Asynchronous on `stream`.  When the sets come straight from
  * orbx_extract_batch_dev, give both calls the SAME non-NULL stream (or synchronise between them): with NULL the
  * extractor works on its handle's stream and this call on the default stream, and nothing orders the next
  * extraction on that handle behind a match that still reads its descriptors. */

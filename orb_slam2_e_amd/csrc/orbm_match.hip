@@ -609,9 +609,11 @@ __global__ __launch_bounds__(MT) void k_bow_transform(const uint4 *__restrict__ 
 __global__ __launch_bounds__(MT) void k_hamming_matrix(const uint4 *__restrict__ A, int nA, const uint4 *__restrict__ B,
                                                        int nB, unsigned short *__restrict__ out)
 {
-    const int j = blockIdx.x * MT + threadIdx.x, i = blockIdx.y;
+    const int j = blockIdx.x * MT + threadIdx.x;
     if (j >= nB) return;
-    out[(size_t)i * nB + j] = (unsigned short)hamming256(A[2 * i], A[2 * i + 1], B[2 * j], B[2 * j + 1]);
+    const uint4 b0 = B[2 * j], b1 = B[2 * j + 1];
+    for (int i = blockIdx.y; i < nA; i += gridDim.y)     // the grid's y dimension holds at most ORBM_MAX_GRID_Y rows: stride over the rest
+        out[(size_t)i * nB + j] = (unsigned short)hamming256(A[2 * i], A[2 * i + 1], b0, b1);
 }
 
 orbx::KernelProfiler g_prof;
@@ -701,6 +703,7 @@ int orbm_match_batch_dev(const uint8_t *desc_dev, const int32_t *counts_dev, int
                          int32_t *second_dev, int32_t *idx_dev, int32_t *match12_dev, int32_t *nmatch_dev, void *stream)
 {
     if (!desc_dev || !counts_dev || cap <= 0 || npairs <= 0) ORBX_FAIL(ORBX_ERR_ARG, "bad match arguments");
+    if (npairs > ORBM_MAX_GRID_Y) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 65,535 pairs in one call (the grid's y dimension)");
     ORBX_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     // sets that are an extractor's resident results, produced on another stream (both calls handed NULL: the extractor then
@@ -892,6 +895,7 @@ int orbm_bow_transform_batch_dev(orbm_vocabulary *v, const uint8_t *desc_dev, co
                                  int levelsup, int32_t *word_id_dev, int32_t *node_id_dev, void *stream)
 {
     if (!v || !desc_dev || !counts_dev || cap <= 0 || nsets <= 0 || !word_id_dev || !node_id_dev) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    if (nsets > ORBM_MAX_GRID_Y) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 65,535 descriptor sets in one call (the grid's y dimension)");
     ORBX_NEED_DEVICE();
     hipEvent_t e0, e1;
     g_prof.pair(1, &e0, &e1);                      // (orbm_profile_enable(2): the kernel's own start and end, as a kernel trace sees them)
@@ -910,7 +914,7 @@ int orbm_hamming_matrix(const uint8_t *A, int nA, const uint8_t *B, int nB, uint
     StagedCall sc;
     const size_t o_a = sc.in(A, (size_t)nA * 32), o_b = sc.in(B, (size_t)nB * 32), o_o = sc.out(sizeof(uint16_t) * (size_t)nA * nB);
     if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
-    hipLaunchKernelGGL(k_hamming_matrix, dim3((nB + MT - 1) / MT, nA), dim3(MT), 0, sc.stream(), sc.d<const uint4>(o_a), nA,
+    hipLaunchKernelGGL(k_hamming_matrix, dim3((nB + MT - 1) / MT, std::min(nA, ORBM_MAX_GRID_Y)), dim3(MT), 0, sc.stream(), sc.d<const uint4>(o_a), nA,
                        sc.d<const uint4>(o_b), nB, sc.d<unsigned short>(o_o));
     ORBX_HIP(hipGetLastError());
     if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
