@@ -72,8 +72,9 @@ struct orbx_extractor {
     int nfeat[orbx_detail::MAXL];
     int taps[4];
     int resident_waves = 8192;              // CUs x 32 wave slots of the device the handle was created on
-    int resize_nxi[orbx_detail::MAXL] = {};
-    int resize_tailwin[orbx_detail::MAXL] = {}; // the tail tiles of k_pyr_resize may use 8-byte source windows at this level // interior workgroups per row group of k_pyr_resize (0: no fast path at this level)
+    int resize_nxi[orbx_detail::MAXL] = {};     // the interior groups of this level keep their source columns in an 8-byte window
+    int resize_copy[orbx_detail::MAXL] = {};    // k_pyr_resize serves this level (window holds, w and h >= 20: borders are copies); 0: k_pyr_resize_small
+    int resize_tailwin[orbx_detail::MAXL] = {}; // k_pyr_resize_small may use 8-byte source windows at this level (border dwords included)
     int kcap; // keypoints per frame the result arrays hold: nfeatures + 3*nlevels, more on wide frames with tiny quotas (orbx_reserve)
     int kcap_params = 0;
     size_t pin_result_off = 0;   // where the last orbx_extract's result block starts in h_pin

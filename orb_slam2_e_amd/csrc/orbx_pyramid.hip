@@ -1,7 +1,8 @@
 // orbx_pyramid.hip -- the extractor's image pyramid (ComputePyramid, ORBextractor.cc:1115-1140): level 0 with its border
-// (k_pyr_level0 / k_pyr_level0_lin), and the levels above it either one launch per level (k_pyr_resize) or, for small batches, all
-// in one launch (k_pyr_chain).  What the kernels require of the host stands below them: the resize tables and the window checks
-// (plan_pyramid), the chain's tiling (plan_chain), and the launch geometry (launch_level0, launch_pyramid).
+// (k_pyr_level0 / k_pyr_level0_lin), and the levels above it either one launch per level (k_pyr_resize; k_pyr_resize_small where its
+// copy rule does not hold) or, for small batches, all in one launch (k_pyr_chain).  What the kernels require of the host stands
+// below them: the resize tables, the window checks and the copy rule (plan_pyramid), the cut of a row into waves (resize_split),
+// the chain's tiling (plan_chain), and the launch geometry (launch_level0, launch_pyramid).
 #include <stdlib.h>
 #include <string.h>
 
@@ -18,8 +19,9 @@ namespace {
 // ------------------------------------------------------------------ pyramid
 // Both pyramid kernels are latency-bound (two dependent global loads per output),
 // so every thread produces 4 pixels (one dword store) in PYR_ROWS rows and keeps
-// all of their loads in flight at once.  The 19-px REFLECT_101 border is
-// recomputed through the reflected coordinate instead of copied afterwards.
+// all of their loads in flight at once.  The 19-px REFLECT_101 border of a resized
+// level is a copy of pixels the same wave has just computed (k_pyr_resize), stored
+// in the same pass; level 0 and the tiny levels read it through the reflected coordinate.
 // Rows per thread, round 4 (same-box A/B of the pipelined step, three rounds each): 4 -> 0.2495 ms, 6 -> 0.2474, 8 -> 0.2447-0.2471,
 // 10 -> 0.2536, 16 -> 0.2568.  A resize launch alone is no faster with 8 (8.7 against 8.1 us: half the waves, each twice as long) -- but
 // the chain then holds half the wave slots while it waits for memory, and the other contexts' kernels get them.
@@ -118,8 +120,9 @@ __global__ __launch_bounds__(64) void k_pyr_level0_lin(const uint8_t *__restrict
 // Interior dword groups (4 pixels with 0 <= x < w, no reflection): the source columns of such a group are
 // non-decreasing and span at most 8 bytes (the host checks it per level), so each source row is ONE unaligned
 // 8-byte load and a pixel's pair (S[sx], S[sx+1]) is one v_perm_b32 into two u16 halves, times (a0, a1) one
-// v_dot2_u32_u16.  The groups that touch the border take their pixels one by one through the reflected
-// coordinate (nxf = 0: every group does).
+// v_dot2_u32_u16.  The last group of a row whose width is no multiple of 4 reads clamped table entries for the pixels past
+// w - 1 (same window, bytes replaced by border bytes before the store).  k_pyr_resize_small takes every pixel one by one
+// through the reflected coordinate instead.
 // (b (r >> 4)) >> 16 = floor((b 2^12) (r & ~15) / 2^32): both factors are below 2^24 (b <= 2048, r <= 255 * 2048), so
 // it is one v_mul_hi_u32_u24 after the mask instead of shift, multiply, shift.  bs = b << 12.
 // (written as asm: from the masked 64-bit product the compiler makes v_mul_hi_u32, a quarter-rate instruction -- 64 of them were
@@ -138,97 +141,187 @@ __device__ __forceinline__ uint32_t resize_vertical(int r0, int r1, uint32_t bs0
     return v > 255u ? 255u : v;
 }
 typedef unsigned short pyr_u16x2 __attribute__((ext_vector_type(2)));
-// Thread -> work.  A row of level 1 has 133 interior groups + 11 border groups: one wave per 64 groups of a row left the
-// third and the border wave of every row 80-90 % empty (45-55 % of all lanes idle).  Now: workgroups 0 .. nff*nrg-1 are full
-// waves of 64 consecutive interior groups of ONE row group (contiguous 256-byte rows in and out: tiling these 16 x 4
-// instead was slower although it saved instructions -- the kernel lives on the memory pipe); the REST of every row
-// (the last ngi % 64 interior groups and the border groups, `ntail` in all) is gathered tw groups x 64/tw row groups per
-// wave and goes through the coordinate-by-coordinate path, which serves interior groups as well.  Dwords of pure row
-// padding (outside the 19-px border) are not written: the workspace is zeroed once.
+// Thread -> work.  A level with the copy rule (plan_pyramid: w, h >= 20 and the 8-byte window holds) is resampled ONCE: image rows
+// 0 .. h-1 only, in row groups of PYR_ROWS, and of a padded row the dwords xlo .. xhi, lane = dword.  A row is cut from the left
+// into full waves of 64 dwords (resize_split); what is left over (fewer than 64) is a TILE of the row's LAST 16, 32 or 64 dwords x
+// 4, 2 or 1 row groups per wave, which stores the leftover dwords and every dword of the right border (a full wave then stores
+// interior dwords only; the other dwords of the tile are computed for the border's sake).  So the first wave of a row holds the
+// left border and pixels 0 .. 20, the last one -- tile or full wave -- the right border and the 20-odd pixels it mirrors.
+// Line ownership: the cuts are at dwords xlo + 64 k = 3 + 64 k, so the 64-byte line that holds a cut is stored by the two waves
+// that meet there (full wave k-1 and full wave k, or the last full wave and the tile), every other line by one wave.  A cut at
+// whole lines (four lines per wave) was measured: the same WRITE_SIZE (54.8 MB per 64-frame step either way, 1.06 x the padded
+// bytes -- the L2 merges the halves), but 25,344 waves and 15.2 M vector instructions per step instead of 24,384 and 13.1 M,
+// because a row of 16 k + a few dwords then costs a whole extra wave per row group; profiles/pyramid_border_copy_notes.md.
+//   interior dword (4 pixels, 0 <= x < w)   the 8-byte-window arithmetic above, stored as computed
+//   border dword, and the dword that straddles the right image edge (w % 4 != 0)   REFLECT_101 says byte x = -k is pixel k and
+//       x = w-1+k is pixel w-1-k: its (up to) four source pixels lie in two neighbouring groups {q, q+1} of the same wave, so the
+//       lane fetches those two finished dwords (ds_bpermute) and picks its bytes with one v_perm_b32 -- selector and source lanes
+//       are set up once per wave; bytes of row padding select the constant 0.  Only the first and the last wave of a row do this
+//       (a wave-uniform branch); their interior lanes fetch themselves with the identity selector.  A border lane computes the
+//       group it is clamped to beside its neighbours (same cache lines) and its own result is dropped.
+//   border ROWS   the lane that holds image row y also stores it to padded row EDGE - y (1 <= y <= 19) and to padded row
+//       EDGE + 2 (h-1) - y (h-20 <= y <= h-2): the same registers, another row address; no row-table entry is read for a border row.
+// The column table carries up to three clamped entries past w (plan_pyramid) so that the last, partial group reads its int4 pair
+// like every other.  Dwords of pure row padding (outside the 19-px border) are not written: the workspace is zeroed once.
+struct ResizeLane {
+    const uint8_t *src;      // level l-1, pixel (sx0, 0) of the lane's window
+    uint8_t *out;            // level l, the lane's dword of padded row 0
+    uint32_t coef[4], sel[4];
+    uint32_t bsel;           // byte selector of the exchange (edge waves)
+    int lane_lo, lane_hi;    // its two source lanes, as ds_bpermute addresses
+    bool store;
+};
+// NR rows from image row y0 on.  UNIFORM: y0 is the same in all lanes (full waves): row table through the scalar cache, the row
+// conditions scalar branches; otherwise (tiles) a vector load and predicated stores -- the row table then lies in vector registers,
+// and a tile takes its row group in two halves to stay within the 64 registers that let 8 waves share a SIMD
+template <bool UNIFORM, int NR>
+__device__ __forceinline__ void resize_rows(const ResizeLane &L, int y0, bool edge, int src_stride, int dst_stride, int h,
+                                            const int4 *__restrict__ yt)
+{
+    if (UNIFORM) y0 = __builtin_amdgcn_readfirstlane(y0);
+    int4 yy[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) yy[r] = yt[min(y0 + r, h - 1)];
+    uint2 w0[NR], w1[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        __builtin_memcpy(&w0[r], L.src + (uint32_t)((yy[r].x + EDGE) * src_stride), 8);
+        __builtin_memcpy(&w1[r], L.src + (uint32_t)((yy[r].y + EDGE) * src_stride), 8);
+    }
+    uint32_t out[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        out[r] = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int r0 = (int)__builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, __builtin_amdgcn_perm(w0[r].y, w0[r].x, L.sel[b])),
+                                                       __builtin_bit_cast(pyr_u16x2, L.coef[b]), 0u, false);
+            const int r1 = (int)__builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, __builtin_amdgcn_perm(w1[r].y, w1[r].x, L.sel[b])),
+                                                       __builtin_bit_cast(pyr_u16x2, L.coef[b]), 0u, false);
+            out[r] |= resize_vertical(r0, r1, (uint32_t)yy[r].z << 12, (uint32_t)yy[r].w << 12) << (8 * b);
+        }
+    }
+    if (edge) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(L.lane_lo, (int)out[r]);
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(L.lane_hi, (int)out[r]);
+            out[r] = __builtin_amdgcn_perm(hi, lo, L.bsel);
+        }
+    }
+    if (L.store) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const int y = y0 + r;
+            if (y < h) {
+                *reinterpret_cast<uint32_t *>(L.out + (uint32_t)((y + EDGE) * dst_stride)) = out[r];
+                if (y >= 1 && y <= EDGE) *reinterpret_cast<uint32_t *>(L.out + (uint32_t)((EDGE - y) * dst_stride)) = out[r];
+                if (y >= h - 1 - EDGE && y <= h - 2) *reinterpret_cast<uint32_t *>(L.out + (uint32_t)((EDGE + 2 * (h - 1) - y) * dst_stride)) = out[r];
+            }
+        }
+    }
+}
 __global__ __launch_bounds__(64) void k_pyr_resize(uint8_t *__restrict__ pyr, size_t frame_bytes, LevelInfo src,
                                                    LevelInfo dst, const int2 *__restrict__ xt,
-                                                   const int4 *__restrict__ yt, int nff, int nint, int nrg, int ntail, int tw_shift, int ntw, int rpw, int tail_window)
+                                                   const int4 *__restrict__ yt, int nfull, int tws, int dtile, int rpw)
+{
+    int f, bx;
+    xcd_frame_item(f, bx);
+    const int tid = threadIdx.x;
+    ORBX_PH_INIT(2);
+    const int nrg = (dst.h + PYR_ROWS - 1) / PYR_ROWS, nrgw = (nrg + rpw - 1) / rpw;
+    const int xlo = (PADX - EDGE) >> 2, xhi = (PADX + dst.w + EDGE - 1) >> 2; // first / last dword that holds border or image bytes
+    const bool tile = bx >= nfull * nrgw;      // full waves first (wave kx of the row, row groups rw * rpw ..), then the tiles
+#ifdef ORBX_PHASE_TIMING
+    if (tid == 0) { ph_rec[12] = dst.w; ph_rec[11] = tile ? 0 : 1; }
+#endif
+    int d0, sub, rg;                            // the wave's first dword of the padded row; lane's place in its row; row group
+    bool edge;
+    if (!tile) {
+        const int rw = bx / nfull, kx = bx - rw * nfull;
+        d0 = xlo + 64 * kx; sub = tid; rg = rw * rpw;
+        edge = kx == 0 || (tws == 0 && kx == nfull - 1);
+    } else {
+        const int tw = 1 << tws;
+        sub = tid & (tw - 1);
+        d0 = xhi + 1 - tw; rg = ((bx - nfull * nrgw) << (6 - tws)) + (tid >> tws);
+        edge = true;
+    }
+    const int D = d0 + sub;
+    ResizeLane L;
+    L.store = tile ? D >= dtile : D < dtile;   // dtile: the first dword the tiles store (xhi + 1: no tiles)
+    // every lane computes a group (the border lanes the nearest one: in-bounds loads, result unused) and stays active for the exchange
+    const int g = min(max(D - PADX / 4, 0), ((dst.w + 3) >> 2) - 1);
+    const int4 xa = *reinterpret_cast<const int4 *>(xt + 4 * g), xb = *reinterpret_cast<const int4 *>(xt + 4 * g + 2);
+    const int sx0 = xa.x;
+    L.coef[0] = (uint32_t)xa.y; L.coef[1] = (uint32_t)xa.w; L.coef[2] = (uint32_t)xb.y; L.coef[3] = (uint32_t)xb.w;
+    // selector {byte o, 0, byte o+1, 0} of the 8-byte window, o = sx - sx0
+    L.sel[0] = 0x0c010c00u; L.sel[1] = 0x0c010c00u + (uint32_t)(xa.z - sx0) * 0x00010001u;
+    L.sel[2] = 0x0c010c00u + (uint32_t)(xb.x - sx0) * 0x00010001u; L.sel[3] = 0x0c010c00u + (uint32_t)(xb.z - sx0) * 0x00010001u;
+    L.bsel = 0; L.lane_lo = 0;
+    if (edge) {
+        // the dword's pixels through the mirror (one fold: w >= 20 > EDGE), the lower of the two groups that hold them, and each
+        // byte's place in that pair of dwords
+        int s[4], smin = 1 << 30;
+        bool in[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int p = 4 * D - PADX + b;
+            in[b] = p >= -EDGE && p < dst.w + EDGE;
+            s[b] = p < 0 ? -p : (p >= dst.w ? 2 * (dst.w - 1) - p : p);
+            smin = in[b] ? min(smin, s[b]) : smin;
+        }
+        const int qlo = smin == (1 << 30) ? 0 : smin >> 2;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) L.bsel |= (in[b] ? (uint32_t)(s[b] - 4 * qlo) : 0x0cu) << (8 * b);
+        L.lane_lo = (PADX / 4 + qlo - d0 + (tid - sub)) * 4;      // (byte address of ds_bpermute; the host checked that the pair lies in this wave's row)
+    }
+    L.lane_hi = (L.lane_lo + 4) & 252;
+    L.src = pyr + (size_t)f * frame_bytes + src.off + PADX + sx0;
+    L.out = pyr + (size_t)f * frame_bytes + dst.off + D * 4;
+    // A full wave works on one row group at a time: the row-table entries are wave-uniform and come through the scalar cache; the
+    // column table is read once and serves all rpw row groups of the wave.  The kernel's time is a wave's life (three dependent
+    // memory round trips, 4-6 us) times the number of wave generations, and a level's wave count is what the host sets through
+    // rpw so that one generation holds them all.
+    if (tile && tws != 6) {
+        resize_rows<false, PYR_ROWS / 2>(L, rg * PYR_ROWS, true, src.stride, dst.stride, dst.h, yt);      // (rows past the last: clamped, nothing stored)
+        resize_rows<false, PYR_ROWS / 2>(L, rg * PYR_ROWS + PYR_ROWS / 2, true, src.stride, dst.stride, dst.h, yt);
+    } else {
+        const int nj = tile ? 1 : rpw;          // (a tile as wide as a wave is one row group: uniform like a full wave)
+        for (int j = 0; j < nj; ++j) {
+            if ((rg + j) * PYR_ROWS >= dst.h) break;
+            resize_rows<true, PYR_ROWS>(L, (rg + j) * PYR_ROWS, edge, src.stride, dst.stride, dst.h, yt);
+        }
+    }
+    ORBX_PH(1, tid == 0);   // column table, source rows, arithmetic, exchange, stores
+    ORBX_PH(2, tid == 0);
+    ORBX_PH_END(tid == 0);
+}
+
+// The levels the copy rule does not cover (narrower or lower than 20 px: the mirror folds more than once; or a scale at which a
+// group's source columns do not fit the 8-byte window): every dword of the padded level, border rows and columns included, pixel by
+// pixel through the reflected coordinate.  A tile is 2^tw_shift dwords x 64 >> tw_shift row groups of the padded level; ntw > 1 (a row
+// wider than a wave) only with tw_shift = 6.  No level of a 640 x 480 or 1242 x 375 pyramid takes it.
+__global__ __launch_bounds__(64) void k_pyr_resize_small(uint8_t *__restrict__ pyr, size_t frame_bytes, LevelInfo src,
+                                                         LevelInfo dst, const int2 *__restrict__ xt,
+                                                         const int4 *__restrict__ yt, int ndw, int tw_shift, int ntw, int tail_window)
 {
     int f, bx;
     xcd_frame_item(f, bx);
     const int tid = threadIdx.x;
     ORBX_PH_INIT(2);
 #ifdef ORBX_PHASE_TIMING
-    if (tid == 0) { ph_rec[12] = dst.w; ph_rec[11] = (bx < nff * ((nrg + rpw - 1) / rpw)) ? 1 : 0; }
+    if (tid == 0) { ph_rec[12] = dst.w; ph_rec[11] = 0; }
 #endif
     const int xlo = (PADX - EDGE) >> 2, xhi = (PADX + dst.w + EDGE - 1) >> 2; // first / last dword that holds border or image bytes
-    const int nrgw = (nrg + rpw - 1) / rpw;   // a full wave takes rpw consecutive row groups, one after the other
-    const bool fast = bx < nff * nrgw;
-    int xw, rowg;
-    if (fast) {
-        const int rw = bx / nff;
-        const int g = (bx - rw * nff) * 64 + tid;
-        if (g >= nint) return;   // the last wave of a row may be partly filled (nint = interior groups the full-wave path takes)
-        xw = PADX / 4 + g;
-        rowg = rw * rpw;
-    } else {
-        // tail tile: 2^tw_shift groups x 64 >> tw_shift row groups; ntw > 1 (a tail wider than a wave) only with tw_shift = 6
-        const int tb = bx - nff * nrgw, tr = tb / ntw;
-        const int col = ((tb - tr * ntw) << tw_shift) + (tid & ((1 << tw_shift) - 1));
-        rowg = (tr << (6 - tw_shift)) + (tid >> tw_shift);
-        if (col >= ntail) return;
-        const int nleft = PADX / 4 - xlo;                                  // border groups on the left
-        xw = col < nleft ? xlo + col : PADX / 4 + nint + (col - nleft);      // left border, leftover interior, right border
-    }
+    const int tr = bx / ntw;
+    const int col = ((bx - tr * ntw) << tw_shift) + (tid & ((1 << tw_shift) - 1));
+    const int rowg = (tr << (6 - tw_shift)) + (tid >> tw_shift);
+    if (col >= ndw) return;
+    const int xw = xlo + col;
     if (xw > xhi || rowg * PYR_ROWS >= dst.h + 2 * EDGE) return;
     const uint8_t *base = pyr + (size_t)f * frame_bytes + src.off + PADX;
     uint32_t out[PYR_ROWS];
-    if (fast) {
-        // A full wave works on one row group at a time: the four row-table entries are wave-uniform and come through the
-        // scalar cache; the column table is read once and serves all rpw row groups of the wave.  The kernel's time is a
-        // wave's life (three dependent memory round trips, 4-6 us) times the number of wave generations, and a level's
-        // wave count is what the host sets through rpw so that one generation holds them all.
-        const int px0 = xw * 4 - PADX;
-        const int4 xa = *reinterpret_cast<const int4 *>(xt + px0), xb = *reinterpret_cast<const int4 *>(xt + px0 + 2);
-        const int sx0 = xa.x;
-        const uint32_t coef[4] = {(uint32_t)xa.y, (uint32_t)xa.w, (uint32_t)xb.y, (uint32_t)xb.w};
-        // selector {byte o, 0, byte o+1, 0} of the 8-byte window, o = sx - sx0
-        const uint32_t sel[4] = {0x0c010c00u, 0x0c010c00u + (uint32_t)(xa.z - sx0) * 0x00010001u,
-                                 0x0c010c00u + (uint32_t)(xb.x - sx0) * 0x00010001u, 0x0c010c00u + (uint32_t)(xb.z - sx0) * 0x00010001u};
-        const int rg0 = __builtin_amdgcn_readfirstlane(rowg);
-        for (int j = 0; j < rpw; ++j) {
-            const int rg = rg0 + j;
-            if (rg * PYR_ROWS >= dst.h + 2 * EDGE) break;
-            int4 yy[PYR_ROWS];
-#pragma unroll
-            for (int r = 0; r < PYR_ROWS; ++r) {
-                const int row = rg * PYR_ROWS + r;
-                yy[r] = yt[reflect101((row < dst.h + 2 * EDGE ? row : 0) - EDGE, dst.h)];
-            }
-            uint2 w0[PYR_ROWS], w1[PYR_ROWS];
-#pragma unroll
-            for (int r = 0; r < PYR_ROWS; ++r) {
-                __builtin_memcpy(&w0[r], base + (uint32_t)((yy[r].x + EDGE) * src.stride + sx0), 8);
-                __builtin_memcpy(&w1[r], base + (uint32_t)((yy[r].y + EDGE) * src.stride + sx0), 8);
-            }
-#pragma unroll
-            for (int r = 0; r < PYR_ROWS; ++r) {
-                out[r] = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const int r0 = (int)__builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, __builtin_amdgcn_perm(w0[r].y, w0[r].x, sel[b])),
-                                                               __builtin_bit_cast(pyr_u16x2, coef[b]), 0u, false);
-                    const int r1 = (int)__builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, __builtin_amdgcn_perm(w1[r].y, w1[r].x, sel[b])),
-                                                               __builtin_bit_cast(pyr_u16x2, coef[b]), 0u, false);
-                    out[r] |= resize_vertical(r0, r1, (uint32_t)yy[r].z << 12, (uint32_t)yy[r].w << 12) << (8 * b);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < PYR_ROWS; ++r) {
-                const int row = rg * PYR_ROWS + r;
-                if (row < dst.h + 2 * EDGE)
-                    *reinterpret_cast<uint32_t *>(pyr + (size_t)f * frame_bytes + dst.off + (uint32_t)(row * dst.stride + xw * 4)) = out[r];
-            }
-        }
-        ORBX_PH(1, tid == 0);
-        ORBX_PH_END(tid == 0);
-        return;
-    }
     {
         int4 yy[PYR_ROWS];
 #pragma unroll
@@ -250,10 +343,8 @@ __global__ __launch_bounds__(64) void k_pyr_resize(uint8_t *__restrict__ pyr, si
             keep |= in ? 0xffu << (8 * b) : 0u;
         }
         if (tail_window) {
-            // The four pixels of a border group are reflections of interior pixels, so their source columns lie as close together as
-            // an interior group's (in mirrored order): one 8-byte window from the smallest of them serves all four, as in the
-            // full waves (the host checks the span per level) -- 8 loads per lane instead of 64 single bytes, which made a tail
-            // wave six times as expensive for the texture addresser as a full one.
+            // The four source columns of a dword lie within 7 bytes (the host checks it per level, reflected and clamped columns
+            // included): one 8-byte window from the smallest of them serves all four -- 8 loads per lane instead of 64 single bytes.
             const int smin = min(min(sxs[0], sxs[1]), min(sxs[2], sxs[3]));
             uint32_t sel[4], coef[4];
 #pragma unroll
@@ -492,12 +583,62 @@ void resize_axis(int dn, int sn, std::vector<int> &ofs, std::vector<int> &c0, st
     }
 }
 
+// k_pyr_resize's cut of a padded row of width w: nfull waves of 64 dwords from dword xlo on, and for what is left (fewer than 64)
+// a tile of the row's last 2^tws dwords (16, 32 or 64: 4, 2 or 1 row groups per wave), which stores from dword dtile on: the
+// leftover, and the straddling and right border dwords where the last full wave reaches into them.  tws = 0: nothing is left, and the
+// last full wave holds the right border (dtile = xhi + 1).
+void resize_split(int w, int &nfull, int &tws, int &dtile)
+{
+    const int xlo = (PADX - EDGE) >> 2, xhi = (PADX + w + EDGE - 1) >> 2, ndw = xhi - xlo + 1;
+    nfull = ndw / 64;
+    const int rem = ndw - 64 * nfull;
+    tws = rem == 0 ? 0 : rem <= 16 ? 4 : rem <= 32 ? 5 : 6;
+    dtile = rem == 0 ? xhi + 1 : std::min(xlo + 64 * nfull, PADX / 4 + (w >> 2));
+}
+
+// Whether every border dword (and the straddling one) of such a row finds the two groups its bytes come from in its own wave's
+// row -- the kernel's own lane arithmetic, dword by dword -- and every other wave holds interior dwords only.  True for every
+// w >= 20 (the left border needs groups 0 .. 5, ten dwords behind xlo; the right border the last seven groups, and the last wave's
+// row is the row's last 16 dwords at least); checked all the same, so that another PADX or EDGE one day cannot make a lane fetch
+// from a lane that holds something else.
+bool resize_pairs_in_wave(int w)
+{
+    int nfull, tws, dtile;
+    resize_split(w, nfull, tws, dtile);
+    const int xlo = (PADX - EDGE) >> 2, xhi = (PADX + w + EDGE - 1) >> 2, ngc = (w + 3) >> 2;
+    if (tws && (dtile < xhi + 1 - (1 << tws) || dtile < xlo)) return false;
+    for (int D = xlo; D <= xhi; ++D) {
+        const bool tile = D >= dtile;
+        const int kx = (D - xlo) / 64;
+        if (!tile && kx != 0 && !(tws == 0 && kx == nfull - 1)) {      // a wave between the edges stores what it computed: interior dwords only
+            if (D < PADX / 4 || 4 * (D - PADX / 4) + 3 >= w) return false;
+            continue;
+        }
+        const int d0 = tile ? xhi + 1 - (1 << tws) : xlo + 64 * kx, d1 = tile ? xhi + 1 : d0 + 64;
+        int smin = 1 << 30, smax = -1;
+        for (int b = 0; b < 4; ++b) {
+            const int p = 4 * D - PADX + b;
+            if (p < -EDGE || p >= w + EDGE) continue;
+            const int s = p < 0 ? -p : (p >= w ? 2 * (w - 1) - p : p);
+            if (s < 0 || s >= w) return false;
+            smin = std::min(smin, s); smax = std::max(smax, s);
+        }
+        if (smax < 0) return false;
+        const int qlo = smin >> 2, qhi = smax >> 2;
+        if (qhi > qlo + 1 || qhi >= ngc) return false;
+        if (PADX / 4 + qlo < d0 || PADX / 4 + qhi >= d1) return false;
+    }
+    return true;
+}
+
 } // namespace
 
 namespace orbx_detail {
 
-// Level l's resize tables from level l-1 (appended to xt / yt, which become d_xt / d_yt), and whether k_pyr_resize's 8-byte source
-// windows hold at this level: resize_nxi (interior groups) and resize_tailwin (tail tiles).
+// Level l's resize tables from level l-1 (appended to xt / yt, which become d_xt / d_yt), and which kernel serves the level:
+// resize_nxi (the interior groups' 8-byte source windows hold), resize_copy (k_pyr_resize's copy rule holds; no level of a
+// 640 x 480 or 1242 x 375 pyramid fails it, and the planner accepts no level under 62 px a side) and, for k_pyr_resize_small,
+// resize_tailwin (every dword of the padded row, border included, keeps its source columns in an 8-byte window).
 int plan_pyramid(orbx_extractor *ex, int l, std::vector<int2> &xt, std::vector<int4> &yt)
 {
     LevelInfo &lv = ex->lv[l];
@@ -520,9 +661,16 @@ int plan_pyramid(orbx_extractor *ex, int l, std::vector<int2> &xt, std::vector<i
         for (int k = 1; k < 4; ++k) window_ok = window_ok && g[k].x >= g[k - 1].x;
         window_ok = window_ok && g[3].x + 1 - g[0].x <= 7;
     }
+    // the last group of a width that is no multiple of 4 is filled up with copies of the last entry (k_pyr_resize reads whole groups;
+    // the bytes past w - 1 are replaced by border bytes): non-decreasing like the others, and no wider than a whole group
+    const int2 xlast = xt[lv.xtab + lv.w - 1];
+    for (int d = lv.w; d & 3; ++d) xt.push_back(xlast);
+    const bool last_ok = (lv.w & 3) == 0 || xt[lv.xtab + lv.w - 1].x + 1 - xt[lv.xtab + (lv.w & ~3)].x <= 7;
     ex->resize_nxi[l] = window_ok ? 1 : 0;   // the 8-byte-window fast path may serve this level's interior groups
-    {   // ... and the tail tiles' groups (border groups: reflected columns; row padding: clamped ones) if every dword group of
-        // the padded row keeps its four source columns within 7 bytes
+    // the copy rule of k_pyr_resize: borders are single mirror images of pixels of the same wave; k_pyr_resize_small otherwise
+    ex->resize_copy[l] = window_ok && last_ok && lv.w >= EDGE + 1 && lv.h >= EDGE + 1 && resize_pairs_in_wave(lv.w) ? 1 : 0;
+    {   // k_pyr_resize_small may use windows too (border dwords: reflected columns; row padding: clamped ones) if every dword
+        // of the padded row keeps its four source columns within 7 bytes
         bool ok = true;
         for (int xw = (PADX - EDGE) >> 2; xw <= (PADX + lv.w + EDGE - 1) >> 2; ++xw) {
             int lo = 1 << 30, hi = -1;
@@ -693,26 +841,28 @@ void launch_pyramid(orbx_extractor *ex, int batch, hipStream_t st)
     }
     for (int l = 1; l < nl; l++) {
         const LevelInfo &lv = ex->lv[l];
-        const int ngi = lv.w >> 2, xlo = (PADX - EDGE) >> 2, xhi = (PADX + lv.w + EDGE - 1) >> 2;
-        // waves of 64 consecutive interior groups of a row group (8-byte-window path); a last, partly filled one when at least
-        // 24 groups are left: the byte-by-byte path of the tail tiles costs 64 loads per lane (at levels 6-7 of a 640 x 480
-        // frame EVERY group went through it: fewer than 64 interior groups per row)
-        const int nff = ex->resize_nxi[l] ? (ngi % 64 >= 24 ? ngi / 64 + 1 : ngi / 64) : 0;
-        const int nint = std::min(nff * 64, ngi);                                  // interior groups the full-wave path takes
-        const int ntail = (xhi - xlo + 1) - nint;                                  // what is left of a row: leftover interior + border groups
-        const int tw_shift = ntail <= 16 ? 4 : ntail <= 32 ? 5 : 6;                // tail tile: 16 x 4, 32 x 2 or 64 x 1 (groups x row groups)
-        const int nrg = (lv.h + 2 * EDGE + PYR_ROWS - 1) / PYR_ROWS, rpt = 64 >> tw_shift;
-        const int ntw = (ntail + (1 << tw_shift) - 1) >> tw_shift;                 // tail waves across a row (> 1 only when ntail > 64)
-        // row groups per full wave: two when one would need a second generation of resident waves (the kernel holds 8 waves
-        // per SIMD) -- a second generation costs a whole wave's life, a longer wave only its extra rows.  Measured per 64-frame
-        // chain of seven launches: 1 -> 0.100, 2 -> 0.094, 3 -> 0.098, 4 -> 0.103 ms
-        const int ntailw = ntw * ((nrg + rpt - 1) / rpt);
-        int rpw = 1;
-        while (rpw < 2 && (size_t)(nff * ((nrg + rpw - 1) / rpw) + ntailw) * batch > (size_t)ex->resident_waves) ++rpw;
-        dim3 g(nff * ((nrg + rpw - 1) / rpw) + ntailw, batch);
         pf.start(1, st);
-        hipLaunchKernelGGL(k_pyr_resize, g, dim3(64), 0, st, ex->d_pyr, ex->frame_bytes, ex->lv[l - 1], lv,
-                           ex->d_xt + lv.xtab, ex->d_yt + lv.ytab, nff, nint, nrg, ntail, tw_shift, ntw, rpw, ex->resize_tailwin[l]);
+        if (ex->resize_copy[l]) {
+            // full waves across a row x row groups of the IMAGE rows (the border rows ride with the rows they mirror), and the tiles
+            int nfull, tws, dtile;
+            resize_split(lv.w, nfull, tws, dtile);
+            const int nrg = (lv.h + PYR_ROWS - 1) / PYR_ROWS;
+            const int ntile = tws ? (nrg + (64 >> tws) - 1) / (64 >> tws) : 0;
+            // row groups per full wave: two when one would need a second generation of resident waves (the kernel holds 8 waves
+            // per SIMD) -- a second generation costs a whole wave's life, a longer wave only its extra rows.  Measured per 64-frame
+            // chain of seven launches (round 4): 1 -> 0.100, 2 -> 0.094, 3 -> 0.098, 4 -> 0.103 ms
+            int rpw = 1;
+            while (rpw < 2 && (size_t)(nfull * ((nrg + rpw - 1) / rpw) + ntile) * batch > (size_t)ex->resident_waves) ++rpw;
+            hipLaunchKernelGGL(k_pyr_resize, dim3(nfull * ((nrg + rpw - 1) / rpw) + ntile, batch), dim3(64), 0, st, ex->d_pyr, ex->frame_bytes,
+                               ex->lv[l - 1], lv, ex->d_xt + lv.xtab, ex->d_yt + lv.ytab, nfull, tws, dtile, rpw);
+        } else {
+            const int ndw = ((PADX + lv.w + EDGE - 1) >> 2) - ((PADX - EDGE) >> 2) + 1;   // dwords of a padded row that hold border or image bytes
+            const int tw_shift = ndw <= 16 ? 4 : ndw <= 32 ? 5 : 6;                      // tile: 16 x 4, 32 x 2 or 64 x 1 (dwords x row groups)
+            const int nrg = (lv.h + 2 * EDGE + PYR_ROWS - 1) / PYR_ROWS, rpt = 64 >> tw_shift;
+            const int ntw = (ndw + (1 << tw_shift) - 1) >> tw_shift;                     // tiles across a row (> 1 only when ndw > 64)
+            hipLaunchKernelGGL(k_pyr_resize_small, dim3(ntw * ((nrg + rpt - 1) / rpt), batch), dim3(64), 0, st, ex->d_pyr, ex->frame_bytes,
+                               ex->lv[l - 1], lv, ex->d_xt + lv.xtab, ex->d_yt + lv.ytab, ndw, tw_shift, ntw, ex->resize_tailwin[l]);
+        }
         pf.stop(1, st);
     }
 }
