@@ -36,7 +36,7 @@ const char *orbx_last_error(void);
  * orbm_debug_last_sim3_waits; orbm_optimize_sim3, orbm_debug_last_sim3_opt_waits; orbm_map_create / _destroy / _size,
  * orbm_search_by_projection_map_poses, orbm_frame_search_by_projection_map_poses, orbm_debug_last_map_poses_waits;
  * orbm_init_find_models, orbm_init_check_rt, orbm_init_reconstruct_f, orbm_debug_last_init_waits, orbm_debug_init_svd;
- * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits. */
+ * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits; orbm_pnp_hypotheses, orbm_debug_last_pnp_waits, orbm_debug_pnp_pose. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -659,6 +659,54 @@ int orbm_sim3_hypotheses(const orbm_sim3_problem *problems, int P, const float *
 /* Host waits (stream synchronisations) of the last orbm_sim3_hypotheses call of this process: 1 when it launched, 0 when it
  * returned before the launch. */
 int orbm_debug_last_sim3_waits(void);
+
+/* ------------------------------------------- PnPsolver: every EPnP RANSAC hypothesis of a relocalisation in one call
+ * PnPsolver::iterate (src/PnPsolver.cc:170-263) draws four indices per iteration from a freshly reset list (:193-206), so no
+ * iteration depends on an earlier one: the caller draws the sets of all iterations first, this call evaluates compute_pose
+ * (:938-986) and CheckInliers (:763-794) for each, runs Refine (:649-694) behind every hypothesis that sets a new best, and what
+ * iterate returns is a fold over the results that the caller runs on the host (include/orbslam_hip.hpp: PnPsolver).  One problem
+ * per candidate keyframe; the pointer walk of the constructor (:81-103) stays with the caller, who passes what it keeps, flat.
+ * All of EPnP is IEEE double with one stated departure from the reference (its SVD's std::hypot). */
+typedef struct orbm_pnp_problem {
+    const float *Xw;          /* [n][3] mvP3Dw, in the constructor's order (:81-103) */
+    const float *uv;          /* [n][2] mvP2D */
+    const int32_t *octave;    /* [n] kp.octave -> mvSigma2 */
+    const int32_t *sets;      /* [H][4] indices into 0..n-1 as the draw loop leaves them */
+    double fu, fv, uc, vc;
+    float th2;                /* 5.991 */
+    int32_t n, H, min_inliers;/* mRansacMinInliers AFTER SetRansacParameters */
+} orbm_pnp_problem;
+
+typedef struct orbm_pnp_hypothesis {
+    double R[9], t[3], rep_error;  /* mRi, mti, compute_pose's return */
+    int32_t ninliers;              /* mnInliersi */
+    int32_t refined;               /* 1: this hypothesis set a new best with >= min_inliers, Refine() ran on ITS inliers */
+    double Rr[9], tr[3];           /* Refine's mRi, mti   (refined == 1; else 0) */
+    int32_t nrefined, pad;         /* mnRefinedInliers    (refined == 1; else 0) */
+} orbm_pnp_hypothesis;
+
+/* P = 0 .. 64 problems, n <= 8,192 correspondences and H <= 1,024 hypotheses each (beyond: ORBX_ERR_UNSUPPORTED).  P = 0, or H = 0
+ * in every problem: ORBX_OK, nothing is launched.  ORBX_ERR_ARG before the launch: n < 4 with H > 0, a set index outside [0, n),
+ * an octave outside [0, nlevels), min_inliers < 1.  A set MAY repeat an index (the second iterate of the reference erases the
+ * wrong element of its draw list, :315); EPnP of a repeated correspondence is well defined.  level_sigma2 [nlevels] =
+ * mvLevelSigma2.  best_in [P] = mnBestInliers as the solvers carry it into the call (NULL: 0 for all).
+ *   hyp[sum H]        the hypotheses of problem 0, then of problem 1, ...  Within a problem, in order, a hypothesis with
+ *                     ninliers >= min_inliers and ninliers > the running best (which starts at best_in) is a record: refined = 1,
+ *                     and Rr, tr, nrefined are what Refine() computes from its inliers.  The reference also calls Refine() behind
+ *                     hypotheses that reach min_inliers without a record: those repeat the previous computation on an unchanged
+ *                     mvbBestInliers and return the same false.  Records behind the one whose Refine succeeds are speculative.
+ *   inliers           (void *: the words are uint64_t) per problem, behind each other, [H][(n + 63) / 64] 64-bit words: bit i % 64
+ *                     of word i / 64 = mvbInliersi[i]; bits past n are 0.
+ *   refined_inliers   the same layout: mvbRefinedInliers of a record, 0 for every other hypothesis.
+ * A Refine set may hold all n correspondences.  A NaN coordinate is never an inlier. */
+int orbm_pnp_hypotheses(const orbm_pnp_problem *problems, int P, const float *level_sigma2, int nlevels, const int32_t *best_in,
+                        orbm_pnp_hypothesis *hyp, void *inliers, void *refined_inliers);
+/* Host waits (stream synchronisations) of the last orbm_pnp_hypotheses call of this process: 1 when it launched, 0 when it
+ * returned before the launch. */
+int orbm_debug_last_pnp_waits(void);
+/* compute_pose (:938-986) of n = 4 .. 2,048 correspondences in double (pws [n][3], us [n][2]) on the HOST, through the same header
+ * the kernels instantiate; needs no device (test aid).  R [9] row-major, t [3], *rep_error = its return value. */
+int orbm_debug_pnp_pose(const double *pws, const double *us, int n, const double *fu_fv_uc_vc, double *R, double *t, double *rep_error);
 
 /* ------------------------------------------- Optimizer::OptimizeSim3: the loop-closing Sim3 refinement in one call
  * The whole of src/Optimizer.cc:1564-1624 -- optimize(5), the outlier cut, optimize(5 or 10), the final count -- for up to 64 loop

@@ -1713,6 +1713,280 @@ private:
     bool mEvaluated = false;
 };
 
+// PnPsolver (include/PnPsolver.h, src/PnPsolver.cc) over orbm_pnp_hypotheses.  The constructor takes the flat problem -- what the
+// reference's constructor keeps of the frame (:81-103): world positions, undistorted pixels and keypoint octaves of the kept
+// matches, where each stands in vpMapPointMatches (indices = mvKeyPointIndices, nMatches = vpMapPointMatches.size()), the
+// calibration -- and a source of draws: a callback int(int lo, int hi) (inclusive, as DUtils::Random::RandomInt) or pre-drawn
+// sets, consumed in order.  An iterate() draws the sets of every iteration it can run, in the reference's order (:193-206),
+// evaluates them in one orbm_pnp_hypotheses call with the carried mnBestInliers (compute_pose, CheckInliers and the Refine behind
+// every new best), and is then the reference's fold (:187-262) over the results.  The first iterate(5) runs every iteration up to
+// mRansacMaxIts (the loop condition of :187 is an OR); each later call runs nIterations more.  evaluate() does that evaluation for
+// all candidates of a relocalisation in one call.
+// One difference to the reference: the draws of one solver are made together; in Tracking::Relocalization they interleave with the
+// other candidates' draws in five-iteration rounds.  Results equal the reference run whose RNG hands each solver these sets (the
+// reference seeds nothing here), with the arithmetic of DESIGN 22.  iterate() returns true and fills Tcw where the reference
+// returns a non-empty matrix.
+class PnPsolver {
+public:
+    struct Problem {
+        std::vector<float> Xw, uv;              // [n][3] mvP3Dw, [n][2] mvP2D
+        std::vector<int32_t> octave;            // [n]
+        std::vector<int32_t> indices;           // [n] mvKeyPointIndices; empty: 0 .. n-1
+        int nMatches = -1;                      // vpMapPointMatches.size(); -1: n
+        double fu = 0, fv = 0, uc = 0, vc = 0;
+        std::vector<float> levelSigma2;         // mvLevelSigma2
+    };
+    struct RecordedPose { double R[9], t[3]; int nInliers, iteration; };      // RPoses / tPoses [iteration], inlierPoses of the fork's first stage
+    typedef int (*DrawFn)(int lo, int hi);
+    typedef bool (*AcceptFn)(const double R[9], const double t[3], void *user);
+
+    PnPsolver(Problem problem, DrawFn draw) : mP(std::move(problem)), mDraw(draw) { init(); }
+    PnPsolver(Problem problem, std::vector<int32_t> sets) : mP(std::move(problem)), mDraw(nullptr), mSets(std::move(sets)) { init(); }
+    PnPsolver(const PnPsolver &) = delete;
+    PnPsolver &operator=(const PnPsolver &) = delete;
+
+    // :123-159
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4f,
+                             float th2 = 5.991f)
+    {
+        mRansacProb = probability; mRansacMinInliers = minInliers; mRansacMaxIts = maxIterations; mRansacEpsilon = epsilon;
+        mRansacMinSet = minSet; mTh2 = th2;
+        int nMinInliers = (int)(N * mRansacEpsilon);
+        if (nMinInliers < mRansacMinInliers) nMinInliers = mRansacMinInliers;
+        if (nMinInliers < minSet) nMinInliers = minSet;
+        mRansacMinInliers = nMinInliers;
+        if (mRansacEpsilon < (float)mRansacMinInliers / N) mRansacEpsilon = (float)mRansacMinInliers / N;
+        int nIterations;
+        if (mRansacMinInliers == N) nIterations = 1;
+        else {
+            const double v = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow(mRansacEpsilon, 3)));
+            nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : std::numeric_limits<int>::min();   // what x86 makes of it
+        }
+        mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+        mHyp.clear();                           // min_inliers decides the records: evaluate again
+    }
+
+    // The evaluation that each solver's next iterate(nIterations) needs, at most 64 solvers per launch.
+    static int evaluate(const std::vector<PnPsolver *> &solvers, int nIterations = 5)
+    {
+        std::vector<PnPsolver *> todo;
+        for (PnPsolver *s : solvers) {
+            if (!s || s->N < s->mRansacMinInliers || s->mRansacMinSet != 4) continue;
+            const int a = s->mnIterations, b = a + s->span(nIterations);
+            if (b > a && !s->covered(a, b)) todo.push_back(s);
+        }
+        int rc = ORBX_OK;
+        for (size_t b0 = 0; b0 < todo.size() && rc == ORBX_OK; b0 += 64) {
+            const size_t e = std::min(todo.size(), b0 + 64);
+            std::vector<orbm_pnp_problem> probs;
+            std::vector<int32_t> best;
+            size_t total = 0, words = 0;
+            for (size_t k = b0; k < e; ++k) {
+                PnPsolver &s = *todo[k];
+                const int a = s.mnIterations, b = a + s.span(nIterations);
+                if ((rc = s.draw(b, false)) != ORBX_OK) break;
+                probs.push_back(s.problem(a, b));
+                best.push_back(s.mnBestInliers);
+                total += (size_t)(b - a); words += (size_t)(b - a) * (size_t)((s.N + 63) / 64);
+            }
+            if (rc != ORBX_OK) break;
+            std::vector<orbm_pnp_hypothesis> hyp(total ? total : 1);
+            std::vector<uint64_t> masks(words ? words : 1), rmasks(words ? words : 1);
+            const std::vector<float> &sg = todo[b0]->mP.levelSigma2;
+            rc = orbm_pnp_hypotheses(probs.data(), (int)probs.size(), sg.data(), (int)sg.size(), best.data(), hyp.data(), masks.data(), rmasks.data());
+            size_t h0 = 0, w0 = 0;
+            for (size_t k = b0; k < e; ++k) {
+                PnPsolver &s = *todo[k];
+                s.mStatus = rc;
+                const size_t H = (size_t)probs[k - b0].H, W = H * (size_t)((s.N + 63) / 64);
+                if (rc == ORBX_OK) s.store(s.mnIterations, hyp.data() + h0, masks.data() + w0, rmasks.data() + w0, H, W);
+                h0 += H; w0 += W;
+            }
+        }
+        return rc;
+    }
+
+    // iterate (:170-263).  Tcw: 4 x 4 row-major, written when the result is true.
+    bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, float Tcw[16])
+    {
+        bNoMore = false;
+        vbInliers = std::vector<bool>(mNMatches, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers) { bNoMore = true; return false; }
+        {
+            std::vector<PnPsolver *> one(1, this);
+            if (evaluate(one, nIterations) != ORBX_OK || mStatus != ORBX_OK) { bNoMore = true; return false; }      // status() has the code
+        }
+        int nCurrentIterations = 0;
+        while (mnIterations < mRansacMaxIts || nCurrentIterations < nIterations) {
+            const int k = mnIterations - mStart;
+            nCurrentIterations++;
+            mnIterations++;
+            if (consider(k) && mnRefinedInliers > mRansacMinInliers) {      // Refine() (:681)
+                nInliers = mnRefinedInliers;
+                scatter(mRefinedMask, vbInliers);
+                toTcw(mRefinedR, mRefinedt, Tcw);
+                return true;
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) {
+            bNoMore = true;
+            if (mnBestInliers >= mRansacMinInliers && !mBestMask.empty()) {
+                nInliers = mnBestInliers;
+                scatter(mBestMask, vbInliers);
+                toTcw(mBestR, mBestt, Tcw);
+                return true;
+            }
+        }
+        return false;
+    }
+
+    bool find(std::vector<bool> &vbInliers, int &nInliers, float Tcw[16])
+    {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers, nInliers, Tcw);
+    }
+
+    // The first stage of iterate(Frame &, .., Map *) (:267-416) as a fold over one evaluation: mnIterations restarts at 0, the sets
+    // are drawn with that function's own erase rule (:315 overwrites element [idx], not [randi], so a set may repeat a
+    // correspondence), every pose with 2 < inliers < mRansacMinInliers is recorded for the second stage, and accept(R, t, user) --
+    // the caller's whole-map SearchByProjection under the refined pose, true for nMatched >= 12 -- decides a successful Refine.
+    // Refines behind the accepted one are speculative: computed in the same call and never read.
+    bool iterateFrameStage1(int nIterations, AcceptFn accept, void *user, std::vector<bool> &vbInliers, int &nInliers, float Tcw[16],
+                            std::vector<RecordedPose> &poses)
+    {
+        vbInliers = std::vector<bool>(mNMatches, false);
+        nInliers = 0;
+        poses.clear();
+        mnIterations = 0;
+        if (mDraw) mSets.clear();
+        const int total = std::max(mRansacMaxIts, nIterations);
+        if ((mStatus = draw(total, true)) != ORBX_OK) return false;
+        const orbm_pnp_problem q = problem(0, total);
+        std::vector<orbm_pnp_hypothesis> hyp((size_t)total);
+        const size_t W = (size_t)total * (size_t)((N + 63) / 64);
+        std::vector<uint64_t> masks(W ? W : 1), rmasks(W ? W : 1);
+        const int32_t best = mnBestInliers;
+        mStatus = orbm_pnp_hypotheses(&q, 1, mP.levelSigma2.data(), (int)mP.levelSigma2.size(), &best, hyp.data(), masks.data(), rmasks.data());
+        if (mStatus != ORBX_OK) return false;
+        store(0, hyp.data(), masks.data(), rmasks.data(), (size_t)total, W);
+        int verdict = -1;
+        for (int k = 0; k < total; ++k) {
+            mnIterations++;
+            const orbm_pnp_hypothesis &h = mHyp[k];
+            if (h.ninliers > 2 && h.ninliers < mRansacMinInliers) {
+                RecordedPose p;
+                std::memcpy(p.R, h.R, sizeof(p.R)); std::memcpy(p.t, h.t, sizeof(p.t)); p.nInliers = h.ninliers; p.iteration = k;
+                poses.push_back(p);
+            }
+            const int before = mnBestInliers;
+            if (consider(k) && mnRefinedInliers > mRansacMinInliers) {
+                if (mnBestInliers != before) verdict = -1;                  // the same pose gives the same search
+                if (verdict < 0) verdict = accept(mRefinedR, mRefinedt, user) ? 1 : 0;
+                if (verdict == 1) {
+                    nInliers = mnRefinedInliers;
+                    scatter(mRefinedMask, vbInliers);
+                    toTcw(mRefinedR, mRefinedt, Tcw);
+                    return true;
+                }
+            }
+        }
+        return false;
+    }
+
+    int GetRansacMaxIts() const { return mRansacMaxIts; }
+    int GetRansacMinInliers() const { return mRansacMinInliers; }
+    float GetRansacEpsilon() const { return mRansacEpsilon; }
+    int GetIterations() const { return mnIterations; }
+    int GetBestInliers() const { return mnBestInliers; }
+    int status() const { return mStatus; }
+
+private:
+    void init()
+    {
+        N = (int)(mP.Xw.size() / 3);
+        mNMatches = mP.nMatches < 0 ? N : mP.nMatches;
+        SetRansacParameters();
+    }
+    int span(int nIterations) const { return std::max(std::max(mRansacMaxIts - mnIterations, nIterations), 0); }
+    bool covered(int a, int b) const { return !mHyp.empty() && mStart <= a && b <= mStart + (int)mHyp.size(); }
+    orbm_pnp_problem problem(int a, int b) const
+    {
+        orbm_pnp_problem q;
+        q.Xw = mP.Xw.data(); q.uv = mP.uv.data(); q.octave = mP.octave.data(); q.sets = mSets.data() + 4 * (size_t)a;
+        q.fu = mP.fu; q.fv = mP.fv; q.uc = mP.uc; q.vc = mP.vc; q.th2 = mTh2;
+        q.n = N; q.H = b - a; q.min_inliers = mRansacMinInliers;
+        return q;
+    }
+    void store(int start, const orbm_pnp_hypothesis *hyp, const uint64_t *masks, const uint64_t *rmasks, size_t H, size_t W)
+    {
+        mStart = start;
+        mHyp.assign(hyp, hyp + H); mMasks.assign(masks, masks + W); mRMasks.assign(rmasks, rmasks + W);
+    }
+    // :214-232 for the stored hypothesis k: false below mRansacMinInliers; a new best takes its pose, flags and Refine result (a
+    // record here is a record on the device: both start from the same mnBestInliers and walk the same counts); Refine() on an
+    // unchanged mvbBestInliers repeats its last result
+    bool consider(int k)
+    {
+        const orbm_pnp_hypothesis &h = mHyp[k];
+        if (h.ninliers < mRansacMinInliers) return false;
+        if (h.ninliers > mnBestInliers) {
+            const size_t W = (size_t)((N + 63) / 64);
+            mnBestInliers = h.ninliers;
+            std::memcpy(mBestR, h.R, sizeof(mBestR)); std::memcpy(mBestt, h.t, sizeof(mBestt));
+            mBestMask.assign(mMasks.begin() + k * W, mMasks.begin() + (k + 1) * W);
+            mnRefinedInliers = h.nrefined;
+            std::memcpy(mRefinedR, h.Rr, sizeof(mRefinedR)); std::memcpy(mRefinedt, h.tr, sizeof(mRefinedt));
+            mRefinedMask.assign(mRMasks.begin() + k * W, mRMasks.begin() + (k + 1) * W);
+        }
+        return true;
+    }
+    void scatter(const std::vector<uint64_t> &mask, std::vector<bool> &vbInliers) const
+    {
+        for (int i = 0; i < N; i++)
+            if ((mask[i / 64] >> (i % 64)) & 1u) vbInliers[mP.indices.empty() ? i : mP.indices[i]] = true;
+    }
+    static void toTcw(const double R[9], const double t[3], float Tcw[16])     // the float conversion of :223-229
+    {
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) Tcw[4 * r + c] = (float)R[3 * r + c];
+            Tcw[4 * r + 3] = (float)t[r];
+            Tcw[12 + r] = 0.f;
+        }
+        Tcw[15] = 1.f;
+    }
+    int draw(int upTo, bool frameRule)      // the draw loop of :193-206 (frameRule: of :304-317) until mSets holds upTo sets
+    {
+        const size_t need = 4 * (size_t)upTo;
+        if (mSets.size() >= need) return ORBX_OK;
+        if (!mDraw || N < 4) return mStatus = ORBX_ERR_ARG;
+        std::vector<int32_t> avail;
+        for (int h = (int)(mSets.size() / 4); h < upTo; ++h) {
+            avail.resize((size_t)N);
+            for (int i = 0; i < N; ++i) avail[i] = i;
+            int size = N;
+            for (int i = 0; i < 4; ++i) {
+                const int randi = mDraw(0, size - 1);
+                if (randi < 0 || randi >= size) return mStatus = ORBX_ERR_ARG;
+                const int idx = avail[randi];
+                mSets.push_back(idx);
+                avail[frameRule ? idx : randi] = avail[size - 1];       // (the fork's write may land behind the list's end: spare capacity)
+                --size;
+            }
+        }
+        return ORBX_OK;
+    }
+    Problem mP;
+    DrawFn mDraw;
+    std::vector<int32_t> mSets;
+    std::vector<orbm_pnp_hypothesis> mHyp;
+    std::vector<uint64_t> mMasks, mRMasks, mBestMask, mRefinedMask;
+    double mRansacProb = 0.99, mBestR[9], mBestt[3], mRefinedR[9], mRefinedt[3];
+    float mRansacEpsilon = 0.4f, mTh2 = 5.991f;
+    int N = 0, mNMatches = 0, mRansacMinInliers = 8, mRansacMaxIts = 300, mRansacMinSet = 4, mnIterations = 0, mnBestInliers = 0,
+        mnRefinedInliers = 0, mStart = 0, mStatus = ORBX_OK;
+};
+
 // Optimizer::OptimizeSim3 (src/Optimizer.cc:1425-1625) over orbm_optimize_sim3: the caller does the pointer walk of :1483-1520 and
 // passes the correspondences it keeps, flat and in that order; the whole of :1564-1624 -- both optimisation rounds, the cut between
 // them and the final count -- is then ONE library call for up to 64 problems.  kept[i] of a problem says whether the reference

@@ -12,3 +12,4 @@ from .pose import pose_optimization_nr, pose_optimization_nr_batch  # noqa: F401
 from .sim3 import Sim3OptProblem, Sim3Problem, Sim3Solver, optimize_sim3, sim3_hypotheses  # noqa: F401
 from .initializer import Initializer, check_rt, find_models, last_init_waits, reconstruct_f  # noqa: F401
 from .keyframe_database import KeyFrameDatabase  # noqa: F401
+from .pnp import PnPsolver, PnpProblem, pnp_hypotheses  # noqa: F401
