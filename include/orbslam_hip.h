@@ -36,7 +36,8 @@ const char *orbx_last_error(void);
  * orbm_debug_last_sim3_waits; orbm_optimize_sim3, orbm_debug_last_sim3_opt_waits; orbm_map_create / _destroy / _size,
  * orbm_search_by_projection_map_poses, orbm_frame_search_by_projection_map_poses, orbm_debug_last_map_poses_waits;
  * orbm_init_find_models, orbm_init_check_rt, orbm_init_reconstruct_f, orbm_debug_last_init_waits, orbm_debug_init_svd;
- * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits; orbm_pnp_hypotheses, orbm_debug_last_pnp_waits, orbm_debug_pnp_pose. */
+ * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits; orbm_pnp_hypotheses, orbm_debug_last_pnp_waits, orbm_debug_pnp_pose;
+ * orbm_debug_fill_workspaces, orbm_debug_last_search_waits. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -1046,6 +1047,20 @@ int orbm_debug_force_sequential_resolver(int on);
 /* Iterations the parallel resolver needed in the last whole-loop projection search of this process (-1: it gave up after
  * its iteration limit and the sequential resolver produced the result). */
 int orbm_debug_last_resolver_iterations(void);
+/* Host waits (stream synchronisations) of the last whole-loop search of this process that launched anything (orbm_search_projection,
+ * orbm_search_for_initialization, orbm_search_by_bow, the orbm_search_by_projection_* forms, the orbm_track_* calls and their
+ * frame forms): 1 on the common path; one more for every repeated attempt (a window list outgrew its region, the parallel resolver
+ * did not settle) and for sizing the exact lists. */
+int orbm_debug_last_search_waits(void);
+/* Test aid: sets what the pooled scratch memory of the orbm_* calls holds before the next call ("What a call may assume
+ * about its workspace").  Every workspace on the pool's free list -- one that a running call has leased is skipped and not counted --
+ * gets its device arena and its entries buffer filled with the 32-bit `word` (on its own stream, waited for) and its pinned arena
+ * likewise from the host.  as_next_generation != 0: `word` is ignored and each workspace is filled with the generation number its
+ * NEXT call will use (the value a raised flag of that call has).  The pooled blocks of destroyed frames, which the next
+ * orbm_frame_create takes as they are, are filled too: with `word`, or with the first free workspace's next generation (1 when
+ * there is none).  *nworkspaces / *nframe_blocks = how many were filled.  Changes no call and sets nothing a kernel reads as a
+ * switch; results never depend on it.  Needs a device. */
+int orbm_debug_fill_workspaces(uint32_t word, int as_next_generation, int *nworkspaces, int *nframe_blocks);
 
 /* Which kernel the all-pairs matchers (orbm_match_batch_dev, orbm_match_bruteforce) launch.  Both produce the same
  * integers.  ORBM_ALLPAIRS_AUTO (default): a matrix-core kernel (FP4 MFMA computes the selection keys, 4x

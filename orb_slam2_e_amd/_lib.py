@@ -17,7 +17,7 @@ _LIB = None
 
 # C type of a parameter passed by value -> ctypes; every pointer is c_void_p (which takes ptr(), None, an int address, byref() and
 # ctypes arrays).  A type outside these tables is an error, not a guess.
-_ARG = {"int": C.c_int, "int32_t": C.c_int, "unsigned int": C.c_uint, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_ARG = {"int": C.c_int, "int32_t": C.c_int, "unsigned int": C.c_uint, "uint32_t": C.c_uint32, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
 _RET = {"int": C.c_int, "const char *": C.c_char_p}
 
 

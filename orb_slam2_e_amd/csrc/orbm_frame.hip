@@ -329,6 +329,18 @@ orbm_frame *frame_new(int n, int has_uright, int nstereo, float min_x, float min
 
 } // namespace
 
+// A recycled block goes to the next orbm_frame_create as it is: the fill and its wait run under the pool's mutex.
+int orbm_detail::frame_pool_fill(uint32_t word)
+{
+    static hipStream_t st = nullptr;        // the fill's own (guarded by the pool's mutex): never the legacy stream, and no workspace's
+    std::lock_guard<std::mutex> lk(g_frame_mu);
+    if (g_frame_pool.empty()) return 0;
+    if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { st = nullptr; return -1; }
+    for (const std::pair<int, char *> &b : g_frame_pool)
+        if (hipMemsetD32Async((hipDeviceptr_t)b.second, (int)word, frame_block_bytes(b.first) / 4, st) != hipSuccess) return -1;
+    return hipStreamSynchronize(st) == hipSuccess ? (int)g_frame_pool.size() : -1;
+}
+
 // Keypoints in the grid (and not excluded by `skip`), ordered by (cell, index).
 void orbm_detail::sort_frame(const orbx_keypoint *kps, const uint8_t *desc, int n, const uint8_t *skip, const float *uright, float min_x,
                              float min_y, float max_x, float max_y, SortedFrame &sf)

@@ -161,7 +161,11 @@ struct Workspace {
     unsigned *ent = nullptr;
     size_t dev_cap = 0, pin_cap = 0, ent_cap = 0, used = 0;
     hipStream_t st = nullptr;
-    unsigned gen = 0;    // call counter: flags a kernel raises are this number (a fresh arena is zeroed, 0 is never a generation)
+    unsigned gen = 0;    // call counter: a flag a kernel raises is this number, 1 .. 0x7ffffffe (0 is never a generation).  The arenas keep
+                         // what earlier calls left: a word that is compared with the generation is WRITTEN by the call before it is read
+                         // (staged as 0 with the inputs, or set either way by a kernel) -- stale memory may hold any number, this one included
+    unsigned next_generation() const { return (gen % 0x7ffffffe) + 1; }    // the number the workspace's next call will use
+    unsigned begin_generation() { return gen = next_generation(); }
     int reserve(size_t dev_bytes, size_t pin_bytes); // discards the contents
     int reserve_entries(size_t n);
     hipStream_t own_stream() { if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) st = nullptr; return st; }   // nullptr = failed (never hand out the legacy stream)
@@ -171,6 +175,9 @@ struct Workspace {
 };
 Workspace *workspace_acquire();
 void workspace_release(Workspace *w);
+// orbm_debug_fill_workspaces' share of orbm_frame.hip: every pooled (destroyed) frame block filled with `word` and waited for.
+// Returns the number of blocks, -1 when a fill failed.
+int frame_pool_fill(uint32_t word);
 struct WorkspaceLease {
     Workspace *w;
     WorkspaceLease() : w(workspace_acquire()) {}
@@ -263,7 +270,8 @@ struct SearchChain {
         const Workspace *w;
         hipStream_t st;
         const int *match_kp;        // [n], device: the resolver's result by keypoint index
-        const int *flags;           // device: match count, "a list outgrew its region" (== gen), "fixed point reached" (== gen), iterations
+        const int *flags;           // device: match count, (unused), "fixed point reached" (== gen), iterations
+        const int *overflow;        // device: "a list outgrew its region" (== gen), staged as 0 with the call's inputs
         const uint8_t *qtakes;      // [nq], device: orbm_points::takes as staged (all 1 when the caller gave none)
         int n, nq, gen;
         bool check_overflow, check_converged;   // which of the two flags this attempt can raise

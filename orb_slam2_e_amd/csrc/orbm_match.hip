@@ -634,7 +634,10 @@ int Workspace::reserve(size_t dev_bytes, size_t pin_bytes)
         dev = nullptr; dev_cap = 0;
         const size_t want = std::max(dev_bytes + dev_bytes / 2, (size_t)1 << 20);
         if (hipMalloc((void **)&dev, want) != hipSuccess) { dev = nullptr; return -1; }
-        if (hipMemsetAsync(dev, 0, want, st) != hipSuccess) return -1;    // flags are generation numbers >= 1: stale memory must not look like one
+        // a new arena starts as zeros; no call depends on that (a REUSED arena holds whatever the last calls left, and so do the
+        // pinned arena and the entries: every word a call reads it has written first -- DESIGN.md, "What a call may assume about its
+        // workspace"; tests/test_gpu_workspace_contents.py fills the arenas through orbm_debug_fill_workspaces)
+        if (hipMemsetAsync(dev, 0, want, st) != hipSuccess) return -1;
         dev_cap = want;
     }
     if (pin_bytes > pin_cap) {
@@ -669,6 +672,27 @@ void workspace_release(Workspace *w)
 {
     std::lock_guard<std::mutex> lk(g_ws_mutex);
     g_ws_free.push_back(w);
+}
+
+// orbm_debug_fill_workspaces: the workspaces on the free list (a leased one belongs to its call), under the pool's mutex
+static int fill_free_workspaces(uint32_t word, bool as_next_generation, int *nworkspaces, uint32_t *frame_word)
+{
+    std::lock_guard<std::mutex> lk(g_ws_mutex);
+    *nworkspaces = 0;
+    for (Workspace *w : g_ws_free) {
+        const uint32_t v = as_next_generation ? w->next_generation() : word;
+        if (*nworkspaces == 0) *frame_word = v;
+        ++*nworkspaces;
+        if (!w->dev_cap && !w->ent_cap && !w->pin_cap) continue;      // (leased once for its stream only: nothing to fill)
+        const hipStream_t st = w->own_stream();
+        if (!st) return -1;
+        if (w->dev_cap && hipMemsetD32Async((hipDeviceptr_t)w->dev, (int)v, w->dev_cap / 4, st) != hipSuccess) return -1;
+        if (w->ent_cap && hipMemsetD32Async((hipDeviceptr_t)w->ent, (int)v, w->ent_cap, st) != hipSuccess) return -1;
+        uint32_t *hp = reinterpret_cast<uint32_t *>(w->pin);
+        for (size_t i = 0; i < w->pin_cap / 4; ++i) hp[i] = v;
+        if (hipStreamSynchronize(st) != hipSuccess) return -1;
+    }
+    return 0;
 }
 
 } // namespace orbm_detail
@@ -919,6 +943,20 @@ int orbm_hamming_matrix(const uint8_t *A, int nA, const uint8_t *B, int nB, uint
     ORBX_HIP(hipGetLastError());
     if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
     memcpy(out, sc.r<uint16_t>(o_o), sizeof(uint16_t) * (size_t)nA * nB);
+    return ORBX_OK;
+}
+
+int orbm_debug_fill_workspaces(uint32_t word, int as_next_generation, int *nworkspaces, int *nframe_blocks)
+{
+    if (!nworkspaces || !nframe_blocks) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    *nworkspaces = 0; *nframe_blocks = 0;
+    ORBX_NEED_DEVICE();
+    uint32_t frame_word = as_next_generation ? 1u : word;
+    if (orbm_detail::fill_free_workspaces(word, as_next_generation != 0, nworkspaces, &frame_word)) ORBX_FAIL(ORBX_ERR_HIP, "workspace fill failed");
+    // the pooled frame blocks have no generation of their own: they take the first free workspace's (1 when there is none)
+    const int nb = orbm_detail::frame_pool_fill(frame_word);
+    if (nb < 0) ORBX_FAIL(ORBX_ERR_HIP, "frame block fill failed");
+    *nframe_blocks = nb;
     return ORBX_OK;
 }
 

@@ -61,7 +61,8 @@ struct PoseSrc {
     const float *base_pos;      // [n][3]          ... their positions ...
     const uint8_t *base_takes;  // [n] or nullptr  ... and Observations() > 0 (nullptr: all)
     float4 *gathered;           // [n] scratch: (Xw, kind) of the keypoints behind the LDS-staged ones, formed once by the prologue
-    const int *flags;           // the search's count and its generation-stamped flags (SearchChain::Ctx)
+    const int *flags;           // the search's count and its generation-stamped "fixed point reached" word (SearchChain::Ctx)
+    const int *overflow;        // the search's "a list outgrew its region" word
     int nq, gen, check_overflow, check_converged, min_matches;
 };
 
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
     if (CHAIN) {
         // the search in front may have to be repeated (a window list outgrew its region, the resolver's fixed point was not reached)
         // or found too few matches: the host sees the same words after its wait; nothing is solved on such a result
-        const bool again = (src.check_overflow && src.flags[1] == src.gen) || (src.check_converged && src.flags[2] != src.gen);
+        const bool again = (src.check_overflow && *src.overflow == src.gen) || (src.check_converged && src.flags[2] != src.gen);
         if (again || src.flags[0] < src.min_matches) {
             if (tid == 0) out.track[0] = again ? TRACK_SEARCH_AGAIN : TRACK_FEW_MATCHES;
             return;
@@ -508,7 +509,7 @@ struct PoseChain : SearchChain {
         const Workspace &w = *c.w;
         PoseSrc src = {nullptr, nullptr, fr->kp, fr->perm, nullptr, nullptr, w.d<int>(o_off), w.d<float>(o_t),
                        c.match_kp, w.d<float>(o_pp), c.qtakes, base_has ? w.d<uint8_t>(o_bh) : nullptr, w.d<float>(o_bp),
-                       base_has && base_takes ? w.d<uint8_t>(o_bt) : nullptr, w.d<float4>(x_g), c.flags, c.nq, c.gen, c.check_overflow ? 1 : 0,
+                       base_has && base_takes ? w.d<uint8_t>(o_bt) : nullptr, w.d<float4>(x_g), c.flags, c.overflow, c.nq, c.gen, c.check_overflow ? 1 : 0,
                        c.check_converged ? 1 : 0, min_matches};
         // (the results go straight into the pinned block, as the parallel resolver's do: posted writes, no copy behind the kernel)
         PoseOut po = {res<float>(c, r_t), res<uint8_t>(c, r_o), res<int32_t>(c, r_g), res<orbm_pose_stats>(c, r_s), res<int32_t>(c, r_k)};

@@ -181,7 +181,7 @@ __global__ __launch_bounds__(MT) void k_win_wave(const WinQuery *__restrict__ q,
     if (FILL) {
         if (FILL == 2 && lane == 0) {
             lbeg[i] = obase; lend[i] = obase + min(c, ocap);
-            if (c > ocap) *overflow = gen;          // this call's generation number: some list did not fit (no preset needed)
+            if (c > ocap) *overflow = gen;          // this call's generation number: some list did not fit (the word arrives as 0 with the call's staged inputs)
         }
         if (FILL == 2 && step <= 4) {
             wave_topk_regs(rkey, ren, lane, top + (size_t)i * TOPK);
@@ -517,12 +517,13 @@ __device__ __forceinline__ void resolve_par(int *__restrict__ sm, const unsigned
                                             const uint8_t *__restrict__ takes, int th, float nnratio, int accept_mode,
                                             const float *__restrict__ qangle, const float *__restrict__ kangle,
                                             const int *__restrict__ perm, int check, int *__restrict__ match_q,
-                                            int *__restrict__ match_kp, int n, const int *__restrict__ flags, int gen,
+                                            int *__restrict__ match_kp, int n, const int *__restrict__ overflow, int gen,
                                             int *__restrict__ host_q, int *__restrict__ host_kp, int *__restrict__ host_nm,
                                             int *__restrict__ dev_nm)
 {
     // dev_nm: the device copy of the count ([0]) and of the "fixed point reached" word ([2]) for work chained behind this kernel
-    // (SearchChain), which must not wait for the host to read them; flags[1] of the same block is only read here.
+    // (SearchChain), which must not wait for the host to read them.  overflow: k_win_wave<2>'s word in the staged block (nullptr:
+    // the lists cannot overflow); it is passed on to the host in host_nm[1].
     // host_*: the call's result block in PINNED HOST memory.  The kernel's last phase writes the results there itself (posted
     // writes over PCIe, each element once): a device-to-host copy behind the kernel cost the call its 5 us plus ~9 us of
     // hand-over between the compute queue and the copy engine.  match_q / match_kp stay the device-side working copies.
@@ -588,7 +589,7 @@ __device__ __forceinline__ void resolve_par(int *__restrict__ sm, const unsigned
         int *t = f_cur; f_cur = f_nxt; f_nxt = t;
         __syncthreads();
     }
-    if (tid == 0) host_nm[1] = flags[1];      // "a list outgrew its region" as k_win_wave left it
+    if (tid == 0) host_nm[1] = overflow ? *overflow : 0;      // "a list outgrew its region" as k_win_wave left it
     if (!done) {            // chains longer than RES_MAXIT: the host repeats the call on the sequential kernel
         if (tid == 0) { host_nm[2] = 0; dev_nm[2] = 0; }
         return;
@@ -634,13 +635,13 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par(const unsigned *__restric
                                                        const uint8_t *__restrict__ takes, int th, float nnratio, int accept_mode,
                                                        const float *__restrict__ qangle, const float *__restrict__ kangle,
                                                        const int *__restrict__ perm, int check, int *__restrict__ match_q,
-                                                       int *__restrict__ match_kp, int n, const int *__restrict__ flags, int gen,
+                                                       int *__restrict__ match_kp, int n, const int *__restrict__ overflow, int gen,
                                                        int *__restrict__ host_q, int *__restrict__ host_kp, int *__restrict__ host_nm,
                                                        int *__restrict__ dev_nm)
 {
     extern __shared__ __align__(16) int sm[];
     resolve_par<false>(sm, ent, top, lbeg, lend, nq, ns, takes, th, nnratio, accept_mode, qangle, kangle, perm, check, match_q, match_kp, n,
-                       flags, gen, host_q, host_kp, host_nm, dev_nm);
+                       overflow, gen, host_q, host_kp, host_nm, dev_nm);
 }
 // One 1024-thread workgroup PER SEARCH of a batch of BoW searches: workgroup b resolves the search of record b, on its own LDS
 // (the launch asks for the dynamic LDS of the batch's largest ns; a workgroup lays out its own ns).  Workgroups never wait for
@@ -650,7 +651,7 @@ __global__ __launch_bounds__(RES_T) void k_resolve_par_pairs(const BowPairDev *_
     extern __shared__ __align__(16) int sm[];
     const BowPairDev &p = recs[blockIdx.x];
     resolve_par<true>(sm, p.ent, p.top, p.off, p.off + 1, p.nq, p.ns, nullptr, th, nnratio, ACCEPT_RATIO, p.qang, p.kangle, p.perm, check,
-                      p.match_q, p.match_kp, p.n, p.dev_nm, gen, p.host_q, p.host_kp, p.host_nm, p.dev_nm);
+                      p.match_q, p.match_kp, p.n, nullptr, gen, p.host_q, p.host_kp, p.host_nm, p.dev_nm);
 }
 
 // SearchForInitialization's loop (ORBmatcher.cc:626-696) as a parallel fixed point.  What couples its queries is
@@ -668,7 +669,7 @@ __global__ __launch_bounds__(RES_T) void k_resolve_init_par(const unsigned *__re
                                                             const int *__restrict__ lbeg, const int *__restrict__ lend, int nq, int ns,
                                                             int C, int th, float nnratio, const float *__restrict__ qangle,
                                                             const float *__restrict__ kangle, const int *__restrict__ perm, int check,
-                                                            unsigned *__restrict__ sel_g, const int *__restrict__ flags, int gen,
+                                                            unsigned *__restrict__ sel_g, const int *__restrict__ overflow, int gen,
                                                             int *__restrict__ host_q, int *__restrict__ host_nm)
 {
     extern __shared__ __align__(16) int sm[];
@@ -741,7 +742,7 @@ __global__ __launch_bounds__(RES_T) void k_resolve_init_par(const unsigned *__re
         __syncthreads();
         if (s_over) break;
     }
-    if (tid == 0) host_nm[1] = flags[1];      // "a list outgrew its region" as k_win_wave left it
+    if (tid == 0) host_nm[1] = overflow ? *overflow : 0;      // "a list outgrew its region" as k_win_wave left it
     if (!done) {            // a crowded slot or chains longer than RES_MAXIT: the host repeats the call on the sequential kernel
         if (tid == 0) host_nm[2] = 0;
         return;
@@ -826,8 +827,10 @@ template <int MODE>
 __global__ __launch_bounds__(MT) void k_rotation(const int *__restrict__ acc_sp, const int *__restrict__ state, int nq, int ns,
                                                  const float *__restrict__ qangle, const float *__restrict__ kangle,
                                                  const int *__restrict__ perm, int check, int *__restrict__ match_q,
-                                                 int *__restrict__ match_kp, int *__restrict__ nmatches)
+                                                 int *__restrict__ match_kp, int *__restrict__ nmatches, const int *__restrict__ overflow)
 {
+    // nmatches: the result block's four words; [1] takes k_win_wave<2>'s overflow word from the staged block (nullptr: the lists cannot
+    // overflow), so that it reaches the host with the results
     __shared__ int hist[HISTO_LENGTH], keep[3], removed;
     const int tid = threadIdx.x;
     if (tid < HISTO_LENGTH) hist[tid] = 0;
@@ -873,7 +876,7 @@ __global__ __launch_bounds__(MT) void k_rotation(const int *__restrict__ acc_sp,
         finish(i, sp, check && sp >= 0 ? bin_of(i, sp) : -1);
     }
     __syncthreads();
-    if (tid == 0) *nmatches -= removed;
+    if (tid == 0) { nmatches[0] -= removed; nmatches[1] = overflow ? *overflow : 0; }
 }
 
 // The projection prefixes of the remaining SearchByProjection forms and of SearchBySim3, one thread per list entry, in the
@@ -981,6 +984,7 @@ __global__ __launch_bounds__(MT) void k_sim3_agree(const int *__restrict__ best1
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(nfound, __popcll(b));
 }
 
+std::atomic<int> g_last_search_waits{0};  // host waits of the last whole-loop search that launched (orbm_debug_last_search_waits)
 std::atomic<int> g_last_iterations{0};    // iterations of the last k_resolve_par (-1: it gave up and k_resolve ran)
 std::atomic<int> g_force_sequential{0};   // orbm_debug_force_sequential_resolver: tests run both resolvers
 std::atomic<int> g_last_bow_pairs_waits{0};   // host waits of the last orbm_frame_search_by_bow_pairs
@@ -1075,6 +1079,7 @@ struct SeqPlan {
     bool sequential = false;    // k_resolve + k_rotation instead of the parallel fixed point
     size_t ent_need = 0;        // candidate entries
     int win_stride = 0, init_c = 0, gen = 0;
+    int waits = 0;              // host waits of the call so far (orbm_debug_last_search_waits)
     size_t lds = 0;             // k_resolve's state
     bool fused_upload = false;  // the prefix kernel uploads the staged block
     const int *lbeg = nullptr, *lend = nullptr;     // every query's list bounds in w.ent, as the list kernels leave them
@@ -1083,7 +1088,7 @@ struct SeqPlan {
 // Workspace offsets of one attempt: the staged inputs (same offsets in the pinned and the device arena: ONE upload), the prefix's
 // inputs (read where they are staged), device-only arrays, then the result block [o_res, ...): the search's results, the chain's.
 struct SeqLayout {
-    size_t o_qh, o_a, o_qang, o_tk, o_occ, o_off, o_cbeg, o_cand, o_seg, staged;
+    size_t o_qh, o_a, o_qang, o_tk, o_occ, o_off, o_cbeg, o_cand, o_seg, o_ovf, staged;
     size_t o_q, o_top, o_cnt, o_acc, o_lend, o_state;
     size_t o_res, o_mq, o_mk, o_nm, search_res_bytes;
     size_t tq_bytes, tp_bytes;      // optional outputs that are not part of the result block travel through the tail of the pinned arena
@@ -1110,6 +1115,7 @@ int seq_layout(const SeqSearch &r, Workspace &w, const SeqPlan &p, SeqLayout &L)
     L.o_off = w.carve(sizeof(int) * (nq + 1));
     L.o_cbeg = w.carve(sizeof(int) * (size_t)nq); L.o_cand = w.carve(sizeof(int) * (size_t)(r.lists.n ? r.lists.n : 1));
     L.o_seg = w.carve(sizeof(int) * (size_t)(r.lists.nseg + 1));
+    L.o_ovf = w.carve(sizeof(int));                 // "a list outgrew its region": staged as 0, raised by k_win_wave<2>
     if (r.chain) r.chain->carve_inputs(w);
     L.staged = w.used;
     if (r.prefix) r.prefix->carve(w);              // read by the prefix kernel where they are staged: not part of the upload
@@ -1154,6 +1160,7 @@ int seq_stage(const SeqSearch &r, Workspace &w, const SeqLayout &L, SeqPlan &p)
         if (r.lists.n) memcpy(w.h<char>(L.o_cand), r.lists.idx, sizeof(int) * r.lists.n);
     }
     if (r.lists.seg) memcpy(w.h<char>(L.o_seg), r.lists.seg, sizeof(int) * (size_t)(r.lists.nseg + 1));
+    *w.h<int>(L.o_ovf) = 0;
     if (r.prefix) r.prefix->fill(w);
     if (r.chain) { r.chain->fill_inputs(w); r.chain->launched = false; }
     p.fused_upload = r.prefix && orbx::stage_ok(w.dev, w.pin, L.staged);
@@ -1161,10 +1168,12 @@ int seq_stage(const SeqSearch &r, Workspace &w, const SeqLayout &L, SeqPlan &p)
     // ONE fill for everything that needs a preset (a launch each was 3-4 us of a 0.1-ms call): match_kp = -1 (slot untouched);
     // segments write back touched slots of the state only, so it is preset to -1 as well (the span in between, match_q, is
     // rewritten in full anyway); and the two counters START AT -1: the match count is overwritten (one workgroup) or added
-    // to (segments: the host adds the 1 back), the overflow flag is CLEARED to 0 by a list that does not fit
-    // (k_resolve_par writes every slot and its count itself; the two flags behind the count -- "a list outgrew its region",
-    // "the fixed point was reached" -- are raised by writing this call's generation number, so nothing needs a preset there)
-    p.gen = (int)(w.gen = (w.gen % 0x7ffffffe) + 1);
+    // to (segments: the host adds the 1 back).  k_resolve_par writes every slot and its count itself.  The two flags are this
+    // call's generation number when raised, and neither relies on what the arena held: "the fixed point was reached" is written
+    // either way (0 or the generation) by the resolver, and "a list outgrew its region", which k_win_wave<2> writes only when a
+    // list overflows, lies in the staged block (o_ovf), where the call's one upload sets it to 0 -- a word left by an earlier call
+    // may equal this generation, so a flag that is only ever raised must not start from stale memory
+    p.gen = (int)w.begin_generation();
     if (p.sequential) {
         const size_t f0 = r.lists.seg ? L.o_state : L.o_mk;
         ORBX_HIP(hipMemsetAsync(w.d<char>(f0), 0xff, L.o_nm + sizeof(int) - f0, st));
@@ -1202,7 +1211,7 @@ int seq_lists(const SeqSearch &r, Workspace &w, const SeqLayout &L, SeqPlan &p)
     } else if (!p.exact) {
         p.lbeg = w.d<int>(L.o_cnt); p.lend = w.d<int>(L.o_lend);
         hipLaunchKernelGGL(k_win_wave<2>, g, dim3(MT), 0, st, dq, da, nq, fv.kp, fv.desc, fv.cell_off, docc, fv.gp, r.has_uright,
-                           init_dist, (int *)nullptr, (const int *)nullptr, w.ent, p.win_stride, w.d<int>(L.o_cnt), w.d<int>(L.o_lend), dnm + 1, dtop, p.gen);
+                           init_dist, (int *)nullptr, (const int *)nullptr, w.ent, p.win_stride, w.d<int>(L.o_cnt), w.d<int>(L.o_lend), w.d<int>(L.o_ovf), dtop, p.gen);
     } else {
         hipLaunchKernelGGL(k_win_wave<0>, g, dim3(MT), 0, st, dq, da, nq, fv.kp, fv.desc, fv.cell_off, docc, fv.gp, r.has_uright,
                            init_dist, w.d<int>(L.o_cnt), (const int *)nullptr, (unsigned *)nullptr, 0, (int *)nullptr, (int *)nullptr,
@@ -1214,6 +1223,7 @@ int seq_lists(const SeqSearch &r, Workspace &w, const SeqLayout &L, SeqPlan &p)
             ORBX_HIP(hipMemcpyAsync(&total, dnm + 1, sizeof(int), hipMemcpyDeviceToHost, st));
             ORBX_HIP(hipStreamSynchronize(st));
             if (r.chain) r.chain->waits++;
+            ++p.waits;
             p.ent_need = (size_t)total;
             if (w.reserve_entries(p.ent_need)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
         }
@@ -1237,13 +1247,14 @@ int seq_resolve(const SeqSearch &r, Workspace &w, const SeqLayout &L, const SeqP
     const float *dqang = w.d<float>(L.o_qang);
     const uint8_t *dtk = w.d<uint8_t>(L.o_tk);
     int *dnm = w.d<int>(L.o_nm);
+    const int *dovf = r.windows() && !p.exact ? w.d<int>(L.o_ovf) : nullptr;    // only the strided window lists can overflow
     if (!p.sequential && r.mode == 1) {
         hipLaunchKernelGGL(k_resolve_init_par, dim3(1), dim3(RES_T), sizeof(int) * (size_t)(p.init_c + 3) * ns, st, dent, dtop, p.lbeg, p.lend,
-                           nq, ns, p.init_c, r.th, r.nnratio, dqang, fv.angle, fv.perm, r.check, w.d<unsigned>(L.o_acc), (const int *)dnm, p.gen,
+                           nq, ns, p.init_c, r.th, r.nnratio, dqang, fv.angle, fv.perm, r.check, w.d<unsigned>(L.o_acc), dovf, p.gen,
                            L.res<int>(w, L.o_mq), L.res<int>(w, L.o_nm));
     } else if (!p.sequential) {
         hipLaunchKernelGGL(k_resolve_par, dim3(1), dim3(RES_T), sizeof(int) * 4 * (size_t)ns, st, dent, dtop, p.lbeg, p.lend, nq, ns, dtk, r.th,
-                           r.nnratio, r.accept_mode, dqang, fv.angle, fv.perm, r.check, w.d<int>(L.o_mq), w.d<int>(L.o_mk), r.n, (const int *)dnm,
+                           r.nnratio, r.accept_mode, dqang, fv.angle, fv.perm, r.check, w.d<int>(L.o_mq), w.d<int>(L.o_mk), r.n, dovf,
                            p.gen, L.res<int>(w, L.o_mq), L.res<int>(w, L.o_mk), L.res<int>(w, L.o_nm), dnm);
     } else {
         const int *dseg = r.lists.seg ? w.d<int>(L.o_seg) : nullptr;
@@ -1253,12 +1264,12 @@ int seq_resolve(const SeqSearch &r, Workspace &w, const SeqLayout &L, const SeqP
             hipLaunchKernelGGL(k_resolve<0>, gr, dim3(64), p.lds, st, dent, dtop, p.lbeg, p.lend, nq, ns, dtk, r.th, r.nnratio, r.accept_mode,
                                dacc, dstate, dnm, dseg);
             hipLaunchKernelGGL(k_rotation<0>, dim3(1), dim3(MT), 0, st, (const int *)dacc, (const int *)dstate, nq, ns, dqang, fv.angle,
-                               fv.perm, r.check, w.d<int>(L.o_mq), w.d<int>(L.o_mk), dnm);
+                               fv.perm, r.check, w.d<int>(L.o_mq), w.d<int>(L.o_mk), dnm, dovf);
         } else {
             hipLaunchKernelGGL(k_resolve<1>, gr, dim3(64), p.lds, st, dent, dtop, p.lbeg, p.lend, nq, ns, dtk, r.th, r.nnratio, 0,
                                dacc, dstate, dnm, dseg);
             hipLaunchKernelGGL(k_rotation<1>, dim3(1), dim3(MT), 0, st, (const int *)dacc, (const int *)dstate, nq, ns, dqang, fv.angle,
-                               fv.perm, r.check, w.d<int>(L.o_mq), w.d<int>(L.o_mk), dnm);
+                               fv.perm, r.check, w.d<int>(L.o_mq), w.d<int>(L.o_mk), dnm, dovf);
         }
     }
     ORBX_HIP(hipGetLastError());
@@ -1329,7 +1340,7 @@ int run_sequential(const SeqSearch &r)
             if (const int rc = seq_lists(r, w, L, p)) return rc;
             if (const int rc = seq_resolve(r, w, L, p)) return rc;
         }               // (else nothing to search: the prefix's outputs are the whole result)
-        const SearchChain::Ctx cx = {&w, w.st, w.d<int>(L.o_mk), w.d<int>(L.o_nm), w.d<uint8_t>(L.o_tk), r.n, nq, p.gen, r.windows() && !p.exact,
+        const SearchChain::Ctx cx = {&w, w.st, w.d<int>(L.o_mk), w.d<int>(L.o_nm), w.d<int>(L.o_ovf), w.d<uint8_t>(L.o_tk), r.n, nq, p.gen, r.windows() && !p.exact,
                                      !p.sequential, L.o_res};
         if (r.chain && ns) {    // its kernel reads the flags the host reads below, and leaves if this attempt does not stand
             if (const int rc = r.chain->launch(cx)) return rc;
@@ -1338,6 +1349,7 @@ int run_sequential(const SeqSearch &r)
         ORBX_HIP(hipStreamSynchronize(w.st));
         if (r.chain) r.chain->waits++;
         if (r.waits) ++*r.waits;
+        g_last_search_waits.store(++p.waits, std::memory_order_relaxed);
         if (ns) {
             if (r.windows() && !p.exact && *L.res<int>(w, L.o_nm + sizeof(int)) == p.gen) { p.exact = true; continue; }
             if (!p.sequential) {
@@ -1422,6 +1434,7 @@ int orbm_debug_force_sequential_resolver(int on)
 }
 
 int orbm_debug_last_resolver_iterations(void) { return g_last_iterations.load(std::memory_order_relaxed); }
+int orbm_debug_last_search_waits(void) { return g_last_search_waits.load(std::memory_order_relaxed); }
 
 int orbm_project_points(int mode, const float *mp_pos, const float *mp_normal, const float *mp_min_distance,
                         const float *mp_max_distance, int m, const float *Rcw, const float *tcw, const float *Ow,
@@ -1640,7 +1653,7 @@ int bow_pairs_launch(const orbm_bow_pair *pairs, std::vector<BowBatchSlot> &act,
     const size_t res_bytes = w.used - o_res;
     if (w.reserve(o_res + res_bytes, std::max(staged, res_bytes))) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
     if (w.reserve_entries(nent)) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation failed");
-    const int gen = (int)(w.gen = (w.gen % 0x7ffffffe) + 1);
+    const int gen = (int)w.begin_generation();
     BowPairDev *rec = w.h<BowPairDev>(o_rec);
     for (size_t a = 0; a < act.size(); ++a) {
         const BowBatchSlot &s = act[a];

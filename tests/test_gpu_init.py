@@ -191,27 +191,39 @@ def _motions(s, M):
     return np.stack([Rs[k] for k in pick]), np.stack([ts[k] for k in pick])
 
 
+def check_rt_against_restatement(s, d, inl, R, t, th2):
+    """orbm_init_check_rt's result d for the motions (R[m], t[m]) against the restatement, motion by motion: bit for bit where the
+    triangulated points agree bit for bit, otherwise the counted flags away from the thresholds and the points within D_MAX"""
+    n = len(s["matches"])
+    for m in range(len(R)):
+        r = io.check_rt(s["keys1"], s["keys2"], s["matches"], inl, K, R[m], t[m], th2)
+        assert not d["counted"][m][~inl].any() and d["ngood"][m] == d["counted"][m].sum()
+        if same_bits(d["P3D"][m], r["P3D"]).all() and same_bits(d["cos_parallax"][m], r["cos_parallax"]).all():
+            assert d["ngood"][m] == r["ngood"] and np.array_equal(d["good"][m], r["good"]) and np.array_equal(d["counted"][m], r["counted"])
+            assert same_bits(d["parallax"][m], r["parallax"]).all(), (n, m)
+        else:
+            far = ~(((r["err"] >= th2 / 2) & (r["err"] <= 2 * th2)).any(1)) & (r["err"] >= 0).all(1)
+            assert np.array_equal(d["counted"][m][far], r["counted"][far]), (n, m)
+            both = d["counted"][m] & r["counted"]
+            first = s["matches"][both, 0]
+            assert rel_diff(d["P3D"][m][first], r["P3D"][first]) <= D_MAX, (n, m)
+
+
+def rt_scene(n, M):
+    """(scene, inlier flags with some outliers on and some inliers off, M motions: the true one first)"""
+    s = scenes.scene(400 + n, n, 1, "general", noise=0.3, outliers=0.1, name=f"rt_n{n}")
+    inl = ~s["bad"]; inl[::7] = ~inl[::7]
+    return (s, inl) + _motions(s, M)
+
+
 @pytest.mark.parametrize("M", [1, 4, 8])
 def test_check_rt_against_the_restatement(M):
     th2 = np.float32(4.0)
     for n in (8, 9, 63, 64, 65, 129):
-        s = scenes.scene(400 + n, n, 1, "general", noise=0.3, outliers=0.1, name=f"rt_n{n}")
-        R, t = _motions(s, M)
-        inl = ~s["bad"]; inl[::7] = ~inl[::7]                   # some outliers on, some inliers off
+        s, inl, R, t = rt_scene(n, M)
         d = check_rt(s["keys1"], s["keys2"], s["matches"], inl, K, R, t, th2)
         assert last_init_waits() == 1 and d["good"].shape == (M, len(s["keys1"])) and d["counted"].shape == (M, n)
-        for m in range(M):
-            r = io.check_rt(s["keys1"], s["keys2"], s["matches"], inl, K, R[m], t[m], th2)
-            assert not d["counted"][m][~inl].any() and d["ngood"][m] == d["counted"][m].sum()
-            if same_bits(d["P3D"][m], r["P3D"]).all() and same_bits(d["cos_parallax"][m], r["cos_parallax"]).all():
-                assert d["ngood"][m] == r["ngood"] and np.array_equal(d["good"][m], r["good"]) and np.array_equal(d["counted"][m], r["counted"])
-                assert same_bits(d["parallax"][m], r["parallax"]).all(), (n, m)
-            else:
-                far = ~(((r["err"] >= th2 / 2) & (r["err"] <= 2 * th2)).any(1)) & (r["err"] >= 0).all(1)
-                assert np.array_equal(d["counted"][m][far], r["counted"][far]), (n, m)
-                both = d["counted"][m] & r["counted"]
-                first = s["matches"][both, 0]
-                assert rel_diff(d["P3D"][m][first], r["P3D"][first]) <= D_MAX, (n, m)
+        check_rt_against_restatement(s, d, inl, R, t, th2)
         assert d["ngood"][0] >= 0.7 * inl.sum()                 # the true motion triangulates the inliers
     # the decision edges of the CPU file through the device
     k1, k2, mt, R, t, X = scenes.rt_scene([4.0, 5.0, 3000.0, -4.0, -3000.0])
