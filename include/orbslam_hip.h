@@ -98,6 +98,12 @@ typedef struct {
 } orbx_plan_info;
 int orbx_plan(const orbx_params *params, int width, int height, orbx_plan_info *info);
 
+/* Development aid, host alone like orbx_plan: what k_fast_cells' tile load reads of a frame's pyramid block, FAST cell by cell in
+ * grid order.  Eight int32 per cell: level, byte offset of the cell's first piece in the frame's block, row pitch, rows read,
+ * 16-byte pieces read per row (rows and pieces 0: a cell without a zone loads nothing), cell width, cell origin x0, y0 in level
+ * coordinates.  *n = cells of a frame; ORBX_ERR_CAPACITY if `cap` cells are too few. */
+int orbx_debug_fast_pieces(const orbx_params *params, int width, int height, int32_t *out, int cap, int *n);
+
 /* ORBextractor::operator()(image, mask, keypoints, descriptors) for ONE host image
  * (CV_8UC1, `stride` bytes per row).  Writes up to `cap` keypoints / 32-byte
  * descriptor rows; *n = count.  An empty image (NULL / 0 size) returns ORBX_OK

@@ -416,6 +416,20 @@ int orbx_plan(const orbx_params *prm, int width, int height, orbx_plan_info *inf
     return rc;
 }
 
+int orbx_debug_fast_pieces(const orbx_params *prm, int width, int height, int32_t *out, int cap, int *n)
+{
+    if (!prm || !out || !n || width <= 0 || height <= 0 || cap < 0) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
+    orbx_extractor *ex = nullptr;
+    int rc = orbx_create(prm, &ex);
+    if (rc != ORBX_OK) return rc;
+    std::vector<int2> xt;
+    std::vector<int4> yt;
+    rc = plan_frame(ex, width, height, xt, yt);
+    if (rc == ORBX_OK) rc = debug_fast_pieces(ex, out, cap, n);
+    orbx_destroy(ex);
+    return rc;
+}
+
 int orbx_extract_batch(orbx_extractor *ex, const uint8_t *images, int is_device, int width, int height, int stride,
                        size_t frame_stride, int batch, void *stream_)
 {

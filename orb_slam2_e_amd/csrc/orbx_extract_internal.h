@@ -95,6 +95,19 @@ __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p)
     return v;
 }
 
+// ... and a 16-byte piece at any byte address (one global_load_dwordx4)
+__device__ __forceinline__ uint4 load_u128_unaligned(const uint8_t *p)
+{
+    uint4 v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+
+// k_fast_cells' tile row of a cell cw px wide: the dwords the LDS tile takes (5 spare bytes, the cell, rounded up) and the
+// 16-byte pieces that bring them over -- the last piece reaches up to 12 bytes past the last dword (plan_fast checks where to)
+__host__ __device__ __forceinline__ int fast_row_dwords(int cw) { return (cw + 5 + 3) >> 2; }
+__host__ __device__ __forceinline__ int fast_row_pieces(int cw) { return (fast_row_dwords(cw) + 3) >> 2; }
+
 inline int cv_round_f(float v) { return (int)lrintf(v); }
 
 // ---- orbx_pyramid.hip: kinds 0 (k_pyr_level0 / _lin) and 1 (k_pyr_chain, or k_pyr_resize per level)
@@ -106,6 +119,7 @@ void launch_pyramid(orbx_extractor *ex, int batch, hipStream_t st);
 // ---- orbx_fast.hip: kind 2
 int plan_fast(orbx_extractor *ex, int maxcw, int maxch);   // widest / tallest cell of the grid plan_frame laid out
 void launch_fast(orbx_extractor *ex, int batch, hipStream_t st);
+int debug_fast_pieces(const orbx_extractor *ex, int32_t *out, int cap, int *n);   // orbx_debug_fast_pieces: what the tile load reads, cell by cell
 // ---- orbx_octree.hip: kind 3
 int plan_octree(orbx_extractor *ex);
 int prepare_octree(orbx_extractor *ex);

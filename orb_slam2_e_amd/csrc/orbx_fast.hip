@@ -1,6 +1,8 @@
 // orbx_fast.hip -- FAST-9/16 per 30-px cell with non-max suppression and the threshold fallback (ComputeKeyPointsOctTree's cell
 // loop, ORBextractor.cc:789-837): k_fast_cells, one wave per cell.  The host side below it sizes the kernel's LDS regions and picks
 // the instantiation from the widest cell of the grid that plan_frame lays out (plan_fast, launch_fast).
+#include <string.h>
+
 #include <algorithm>
 
 #include "orbx_extract_internal.h"
@@ -148,7 +150,7 @@ __device__ __forceinline__ uint32_t fast_arc_best_packed(const uint32_t X[8])
 // in FAST raster order, coordinates relative to (minBorderX, minBorderY).
 // Packed candidate: y<<20 | x<<8 | score.
 //
-// Phases: (1) cell tile -> LDS as dwords; then, as the reference does, one pass at iniThFAST and -- only if that
+// Phases: (1) cell tile -> LDS, loaded as 16-byte pieces, four lanes to a tile row; then, as the reference does, one pass at iniThFAST and -- only if that
 // pass emits nothing (a wave-uniform branch; on textured frames almost every cell has a corner at iniThFAST) -- a
 // second one at minThFAST:
 // (2a) every pixel, 4 adjacent pixels per lane on packed u16: the opposite-pair pre-test on the two compass
@@ -189,30 +191,47 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t *__restrict__ p
     if (zw > 0 && zh > 0) {
         // (1) tile: pixel (x, y) of the cell lives at tile[y*TS + 5 + x], so that zone pixel 0 (cell pixel 3) sits
         // on the dword boundary at column 8 whatever the cell's position: the pre-test's 4-pixel groups then cover a
-        // zone row with ceil(zw/4) groups.  Dword loads at byte addresses (see load_u32_unaligned).
-        // LW lanes side by side on a tile row (ndw <= LW by the choice of TS), 64 / LW rows per step: a lane's column never
-        // changes.  All loads of a chunk of NB steps are issued before the first is stored, and none of them sits behind a
-        // branch (a lane without work in a step reads the cell's last row / last dword again): the wave spends ONE memory
+        // zone row with ceil(zw/4) groups.  The row's ndw dwords come over as 16-byte PIECES at byte addresses (see
+        // load_u128_unaligned), LP lanes side by side on a tile row -- four where a row is at most 64 bytes -- and 64 / LP
+        // rows per instruction: a lane's piece never changes.  Three load instructions per cell instead of eleven dword
+        // loads, and 4.2 % fewer vector instructions in the kernel.  What the pieces do NOT save are texture-addresser
+        // accesses ("quads and spans"): a 16-byte lane counts like four dword lanes, 1.23 accesses at an
+        // arbitrary byte address, 227 per wave against 209 before (profiles/vmem_pieces_notes.md).  All
+        // loads of a chunk of NB instructions are issued before the first is stored, and none of them sits behind a
+        // branch (a lane without work reads the cell's last row / the row's last piece again): the wave spends ONE memory
         // latency here, not one per step -- this phase was 44 % of a wave's life when every load was followed by its
-        // store.  44 rows = one chunk covers every cell of a 640 x 480 frame.  (Several cells per wave with the next
-        // cell's tile in flight during the current one's work: kernel 3-20 % slower, the tail grows; dropped.)
-        constexpr int LW = TS > 64 ? 32 : 16, RPI = 64 / LW, NB = TS > 64 ? 16 : 11;
-        const int ndw = (cw + 5 + 3) >> 2;
+        // store.  48 rows = one chunk of three instructions covers every cell of a 640 x 480 frame.  The last piece of a
+        // row reads up to 12 bytes past the dwords the pre-test needs: plan_fast proves for every cell that they lie inside
+        // the level's padded row.  The stores know no branch either: the lane that read a row or a piece again stores it
+        // again (same bytes to the same place), and a piece goes into the tile whole -- what lies past the row's ndw dwords
+        // are image bytes where nothing was written before, in columns whose pixels stage (2b) masks -- except that the
+        // fourth piece of a 52-byte row (TS = 52 is no multiple of 16, hence dword stores) ends with its first dword.
+        // The wait for the chunk's loads is ONE, in front of the stores: the compiler otherwise moves a load whose
+        // value only a predicated store takes behind that store's branch.  (Several cells per wave with the next cell's
+        // tile in flight during the current one's work: kernel 3-20 % slower, the tail grows; dropped.)
+        constexpr int LP = TS > 64 ? 8 : 4, RPI = 64 / LP, NB = TS == 52 ? 3 : TS == 64 ? 4 : 6;
+        static_assert(TS % 16 == 0 || TS == 52, "a row takes whole pieces, or three and a dword");
+        const int npc = fast_row_pieces(cw);
         const uint8_t *img = pyr + (size_t)f * frame_bytes + ci.img_off;
         {
-            const int xw = lane & (LW - 1), yr = lane / LW;
-            const uint32_t xoff = 4u * (uint32_t)min(xw, ndw - 1);
-            uint8_t *dst = tile + yr * TS + 4 * xw;
-            const int ylim = xw < ndw ? ch - yr : 0;      // rows y0 = 0, RPI, 2 RPI, ... < ylim are this lane's
+            const int xp = min(lane & (LP - 1), npc - 1), yr = lane / LP;
             for (int yb = 0; yb < ch; yb += NB * RPI) {
-                uint32_t v[NB];
+                uint4 v[NB];
+                uint32_t *d[NB];
 #pragma unroll
-                for (int i = 0; i < NB; ++i)
-                    v[i] = load_u32_unaligned(img + ((uint32_t)__mul24(min(yb + yr + i * RPI, ch - 1), ci.stride) + xoff));
+                for (int i = 0; i < NB; ++i) {
+                    const int y = min(yb + yr + i * RPI, ch - 1);
+                    v[i] = load_u128_unaligned(img + ((uint32_t)__mul24(y, ci.stride) + 16u * (uint32_t)xp));
+                    d[i] = reinterpret_cast<uint32_t *>(tile + __mul24(y, TS) + 16 * xp);
+                }
 #pragma unroll
-                for (int i = 0; i < NB; ++i)
-                    if (yb + i * RPI < ylim) *reinterpret_cast<uint32_t *>(dst + i * RPI * TS) = v[i];
-                dst += NB * RPI * TS;
+                for (int i = 0; i < NB; ++i) asm volatile("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i].z), "+v"(v[i].w));
+#pragma unroll
+                for (int i = 0; i < NB; ++i) d[i][0] = v[i].x;
+                if (TS != 52 || xp < 3) {
+#pragma unroll
+                    for (int i = 0; i < NB; ++i) { d[i][1] = v[i].y; d[i][2] = v[i].z; d[i][3] = v[i].w; }
+                }
             }
         }
         __syncthreads();
@@ -377,6 +396,33 @@ int plan_fast(orbx_extractor *ex, int maxcw, int maxch)
     ex->sc_bytes = (std::max(ex->SS * (maxch - 6 + 2), gq_bytes) + 15) & ~15;                      // score map, sharing the group queue's region
     ex->queue_bytes = (2 * (maxcw - 6) * (maxch - 6) + 2 * 64 + 15) & ~15;                         // pixel queue + the pre-test's dump slots
     ex->fast_lds = ex->tile_bytes + ex->sc_bytes + ex->queue_bytes;
+    // The tile load's 16-byte pieces: piece p < fast_row_pieces(cw) of cell row y < ch covers bytes [16 p, 16 p + 16) from
+    // img_off + y stride, i.e. columns PADX + x0 - 5 + 16 p ... of padded row y0 + EDGE + y.  By the grid (x0 >= MIN_BORDER,
+    // x0 + cw <= w - 16, 4 ndw <= cw + 8, 16 npc <= 4 ndw + 12) the last byte read is at most column PADX + w - 2 of row
+    // h + 2 -- inside the inner image, the last cell of the last level included, and frames lie frame_bytes apart, so the
+    // last frame reads nothing behind the allocation.  Checked cell by cell all the same: a grid that breaks it is refused.
+    for (const CellInfo &c : ex->cells) {
+        if (c.cw <= 6 || c.ch <= 6) continue;   // no zone: the kernel loads nothing
+        const LevelInfo &lv = ex->lv[c.level];
+        const int col0 = PADX + c.x0 - 5, col1 = col0 + 16 * fast_row_pieces(c.cw), row0 = c.y0 + EDGE, row1 = row0 + c.ch;
+        const bool in_row = col0 >= 0 && col1 <= lv.stride && row0 >= 0 && row1 <= lv.h + 2 * EDGE;
+        const bool at_cell = c.img_off == lv.off + row0 * lv.stride + col0 && c.stride == lv.stride;
+        if (!in_row || !at_cell || (size_t)lv.off + (size_t)lv.stride * (lv.h + 2 * EDGE) > ex->frame_bytes)
+            ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "FAST tile pieces would read outside the level's padded rows");
+    }
+    return ORBX_OK;
+}
+
+int debug_fast_pieces(const orbx_extractor *ex, int32_t *out, int cap, int *n)
+{
+    *n = (int)ex->cells.size();
+    if (*n > cap) ORBX_FAIL(ORBX_ERR_CAPACITY, "cell buffer too small");
+    for (const CellInfo &c : ex->cells) {
+        const bool loads = c.cw > 6 && c.ch > 6;
+        const int32_t rec[8] = {c.level, c.img_off, c.stride, loads ? c.ch : 0, loads ? fast_row_pieces(c.cw) : 0, c.cw, c.x0, c.y0};
+        memcpy(out, rec, sizeof(rec));
+        out += 8;
+    }
     return ORBX_OK;
 }
 

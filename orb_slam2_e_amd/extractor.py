@@ -186,6 +186,24 @@ def plan(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height):
     return out
 
 
+FAST_PIECE_FIELDS = ("level", "img_off", "stride", "rows", "pieces", "cw", "x0", "y0")
+
+
+def fast_pieces(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height):
+    """orbx_debug_fast_pieces: what k_fast_cells' tile load reads of a frame's pyramid block, on the host alone.  An int32 array
+    [cells, 8] with the columns FAST_PIECE_FIELDS: a cell reads `pieces` 16-byte pieces of each of `rows` rows `stride` bytes
+    apart, the first at byte `img_off` of the block."""
+    L = lib()
+    prm = _Params(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, 0)
+    info = _ExtractPlan()
+    check(L.orbx_plan(C.byref(prm), int(width), int(height), C.byref(info)))
+    out = np.zeros((info.cells_per_frame, len(FAST_PIECE_FIELDS)), np.int32)
+    n = C.c_int(0)
+    check(L.orbx_debug_fast_pieces(C.byref(prm), int(width), int(height), _p(out), len(out), C.byref(n)))
+    assert n.value == len(out)
+    return out
+
+
 def extract_pair(left, right, image_left, image_right):
     """The two images of a stereo frame through their two extractors in ONE call from one host thread (orbx_extract_pair: both
     kernel chains enqueued before the host waits; the reference runs them on two threads, Frame.cc:78-81).
