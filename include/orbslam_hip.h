@@ -37,7 +37,7 @@ const char *orbx_last_error(void);
  * orbm_search_by_projection_map_poses, orbm_frame_search_by_projection_map_poses, orbm_debug_last_map_poses_waits;
  * orbm_init_find_models, orbm_init_check_rt, orbm_init_reconstruct_f, orbm_debug_last_init_waits, orbm_debug_init_svd;
  * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits; orbm_pnp_hypotheses, orbm_debug_last_pnp_waits, orbm_debug_pnp_pose;
- * orbm_debug_fill_workspaces, orbm_debug_last_search_waits. */
+ * orbm_debug_fill_workspaces, orbm_debug_last_search_waits; orbm_bundle_adjustment, orbm_ba_plan, orbm_debug_last_ba_waits. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -1005,6 +1005,84 @@ int orbm_track_local_map(const orbm_frame *cur, const orbm_view *view, const orb
                          uint8_t *outlier, float *Tcw_out, orbm_track_result *result, orbm_pose_stats *stats);
 /* Host waits (stream synchronisations) of the last orbm_track_* call of this process: 1 on the common path. */
 int orbm_debug_last_track_waits(void);
+
+/* ------------------------------------------------------------------ bundle adjustment
+ * Optimizer::LocalBundleAdjustment (src/Optimizer.cc:837-1162) and Optimizer::BundleAdjustment (:74-262) on the graph the caller
+ * has flattened: g2o's Levenberg loop (optimization_algorithm_levenberg.cpp:63-241) runs on the host and drives
+ * device passes -- errors + robust chi2, build, Schur complement, a dense LLT of the reduced system, back-substitution + update --
+ * with one host wait per trial and one per round.
+ *   poses      [nfree + nfixed][16]: GetPose() of the local keyframes (lLocalKeyFrames order), then of the fixed ones
+ *   fixed      [nfree] or NULL: 1 = this local keyframe is a fixed vertex (mnId == 0, :913)
+ *   points     [npoints][3]: GetWorldPos()
+ *   edges      grouped by point, points ascending, within a point in the observations map's order: e_point, e_cam (an index
+ *              into poses), e_obs = (u, v, ur) with ur < 0 for a monocular edge, e_inv_sigma2 = mvInvLevelSigma2[octave],
+ *              e_cam_k = fx fy cx cy bf of the observing keyframe.  A keyframe observes a point at most once.
+ * Limits (ORBX_ERR_UNSUPPORTED before any device work, nothing written): nfree <= 64, nfixed <= 1,024, npoints <= 65,536,
+ * nedges <= 524,288.  ORBX_ERR_ARG: a NULL array, a negative size, an index out of range, edges not grouped by ascending point, a
+ * keyframe that observes a point twice, an option outside its range.  nfree = 0 or nedges = 0: the input is returned, no launch. */
+typedef struct orbm_ba_graph {
+    int32_t nfree, nfixed, npoints, nedges;
+    const float *poses;
+    const uint8_t *fixed;
+    const float *points;
+    const int32_t *e_point, *e_cam;
+    const float *e_obs, *e_inv_sigma2, *e_cam_k;
+} orbm_ba_graph;
+/* nrounds 1 or 2, iterations[r] 0 .. 64 = optimize(n) of round r.  Round 0 carries Huber kernels iff robust_round0 (huber_mono /
+ * huber_stereo = delta, the double of the reference's float); round 1 never does.  classify: after round 0 an edge whose stored
+ * chi2 is > chi2_mono / chi2_stereo or whose point is not in front of its camera goes to level 1 (:1043-1087), and after the last
+ * round the same test fills result->erase (:1091-1127).  The two uses: */
+typedef struct orbm_ba_options {
+    int32_t nrounds, iterations[2], robust_round0, classify;
+    int32_t reserved;
+    double huber_mono, huber_stereo, chi2_mono, chi2_stereo;
+} orbm_ba_options;
+/* LocalBundleAdjustment: optimize(5), the level pass, optimize(10); (float)sqrt(5.991), (float)sqrt(7.815) */
+#define ORBM_BA_OPTIONS_LOCAL {2, {5, 10}, 1, 1, 0, 2.4476518630981445, 2.7955322265625, 5.991, 7.815}
+/* BundleAdjustment(nIterations, bRobust): one round, no level pass; (float)sqrt(5.99) -- not 5.991 -- and (float)sqrt(7.815) */
+#define ORBM_BA_OPTIONS_GLOBAL(nIterations, bRobust) {1, {(nIterations), 0}, (bRobust) ? 1 : 0, 0, 0, 2.4474475383758545, 2.7955322265625, 5.99, 7.815}
+typedef struct orbm_ba_result {
+    float *poses;                       /* [nfree][16]: what SetPose receives (the fixed keyframe too: its pose through toSE3Quat / toCvMat) */
+    float *points;                      /* [npoints][3] */
+    uint8_t *erase;                     /* [nedges]: the edge is in vToErase; written iff classify (may be NULL otherwise) */
+    uint8_t *not_included;              /* [npoints] or NULL: the point has no edge (BundleAdjustment :200-208) */
+    int32_t stopped;                    /* 0 ran to the end; 1 the stop flag was set before the first optimize (nothing changed);
+                                           2 it was seen later (behind the first round: bDoMore = false, no level pass and no second round;
+                                           the final pass still ran) */
+} orbm_ba_result;
+typedef struct orbm_ba_trial {
+    double tempChi, currentChi, rho, lambda, scale;     /* lambda: after the trial's update of it */
+    int32_t round, qmax, accepted, ok2;
+} orbm_ba_trial;
+/* Optional out-struct (test aid).  trial_log / poses / points / chi2 / level are the caller's arrays (or NULL). */
+typedef struct orbm_ba_stats {
+    int32_t rounds;                     /* rounds that ran optimize() */
+    int32_t iterations[2], trials[2];
+    int32_t nresults;
+    int32_t results[128];               /* SolverResult of every iteration: 1 OK, 2 Terminate */
+    int32_t trial_capacity, ntrials, trial_overflow;
+    orbm_ba_trial *trial_log;           /* [trial_capacity] */
+    double *poses;                      /* [nfree][7]: the final estimates, q (x y z w) and t */
+    double *points;                     /* [npoints][3] */
+    double *chi2;                       /* [nedges]: chi2() of the edge's stored error */
+    uint8_t *level;                     /* [nedges] */
+} orbm_ba_stats;
+/* stop_flag (or NULL) = pbStopFlag: read where g2o reads it (before each iteration, in the trial loop's condition) and where
+ * LocalBundleAdjustment does (:1039-1041, :1047-1049). */
+int orbm_bundle_adjustment(const orbm_ba_graph *g, const orbm_ba_options *opt, const volatile uint8_t *stop_flag, orbm_ba_result *out,
+                           orbm_ba_stats *stats);
+/* Host only, no device: the index lists the call would use.  Any output may be NULL.
+ *   pose_class[nfree + nfixed]   0 free and connected, 1 fixed, 2 free without an edge (not a vertex of the system)
+ *   point_class[npoints]         0 connected, 1 without an edge
+ *   pose_edge_start[nfree + 1], pose_edges[]   a free keyframe's edges, ascending (a fixed local keyframe: none)
+ *   block_start[nfree (nfree + 1) / 2 + 1], block_entries[][3]   block (i1 <= i2) has index i1 nfree - i1 (i1 - 1) / 2 + i2 - i1;
+ *                                its entries (point, edge of i1, edge of i2), points ascending
+ *   counts[2]                    entries of pose_edges and of block_entries (call once with NULL lists to size them) */
+int orbm_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
+                 int32_t *block_start, int32_t *block_entries, int32_t *counts);
+/* Host waits of the last orbm_bundle_adjustment of this process: trials + rounds (the stop flag seen behind the first round saves
+ * that round's wait); 0 when nothing was launched. */
+int orbm_debug_last_ba_waits(void);
 
 /* KeyFrameDatabase on the device (src/KeyFrameDatabase.cc:40-309, src/LoopClosing.cc:120-141): the BowVectors of the
  * added keyframes live in HBM, one row of (word id, value) per keyframe under a SLOT number.  Slots are handed out in ascending

@@ -1492,6 +1492,83 @@ private:
     int mStatus = ORBX_OK;
 };
 
+// Optimizer::LocalBundleAdjustment (src/Optimizer.cc:837-1162) and Optimizer::BundleAdjustment (:74-262) over orbm_bundle_adjustment:
+// a builder for the flat graph the caller fills from its walk over KeyFrame* / MapPoint* (integration/Optimizer_ba_hip.cc) and the
+// call.  Keyframes: addKeyFrame for the local ones in lLocalKeyFrames order (fixed = mnId == 0), then addFixedKeyFrame; points in
+// ascending index with their observations in the observations map's order.  Local() / Global() run the two protocols; poses / points
+// are replaced by what SetPose / SetWorldPos receive, erase[e] = the edge is in vToErase, notIncluded[n] = the point had no edge.
+// false on a library error (status(): ORBX_ERR_UNSUPPORTED beyond 64 free keyframes, where g2o remains the path).
+class BundleAdjustment {
+public:
+    std::vector<float> poses, points;               // [nfree + nfixed][16], [npoints][3]
+    std::vector<uint8_t> fixed;                     // [nfree]
+    std::vector<int32_t> ePoint, eCam;
+    std::vector<float> eObs, eInvSigma2, eCamK;     // [ne][3] (ur < 0: monocular), [ne], [ne][5] = fx fy cx cy bf
+    std::vector<uint8_t> erase, notIncluded;
+    int stopped = 0;
+
+    int addKeyFrame(const float Tcw[16], bool isFixed = false)
+    {
+        if (nFixed) return -1;                      // the local keyframes come first
+        poses.insert(poses.end(), Tcw, Tcw + 16); fixed.push_back(isFixed ? 1 : 0);
+        return nFree++;
+    }
+    int addFixedKeyFrame(const float Tcw[16])
+    {
+        poses.insert(poses.end(), Tcw, Tcw + 16);
+        return nFree + nFixed++;
+    }
+    int addPoint(const float X[3])
+    {
+        points.insert(points.end(), X, X + 3);
+        return (int)(points.size() / 3) - 1;
+    }
+    // an observation of the LAST added point
+    void addObservation(int keyframe, float u, float v, float ur, float invSigma2, float fx, float fy, float cx, float cy, float bf)
+    {
+        ePoint.push_back((int32_t)(points.size() / 3) - 1); eCam.push_back(keyframe);
+        eObs.push_back(u); eObs.push_back(v); eObs.push_back(ur); eInvSigma2.push_back(invSigma2);
+        const float k[5] = {fx, fy, cx, cy, bf};
+        eCamK.insert(eCamK.end(), k, k + 5);
+    }
+
+    bool Local(const volatile uint8_t *pbStopFlag = nullptr, orbm_ba_stats *stats = nullptr)
+    {
+        const orbm_ba_options o = ORBM_BA_OPTIONS_LOCAL;
+        return run(o, pbStopFlag, stats);
+    }
+    bool Global(int nIterations, bool bRobust, const volatile uint8_t *pbStopFlag = nullptr, orbm_ba_stats *stats = nullptr)
+    {
+        const orbm_ba_options o = ORBM_BA_OPTIONS_GLOBAL(nIterations, bRobust);
+        return run(o, pbStopFlag, stats);
+    }
+    int status() const { return mStatus; }
+    int nFreeKeyFrames() const { return nFree; }
+
+private:
+    bool run(const orbm_ba_options &o, const volatile uint8_t *pbStopFlag, orbm_ba_stats *stats)
+    {
+        orbm_ba_graph g;
+        std::memset(&g, 0, sizeof(g));
+        g.nfree = nFree; g.nfixed = nFixed; g.npoints = (int32_t)(points.size() / 3); g.nedges = (int32_t)ePoint.size();
+        g.poses = poses.data(); g.fixed = fixed.data(); g.points = points.data(); g.e_point = ePoint.data(); g.e_cam = eCam.data();
+        g.e_obs = eObs.data(); g.e_inv_sigma2 = eInvSigma2.data(); g.e_cam_k = eCamK.data();
+        std::vector<float> posesOut(16 * (size_t)nFree + 1), pointsOut(points.size() + 1);
+        erase.assign(ePoint.size() + 1, 0); notIncluded.assign(points.size() / 3 + 1, 0);
+        orbm_ba_result r;
+        std::memset(&r, 0, sizeof(r));
+        r.poses = posesOut.data(); r.points = pointsOut.data(); r.erase = erase.data(); r.not_included = notIncluded.data();
+        mStatus = orbm_bundle_adjustment(&g, &o, pbStopFlag, &r, stats);
+        if (mStatus != ORBX_OK) return false;
+        std::copy(posesOut.begin(), posesOut.begin() + 16 * (size_t)nFree, poses.begin());
+        std::copy(pointsOut.begin(), pointsOut.begin() + points.size(), points.begin());
+        erase.resize(ePoint.size()); notIncluded.resize(points.size() / 3);
+        stopped = r.stopped;
+        return true;
+    }
+    int nFree = 0, nFixed = 0, mStatus = ORBX_OK;
+};
+
 // Optimizer::PoseOptimization(Frame *pFrame) (src/Optimizer.cc:264-476) on the flattened frame: one call of
 // orbm_pose_optimization (host arrays) or orbm_frame_pose_optimization (the frame's resident handle).  kpsUn = mvKeysUn,
 // uright = mvuRight (empty: monocular), hasMp[i] = mvpMapPoints[i] != NULL, mpPos[3 i ..] = its GetWorldPos(), Tcw = mTcw

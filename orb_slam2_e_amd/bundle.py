@@ -1,0 +1,121 @@
+"""Optimizer::LocalBundleAdjustment / Optimizer::BundleAdjustment on the device (include/orbslam_hip.h, orbm_bundle_adjustment;
+DESIGN.md 24): the struct mirrors of the C ABI, the flat graph from numpy arrays, and the two calls."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, lib, ptr
+
+_vp = C.c_void_p
+HUBER_MONO_LOCAL = float(np.float32(np.sqrt(5.991)))        # (float)sqrt(5.991)
+HUBER_MONO_GLOBAL = float(np.float32(np.sqrt(5.99)))        # BundleAdjustment: 5.99
+HUBER_STEREO = float(np.float32(np.sqrt(7.815)))
+
+
+class BaGraph(C.Structure):
+    _fields_ = [("nfree", C.c_int32), ("nfixed", C.c_int32), ("npoints", C.c_int32), ("nedges", C.c_int32), ("poses", _vp), ("fixed", _vp),
+                ("points", _vp), ("e_point", _vp), ("e_cam", _vp), ("e_obs", _vp), ("e_inv_sigma2", _vp), ("e_cam_k", _vp)]
+
+
+class BaOptions(C.Structure):
+    _fields_ = [("nrounds", C.c_int32), ("iterations", C.c_int32 * 2), ("robust_round0", C.c_int32), ("classify", C.c_int32),
+                ("reserved", C.c_int32), ("huber_mono", C.c_double), ("huber_stereo", C.c_double), ("chi2_mono", C.c_double),
+                ("chi2_stereo", C.c_double)]
+
+
+class BaResult(C.Structure):
+    _fields_ = [("poses", _vp), ("points", _vp), ("erase", _vp), ("not_included", _vp), ("stopped", C.c_int32)]
+
+
+class BaStats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("nresults", C.c_int32),
+                ("results", C.c_int32 * 128), ("trial_capacity", C.c_int32), ("ntrials", C.c_int32), ("trial_overflow", C.c_int32),
+                ("trial_log", _vp), ("poses", _vp), ("points", _vp), ("chi2", _vp), ("level", _vp)]
+
+
+# orbm_ba_trial
+BA_TRIAL_DTYPE = np.dtype([("tempChi", "<f8"), ("currentChi", "<f8"), ("rho", "<f8"), ("lam", "<f8"), ("scale", "<f8"), ("round", "<i4"),
+                           ("qmax", "<i4"), ("accepted", "<i4"), ("ok2", "<i4")], align=True)
+TRIAL_CAPACITY = 10 * 128
+
+
+def local_options():
+    """ORBM_BA_OPTIONS_LOCAL"""
+    return BaOptions(2, (5, 10), 1, 1, 0, HUBER_MONO_LOCAL, HUBER_STEREO, 5.991, 7.815)
+
+
+def global_options(iterations=5, robust=True):
+    """ORBM_BA_OPTIONS_GLOBAL(nIterations, bRobust)"""
+    return BaOptions(1, (iterations, 0), 1 if robust else 0, 0, 0, HUBER_MONO_GLOBAL, HUBER_STEREO, 5.99, 7.815)
+
+
+def make_graph(poses, nfree, points, e_point, e_cam, e_obs, e_inv_sigma2, e_cam_k, fixed=None):
+    """The arrays of orbm_ba_graph as the C ABI takes them (float32 / int32, contiguous), in a dict that keeps them alive."""
+    g = {"poses": np.ascontiguousarray(poses, np.float32).reshape(-1, 16), "points": np.ascontiguousarray(points, np.float32).reshape(-1, 3),
+         "e_point": np.ascontiguousarray(e_point, np.int32), "e_cam": np.ascontiguousarray(e_cam, np.int32),
+         "e_obs": np.ascontiguousarray(e_obs, np.float32).reshape(-1, 3), "e_inv_sigma2": np.ascontiguousarray(e_inv_sigma2, np.float32),
+         "e_cam_k": np.ascontiguousarray(e_cam_k, np.float32).reshape(-1, 5), "nfree": int(nfree),
+         "fixed": None if fixed is None else np.ascontiguousarray(fixed, np.uint8)}
+    return g
+
+
+def c_graph(g):
+    def p(a):
+        return None if a is None or a.size == 0 else ptr(a)
+    return BaGraph(g["nfree"], len(g["poses"]) - g["nfree"], len(g["points"]), len(g["e_point"]), p(g["poses"]), p(g["fixed"]), p(g["points"]),
+                   p(g["e_point"]), p(g["e_cam"]), p(g["e_obs"]), p(g["e_inv_sigma2"]), p(g["e_cam_k"]))
+
+
+def plan(g):
+    """orbm_ba_plan: the vertex classes and the index lists the call would use (host only)."""
+    L = lib()
+    cg = c_graph(g)
+    nfree, npose, npts = g["nfree"], len(g["poses"]), len(g["points"])
+    counts = np.zeros(2, np.int32)
+    check(L.orbm_ba_plan(C.byref(cg), None, None, None, None, None, None, ptr(counts)))
+    out = {"pose_class": np.zeros(npose, np.int32), "point_class": np.zeros(npts, np.int32), "pose_edge_start": np.zeros(nfree + 1, np.int32),
+           "pose_edges": np.zeros(max(int(counts[0]), 1), np.int32), "block_start": np.zeros(nfree * (nfree + 1) // 2 + 1, np.int32),
+           "block_entries": np.zeros((max(int(counts[1]), 1), 3), np.int32)}
+    check(L.orbm_ba_plan(C.byref(cg), *(ptr(out[k]) if out[k].size else None for k in
+                                         ("pose_class", "point_class", "pose_edge_start", "pose_edges", "block_start", "block_entries")), ptr(counts)))
+    out["pose_edges"] = out["pose_edges"][:counts[0]]
+    out["block_entries"] = out["block_entries"][:counts[1]]
+    return out
+
+
+def run(g, options, stop_flag=None, want_stats=False):
+    """orbm_bundle_adjustment.  stop_flag: a numpy uint8 array of one element (pbStopFlag) or None.  Returns a dict: poses
+    [nfree][16], points [npoints][3], erase [nedges] (with classify), not_included [npoints], stopped, and with want_stats the
+    fields of orbm_ba_stats."""
+    L = lib()
+    cg = c_graph(g)
+    nfree, npts, ne = g["nfree"], len(g["points"]), len(g["e_point"])
+    poses = np.zeros((max(nfree, 1), 16), np.float32); points = np.zeros((max(npts, 1), 3), np.float32)
+    erase = np.zeros(max(ne, 1), np.uint8); notinc = np.zeros(max(npts, 1), np.uint8)
+    res = BaResult(ptr(poses), ptr(points), ptr(erase), ptr(notinc), 0)
+    st = None
+    if want_stats:
+        log = np.zeros(TRIAL_CAPACITY, BA_TRIAL_DTYPE)
+        pd = np.zeros((max(nfree, 1), 7)); xd = np.zeros((max(npts, 1), 3)); chi2 = np.zeros(max(ne, 1)); level = np.zeros(max(ne, 1), np.uint8)
+        st = BaStats()
+        st.trial_capacity = TRIAL_CAPACITY
+        st.trial_log, st.poses, st.points, st.chi2, st.level = (ptr(a).value for a in (log, pd, xd, chi2, level))
+    check(L.orbm_bundle_adjustment(C.byref(cg), C.byref(options), None if stop_flag is None else ptr(stop_flag), C.byref(res),
+                                   C.byref(st) if st is not None else None))
+    out = {"poses": poses[:nfree], "points": points[:npts], "erase": erase[:ne], "not_included": notinc[:npts], "stopped": res.stopped,
+           "waits": L.orbm_debug_last_ba_waits()}
+    if want_stats:
+        out.update(rounds=st.rounds, iterations=list(st.iterations), trials=list(st.trials), results=list(st.results[:min(st.nresults, 128)]),
+                   ntrials=st.ntrials, trial_overflow=st.trial_overflow, trial_log=log[:min(st.ntrials, TRIAL_CAPACITY)], poses_d=pd[:nfree],
+                   points_d=xd[:npts], chi2=chi2[:ne], level=level[:ne])
+    return out
+
+
+def local_bundle_adjustment(g, stop_flag=None, want_stats=False):
+    """Optimizer::LocalBundleAdjustment on the flattened graph: optimize(5) with Huber, the level pass, optimize(10), vToErase."""
+    return run(g, local_options(), stop_flag, want_stats)
+
+
+def bundle_adjustment(g, iterations=5, robust=True, stop_flag=None, want_stats=False):
+    """Optimizer::BundleAdjustment on the flattened graph: one round of optimize(iterations); not_included marks the points left out."""
+    return run(g, global_options(iterations, robust), stop_flag, want_stats)
