@@ -37,7 +37,8 @@ const char *orbx_last_error(void);
  * orbm_search_by_projection_map_poses, orbm_frame_search_by_projection_map_poses, orbm_debug_last_map_poses_waits;
  * orbm_init_find_models, orbm_init_check_rt, orbm_init_reconstruct_f, orbm_debug_last_init_waits, orbm_debug_init_svd;
  * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits; orbm_pnp_hypotheses, orbm_debug_last_pnp_waits, orbm_debug_pnp_pose;
- * orbm_debug_fill_workspaces, orbm_debug_last_search_waits; orbm_bundle_adjustment, orbm_ba_plan, orbm_debug_last_ba_waits. */
+ * orbm_debug_fill_workspaces, orbm_debug_last_search_waits; orbm_bundle_adjustment, orbm_ba_plan, orbm_debug_last_ba_waits;
+ * orbm_global_bundle_adjustment, orbm_global_ba_plan, orbm_llt_tile, orbm_llt_solve_dev, orbm_debug_last_llt_launches. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -1080,9 +1081,42 @@ int orbm_bundle_adjustment(const orbm_ba_graph *g, const orbm_ba_options *opt, c
  *   counts[2]                    entries of pose_edges and of block_entries (call once with NULL lists to size them) */
 int orbm_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
                  int32_t *block_start, int32_t *block_entries, int32_t *counts);
-/* Host waits of the last orbm_bundle_adjustment of this process: trials + rounds (the stop flag seen behind the first round saves
- * that round's wait); 0 when nothing was launched. */
+/* Host waits of the last orbm_bundle_adjustment or orbm_global_bundle_adjustment of this process: trials + rounds (the stop flag
+ * seen behind the first round saves that round's wait); 0 when nothing was launched. */
 int orbm_debug_last_ba_waits(void);
+/* The same call for a map of up to 512 keyframes (the global BA behind a loop closure, LoopClosing::RunGlobalBundleAdjustment;
+ * DESIGN.md 25): signatures, structs, options (either ORBM_BA_OPTIONS_* form), stop flag, waits and every documented deviation as
+ * orbm_bundle_adjustment / orbm_ba_plan.  What differs: nfree <= 512 (nfixed, npoints, nedges as above), and block_entries may hold at
+ * most 2^25 = 33,554,432 entries (ORBX_ERR_UNSUPPORTED before any device work, nothing written; no graph the other entry admits
+ * exceeds it).  The reduced system, up to 3,072 wide, is ALWAYS solved by orbm_llt_solve_dev, at every size: a graph both entries
+ * admit gives the same bytes through either.  The leased workspace grows to about 80 MB at 512 keyframes and stays leased to the
+ * process like every arena. */
+int orbm_global_bundle_adjustment(const orbm_ba_graph *g, const orbm_ba_options *opt, const volatile uint8_t *stop_flag, orbm_ba_result *out,
+                                  orbm_ba_stats *stats);
+int orbm_global_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
+                        int32_t *block_start, int32_t *block_entries, int32_t *counts);
+
+/* ------------------------------------------------------------------ tiled dense Cholesky solve
+ * S x = b for a symmetric positive definite S of 1 <= n <= 3,072 rows, over many workgroups, in T x T tiles (T = orbm_llt_tile()).
+ * Everything is DEVICE memory; the call is asynchronous on `stream`, waits for nothing on the host and allocates nothing.
+ *   S_dev   [n][n] column-major: entry (row i, column j) is S[j * n + i].  Only i >= j is read as input.  On return the lower
+ *           triangle holds L with S = L L^T; the strict upper triangle is the call's scratch (written before read, contents
+ *           unspecified afterwards)
+ *   b_dev   [n], read only; must not overlap x_dev
+ *   x_dev   [n]: the solution (scratch of the call until then)
+ *   ok_dev  one word: 1, or 0 when a pivot was not > 0 (<= 0 or NaN); then x = 0.0 everywhere and L is unspecified.  Both are
+ *           written on every path; the host never reads the word
+ * The arithmetic, operation by operation (plain double multiplies and adds, no fused multiply-add, no matrix instruction, no
+ * floating-point atomic), which makes the result independent of T and equal to the one-workgroup solve of orbm_bundle_adjustment:
+ *   L[i][j] = (a[i][j] - dot) / L[j][j], pivot L[j][j] = sqrt(a[j][j] - dot); column 0 has no dot
+ *   dot = L[i][0] L[j][0] (not 0.0 + it), then dot = dot + L[i][k] L[j][k] for k = 1 .. j - 1 in ascending k
+ *   y_i = b_i, y_i -= L[i][j] y_j for j = 0 .. i - 1 ascending, then y_i / L[i][i]
+ *   x_i = y_i, x_i -= L[j][i] x_j for j = n - 1 .. i + 1 descending, then x_i / L[i][i]
+ * n outside 1 .. 3,072 or a NULL pointer: ORBX_ERR_ARG before any device work.  4 ceil(n / T) - 1 launches. */
+int orbm_llt_tile(void);
+int orbm_llt_solve_dev(int n, double *S_dev, const double *b_dev, double *x_dev, int32_t *ok_dev, void *stream);
+/* Kernel launches of the last orbm_llt_solve_dev of this process. */
+int orbm_debug_last_llt_launches(void);
 
 /* KeyFrameDatabase on the device (src/KeyFrameDatabase.cc:40-309, src/LoopClosing.cc:120-141): the BowVectors of the
  * added keyframes live in HBM, one row of (word id, value) per keyframe under a SLOT number.  Slots are handed out in ascending

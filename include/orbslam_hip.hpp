@@ -1497,7 +1497,9 @@ private:
 // call.  Keyframes: addKeyFrame for the local ones in lLocalKeyFrames order (fixed = mnId == 0), then addFixedKeyFrame; points in
 // ascending index with their observations in the observations map's order.  Local() / Global() run the two protocols; poses / points
 // are replaced by what SetPose / SetWorldPos receive, erase[e] = the edge is in vToErase, notIncluded[n] = the point had no edge.
-// false on a library error (status(): ORBX_ERR_UNSUPPORTED beyond 64 free keyframes, where g2o remains the path).
+// false on a library error (status(): ORBX_ERR_UNSUPPORTED beyond 64 free keyframes, where g2o remains the path).  GlobalMap() is
+// Global() over orbm_global_bundle_adjustment: a whole map of up to 512 keyframes (Optimizer::GlobalBundleAdjustemnt behind a loop
+// closure), the reduced system solved by the tiled multi-workgroup Cholesky; the same bytes as Global() where both accept the graph.
 class BundleAdjustment {
 public:
     std::vector<float> poses, points;               // [nfree + nfixed][16], [npoints][3]
@@ -1542,11 +1544,16 @@ public:
         const orbm_ba_options o = ORBM_BA_OPTIONS_GLOBAL(nIterations, bRobust);
         return run(o, pbStopFlag, stats);
     }
+    bool GlobalMap(int nIterations, bool bRobust, const volatile uint8_t *pbStopFlag = nullptr, orbm_ba_stats *stats = nullptr)
+    {
+        const orbm_ba_options o = ORBM_BA_OPTIONS_GLOBAL(nIterations, bRobust);
+        return run(o, pbStopFlag, stats, true);
+    }
     int status() const { return mStatus; }
     int nFreeKeyFrames() const { return nFree; }
 
 private:
-    bool run(const orbm_ba_options &o, const volatile uint8_t *pbStopFlag, orbm_ba_stats *stats)
+    bool run(const orbm_ba_options &o, const volatile uint8_t *pbStopFlag, orbm_ba_stats *stats, bool wholeMap = false)
     {
         orbm_ba_graph g;
         std::memset(&g, 0, sizeof(g));
@@ -1558,7 +1565,7 @@ private:
         orbm_ba_result r;
         std::memset(&r, 0, sizeof(r));
         r.poses = posesOut.data(); r.points = pointsOut.data(); r.erase = erase.data(); r.not_included = notIncluded.data();
-        mStatus = orbm_bundle_adjustment(&g, &o, pbStopFlag, &r, stats);
+        mStatus = wholeMap ? orbm_global_bundle_adjustment(&g, &o, pbStopFlag, &r, stats) : orbm_bundle_adjustment(&g, &o, pbStopFlag, &r, stats);
         if (mStatus != ORBX_OK) return false;
         std::copy(posesOut.begin(), posesOut.begin() + 16 * (size_t)nFree, poses.begin());
         std::copy(pointsOut.begin(), pointsOut.begin() + points.size(), points.begin());

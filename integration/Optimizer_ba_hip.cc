@@ -6,8 +6,11 @@
 // the two functions keep their bodies and gain one first line each,
 //     if (HipLocalBundleAdjustment(pKF, pbStopFlag, pMap)) return;
 //     if (HipBundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)) return;
-// Both return false beyond the library's limits (ORBX_ERR_UNSUPPORTED: more than 64 free keyframes, 1,024 fixed ones, 65,536
-// points or 524,288 edges -- the global BA after a loop closure of a long session): the caller keeps g2o there.  A refusal leaves
+// Both return false beyond the library's limits (ORBX_ERR_UNSUPPORTED: more than 64 local keyframes, 1,024 fixed ones, 65,536
+// points or 524,288 edges; for BundleAdjustment more than 512 keyframes -- the global BA after a loop closure of a long session):
+// the caller keeps g2o there.  BundleAdjustment over more than 64 keyframes (LoopClosing::RunGlobalBundleAdjustment's
+// GlobalBundleAdjustemnt over the whole map) goes through orbm_global_bundle_adjustment, whose reduced system is solved by the tiled
+// multi-workgroup Cholesky; up to 64 it keeps orbm_bundle_adjustment.  A refusal leaves
 // the map as it found it: BundleAdjustment's walk writes nothing, and LocalBundleAdjustment's walk, which marks keyframes and points
 // with mnBALocalForKF / mnBAFixedForKF and tests those marks, counts the local keyframes before it marks anything and puts every
 // mark back when a later limit refuses, so that the reference's walk behind it finds what it would have found without the shell.
@@ -218,6 +221,7 @@ bool HipBundleAdjustment(const std::vector<KeyFrame *> &vpKFs, const std::vector
         if (pKF->mnId > maxKFid) maxKFid = pKF->mnId;
     }
     if (nIterations > 64) return false;                                         // (the library's range of optimize(n))
+    if (vpUsedKFs.size() > 512) return false;                                   // orbm_global_bundle_adjustment's limit; nothing has been touched
     // ---- :114-209: a point that is bad gets no vertex; one without an edge is left out by the library (not_included)
     std::vector<MapPoint *> vpUsedMPs;
     for (size_t i = 0; i < vpMP.size(); i++) {
@@ -241,7 +245,8 @@ bool HipBundleAdjustment(const std::vector<KeyFrame *> &vpKFs, const std::vector
     std::vector<uint8_t> notIncluded(vpUsedMPs.size() + 1, 0);
     orbm_ba_result res;
     res.poses = posesOut.data(); res.points = pointsOut.data(); res.erase = NULL; res.not_included = notIncluded.data(); res.stopped = 0;
-    const int rc = orbm_bundle_adjustment(&g, &opt, reinterpret_cast<const volatile uint8_t *>(pbStopFlag), &res, NULL);
+    const volatile uint8_t *stop = reinterpret_cast<const volatile uint8_t *>(pbStopFlag);
+    const int rc = nfree > 64 ? orbm_global_bundle_adjustment(&g, &opt, stop, &res, NULL) : orbm_bundle_adjustment(&g, &opt, stop, &res, NULL);
     if (rc == ORBX_ERR_UNSUPPORTED) return false;
     if (rc != ORBX_OK) throw std::runtime_error(std::string("orbm_bundle_adjustment: ") + orbx_last_error());
 

@@ -13,4 +13,5 @@ from .sim3 import Sim3OptProblem, Sim3Problem, Sim3Solver, optimize_sim3, sim3_h
 from .initializer import Initializer, check_rt, find_models, last_init_waits, reconstruct_f  # noqa: F401
 from .keyframe_database import KeyFrameDatabase  # noqa: F401
 from .pnp import PnPsolver, PnpProblem, pnp_hypotheses  # noqa: F401
-from .bundle import BaGraph, BaOptions, BaResult, BaStats, bundle_adjustment, local_bundle_adjustment  # noqa: F401
+from .bundle import (BaGraph, BaOptions, BaResult, BaStats, bundle_adjustment, global_bundle_adjustment,  # noqa: F401
+                     llt_solve_device, local_bundle_adjustment)

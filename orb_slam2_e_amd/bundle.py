@@ -1,5 +1,6 @@
 """Optimizer::LocalBundleAdjustment / Optimizer::BundleAdjustment on the device (include/orbslam_hip.h, orbm_bundle_adjustment;
-DESIGN.md 24): the struct mirrors of the C ABI, the flat graph from numpy arrays, and the two calls."""
+DESIGN.md 24): the struct mirrors of the C ABI, the flat graph from numpy arrays, and the two calls.  The same for a whole map of up
+to 512 keyframes (orbm_global_bundle_adjustment) and the tiled Cholesky solve under it on torch device tensors."""
 import ctypes as C
 
 import numpy as np
@@ -68,23 +69,42 @@ def c_graph(g):
 
 def plan(g):
     """orbm_ba_plan: the vertex classes and the index lists the call would use (host only)."""
-    L = lib()
+    return _plan(g, lib().orbm_ba_plan)
+
+
+def plan_global(g):
+    """orbm_global_ba_plan: the same lists under the limits of orbm_global_bundle_adjustment (512 free keyframes)."""
+    return _plan(g, lib().orbm_global_ba_plan)
+
+
+def _plan(g, entry):
     cg = c_graph(g)
     nfree, npose, npts = g["nfree"], len(g["poses"]), len(g["points"])
     counts = np.zeros(2, np.int32)
-    check(L.orbm_ba_plan(C.byref(cg), None, None, None, None, None, None, ptr(counts)))
+    check(entry(C.byref(cg), None, None, None, None, None, None, ptr(counts)))
     out = {"pose_class": np.zeros(npose, np.int32), "point_class": np.zeros(npts, np.int32), "pose_edge_start": np.zeros(nfree + 1, np.int32),
            "pose_edges": np.zeros(max(int(counts[0]), 1), np.int32), "block_start": np.zeros(nfree * (nfree + 1) // 2 + 1, np.int32),
            "block_entries": np.zeros((max(int(counts[1]), 1), 3), np.int32)}
-    check(L.orbm_ba_plan(C.byref(cg), *(ptr(out[k]) if out[k].size else None for k in
-                                         ("pose_class", "point_class", "pose_edge_start", "pose_edges", "block_start", "block_entries")), ptr(counts)))
+    check(entry(C.byref(cg), *(ptr(out[k]) if out[k].size else None for k in
+                               ("pose_class", "point_class", "pose_edge_start", "pose_edges", "block_start", "block_entries")), ptr(counts)))
     out["pose_edges"] = out["pose_edges"][:counts[0]]
     out["block_entries"] = out["block_entries"][:counts[1]]
     return out
 
 
 def run(g, options, stop_flag=None, want_stats=False):
-    """orbm_bundle_adjustment.  stop_flag: a numpy uint8 array of one element (pbStopFlag) or None.  Returns a dict: poses
+    """orbm_bundle_adjustment (up to 64 free keyframes).  See _run for the arguments and the result."""
+    return _run(g, options, stop_flag, want_stats, lib().orbm_bundle_adjustment)
+
+
+def run_global(g, options, stop_flag=None, want_stats=False):
+    """orbm_global_bundle_adjustment: the same call for up to 512 free keyframes; its reduced system is always solved by the tiled
+    multi-workgroup Cholesky (llt_solve_device), which gives run()'s bytes wherever both accept the graph."""
+    return _run(g, options, stop_flag, want_stats, lib().orbm_global_bundle_adjustment)
+
+
+def _run(g, options, stop_flag, want_stats, entry):
+    """Either bundle-adjustment entry.  stop_flag: a numpy uint8 array of one element (pbStopFlag) or None.  Returns a dict: poses
     [nfree][16], points [npoints][3], erase [nedges] (with classify), not_included [npoints], stopped, and with want_stats the
     fields of orbm_ba_stats."""
     L = lib()
@@ -100,8 +120,8 @@ def run(g, options, stop_flag=None, want_stats=False):
         st = BaStats()
         st.trial_capacity = TRIAL_CAPACITY
         st.trial_log, st.poses, st.points, st.chi2, st.level = (ptr(a).value for a in (log, pd, xd, chi2, level))
-    check(L.orbm_bundle_adjustment(C.byref(cg), C.byref(options), None if stop_flag is None else ptr(stop_flag), C.byref(res),
-                                   C.byref(st) if st is not None else None))
+    check(entry(C.byref(cg), C.byref(options), None if stop_flag is None else ptr(stop_flag), C.byref(res),
+                C.byref(st) if st is not None else None))
     out = {"poses": poses[:nfree], "points": points[:npts], "erase": erase[:ne], "not_included": notinc[:npts], "stopped": res.stopped,
            "waits": L.orbm_debug_last_ba_waits()}
     if want_stats:
@@ -119,3 +139,27 @@ def local_bundle_adjustment(g, stop_flag=None, want_stats=False):
 def bundle_adjustment(g, iterations=5, robust=True, stop_flag=None, want_stats=False):
     """Optimizer::BundleAdjustment on the flattened graph: one round of optimize(iterations); not_included marks the points left out."""
     return run(g, global_options(iterations, robust), stop_flag, want_stats)
+
+
+def global_bundle_adjustment(g, iterations=10, robust=False, stop_flag=None, want_stats=False):
+    """Optimizer::GlobalBundleAdjustemnt on the flattened graph of a whole map, up to 512 keyframes (LoopClosing runs it with 10
+    iterations and bRobust = false): bundle_adjustment through orbm_global_bundle_adjustment."""
+    return run_global(g, global_options(iterations, robust), stop_flag, want_stats)
+
+
+def llt_tile():
+    """orbm_llt_tile: the tile edge of the tiled Cholesky solve."""
+    return lib().orbm_llt_tile()
+
+
+def llt_solve_device(S_dev, b_dev, x_dev, ok_dev, stream=None):
+    """orbm_llt_solve_dev on torch device tensors, asynchronous on `stream` (a torch.cuda.Stream; None: the current one).  S_dev:
+    float64 [n][n], contiguous, whose element [j][i] is entry (row i, column j) of the matrix -- only i >= j is read; it comes back
+    with L in that triangle and scratch in the other.  b_dev, x_dev: float64 [n]; ok_dev: int32 [1].  Nothing is waited for."""
+    import torch
+    n = int(b_dev.numel())
+    for t, dt, numel in ((S_dev, torch.float64, n * n), (b_dev, torch.float64, n), (x_dev, torch.float64, n), (ok_dev, torch.int32, 1)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == numel):
+            raise ValueError("llt_solve_device: contiguous device tensors float64 [n][n], [n], [n] and int32 [1]")
+    st = (stream if stream is not None else torch.cuda.current_stream(S_dev.device)).cuda_stream
+    check(lib().orbm_llt_solve_dev(n, S_dev.data_ptr(), b_dev.data_ptr(), x_dev.data_ptr(), ok_dev.data_ptr(), st))

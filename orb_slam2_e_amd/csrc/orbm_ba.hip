@@ -13,7 +13,9 @@
 //   k_ba_schur        BlockSolver::solve (core/block_solver.hpp:354-496): one wave per upper block (i1 <= i2), lane (r, c) subtracts
 //                     (B_i1 Dinv) B_i2^T entry by entry over the block's (point, edge, edge) list, points ascending; bschur likewise
 //   k_ba_solve        dense LLT of the 6 nact reduced system, lower triangle, every entry's dot product in ascending k; ONE
-//                     workgroup; the matrix lives in the workspace, a row at a time goes through LDS
+//                     workgroup; the matrix lives in the workspace, a row at a time goes through LDS.  orbm_global_bundle_adjustment
+//                     (up to 512 free keyframes, a system up to 3,072 wide) calls orbm_llt_solve_dev (orbm_llt.hip) in its place:
+//                     the same operations in the same order over many workgroups, hence the same bytes
 //   k_ba_update(_pose) push; xl = Dinv (bl - B^T xp); oplus on points and poses; computeScale's terms
 //   k_ba_reduce       the block partials of chi2 / scale / the largest diagonal entry joined in a fixed tree
 //   k_ba_pop, k_ba_classify, k_ba_activate, k_ba_final   the copies, the level pass, initializeOptimization(0)'s vertex set, write-back
@@ -44,6 +46,10 @@ constexpr int RT = 256;                 // the reduction's one block
 constexpr int ST = 384;                 // the solve's one block: a thread per row of the largest system
 constexpr int BA_MAXFREE = 64, BA_MAXFIXED = 1024, BA_MAXPOINTS = 65536, BA_MAXEDGES = 524288, BA_MAXITER = 64;
 static_assert(ST == 6 * BA_MAXFREE, "a thread per row");
+// orbm_global_bundle_adjustment: the tiled solve takes the reduced system of 512 keyframes; its block-entry list is capped (403 MB)
+constexpr int BA_MAXFREE_GLOBAL = 512;
+constexpr int64_t BA_MAXBLOCKENT_GLOBAL = (int64_t)1 << 25;
+static_assert(BA_MAXFREE_GLOBAL * (BA_MAXFREE_GLOBAL + 1) / 2 < (1 << 30), "block indices are ints");
 
 // the call's arrays on the device
 struct BaDev {
@@ -174,7 +180,7 @@ __global__ __launch_bounds__(PT) void k_ba_init(BaDev D)
 // initializeOptimization(level 0): a vertex is in the system iff one of its edges is on level 0.  One block.
 __global__ __launch_bounds__(RT) void k_ba_activate(BaDev D)
 {
-    __shared__ int s_act[BA_MAXFREE];
+    __shared__ int s_act[BA_MAXFREE_GLOBAL];
     __shared__ int s_edges;
     if (threadIdx.x == 0) s_edges = 0;
     __syncthreads();
@@ -344,6 +350,8 @@ __global__ __launch_bounds__(PT) void k_ba_dinv(BaDev D, double lambda, int lamb
 
 // One wave per upper block (i1 <= i2) of the free poses.  Lane 6 r + c owns entry (r, c) of the block: Hpp (+ lambda on the
 // diagonal) minus (B_i1 Dinv) B_i2^T, point after point.  Lanes 36 .. 41 of a diagonal block: bschur = bp - sum B_i (Dinv bl).
+// The block's (i1, i2) is found by walking the rows: at most nfree steps (512, for the 131,328 blocks of the largest graph of
+// orbm_global_bundle_adjustment), which is short beside the entry list of any block that has work.
 __global__ __launch_bounds__(PT) void k_ba_schur(BaDev D, double lambda, int lambda_on_device)
 {
     int i1 = 0, b = blockIdx.x;
@@ -473,10 +481,10 @@ __global__ __launch_bounds__(PT) void k_ba_update(BaDev D, double lambda, int la
     if (threadIdx.x == 0) D.part_scale[blockIdx.x] = sc;
 }
 
-// push; SE3Quat::exp(update) * estimate; a pose's terms of computeScale.  One block.
+// push; SE3Quat::exp(update) * estimate; a pose's terms of computeScale.  A thread per free pose.
 __global__ __launch_bounds__(PT) void k_ba_update_pose(BaDev D, double lambda, int lambda_on_device)
 {
-    const int p = threadIdx.x;
+    const int p = blockIdx.x * PT + threadIdx.x;
     if (p >= D.nfree) return;
     Se3 T;
     load_pose(D.est, p, T);
@@ -564,10 +572,11 @@ struct BaPlan {
 inline int block_index(int nfree, int i1, int i2) { return i1 * nfree - i1 * (i1 - 1) / 2 + (i2 - i1); }
 
 // limits, indices, grouping; the vertex classes, the pose -> edge lists and the block -> (point, edge, edge) lists
-int ba_plan(const orbm_ba_graph &g, BaPlan &P)
+int ba_plan(const orbm_ba_graph &g, BaPlan &P, bool global)
 {
     if (g.nfree < 0 || g.nfixed < 0 || g.npoints < 0 || g.nedges < 0) ORBX_FAIL(ORBX_ERR_ARG, "negative size");
-    if (g.nfree > BA_MAXFREE) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 64 free keyframes");
+    if (!global && g.nfree > BA_MAXFREE) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 64 free keyframes");
+    if (global && g.nfree > BA_MAXFREE_GLOBAL) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 512 free keyframes");
     if (g.nfixed > BA_MAXFIXED) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 1,024 fixed keyframes");
     if (g.npoints > BA_MAXPOINTS) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 65,536 points");
     if (g.nedges > BA_MAXEDGES) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 524,288 edges");
@@ -601,6 +610,15 @@ int ba_plan(const orbm_ba_graph &g, BaPlan &P)
         }
     }
     auto is_free = [&](int c) { return c < g.nfree && P.pose_class[c] == 0; };
+    if (global) {                                                       // the block lists' size, before they are counted block by block
+        int64_t entries = 0;
+        for (int n = 0; n < g.npoints; ++n) {
+            int64_t d = 0;
+            for (int a = P.e_start[n]; a < P.e_start[n + 1]; ++a) d += is_free(g.e_cam[a]);
+            entries += d * (d + 1) / 2;
+        }
+        if (entries > BA_MAXBLOCKENT_GLOBAL) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "the block lists exceed 2^25 entries");
+    }
     const int nblk = g.nfree * (g.nfree + 1) / 2;
     P.pe_start.assign((size_t)g.nfree + 1, 0);
     P.blk_start.assign((size_t)nblk + 1, 0);
@@ -650,7 +668,7 @@ int check_options(const orbm_ba_options &o)
     return ORBX_OK;
 }
 
-std::atomic<int> g_last_ba_waits{0};    // host waits of the last orbm_bundle_adjustment of this process
+std::atomic<int> g_last_ba_waits{0};    // host waits of the last orbm_bundle_adjustment / orbm_global_bundle_adjustment of this process
 
 void reset_stats(orbm_ba_stats *st)
 {
@@ -673,14 +691,12 @@ void answer_unchanged(const orbm_ba_graph &g, const orbm_ba_options &opt, const 
     reset_stats(st);
 }
 
-} // namespace
-
-int orbm_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
-                 int32_t *block_start, int32_t *block_entries, int32_t *counts)
+int plan_out(const orbm_ba_graph *g, bool global, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
+             int32_t *block_start, int32_t *block_entries, int32_t *counts)
 {
     if (!g) ORBX_FAIL(ORBX_ERR_ARG, "null graph");
     BaPlan P;
-    const int rc = ba_plan(*g, P);
+    const int rc = ba_plan(*g, P, global);
     if (rc != ORBX_OK) return rc;
     auto copy = [](int32_t *dst, const std::vector<int32_t> &v) { if (dst && !v.empty()) memcpy(dst, v.data(), sizeof(int32_t) * v.size()); };
     copy(pose_class, P.pose_class); copy(point_class, P.point_class); copy(pose_edge_start, P.pe_start); copy(pose_edges, P.pe_list);
@@ -689,17 +705,18 @@ int orbm_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_cla
     return ORBX_OK;
 }
 
-int orbm_debug_last_ba_waits(void) { return g_last_ba_waits.load(); }
-
-int orbm_bundle_adjustment(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile uint8_t *stop_flag, orbm_ba_result *outp,
-                           orbm_ba_stats *stats)
+// The body of both public entries.  global: the limits of orbm_global_bundle_adjustment and the tiled solve (orbm_llt_solve_dev over
+// the arena's S, bschur, xp and the trial block's ok2 word) in k_ba_solve's place, at every size.  results[128] holds for both: an
+// iteration writes one, and two rounds of at most 64 make 128.
+int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile uint8_t *stop_flag, orbm_ba_result *outp, orbm_ba_stats *stats,
+           bool global)
 {
     if (!gp || !op || !outp) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     const orbm_ba_graph &g = *gp;
     const orbm_ba_options &opt = *op;
     orbm_ba_result &out = *outp;
     BaPlan P;
-    int rc = ba_plan(g, P);
+    int rc = ba_plan(g, P, global);
     if (rc != ORBX_OK) return rc;
     if ((rc = check_options(opt)) != ORBX_OK) return rc;
     if ((g.nfree && !out.poses) || (g.npoints && !out.points) || (opt.classify && g.nedges && !out.erase)) ORBX_FAIL(ORBX_ERR_ARG, "null result array");
@@ -801,9 +818,10 @@ int orbm_bundle_adjustment(const orbm_ba_graph *gp, const orbm_ba_options *op, c
                     const int on_dev = it == 0 && qmax == 0;                    // computeLambdaInit's value is still on the device
                     hipLaunchKernelGGL(k_ba_dinv, g_pts, b_pt, 0, st, D, lambda, on_dev);
                     hipLaunchKernelGGL(k_ba_schur, dim3(nblocks_schur), b_pt, 0, st, D, lambda, on_dev);
-                    hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(ST), 0, st, D);
+                    if (!global) hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(ST), 0, st, D);
+                    else if ((rc = orbm_llt_solve_dev(6 * nact, D.S, D.bsch, D.xp, D.isc + 1, st)) != ORBX_OK) return rc;   // nact: what k_ba_activate left in isc[0]
                     hipLaunchKernelGGL(k_ba_update, g_pts, b_pt, 0, st, D, lambda, on_dev);
-                    hipLaunchKernelGGL(k_ba_update_pose, dim3(1), b_pt, 0, st, D, lambda, on_dev);
+                    hipLaunchKernelGGL(k_ba_update_pose, dim3((unsigned)((g.nfree + PT - 1) / PT)), b_pt, 0, st, D, lambda, on_dev);
                     hipLaunchKernelGGL(k_ba_errors, g_pts, b_pt, 0, st, D, robust, dm, ds);
                     hipLaunchKernelGGL(k_ba_reduce, dim3(1), dim3(RT), 0, st, D, 1);
                     ORBX_HIP(hipGetLastError());
@@ -893,4 +911,32 @@ int orbm_bundle_adjustment(const orbm_ba_graph *gp, const orbm_ba_options *op, c
     }
     g_last_ba_waits = waits;
     return ORBX_OK;
+}
+
+} // namespace
+
+int orbm_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
+                 int32_t *block_start, int32_t *block_entries, int32_t *counts)
+{
+    return plan_out(g, false, pose_class, point_class, pose_edge_start, pose_edges, block_start, block_entries, counts);
+}
+
+int orbm_global_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
+                        int32_t *block_start, int32_t *block_entries, int32_t *counts)
+{
+    return plan_out(g, true, pose_class, point_class, pose_edge_start, pose_edges, block_start, block_entries, counts);
+}
+
+int orbm_debug_last_ba_waits(void) { return g_last_ba_waits.load(); }
+
+int orbm_bundle_adjustment(const orbm_ba_graph *g, const orbm_ba_options *opt, const volatile uint8_t *stop_flag, orbm_ba_result *out,
+                           orbm_ba_stats *stats)
+{
+    return ba_run(g, opt, stop_flag, out, stats, false);
+}
+
+int orbm_global_bundle_adjustment(const orbm_ba_graph *g, const orbm_ba_options *opt, const volatile uint8_t *stop_flag, orbm_ba_result *out,
+                                  orbm_ba_stats *stats)
+{
+    return ba_run(g, opt, stop_flag, out, stats, true);
 }
