@@ -38,7 +38,8 @@ const char *orbx_last_error(void);
  * orbm_init_find_models, orbm_init_check_rt, orbm_init_reconstruct_f, orbm_debug_last_init_waits, orbm_debug_init_svd;
  * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits; orbm_pnp_hypotheses, orbm_debug_last_pnp_waits, orbm_debug_pnp_pose;
  * orbm_debug_fill_workspaces, orbm_debug_last_search_waits; orbm_bundle_adjustment, orbm_ba_plan, orbm_debug_last_ba_waits;
- * orbm_global_bundle_adjustment, orbm_global_ba_plan, orbm_llt_tile, orbm_llt_solve_dev, orbm_debug_last_llt_launches. */
+ * orbm_global_bundle_adjustment, orbm_global_ba_plan, orbm_llt_tile, orbm_llt_solve_dev, orbm_debug_last_llt_launches;
+ * orbm_essential_graph, orbm_eg_plan, orbm_debug_last_eg_waits. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -1117,6 +1118,73 @@ int orbm_llt_tile(void);
 int orbm_llt_solve_dev(int n, double *S_dev, const double *b_dev, double *x_dev, int32_t *ok_dev, void *stream);
 /* Kernel launches of the last orbm_llt_solve_dev of this process. */
 int orbm_debug_last_llt_launches(void);
+
+/* ------------------------------------------------------------------ essential graph
+ * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1165-1428): the Sim3 pose graph LoopClosing::CorrectLoop
+ * optimises between SearchAndFuse and the global BA, on the graph the caller has flattened.  The caller only walks pointers: vScw,
+ * the measurements Sji, the 20 Levenberg iterations, the SE3 recovery and the map-point correction are the call's.  g2o's Levenberg
+ * loop runs on the host and drives device passes -- errors + chi2, g2o's NUMERIC Jacobians of every edge, the 7-wide blocks into a
+ * dense system, orbm_llt_solve_dev (at every size), the update -- with one host wait per trial and one at the end.
+ *   poses              [nvert][16]: GetPose() of every non-bad keyframe, in vpKFs order
+ *   corrected          [nvert]: row of corrected_sim3 [ncorr][8] (q xyzw, t, s: the CorrectedSim3 entry), or -1
+ *   noncorrected       [nvert]: the same into noncorrected_sim3 [nnc][8]
+ *   fixed              [nvert]: 1 = pLoopKF
+ *   edges              in the reference's creation order (:1236-1367): e_v0 = nIDi (vertex 0), e_v1 = nIDj (vertex 1), e_kind 0 = an
+ *                      edge of the LoopConnections loop (Sji = vScw[j] vScw[i]^-1), 1 = a spanning-tree, old-loop or covisibility edge
+ *                      (each side takes its NonCorrectedSim3 where it has one, else vScw)
+ *   points, p_ref      [npoints][3] GetWorldPos(), and the vertex index of the keyframe :1404-1413 choose
+ * Limits (ORBX_ERR_UNSUPPORTED before any device work, nothing written): nact <= 438 (the free vertices that have an edge: the system
+ * is 7 nact wide and orbm_llt_solve_dev takes 3,072), nvert <= 1,024, nedges <= 32,768, npoints <= 1,048,576.  ORBX_ERR_ARG: a NULL
+ * array, a negative size, an index out of range, e_v0 == e_v1, an edge between two fixed vertices, a non-finite input value,
+ * iterations outside 0 .. 64, lambda_init not positive and finite.  nedges = 0, nact = 0 or iterations = 0: no solve; the
+ * conversions and the point correction still run on the unchanged estimates. */
+typedef struct orbm_eg_graph {
+    int32_t nvert, ncorr, nnc, nedges, npoints, fix_scale;
+    const float *poses;
+    const int32_t *corrected;
+    const double *corrected_sim3;
+    const int32_t *noncorrected;
+    const double *noncorrected_sim3;
+    const uint8_t *fixed;
+    const int32_t *e_v0, *e_v1;
+    const uint8_t *e_kind;
+    const float *points;
+    const int32_t *p_ref;
+} orbm_eg_graph;
+typedef struct orbm_eg_options {
+    int32_t iterations;                 /* optimize(n), 0 .. 64 */
+    int32_t reserved;
+    double lambda_init;                 /* setUserLambdaInit: > 0 */
+} orbm_eg_options;
+#define ORBM_EG_ITERATIONS 20
+#define ORBM_EG_OPTIONS_DEFAULT {ORBM_EG_ITERATIONS, 0, 1e-16}
+typedef struct orbm_eg_result {
+    float *poses;                       /* [nvert][16]: [R | t / s] as :1383-1393 form it, of every vertex (the fixed and the edgeless too) */
+    float *points;                      /* [npoints][3]: correctedSwr.map(Srw.map(P)) */
+} orbm_eg_result;
+/* Optional out-struct (test aid).  trial_log / estimates / chi2 are the caller's arrays (or NULL).  A trial's `round` is 0. */
+typedef struct orbm_eg_stats {
+    int32_t iterations, trials;
+    int32_t nresults;
+    int32_t results[64];                /* SolverResult of every iteration: 1 OK, 2 Terminate */
+    int32_t trial_capacity, ntrials, trial_overflow;
+    orbm_ba_trial *trial_log;           /* [trial_capacity] */
+    double *estimates;                  /* [nvert][8]: the final estimates, q (x y z w), t, s */
+    double *chi2;                       /* [nedges]: chi2() of the edge's stored error */
+} orbm_eg_stats;
+int orbm_essential_graph(const orbm_eg_graph *g, const orbm_eg_options *opt, orbm_eg_result *out, orbm_eg_stats *stats);
+/* Host only, no device: the index lists the call would use.  Any output may be NULL.
+ *   vertex_class[nvert]      0 free with an edge (a vertex of the system), 1 fixed, 2 free without an edge
+ *   row[nvert]               block row of a class-0 vertex in the system (ascending in vertex order), else -1
+ *   vert_edge_start[nvert + 1], vert_edges[]   a class-0 vertex's edges in edge order, as 2 edge + side (side: the vertex is vertex 0 / 1)
+ *   pair_start[npairs + 1], pair_v[npairs][2], pair_edges[]   the pairs of class-0 vertices an edge joins, ascending by (smaller row,
+ *                            larger row); pair_v = (vertex of the smaller row, of the larger); its edges in edge order as 2 edge + o,
+ *                            o = 1 when the edge's vertex 0 has the larger row
+ *   counts[3]                entries of vert_edges, pairs, entries of pair_edges (call once with NULL lists to size them) */
+int orbm_eg_plan(const orbm_eg_graph *g, int32_t *vertex_class, int32_t *row, int32_t *vert_edge_start, int32_t *vert_edges,
+                 int32_t *pair_start, int32_t *pair_v, int32_t *pair_edges, int32_t *counts);
+/* Host waits of the last orbm_essential_graph of this process: trials + 1; 0 when nothing was launched. */
+int orbm_debug_last_eg_waits(void);
 
 /* KeyFrameDatabase on the device (src/KeyFrameDatabase.cc:40-309, src/LoopClosing.cc:120-141): the BowVectors of the
  * added keyframes live in HBM, one row of (word id, value) per keyframe under a SLOT number.  Slots are handed out in ascending

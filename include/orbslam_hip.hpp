@@ -1576,6 +1576,68 @@ private:
     int nFree = 0, nFixed = 0, mStatus = ORBX_OK;
 };
 
+// Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1165-1428) over orbm_essential_graph: a builder for the flat graph the caller
+// fills from its walk (integration/Optimizer_essential_graph_hip.cc) and the call.  addKeyFrame in vpKFs order (corrected /
+// nonCorrected: the CorrectedSim3 / NonCorrectedSim3 entry as q xyzw, t, s, or nullptr); the edges in the reference's creation order:
+// addLoopConnection for the LoopConnections loop (:1236-1264), addEdge for a spanning-tree, old-loop or covisibility edge
+// (:1284-1366), vertex 0 = nIDi first; addPoint with the index of the keyframe :1404-1413 choose.  Optimize() replaces poses by what
+// SetPose receives and points by what SetWorldPos receives.  false on a library error (status(): ORBX_ERR_UNSUPPORTED beyond 438
+// free keyframes with an edge, where g2o remains the path).
+class EssentialGraph {
+public:
+    std::vector<float> poses, points;               // [nvert][16], [npoints][3]
+    std::vector<int32_t> corrected, nonCorrected;   // [nvert]: row of the table, or -1
+    std::vector<double> correctedSim3, nonCorrectedSim3;    // [..][8]
+    std::vector<uint8_t> fixed, eKind;
+    std::vector<int32_t> eV0, eV1, pRef;
+    bool fixScale = true;
+
+    int addKeyFrame(const float Tcw[16], bool isFixed = false, const double *correctedEntry = nullptr, const double *nonCorrectedEntry = nullptr)
+    {
+        poses.insert(poses.end(), Tcw, Tcw + 16); fixed.push_back(isFixed ? 1 : 0);
+        corrected.push_back(entry(correctedSim3, correctedEntry)); nonCorrected.push_back(entry(nonCorrectedSim3, nonCorrectedEntry));
+        return (int)fixed.size() - 1;
+    }
+    void addLoopConnection(int vi, int vj) { eV0.push_back(vi); eV1.push_back(vj); eKind.push_back(0); }
+    void addEdge(int vi, int vj) { eV0.push_back(vi); eV1.push_back(vj); eKind.push_back(1); }
+    int addPoint(const float X[3], int reference)
+    {
+        points.insert(points.end(), X, X + 3); pRef.push_back(reference);
+        return (int)pRef.size() - 1;
+    }
+
+    bool Optimize(int nIterations = ORBM_EG_ITERATIONS, orbm_eg_stats *stats = nullptr)
+    {
+        orbm_eg_graph g;
+        std::memset(&g, 0, sizeof(g));
+        g.nvert = (int32_t)fixed.size(); g.ncorr = (int32_t)(correctedSim3.size() / 8); g.nnc = (int32_t)(nonCorrectedSim3.size() / 8);
+        g.nedges = (int32_t)eV0.size(); g.npoints = (int32_t)pRef.size(); g.fix_scale = fixScale ? 1 : 0;
+        g.poses = poses.data(); g.corrected = corrected.data(); g.corrected_sim3 = correctedSim3.data(); g.noncorrected = nonCorrected.data();
+        g.noncorrected_sim3 = nonCorrectedSim3.data(); g.fixed = fixed.data(); g.e_v0 = eV0.data(); g.e_v1 = eV1.data(); g.e_kind = eKind.data();
+        g.points = points.data(); g.p_ref = pRef.data();
+        orbm_eg_options o = ORBM_EG_OPTIONS_DEFAULT;
+        o.iterations = nIterations;
+        std::vector<float> posesOut(poses.size() + 1), pointsOut(points.size() + 1);
+        orbm_eg_result r;
+        r.poses = posesOut.data(); r.points = pointsOut.data();
+        mStatus = orbm_essential_graph(&g, &o, &r, stats);
+        if (mStatus != ORBX_OK) return false;
+        std::copy(posesOut.begin(), posesOut.begin() + poses.size(), poses.begin());
+        std::copy(pointsOut.begin(), pointsOut.begin() + points.size(), points.begin());
+        return true;
+    }
+    int status() const { return mStatus; }
+
+private:
+    static int32_t entry(std::vector<double> &table, const double *e)
+    {
+        if (!e) return -1;
+        table.insert(table.end(), e, e + 8);
+        return (int32_t)(table.size() / 8) - 1;
+    }
+    int mStatus = ORBX_OK;
+};
+
 // Optimizer::PoseOptimization(Frame *pFrame) (src/Optimizer.cc:264-476) on the flattened frame: one call of
 // orbm_pose_optimization (host arrays) or orbm_frame_pose_optimization (the frame's resident handle).  kpsUn = mvKeysUn,
 // uright = mvuRight (empty: monocular), hasMp[i] = mvpMapPoints[i] != NULL, mpPos[3 i ..] = its GetWorldPos(), Tcw = mTcw

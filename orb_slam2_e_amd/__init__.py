@@ -15,3 +15,5 @@ from .keyframe_database import KeyFrameDatabase  # noqa: F401
 from .pnp import PnPsolver, PnpProblem, pnp_hypotheses  # noqa: F401
 from .bundle import (BaGraph, BaOptions, BaResult, BaStats, bundle_adjustment, global_bundle_adjustment,  # noqa: F401
                      llt_solve_device, local_bundle_adjustment)
+from .essential_graph import EgGraph, EgOptions, EgResult, EgStats  # noqa: F401
+from .essential_graph import optimize as optimize_essential_graph  # noqa: F401

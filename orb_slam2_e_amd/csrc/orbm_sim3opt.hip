@@ -13,11 +13,12 @@
 // 7 x 7 LDLT, Sim3(update), the compose and the inverse are computed by every lane from the same reduced values (identical bits in
 // every lane: wave-uniform without a broadcast barrier).  A pair's constants are staged once, in LDS for the first SO_LDS_PAIRS
 // pairs and in the workspace beyond.  The quaternion / LDLT / Huber helpers and the reductions are the ones orbm_pose.hip uses
-// (orbm_g2o_math.h).
+// (orbm_g2o_math.h); g2o's Sim3 with its exp, product and inverse is orbm_sim3_math.h, which orbm_essential_graph.hip shares.
 #include <atomic>
 
 #include "orbm_g2o_math.h"
 #include "orbm_internal.h"
+#include "orbm_sim3_math.h"
 
 using namespace orbm_detail;
 
@@ -27,8 +28,6 @@ constexpr int SO_MAX_P = 64, SO_MAX_N = 8192;
 constexpr int SO_NT = 256;              // threads per problem: four waves (one wave, NT = 64, was measured too and lost: DESIGN.md 14)
 constexpr int SO_LDS_PAIRS = 512;       // pairs whose constants are staged in LDS (48 B each)
 constexpr int SO_NSYS = 28 + 7 + 1;     // lower triangle of H, J^T rho1 omega e, robust chi2
-
-struct Sim3 { double q[4], t[3], s; };  // q = x y z w
 
 // One problem of a call, staged with the inputs.  o_*: byte offsets in the workspace.
 struct Sim3OptDev {
@@ -43,87 +42,6 @@ struct Sim3OptDev {
 };
 
 struct PairC { float v[12]; };          // Xc1 [3], Xc2 [3], obs1 [2], obs2 [2], info1, info2
-
-// ------------------------------------------------------------------ sim3.h
-
-__host__ __device__ inline void sim3_from_rts(const float *R, const float *t, float s, Sim3 &o)   // :64-67 from the float inputs
-{
-    double Rd[9];
-    for (int k = 0; k < 9; ++k) Rd[k] = R[k];
-    quat_from_matrix(Rd, o.q);
-    for (int k = 0; k < 3; ++k) o.t[k] = t[k];
-    o.s = s;
-}
-
-__device__ void sim3_exp(const double u[7], Sim3 &o)   // Sim3(const Vector7d&), :70-142
-{
-    const double w0 = u[0], w1 = u[1], w2 = u[2], sigma = u[6];
-    const double theta = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-    const double Om[9] = {0., -w2, w1, w2, 0., -w0, -w1, w0, 0.};
-    const double s = exp(sigma);
-    double O2[9], R[9], A, B, C;
-    ORBM_UNROLL for (int i = 0; i < 3; ++i)
-        ORBM_UNROLL for (int j = 0; j < 3; ++j) O2[3 * i + j] = Om[3 * i] * Om[j] + Om[3 * i + 1] * Om[3 + j] + Om[3 * i + 2] * Om[6 + j];
-    const double eps = 0.00001;
-    const bool small_theta = theta < eps;
-    if (fabs(sigma) < eps) {
-        C = 1;
-        if (small_theta) { A = 1. / 2.; B = 1. / 6.; }
-        else {
-            const double theta2 = theta * theta;
-            A = (1 - cos(theta)) / (theta2);
-            B = (theta - sin(theta)) / (theta2 * theta);
-        }
-    } else {
-        C = (s - 1) / sigma;
-        if (small_theta) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1) * s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
-        } else {
-            const double a = s * sin(theta), b = s * cos(theta), theta2 = theta * theta, sigma2 = sigma * sigma, c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
-        }
-    }
-    if (small_theta) {      // the first-order rotation: not orthogonal, and its quaternion is taken unnormalised
-        ORBM_UNROLL for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + Om[k] + O2[k];
-    } else {
-        const double ra = sin(theta) / theta, rb = (1 - cos(theta)) / (theta * theta);
-        ORBM_UNROLL for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + ra * Om[k] + rb * O2[k];
-    }
-    quat_from_matrix(R, o.q);
-    double W[9];
-    ORBM_UNROLL for (int k = 0; k < 9; ++k) W[k] = A * Om[k] + B * O2[k] + C * ((k % 4 == 0) ? 1.0 : 0.0);
-    ORBM_UNROLL for (int i = 0; i < 3; ++i) o.t[i] = W[3 * i] * u[3] + W[3 * i + 1] * u[4] + W[3 * i + 2] * u[5];
-    o.s = s;
-}
-
-__device__ __forceinline__ void sim3_mul(const Sim3 &A, const Sim3 &B, Sim3 &O)   // :266-272
-{
-    Sim3 r;
-    double rt[3];
-    const double *a = A.q, *b = B.q;
-    r.q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    r.q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-    q_rotate(A.q, B.t, rt);
-    ORBM_UNROLL for (int k = 0; k < 3; ++k) r.t[k] = A.s * rt[k] + A.t[k];
-    r.s = A.s * B.s;
-    O = r;
-}
-
-__device__ __forceinline__ void sim3_inverse(const Sim3 &A, Sim3 &O)   // :233-236
-{
-    Sim3 r;
-    const double f = -1. / A.s;
-    const double v[3] = {f * A.t[0], f * A.t[1], f * A.t[2]};
-    r.q[0] = -A.q[0]; r.q[1] = -A.q[1]; r.q[2] = -A.q[2]; r.q[3] = A.q[3];
-    q_rotate(r.q, v, r.t);
-    r.s = 1. / A.s;
-    O = r;
-}
 
 // computeError of EdgeSim3ProjectXYZ (S = the estimate, X = the point of keyframe 2) and of EdgeInverseSim3ProjectXYZ (S = its
 // inverse, X = the point of keyframe 1): obs - cam_map(project(S.map(X)))
