@@ -39,7 +39,7 @@ const char *orbx_last_error(void);
  * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits; orbm_pnp_hypotheses, orbm_debug_last_pnp_waits, orbm_debug_pnp_pose;
  * orbm_debug_fill_workspaces, orbm_debug_last_search_waits; orbm_bundle_adjustment, orbm_ba_plan, orbm_debug_last_ba_waits;
  * orbm_global_bundle_adjustment, orbm_global_ba_plan, orbm_llt_tile, orbm_llt_solve_dev, orbm_debug_last_llt_launches;
- * orbm_essential_graph, orbm_eg_plan, orbm_debug_last_eg_waits. */
+ * orbm_essential_graph, orbm_eg_plan, orbm_debug_last_eg_waits; orbm_refine_sim3_candidates, orbm_debug_last_refine_sim3_waits. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -917,6 +917,44 @@ int orbm_search_by_sim3(const orbm_frame *kf1, const orbm_frame *kf2, const orbm
                         const float *R12, const float *t12, const orbm_points *points1, const orbm_points *points2, float th, int th_high,
                         int32_t *vnMatch1, int32_t *vnMatch2, int32_t *match12, int *nfound, orbm_window_query *q12_out,
                         orbm_window_query *q21_out);
+
+/* ------------------------------------------- LoopClosing::ComputeSim3's refinement: SearchBySim3 chained into OptimizeSim3
+ * src/LoopClosing.cc:311-341 for up to 64 refinement attempts against one current keyframe in ONE call: per attempt SearchBySim3
+ * (src/ORBmatcher.cc:1303-1527), the correspondence walk of OptimizeSim3 (src/Optimizer.cc:1483-1520) and OptimizeSim3 itself, with
+ * one staged upload and one host wait; nothing returns to the host in between.  An attempt has no side effects in the
+ * reference (vpMapPointMatches and gScm are its locals), so the attempts of one pass of the loop at :288 can be evaluated together
+ * and the host takes the first in order with nin >= 20.
+ * Shared: kf1 = mpCurrentKF, points1 = one entry per keypoint of kf1 (valid = map point non-NULL and not bad; pos, desc,
+ * min_distance, max_distance), T1w, view (fx .. cy serve both keyframes, as in orbm_search_by_sim3), inv_level_sigma2 [view->nlevels].
+ * Per attempt: kf2, points2 (one entry per keypoint of kf2), T2w, the Sim3 as LoopClosing.cc:320-325 hands it over, and
+ *   seed12[n1]     vpMapPointMatches as the attempt starts from it (:313-319): >= 0 the point's GetIndexInKeyFrame(pKF2), -1 NULL,
+ *                  -2 non-NULL without an index in KF2 (blocks slot i1 in the search, ORBmatcher.cc:1335-1338, marks nothing in
+ *                  KF2, and OptimizeSim3 skips it at Optimizer.cc:1498).  vbAlreadyMatched1 / 2 are derived from it by the library:
+ *                  valid does NOT fold them in, unlike orbm_search_by_sim3.  NULL = all -1.
+ *   found12[n1]    (out) match12 of orbm_search_by_sim3 alone; nfound[p] its count
+ *   matches12[n1]  (out) vpMatches1 as OptimizeSim3 leaves it: seed12[i1] >= 0 ? seed12[i1] : found12[i1], set to -1 where the cut
+ *                  (:1577-1590 / :1611-1620) erased it; -2 stays -2
+ * results[P]: as orbm_optimize_sim3.  A pair (i1, i2 = the merged index) is a correspondence iff i2 >= 0, points1.valid[i1] and
+ * points2.valid[i2]; the correspondences are optimised in ascending i1. */
+typedef struct orbm_refine_sim3_attempt {
+    const orbm_frame *kf2;
+    const orbm_points *points2;
+    const float *T2w;                  /* 4 x 4 row-major */
+    float R12[9], t12[3], s12;
+    const int32_t *seed12;
+    int32_t *found12, *matches12;
+} orbm_refine_sim3_attempt;
+
+/* P = 0 .. 64 attempts (beyond: ORBX_ERR_UNSUPPORTED), frames of at most 8,192 keypoints.  ORBX_ERR_ARG before anything is launched,
+ * with every output untouched: points.n != the handle's n, a seed >= n2 or < -2, a keypoint octave outside [0, nlevels).  P = 0, or
+ * a kf1 without keypoints: ORBX_OK, nothing is launched.  An attempt whose kf2 has no keypoints returns the input Sim3 and nin = 0,
+ * as orbm_optimize_sim3 does for n = 0.  th = 7.5, th_high = TH_HIGH, th2 = 10 in the reference. */
+int orbm_refine_sim3_candidates(const orbm_frame *kf1, const orbm_points *points1, const float *T1w, const orbm_view *view,
+                                const float *inv_level_sigma2, const orbm_refine_sim3_attempt *attempts, int P, float th, int th_high,
+                                float th2, int fix_scale, int32_t *nfound, orbm_sim3_opt_result *results);
+/* Host waits (stream synchronisations) of the last orbm_refine_sim3_candidates call of this process: 1 when it launched, 0 when it
+ * returned before the launch. */
+int orbm_debug_last_refine_sim3_waits(void);
 
 /* ------------------------------------------------------------------ pose-only optimisation
  * Optimizer::PoseOptimization(Frame *pFrame)   src/Optimizer.cc:264-476, the g2o graph it builds and the Levenberg loop g2o runs on

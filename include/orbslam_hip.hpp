@@ -2179,6 +2179,58 @@ inline int OptimizeSim3(const std::vector<Sim3OptProblem> &problems, const std::
     return ORBX_OK;
 }
 
+// The refinement tail of LoopClosing::ComputeSim3 (src/LoopClosing.cc:311-341) over orbm_refine_sim3_candidates: per attempt
+// SearchBySim3 chained into OptimizeSim3, pointer walk included, for every candidate whose solver returned a similarity in one pass of
+// the loop at :288 -- ONE library call, one host wait.  An attempt has no side effects in the reference, so evaluating the attempts of
+// a pass together and taking the first in order with nin >= 20 gives the reference's result.
+struct RefineSim3Attempt {
+    const ORBmatcher::ResidentFrame *KF2 = nullptr;
+    const ORBmatcher::PointList *points2 = nullptr;     // one entry per keypoint of KF2: valid = map point non-NULL and not bad
+    float T2w[16];
+    float R12[9], t12[3], s12 = 1.f;                    // the Sim3 as LoopClosing.cc:320-325 hands it over
+    std::vector<int32_t> seed12;                        // [N1] vpMapPointMatches (:313-319): >= 0 GetIndexInKeyFrame(pKF2), -1 NULL, -2 without an index; empty: all -1
+    // results
+    std::vector<int32_t> found12, matches12;            // what SearchBySim3 alone writes; vpMatches1 as OptimizeSim3 leaves it
+    int nFound = 0;
+    orbm_sim3_opt_result result;                        // result.nin = OptimizeSim3's return value, (q, t, s) = gScm on return
+};
+
+// Returns the library's status.  *accepted (optional) = the fold of the loop at :288 over this pass: the index of the first attempt in
+// order with nin >= minInliers, -1 when there is none.  points1: one entry per keypoint of KF1 (mpCurrentKF).
+inline int RefineSim3Candidates(const ORBmatcher::ResidentFrame &KF1, const ORBmatcher::PointList &points1, const float *T1w,
+                                const ORBmatcher::Calibration &K, const std::vector<float> &invLevelSigma2,
+                                std::vector<RefineSim3Attempt> &attempts, bool bFixScale, int *accepted = nullptr, float th = 7.5f,
+                                float th2 = 10.f, int minInliers = 20)
+{
+    if (accepted) *accepted = -1;
+    const size_t N1 = (size_t)KF1.N;
+    const orbm_points p1 = points1.view(); const orbm_view v = K.view();
+    std::vector<orbm_refine_sim3_attempt> flat(attempts.size());
+    std::vector<orbm_points> p2(attempts.size());
+    for (size_t k = 0; k < attempts.size(); ++k) {
+        RefineSim3Attempt &a = attempts[k];
+        orbm_refine_sim3_attempt &q = flat[k];
+        if (!a.KF2 || !a.points2 || (!a.seed12.empty() && a.seed12.size() != N1)) return ORBX_ERR_ARG;
+        p2[k] = a.points2->view();
+        a.found12.assign(N1 ? N1 : 1, -1); a.matches12.assign(N1 ? N1 : 1, -1);
+        q.kf2 = a.KF2->handle(); q.points2 = &p2[k]; q.T2w = a.T2w;
+        memcpy(q.R12, a.R12, sizeof(q.R12)); memcpy(q.t12, a.t12, sizeof(q.t12)); q.s12 = a.s12;
+        q.seed12 = a.seed12.empty() ? nullptr : a.seed12.data(); q.found12 = a.found12.data(); q.matches12 = a.matches12.data();
+    }
+    std::vector<int32_t> nfound(attempts.size() ? attempts.size() : 1, 0);
+    std::vector<orbm_sim3_opt_result> results(attempts.size() ? attempts.size() : 1, orbm_sim3_opt_result());
+    const int rc = orbm_refine_sim3_candidates(KF1.handle(), &p1, T1w, &v, invLevelSigma2.data(), flat.data(), (int)flat.size(), th,
+                                               ORBmatcher::TH_HIGH, th2, bFixScale ? 1 : 0, nfound.data(), results.data());
+    if (rc != ORBX_OK) return rc;
+    for (size_t k = 0; k < attempts.size(); ++k) {
+        RefineSim3Attempt &a = attempts[k];
+        a.found12.resize(N1); a.matches12.resize(N1);
+        a.nFound = nfound[k]; a.result = results[k];
+        if (accepted && *accepted < 0 && a.result.nin >= minInliers) *accepted = (int)k;
+    }
+    return ORBX_OK;
+}
+
 // Initializer (include/Initializer.h, src/Initializer.cc) over orbm_init_find_models / orbm_init_reconstruct_f.  The constructor takes
 // what the reference's takes of the reference frame -- mvKeysUn[i].pt of every keypoint, K (3 x 3 row-major), sigma and the iteration
 // count -- and Initialize what it takes of the current frame plus a source of draws: a callback int(int lo, int hi) (inclusive, as

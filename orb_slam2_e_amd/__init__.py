@@ -9,7 +9,8 @@ from .extractor import KP_DTYPE, ComputeStereoMatches, ORBextractor, extract_pai
 from .matcher import Distortion, Frame, FuseTarget, MapSnapshot, ORBmatcher, Points, TriangKeyFrame, View, image_bounds, undistort_points  # noqa: F401
 from .pose import PoseCamera, PoseStats, pose_optimization, pose_optimization_batch, pose_optimization_batch_device  # noqa: F401
 from .pose import pose_optimization_nr, pose_optimization_nr_batch  # noqa: F401
-from .sim3 import Sim3OptProblem, Sim3Problem, Sim3Solver, optimize_sim3, sim3_hypotheses  # noqa: F401
+from .sim3 import (RefineSim3Attempt, Sim3OptProblem, Sim3Problem, Sim3Solver, first_accepted, optimize_sim3,  # noqa: F401
+                   refine_sim3_candidates, sim3_hypotheses)
 from .initializer import Initializer, check_rt, find_models, last_init_waits, reconstruct_f  # noqa: F401
 from .keyframe_database import KeyFrameDatabase  # noqa: F401
 from .pnp import PnPsolver, PnpProblem, pnp_hypotheses  # noqa: F401

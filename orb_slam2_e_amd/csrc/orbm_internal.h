@@ -1,5 +1,5 @@
 // orbm_internal.h -- pieces shared by the matcher translation units (orbm_match.hip, orbm_frame.hip, orbm_window.hip,
-// orbm_search.hip, orbm_triang.hip, orbm_pose.hip, orbm_pose_nr.hip, orbm_sim3.hip, orbm_sim3opt.hip, orbm_init.hip, orbm_pnp.hip, orbm_essential_graph.hip): the Frame grid
+// orbm_search.hip, orbm_triang.hip, orbm_pose.hip, orbm_pose_nr.hip, orbm_sim3.hip, orbm_sim3opt.hip, orbm_refine_sim3.hip, orbm_init.hip, orbm_pnp.hip, orbm_essential_graph.hip): the Frame grid
 // constants, the keypoint / query records of the windowed searches, the resident frame (struct orbm_frame) and the map snapshot
 // (struct orbm_map), the per-call workspace and small host / device helpers.  What only orbm_frame.hip, orbm_window.hip and
 // orbm_search.hip share among themselves is in orbm_search_internal.h.

@@ -885,23 +885,14 @@ __global__ __launch_bounds__(MT) void k_rotation(const int *__restrict__ acc_sp,
 //   FORM_KF     SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) :1702-1735  (no depth test, as the reference)
 //   FORM_SIM3   SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)             :518-563    (pose = the decomposed Scw)
 //   FORM_PAIR   one direction of SearchBySim3                                     :1360-1396 / :1442-1478 (two transforms)
-// Output: the GetFeaturesInArea query of every entry (r < 0: the entry is skipped before the search).
-enum { FORM_LAST = 0, FORM_KF = 1, FORM_SIM3 = 2, FORM_PAIR = 3 };
-struct FormCam {
-    float fx, fy, cx, cy, min_x, max_x, min_y, max_y, mbf, log_scale, th;
-    float R[9], t[3], Ow[3];      // Rcw, tcw, Ow  (FORM_PAIR: Ra, ta = first transform)
-    float R2[9], t2[3];           // FORM_PAIR: the second transform (sR21, t21 / sR12, t12)
-    int nlevels, form, forward, backward;
-};
-
-__global__ __launch_bounds__(MT) void k_project_form(const uint8_t *__restrict__ valid, const float *__restrict__ pos,
-                                                     const float *__restrict__ nrm, const float *__restrict__ mind,
-                                                     const float *__restrict__ maxd, const int *__restrict__ octave, int m, FormCam cam,
-                                                     const float *__restrict__ scale, WinQuery *__restrict__ q, StageJob job)
+// Output: the GetFeaturesInArea query of every entry (r < 0: the entry is skipped before the search).  project_form_entry is
+// entry i of a list under `cam` (FormCam: orbm_search_internal.h); k_project_form runs one list, k_project_pair_jobs the FORM_PAIR
+// lists of a batch of SearchBySim3 attempts (orbm_refine_sim3.hip).
+__device__ __forceinline__ WinQuery project_form_entry(int i, const uint8_t *__restrict__ valid, const float *__restrict__ pos,
+                                                       const float *__restrict__ nrm, const float *__restrict__ mind,
+                                                       const float *__restrict__ maxd, const int *__restrict__ octave, const FormCam &cam,
+                                                       const float *__restrict__ scale)
 {
-    if (stage_block(job)) return;
-    const int i = (blockIdx.x - job.nblocks) * MT + threadIdx.x;
-    if (i >= m) return;
     WinQuery w = {0.f, 0.f, -1.f, 0.f, 0, -1}; // r < 0: no candidates
     if (valid[i]) {
         const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
@@ -963,7 +954,29 @@ __global__ __launch_bounds__(MT) void k_project_form(const uint8_t *__restrict__
             }
         }
     }
-    q[i] = w;
+    return w;
+}
+
+__global__ __launch_bounds__(MT) void k_project_form(const uint8_t *__restrict__ valid, const float *__restrict__ pos,
+                                                     const float *__restrict__ nrm, const float *__restrict__ mind,
+                                                     const float *__restrict__ maxd, const int *__restrict__ octave, int m, FormCam cam,
+                                                     const float *__restrict__ scale, WinQuery *__restrict__ q, StageJob job)
+{
+    if (stage_block(job)) return;
+    const int i = (blockIdx.x - job.nblocks) * MT + threadIdx.x;
+    if (i >= m) return;
+    q[i] = project_form_entry(i, valid, pos, nrm, mind, maxd, octave, cam, scale);
+}
+
+// SearchBySim3's two projection passes for every (attempt, direction) of a batch: job blockIdx.y, entry by blockIdx.x
+__global__ __launch_bounds__(MT) void k_project_pair_jobs(const PairSearchJob *__restrict__ jobs, char *__restrict__ ws, const float *__restrict__ scale)
+{
+    const PairSearchJob &J = jobs[blockIdx.y];
+    const int i = blockIdx.x * MT + threadIdx.x;
+    if (i >= J.nq) return;
+    reinterpret_cast<WinQuery *>(ws + J.o_q)[i] =
+        project_form_entry(i, reinterpret_cast<const uint8_t *>(ws + J.o_valid), reinterpret_cast<const float *>(ws + J.o_pos), nullptr,
+                           reinterpret_cast<const float *>(ws + J.o_min), reinterpret_cast<const float *>(ws + J.o_max), nullptr, J.cam, scale);
 }
 
 // SearchBySim3's acceptance and agreement check (src/ORBmatcher.cc:1426-1429, :1505-1507, :1509-1524) over the two window searches.
@@ -972,12 +985,12 @@ __global__ __launch_bounds__(MT) void k_sim3_agree(const int *__restrict__ best1
                                                    int *__restrict__ vn1, int *__restrict__ vn2, int *__restrict__ m12, int *__restrict__ nfound)
 {
     const int i = blockIdx.x * MT + threadIdx.x;
-    if (i < n2) vn2[i] = idx2[i] >= 0 && best2[i] <= th_high ? idx2[i] : -1;
+    if (i < n2) vn2[i] = sim3_accepted(best2[i], idx2[i], th_high);
     bool found = false;
     if (i < n1) {
-        const int a = idx1[i] >= 0 && best1[i] <= th_high ? idx1[i] : -1;
+        const int a = sim3_accepted(best1[i], idx1[i], th_high);
         vn1[i] = a;
-        if (a >= 0 && a < n2) found = (idx2[a] >= 0 && best2[a] <= th_high ? idx2[a] : -1) == i;
+        found = sim3_agreed(i, a, best2, idx2, n2, th_high);
         m12[i] = found ? a : -1;
     }
     const unsigned long long b = __ballot(found);
@@ -1363,30 +1376,6 @@ int run_sequential(const SeqSearch &r)
         break;
     }
     return ORBX_OK;
-}
-
-void form_cam_common(FormCam &c, const orbm_view *v, const orbm_frame *f, int form, float th)
-{
-    memset(&c, 0, sizeof(c));
-    c.fx = v->fx; c.fy = v->fy; c.cx = v->cx; c.cy = v->cy;
-    c.min_x = f->min_x; c.max_x = f->max_x; c.min_y = f->min_y; c.max_y = f->max_y;
-    c.mbf = v->mbf; c.log_scale = v->log_scale_factor; c.th = th; c.nlevels = v->nlevels; c.form = form;
-}
-
-bool bad_view(const orbm_view *v) { return !v || !v->scale_factors || v->nlevels < 1 || v->nlevels > 16; }
-bool bad_points(const orbm_points *p, bool need_range, bool need_normal, bool need_octave, int nlevels)
-{
-    if (!p || p->n < 0 || p->n > 65536) return true;
-    if (p->n == 0) return false;
-    if (!p->valid || !p->pos || !p->desc) return true;
-    if (need_range && (!p->min_distance || !p->max_distance)) return true;
-    if (need_normal && !p->normal) return true;
-    if (need_octave) {
-        if (!p->octave) return true;
-        for (int i = 0; i < p->n; ++i)
-            if (p->valid[i] && (p->octave[i] < 0 || p->octave[i] >= nlevels)) return true;
-    }
-    return false;
 }
 
 // orbm_search_projection on a frame from either source: the caller's windows, the loop of SearchByProjection (:69-130)
@@ -1968,18 +1957,7 @@ int orbm_search_by_sim3(const orbm_frame *kf1, const orbm_frame *kf2, const orbm
     if (n1 == 0 || n2 == 0) return ORBX_OK;
     PointsPrefix p12, p21;
     p12.pts = points1; p21.pts = points2; p12.scale = p21.scale = view->scale_factors;
-    form_cam_common(p12.cam, view, kf2, FORM_PAIR, th);       // KF1's points into KF2 (:1348-1428)
-    form_cam_common(p21.cam, view, kf1, FORM_PAIR, th);       // and back (:1430-1507)
-    pose_parts(T1w, p12.cam.R, p12.cam.t);
-    pose_parts(T2w, p21.cam.R, p21.cam.t);
-    {   // :1320-1323: sR12 = s12 * R12, sR21 = (1.0 / s12) * R12.t(), t21 = -sR21 * t12
-        float R12t[9];
-        scale_mat(R12, 9, (double)s12, p21.cam.R2);
-        memcpy(p21.cam.t2, t12, sizeof(float) * 3);
-        transpose3(R12, R12t);
-        scale_mat(R12t, 9, 1.0 / (double)s12, p12.cam.R2);
-        gemm3(p12.cam.R2, t12, -1.0, nullptr, 0.0, p12.cam.t2);
-    }
+    form_pair_cams(p12.cam, p21.cam, view, kf1, kf2, T1w, T2w, s12, R12, t12, th);
     WorkspaceLease lease;
     Workspace &w = *lease.w;
     w.used = 0;
@@ -2023,3 +2001,8 @@ int orbm_search_by_sim3(const orbm_frame *kf1, const orbm_frame *kf2, const orbm
 }
 
 } // extern "C"
+
+void orbm_detail::launch_project_pair_jobs(hipStream_t st, const PairSearchJob *djobs, int njobs, int max_nq, char *ws, const float *dscale)
+{
+    hipLaunchKernelGGL(k_project_pair_jobs, dim3((max_nq + MT - 1) / MT, njobs), dim3(MT), 0, st, djobs, ws, dscale);
+}

@@ -1,7 +1,8 @@
-// orbm_search_internal.h -- what the three units of the windowed searches share and nothing else:
+// orbm_search_internal.h -- what the units of the windowed searches share and nothing else:
 //   orbm_frame.hip   makes frames: sorted on the host for one call (sort_frame) or resident in HBM (k_frame_build);
 //   orbm_window.hip  searches them with independent queries (k_win_best, k_map_search_poses, k_fuse_keyframes);
 //   orbm_search.hip  searches them with the reference's coupled loops (run_sequential), and SearchBySim3 through launch_win_best.
+//   orbm_refine_sim3.hip runs SearchBySim3 for a batch of attempts through the two job kernels of those units (PairSearchJob).
 // A frame reaches a search as a FrameSrc and its kernels as a FrameView; the projection of a map point (project_point) exists once,
 // for k_project_points and k_fuse_keyframes.  What only one unit uses stays in that unit; what the
 // other matcher units need as well is in orbm_internal.h.
@@ -180,6 +181,77 @@ inline bool bad_octaves(const orbm_frame *f) { return f->n && (f->min_octave < 0
 // level, second, second level, idx).
 void launch_win_best(hipStream_t st, const WinQuery *dq, const uint4 *da, int nq, const FrameView &fv, const uint8_t *docc, int has_uright,
                      int init_dist, const float *inv_sigma2, int fuse_gate, int *ob);
+
+// ---- The projection prefixes of the whole-function searches (k_project_form, orbm_search.hip): the form and what it reads of the
+// view, the searched frame and the poses.
+enum { FORM_LAST = 0, FORM_KF = 1, FORM_SIM3 = 2, FORM_PAIR = 3 };
+struct FormCam {
+    float fx, fy, cx, cy, min_x, max_x, min_y, max_y, mbf, log_scale, th;
+    float R[9], t[3], Ow[3];      // Rcw, tcw, Ow  (FORM_PAIR: Ra, ta = first transform)
+    float R2[9], t2[3];           // FORM_PAIR: the second transform (sR21, t21 / sR12, t12)
+    int nlevels, form, forward, backward;
+};
+
+inline void form_cam_common(FormCam &c, const orbm_view *v, const orbm_frame *f, int form, float th)
+{
+    memset(&c, 0, sizeof(c));
+    c.fx = v->fx; c.fy = v->fy; c.cx = v->cx; c.cy = v->cy;
+    c.min_x = f->min_x; c.max_x = f->max_x; c.min_y = f->min_y; c.max_y = f->max_y;
+    c.mbf = v->mbf; c.log_scale = v->log_scale_factor; c.th = th; c.nlevels = v->nlevels; c.form = form;
+}
+
+inline bool bad_view(const orbm_view *v) { return !v || !v->scale_factors || v->nlevels < 1 || v->nlevels > 16; }
+inline bool bad_points(const orbm_points *p, bool need_range, bool need_normal, bool need_octave, int nlevels)
+{
+    if (!p || p->n < 0 || p->n > 65536) return true;
+    if (p->n == 0) return false;
+    if (!p->valid || !p->pos || !p->desc) return true;
+    if (need_range && (!p->min_distance || !p->max_distance)) return true;
+    if (need_normal && !p->normal) return true;
+    if (need_octave) {
+        if (!p->octave) return true;
+        for (int i = 0; i < p->n; ++i)
+            if (p->valid[i] && (p->octave[i] < 0 || p->octave[i] >= nlevels)) return true;
+    }
+    return false;
+}
+
+// The two cameras of SearchBySim3: c12 takes KF1's points into KF2 (src/ORBmatcher.cc:1348-1428), c21 KF2's into KF1 (:1430-1507).
+inline void form_pair_cams(FormCam &c12, FormCam &c21, const orbm_view *view, const orbm_frame *kf1, const orbm_frame *kf2, const float *T1w,
+                           const float *T2w, float s12, const float *R12, const float *t12, float th)
+{
+    form_cam_common(c12, view, kf2, FORM_PAIR, th);
+    form_cam_common(c21, view, kf1, FORM_PAIR, th);
+    pose_parts(T1w, c12.R, c12.t);
+    pose_parts(T2w, c21.R, c21.t);
+    // :1320-1323: sR12 = s12 * R12, sR21 = (1.0 / s12) * R12.t(), t21 = -sR21 * t12
+    float R12t[9];
+    scale_mat(R12, 9, (double)s12, c21.R2);
+    memcpy(c21.t2, t12, sizeof(float) * 3);
+    transpose3(R12, R12t);
+    scale_mat(R12t, 9, 1.0 / (double)s12, c12.R2);
+    gemm3(c12.R2, t12, -1.0, nullptr, 0.0, c12.t2);
+}
+
+// SearchBySim3's acceptance of a direction's best candidate (:1426-1429, :1505-1507) and the agreement of the two (:1509-1524)
+__device__ __forceinline__ int sim3_accepted(int best, int idx, int th_high) { return idx >= 0 && best <= th_high ? idx : -1; }
+__device__ __forceinline__ bool sim3_agreed(int i1, int a, const int *__restrict__ best2, const int *__restrict__ idx2, int n2, int th_high)
+{
+    return a >= 0 && a < n2 && sim3_accepted(best2[a], idx2[a], th_high) == i1;
+}
+
+// One direction of one SearchBySim3 of a batch (orbm_refine_sim3.hip), as a record in the call's staged block: o_* are byte offsets
+// in the workspace.  k_project_pair_jobs (orbm_search.hip) turns the nq list entries into queries, k_win_best_jobs (orbm_window.hip)
+// searches `frame` with them: best [nq] (INT_MAX when absent) and idx [nq] (keypoint index, -1).
+struct PairSearchJob {
+    FormCam cam;
+    FrameView frame;
+    unsigned o_valid, o_pos, o_min, o_max, o_desc;  // the list: valid as the search sees it, pos, the distance bounds, descriptors
+    unsigned o_q, o_best, o_idx;                    // scratch: queries, results
+    int nq;
+};
+void launch_project_pair_jobs(hipStream_t st, const PairSearchJob *djobs, int njobs, int max_nq, char *ws, const float *dscale);
+void launch_win_best_jobs(hipStream_t st, const PairSearchJob *djobs, int njobs, int max_nq, char *ws);
 
 // Copies outside a call's staged traffic (a resident frame's arrays for an accessor, a snapshot's upload), all in one direction: on
 // the own stream of a leased workspace, like every other call, waited for once.

@@ -19,29 +19,17 @@
 #include "orbm_g2o_math.h"
 #include "orbm_internal.h"
 #include "orbm_sim3_math.h"
+#include "orbm_sim3opt_internal.h"
 
 using namespace orbm_detail;
 
 namespace {
 
-constexpr int SO_MAX_P = 64, SO_MAX_N = 8192;
 constexpr int SO_NT = 256;              // threads per problem: four waves (one wave, NT = 64, was measured too and lost: DESIGN.md 14)
-constexpr int SO_LDS_PAIRS = 512;       // pairs whose constants are staged in LDS (48 B each)
 constexpr int SO_NSYS = 28 + 7 + 1;     // lower triangle of H, J^T rho1 omega e, robust chi2
 
-// One problem of a call, staged with the inputs.  o_*: byte offsets in the workspace.
-struct Sim3OptDev {
-    unsigned o_X1w, o_X2w, o_obs1, o_obs2, o_oct1, o_oct2;          // staged inputs
-    unsigned o_pair;                                                 // scratch: the constants of the pairs behind the LDS-staged ones
-    unsigned o_kept;                                                 // result: [n] bytes
-    int n, fix_scale;
-    float th2, s12;
-    float R1[9], t1[3], R2[9], t2[3];                                // Tcw1, Tcw2
-    float cam1[4], cam2[4];                                          // fx, fy, cx, cy
-    float R12[9], t12[3];
-};
-
 struct PairC { float v[12]; };          // Xc1 [3], Xc2 [3], obs1 [2], obs2 [2], info1, info2
+static_assert(sizeof(PairC) == SO_PAIR_BYTES, "the o_pair scratch is sized by SO_PAIR_BYTES");
 
 // computeError of EdgeSim3ProjectXYZ (S = the estimate, X = the point of keyframe 2) and of EdgeInverseSim3ProjectXYZ (S = its
 // inverse, X = the point of keyframe 1): obs - cam_map(project(S.map(X)))
@@ -298,6 +286,22 @@ std::atomic<int> g_last_sim3_opt_waits{0};     // host waits of the last orbm_op
 
 } // namespace
 
+void orbm_detail::launch_sim3_optimize(hipStream_t st, const Sim3OptDev *dprobs, int P, char *ws, const float *dinv_sigma2,
+                                       orbm_sim3_opt_result *dresults)
+{
+    hipLaunchKernelGGL(k_sim3_optimize<SO_NT>, dim3((unsigned)P), dim3(SO_NT), 0, st, dprobs, ws, dinv_sigma2, dresults);
+}
+
+void orbm_detail::sim3_opt_empty_result(const float *R12, const float *t12, float s12, orbm_sim3_opt_result &r)
+{
+    memset(&r, 0, sizeof(r));
+    Sim3 S;
+    sim3_from_rts(R12, t12, s12, S);
+    for (int k = 0; k < 4; ++k) r.q[k] = S.q[k];
+    for (int k = 0; k < 3; ++k) r.t[k] = S.t[k];
+    r.s = S.s;
+}
+
 extern "C" {
 
 int orbm_optimize_sim3(const orbm_sim3_opt_problem *problems, int P, const float *inv_level_sigma2, int nlevels,
@@ -318,16 +322,7 @@ int orbm_optimize_sim3(const orbm_sim3_opt_problem *problems, int P, const float
         if (!octaves_in_range(q, nlevels)) ORBX_FAIL(ORBX_ERR_ARG, "octave out of range");
         total += (size_t)q.n;
     }
-    for (int p = 0; p < P; ++p) {               // what a problem without a correspondence returns (:1595 with nothing optimised)
-        const orbm_sim3_opt_problem &q = problems[p];
-        orbm_sim3_opt_result &r = results[p];
-        memset(&r, 0, sizeof(r));
-        Sim3 S;
-        sim3_from_rts(q.R12, q.t12, q.s12, S);
-        for (int k = 0; k < 4; ++k) r.q[k] = S.q[k];
-        for (int k = 0; k < 3; ++k) r.t[k] = S.t[k];
-        r.s = S.s;
-    }
+    for (int p = 0; p < P; ++p) sim3_opt_empty_result(problems[p].R12, problems[p].t12, problems[p].s12, results[p]);
     if (total == 0) return ORBX_OK;
     ORBX_NEED_DEVICE();
     std::vector<Sim3OptDev> dev((size_t)P);
@@ -351,8 +346,7 @@ int orbm_optimize_sim3(const orbm_sim3_opt_problem *problems, int P, const float
         if (dev[p].n) dev[p].o_kept = (unsigned)sc.out((size_t)dev[p].n);
     if (!sc.offsets_fit_32_bits()) ORBX_FAIL(ORBX_ERR_CAPACITY, "the call's arrays exceed 4 GiB");
     if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
-    hipLaunchKernelGGL(k_sim3_optimize<SO_NT>, dim3((unsigned)P), dim3(SO_NT), 0, sc.stream(), sc.d<const Sim3OptDev>(o_dev), sc.d<char>(0),
-                       sc.d<const float>(o_sg), sc.d<orbm_sim3_opt_result>(o_res));
+    launch_sim3_optimize(sc.stream(), sc.d<const Sim3OptDev>(o_dev), P, sc.d<char>(0), sc.d<const float>(o_sg), sc.d<orbm_sim3_opt_result>(o_res));
     ORBX_HIP(hipGetLastError());
     const int drc = sc.download();
     g_last_sim3_opt_waits.store(sc.waits, std::memory_order_relaxed);  // counted where the stream is waited for

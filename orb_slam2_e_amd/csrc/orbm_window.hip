@@ -143,6 +143,23 @@ __global__ __launch_bounds__(MT) void k_win_best(const WinQuery *__restrict__ q,
     }
 }
 
+// k_win_best as SearchBySim3 runs it (no occupancy, no stereo test, best from INT_MAX) for the jobs of a batch: job blockIdx.y, one
+// wave per query.  Only best and idx leave (what the acceptance reads).
+__global__ __launch_bounds__(MT) void k_win_best_jobs(const PairSearchJob *__restrict__ jobs, char *__restrict__ ws)
+{
+    const PairSearchJob &J = jobs[blockIdx.y];
+    const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * (MT / 64) + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    if (i >= J.nq) return;
+    const WinQuery w = reinterpret_cast<const WinQuery *>(ws + J.o_q)[i];
+    const WinPick o = win_best_select(win_best_walk(w, reinterpret_cast<const uint4 *>(ws + J.o_desc) + 2 * i, lane, J.frame.kp, J.frame.desc,
+                                                    J.frame.cell_off, nullptr, J.frame.gp, 0, INT_MAX, nullptr, 0),
+                                      INT_MAX);
+    if (lane == 0) {
+        reinterpret_cast<int *>(ws + J.o_best)[i] = o.best;
+        reinterpret_cast<int *>(ws + J.o_idx)[i] = o.sp >= 0 ? J.frame.perm[o.sp] : -1;
+    }
+}
+
 // The fork's whole-map relocalisation search (ORBmatcher.cc:134-222): isInFrustum
 // (:262-330) + ComputeDistance (:224-260) per map point in the reference's mixed
 // float / double arithmetic (fixed op order, no contraction), producing the
@@ -376,6 +393,11 @@ void orbm_detail::launch_win_best(hipStream_t st, const WinQuery *dq, const uint
 {
     hipLaunchKernelGGL(k_win_best, dim3((nq + MT / 64 - 1) / (MT / 64)), dim3(MT), 0, st, dq, da, nq, fv.kp, fv.desc, fv.cell_off, fv.perm, docc,
                        fv.gp, has_uright, init_dist, inv_sigma2, fuse_gate, ob, ob + nq, ob + 2 * nq, ob + 3 * nq, ob + 4 * nq);
+}
+
+void orbm_detail::launch_win_best_jobs(hipStream_t st, const PairSearchJob *djobs, int njobs, int max_nq, char *ws)
+{
+    hipLaunchKernelGGL(k_win_best_jobs, dim3((max_nq + MT / 64 - 1) / (MT / 64), njobs), dim3(MT), 0, st, djobs, ws);
 }
 
 namespace {

@@ -114,6 +114,66 @@ def optimize_sim3(problems, inv_level_sigma2):
     return out
 
 
+class _CRefineSim3Attempt(C.Structure):
+    """orbm_refine_sim3_attempt"""
+    _fields_ = [("kf2", C.c_void_p), ("points2", C.c_void_p), ("T2w", C.c_void_p), ("R12", C.c_float * 9), ("t12", C.c_float * 3),
+                ("s12", C.c_float), ("seed12", C.c_void_p), ("found12", C.c_void_p), ("matches12", C.c_void_p)]
+
+
+class RefineSim3Attempt:
+    """orbm_refine_sim3_attempt: one pass of LoopClosing.cc:311-341 -- kf2 a resident Frame, points2 a Points with one entry per
+    keypoint of kf2 (valid = map point non-NULL and not bad), T2w, the Sim3 as :320-325 hands it over, seed12 [n1] (>= 0 the
+    point's index in KF2, -1 NULL, -2 non-NULL without an index in KF2; None: all -1)."""
+
+    def __init__(self, kf2, points2, T2w, R12, t12, s12, seed12=None):
+        f = np.ascontiguousarray
+        self.kf2, self.points2 = kf2, points2
+        self.T2w, self.R12, self.t12 = f(T2w, np.float32).reshape(16), f(R12, np.float32).reshape(9), f(t12, np.float32).reshape(3)
+        self.s12 = float(np.float32(s12))
+        self.seed12 = f(seed12, np.int32) if seed12 is not None else None
+
+
+REFINE_MIN_INLIERS = 20     # LoopClosing.cc:333
+
+
+def refine_sim3_candidates(kf1, points1, T1w, view, inv_level_sigma2, attempts, th=7.5, th_high=95, th2=10.0, fix_scale=False):
+    """orbm_refine_sim3_candidates (SearchBySim3 chained into OptimizeSim3 for every attempt against kf1, one host wait): per attempt
+    (found12 [n1], nfound, matches12 [n1], Sim3OptResult) -- found12 = what SearchBySim3 alone writes, matches12 = vpMatches1 as
+    OptimizeSim3 leaves it"""
+    P = len(attempts)
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    T1 = np.ascontiguousarray(T1w, np.float32).reshape(16)
+    arr = (_CRefineSim3Attempt * max(P, 1))()
+    out = []
+    addr = lambda a: _p(a).value if a is not None and len(a) else None
+    for c, a in zip(arr, attempts):
+        found = np.full(max(kf1.n, 1), -9, np.int32); matches = np.full(max(kf1.n, 1), -9, np.int32)
+        h = a.kf2._h.value if isinstance(a.kf2._h, C.c_void_p) else a.kf2._h
+        c.kf2, c.points2, c.T2w = h, C.addressof(a.points2.c), addr(a.T2w)
+        c.R12, c.t12, c.s12 = (C.c_float * 9)(*a.R12), (C.c_float * 3)(*a.t12), a.s12
+        c.seed12, c.found12, c.matches12 = addr(a.seed12), addr(found), addr(matches)
+        out.append((found, matches))
+    nf = np.full(max(P, 1), -9, np.int32)
+    res = (Sim3OptResult * max(P, 1))()
+    check(lib().orbm_refine_sim3_candidates(kf1._h, C.byref(points1.c), _p(T1), C.byref(view.c), _p(sg), arr if P else None, P, th,
+                                            int(th_high), th2, int(bool(fix_scale)), _p(nf), res))
+    return [(f[:kf1.n], int(nf[p]), m[:kf1.n], res[p]) for p, (f, m) in enumerate(out)]
+
+
+def first_accepted(results, min_inliers=REFINE_MIN_INLIERS):
+    """the fold of the loop at LoopClosing.cc:288 over the attempts of one pass: the index of the first attempt, in order, whose
+    refinement returned nin >= min_inliers, or None"""
+    for p, r in enumerate(results):
+        if r[3].nin >= min_inliers:
+            return p
+    return None
+
+
+def last_refine_sim3_waits():
+    """orbm_debug_last_refine_sim3_waits: host waits of the last orbm_refine_sim3_candidates call of this process."""
+    return lib().orbm_debug_last_refine_sim3_waits()
+
+
 def last_sim3_opt_waits():
     """orbm_debug_last_sim3_opt_waits: host waits of the last orbm_optimize_sim3 call of this process."""
     return lib().orbm_debug_last_sim3_opt_waits()
