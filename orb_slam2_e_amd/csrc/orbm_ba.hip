@@ -69,8 +69,8 @@ struct BaDev {
     double *part_chi, *part_max, *part_scale;   // [nblocks]
     uint8_t *e_level, *pact;            // [nedges], [npoints]
     int *ridx;                          // [nfree]: row block in the reduced system, -1: not a vertex of this round
-    double *sc;                         // 0 chi2 at the iteration's start, 3 largest diagonal, 4 tau * that, 5 tempChi, 6 scale
-    int *isc;                           // 0 nact, 1 ok2, 2 active edges
+    double *sc;                         // the block a trial reads back (LM_SC_*, LM_ISC_*: orbm_internal.h)
+    int *isc;
     float *poses_out, *points_out;
     uint8_t *erase, *level_out;
     double *chi2_out, *poses_d, *points_d;
@@ -85,21 +85,6 @@ __device__ __forceinline__ void store_pose(double *est, int k, const Se3 &T)
 {
     double *o = est + 7 * (size_t)k;
     o[0] = T.q[0]; o[1] = T.q[1]; o[2] = T.q[2]; o[3] = T.q[3]; o[4] = T.t[0]; o[5] = T.t[1]; o[6] = T.t[2];
-}
-
-// Eigen's fixed-size inverse (compute_inverse<Matrix3d>), as orbm_pose_nr.hip's
-__device__ __forceinline__ void ba_inverse3(const double m[9], double o[9])
-{
-#define M(i, j) m[3 * (i) + (j)]
-#define COF(i, j) (M(((i) + 1) % 3, ((j) + 1) % 3) * M(((i) + 2) % 3, ((j) + 2) % 3) - M(((i) + 1) % 3, ((j) + 2) % 3) * M(((i) + 2) % 3, ((j) + 1) % 3))
-    const double c0 = COF(0, 0), c1 = COF(1, 0), c2 = COF(2, 0);
-    const double det = (c0 * M(0, 0) + c1 * M(1, 0)) + c2 * M(2, 0);
-    const double invdet = 1.0 / det;
-    o[0] = c0 * invdet; o[1] = c1 * invdet; o[2] = c2 * invdet;
-    o[3] = COF(0, 1) * invdet; o[4] = COF(1, 1) * invdet; o[5] = COF(2, 1) * invdet;
-    o[6] = COF(0, 2) * invdet; o[7] = COF(1, 2) * invdet; o[8] = COF(2, 2) * invdet;
-#undef COF
-#undef M
 }
 
 // computeError of either edge type at the mapped point c; a monocular edge (obs[2] < 0) has err[2] = 0
@@ -148,17 +133,6 @@ __device__ __forceinline__ void ba_jacobians(const double c[3], const double R[9
     }
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // Converter::toSE3Quat / toVector3d; every edge at level 0
 __global__ __launch_bounds__(PT) void k_ba_init(BaDev D)
 {
@@ -202,7 +176,7 @@ __global__ __launch_bounds__(RT) void k_ba_activate(BaDev D)
     if (threadIdx.x == 0) {
         int r = 0;
         for (int p = 0; p < D.nfree; ++p) D.ridx[p] = s_act[p] ? r++ : -1;
-        D.isc[0] = r; D.isc[1] = 1; D.isc[2] = s_edges; D.isc[3] = 0;
+        D.isc[LM_ISC_NACT] = r; D.isc[LM_ISC_OK2] = 1; D.isc[LM_ISC_NEDGES] = s_edges;
     }
 }
 
@@ -324,11 +298,11 @@ __global__ __launch_bounds__(RT) void k_ba_reduce(BaDev D, int mode)
         mx = fmax(fmax(s_red[0][0], s_red[1][0]), fmax(s_red[2][0], s_red[3][0]));
     }
     if (threadIdx.x == 0) {
-        if (!mode) { D.sc[0] = v[0]; D.sc[3] = mx; D.sc[4] = 1e-5 * mx; }
+        if (!mode) { D.sc[LM_SC_CHI2] = v[0]; D.sc[LM_SC_MAXDIAG] = mx; D.sc[LM_SC_LAMBDA_INIT] = 1e-5 * mx; }
         else {
             double sp = 0.0;
             for (int p = 0; p < D.nfree; ++p) sp += D.pose_scale[p];
-            D.sc[5] = v[0]; D.sc[6] = sp + v[1];
+            D.sc[LM_SC_TEMPCHI] = v[0]; D.sc[LM_SC_SCALE] = sp + v[1];
         }
     }
 }
@@ -337,12 +311,12 @@ __global__ __launch_bounds__(PT) void k_ba_dinv(BaDev D, double lambda, int lamb
 {
     const int n = blockIdx.x * PT + threadIdx.x;
     if (n >= D.npoints || !D.pact[n]) return;
-    const double lam = lambda_on_device ? D.sc[4] : lambda;
+    const double lam = lambda_on_device ? D.sc[LM_SC_LAMBDA_INIT] : lambda;
     const double *blk = D.Hll + 12 * (size_t)n;
     double M[9], inv[9];
     ORBM_UNROLL for (int j = 0; j < 9; ++j) M[j] = blk[j];
     ORBM_UNROLL for (int j = 0; j < 3; ++j) M[4 * j] += lam;
-    ba_inverse3(M, inv);
+    inverse3(M, inv);
     double *o = D.Dinv + 12 * (size_t)n;
     ORBM_UNROLL for (int j = 0; j < 9; ++j) o[j] = inv[j];
     ORBM_UNROLL for (int j = 0; j < 3; ++j) o[9 + j] = inv[3 * j] * blk[9] + inv[3 * j + 1] * blk[10] + inv[3 * j + 2] * blk[11];
@@ -359,8 +333,8 @@ __global__ __launch_bounds__(PT) void k_ba_schur(BaDev D, double lambda, int lam
     const int i2 = i1 + b;
     const int r1 = D.ridx[i1], r2 = D.ridx[i2];
     if (r1 < 0 || r2 < 0) return;
-    const double lam = lambda_on_device ? D.sc[4] : lambda;
-    const int n = 6 * D.isc[0], l = threadIdx.x;
+    const double lam = lambda_on_device ? D.sc[LM_SC_LAMBDA_INIT] : lambda;
+    const int n = 6 * D.isc[LM_ISC_NACT], l = threadIdx.x;
     if (l < 36) {
         const int r = l / 6, c = l % 6;
         double v = 0.0;
@@ -400,7 +374,7 @@ __global__ __launch_bounds__(ST) void k_ba_solve(BaDev D)
     __shared__ double s_row[ST];
     __shared__ double s_b[2];
     __shared__ int s_ok;
-    const int n = 6 * D.isc[0], i = threadIdx.x;
+    const int n = 6 * D.isc[LM_ISC_NACT], i = threadIdx.x;
     double *S = D.S;
     if (i == 0) s_ok = 1;
     __syncthreads();
@@ -426,7 +400,7 @@ __global__ __launch_bounds__(ST) void k_ba_solve(BaDev D)
         __syncthreads();
     }
     const bool ok = s_ok != 0;
-    if (i == 0) D.isc[1] = ok ? 1 : 0;
+    if (i == 0) D.isc[LM_ISC_OK2] = ok ? 1 : 0;
     if (!ok) {
         if (i < n) D.xp[i] = 0.0;
         return;
@@ -454,8 +428,8 @@ __global__ __launch_bounds__(PT) void k_ba_update(BaDev D, double lambda, int la
     if (n < D.npoints) {
         double X[3] = {D.X[3 * (size_t)n], D.X[3 * (size_t)n + 1], D.X[3 * (size_t)n + 2]};
         ORBM_UNROLL for (int j = 0; j < 3; ++j) D.X_bak[3 * (size_t)n + j] = X[j];
-        if (D.pact[n] && D.isc[1]) {
-            const double lam = lambda_on_device ? D.sc[4] : lambda;
+        if (D.pact[n] && D.isc[LM_ISC_OK2]) {
+            const double lam = lambda_on_device ? D.sc[LM_SC_LAMBDA_INIT] : lambda;
             const double *blk = D.Hll + 12 * (size_t)n, *inv = D.Dinv + 12 * (size_t)n;
             double cl[3] = {blk[9], blk[10], blk[11]};
             for (int e = D.e_start[n]; e < D.e_start[n + 1]; ++e) {
@@ -491,8 +465,8 @@ __global__ __launch_bounds__(PT) void k_ba_update_pose(BaDev D, double lambda, i
     store_pose(D.est_bak, p, T);
     double sc = 0.0;
     const int r = D.ridx[p];
-    if (r >= 0 && D.isc[1]) {
-        const double lam = lambda_on_device ? D.sc[4] : lambda;
+    if (r >= 0 && D.isc[LM_ISC_OK2]) {
+        const double lam = lambda_on_device ? D.sc[LM_SC_LAMBDA_INIT] : lambda;
         double x[6];
         ORBM_UNROLL for (int j = 0; j < 6; ++j) x[j] = D.xp[6 * r + j];
         Se3 up, o;
@@ -763,7 +737,7 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
     const size_t o_S = sc.scratch(sizeof(double) * nmax * nmax), o_bsch = sc.scratch(sizeof(double) * nmax), o_xp = sc.scratch(sizeof(double) * nmax);
     const size_t o_pchi = sc.scratch(sizeof(double) * nblk), o_pmax = sc.scratch(sizeof(double) * nblk), o_pscale = sc.scratch(sizeof(double) * nblk);
     const size_t o_lvl = sc.scratch(ne), o_pact = sc.scratch(np), o_ridx = sc.scratch(sizeof(int) * nf);
-    const size_t o_sc = sc.out(128);                                            // what a trial reads back: 8 doubles, 16 ints
+    const size_t o_sc = sc.out(LM_BLOCK_BYTES);                                 // what a trial reads back
     const size_t o_pout = sc.out(sizeof(float) * 16 * nf), o_xout = sc.out(sizeof(float) * 3 * np), o_erase = sc.out(ne), o_lout = sc.out(ne);
     const size_t o_chi = sc.out(sizeof(double) * ne), o_pd = sc.out(sizeof(double) * 7 * nf), o_xd = sc.out(sizeof(double) * 3 * np);
     if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
@@ -784,26 +758,16 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
     const size_t nall = std::max(std::max(npose, np), ne);
     const dim3 g_all((unsigned)((nall + PT - 1) / PT)), g_pts((unsigned)nblk), b_pt(PT);
     const unsigned nblocks_schur = (unsigned)(g.nfree * (g.nfree + 1) / 2);
-    int waits = 0;
-    // the first 128 bytes of the result block: the scalars of a trial (or of a round's end)
-    auto read_scalars = [&]() -> int {
-        if (orbx::stage_out(sc.w.pin, sc.w.dev + sc.res_off, 128, st) != hipSuccess) return -1;
-        ++waits;
-        return hipStreamSynchronize(st) == hipSuccess ? 0 : -1;
-    };
-    const double *h_sc = reinterpret_cast<const double *>(sc.w.pin);
-    const int *h_isc = reinterpret_cast<const int *>(sc.w.pin + 64);
+    LmHostLoop L{sc, stats ? stats->trial_log : nullptr, stats ? stats->trial_capacity : 0};
 
     hipLaunchKernelGGL(k_ba_init, g_all, b_pt, 0, st, D);
     hipLaunchKernelGGL(k_ba_activate, dim3(1), dim3(RT), 0, st, D);
     reset_stats(stats);
     const double dm = opt.huber_mono, ds = opt.huber_stereo;
-    int stopped = 0, nt = 0, nr = 0, rounds_run = 0;
+    int stopped = 0, nr = 0, rounds_run = 0;
     int st_iter[2] = {0, 0}, st_trials[2] = {0, 0};
     for (int round = 0; round < opt.nrounds; ++round) {
         const int robust = round == 0 && opt.robust_round0;
-        double lambda = -1., ni = 2., currentChi = 0.;
-        int lmBad = 0;
         bool ok = true;
         if (nact > 0 && nactive_edges > 0) {
             ++rounds_run;
@@ -812,65 +776,31 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
                 hipLaunchKernelGGL(k_ba_build, g_pts, b_pt, 0, st, D, robust, dm, ds);
                 hipLaunchKernelGGL(k_ba_pose, dim3((unsigned)g.nfree), b_pt, 0, st, D);
                 hipLaunchKernelGGL(k_ba_reduce, dim3(1), dim3(RT), 0, st, D, 0);
-                double iniChi = currentChi, tempChi = currentChi, rho = 0;
-                int qmax = 0;
-                do {
-                    const int on_dev = it == 0 && qmax == 0;                    // computeLambdaInit's value is still on the device
-                    hipLaunchKernelGGL(k_ba_dinv, g_pts, b_pt, 0, st, D, lambda, on_dev);
-                    hipLaunchKernelGGL(k_ba_schur, dim3(nblocks_schur), b_pt, 0, st, D, lambda, on_dev);
+                // (the first trial of an optimize() call runs at computeLambdaInit's value, which is still on the device: its
+                // read-back brings the iteration's chi2 and that lambda, levenberg.cpp:97-115)
+                auto on_dev = [&]() { return it == 0 && L.qmax == 0; };
+                auto trial = [&](double lambda) -> int {
+                    const int od = on_dev();
+                    hipLaunchKernelGGL(k_ba_dinv, g_pts, b_pt, 0, st, D, lambda, od);
+                    hipLaunchKernelGGL(k_ba_schur, dim3(nblocks_schur), b_pt, 0, st, D, lambda, od);
                     if (!global) hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(ST), 0, st, D);
-                    else if ((rc = orbm_llt_solve_dev(6 * nact, D.S, D.bsch, D.xp, D.isc + 1, st)) != ORBX_OK) return rc;   // nact: what k_ba_activate left in isc[0]
-                    hipLaunchKernelGGL(k_ba_update, g_pts, b_pt, 0, st, D, lambda, on_dev);
-                    hipLaunchKernelGGL(k_ba_update_pose, dim3((unsigned)((g.nfree + PT - 1) / PT)), b_pt, 0, st, D, lambda, on_dev);
+                    else if (const int e = orbm_llt_solve_dev(6 * nact, D.S, D.bsch, D.xp, D.isc + LM_ISC_OK2, st)) return e;   // nact: what k_ba_activate left in isc[LM_ISC_NACT]
+                    hipLaunchKernelGGL(k_ba_update, g_pts, b_pt, 0, st, D, lambda, od);
+                    hipLaunchKernelGGL(k_ba_update_pose, dim3((unsigned)((g.nfree + PT - 1) / PT)), b_pt, 0, st, D, lambda, od);
                     hipLaunchKernelGGL(k_ba_errors, g_pts, b_pt, 0, st, D, robust, dm, ds);
                     hipLaunchKernelGGL(k_ba_reduce, dim3(1), dim3(RT), 0, st, D, 1);
-                    ORBX_HIP(hipGetLastError());
-                    if (read_scalars()) ORBX_FAIL(ORBX_ERR_HIP, "a trial's read-back failed");
-                    if (on_dev) {                                               // levenberg.cpp:97-115
-                        currentChi = h_sc[0];
-                        iniChi = currentChi;
-                        lambda = h_sc[4];
-                        ni = 2;
-                        lmBad = 0;
-                    }
-                    const bool ok2 = h_isc[1] != 0;
-                    tempChi = ok2 ? h_sc[5] : DBL_MAX;
-                    rho = currentChi - tempChi;
-                    double scale = ok2 ? h_sc[6] : 0.0;
-                    scale += 1e-3;
-                    rho /= scale;
-                    const bool good = rho > 0 && std::isfinite(tempChi);
-                    if (good) {
-                        double alpha = 1. - pow((2 * rho - 1), 3.0);
-                        alpha = (alpha < 2. / 3.) ? alpha : 2. / 3.;
-                        const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;
-                        lambda *= scaleFactor;
-                        ni = 2;
-                        currentChi = tempChi;
-                    } else {
-                        lambda *= ni;
-                        ni *= 2;
-                        hipLaunchKernelGGL(k_ba_pop, g_all, b_pt, 0, st, D);
-                    }
-                    if (stats) {
-                        if (nt < stats->trial_capacity) {
-                            orbm_ba_trial &t = stats->trial_log[nt];
-                            t.tempChi = tempChi; t.currentChi = currentChi; t.rho = rho; t.lambda = lambda; t.scale = scale;
-                            t.round = round; t.qmax = qmax; t.accepted = good ? 1 : 0; t.ok2 = ok2 ? 1 : 0;
-                        }
-                    }
-                    ++nt;
-                    qmax++;
-                } while (rho < 0 && qmax < 10 && !terminate());
+                    return ORBX_OK;
+                };
+                auto after_read = [&]() {
+                    if (!on_dev()) return;
+                    L.currentChi = L.iniChi = L.scalar(LM_SC_CHI2);
+                    L.lm.start(L.scalar(LM_SC_LAMBDA_INIT));
+                };
+                auto pop = [&]() { hipLaunchKernelGGL(k_ba_pop, g_all, b_pt, 0, st, D); };
+                if ((rc = L.trials(round, trial, after_read, pop, terminate)) != ORBX_OK) return rc;
                 st_iter[round]++;
-                st_trials[round] += qmax;
-                int result;
-                if (qmax == 10 || rho == 0) result = 2;
-                else {
-                    if ((iniChi - currentChi) * 1e3 < iniChi) lmBad++;
-                    else lmBad = 0;
-                    result = lmBad >= 3 ? 2 : 1;
-                }
+                st_trials[round] += L.qmax;
+                const int result = L.lm.end_iteration(L.qmax, L.rho, L.iniChi, L.currentChi);
                 if (stats && nr < 128) stats->results[nr] = result;
                 ++nr;
                 ok = result == 1;
@@ -884,16 +814,15 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
             if (opt.classify) hipLaunchKernelGGL(k_ba_classify, g_pts, b_pt, 0, st, D, opt.chi2_mono, opt.chi2_stereo, 0);
             hipLaunchKernelGGL(k_ba_activate, dim3(1), dim3(RT), 0, st, D);
             ORBX_HIP(hipGetLastError());
-            if (read_scalars()) ORBX_FAIL(ORBX_ERR_HIP, "a round's read-back failed");
-            nact = h_isc[0];
-            nactive_edges = h_isc[2];
+            if (L.read_block()) ORBX_FAIL(ORBX_ERR_HIP, "a round's read-back failed");
+            nact = L.flag(LM_ISC_NACT);
+            nactive_edges = L.flag(LM_ISC_NEDGES);
         }
     }
     if (opt.classify) hipLaunchKernelGGL(k_ba_classify, g_pts, b_pt, 0, st, D, opt.chi2_mono, opt.chi2_stereo, 1);
     hipLaunchKernelGGL(k_ba_final, g_all, b_pt, 0, st, D);
     ORBX_HIP(hipGetLastError());
     if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
-    ++waits;
     memcpy(out.poses, sc.r<float>(o_pout), sizeof(float) * 16 * nf);
     memcpy(out.points, sc.r<float>(o_xout), sizeof(float) * 3 * np);
     if (opt.classify) memcpy(out.erase, sc.r<uint8_t>(o_erase), ne);
@@ -903,13 +832,13 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
         stats->rounds = rounds_run;
         for (int r = 0; r < 2; ++r) { stats->iterations[r] = st_iter[r]; stats->trials[r] = st_trials[r]; }
         stats->nresults = nr;
-        stats->ntrials = nt; stats->trial_overflow = nt > stats->trial_capacity ? 1 : 0;
+        stats->ntrials = L.nt; stats->trial_overflow = L.nt > stats->trial_capacity ? 1 : 0;
         if (stats->poses) memcpy(stats->poses, sc.r<double>(o_pd), sizeof(double) * 7 * nf);
         if (stats->points) memcpy(stats->points, sc.r<double>(o_xd), sizeof(double) * 3 * np);
         if (stats->chi2) memcpy(stats->chi2, sc.r<double>(o_chi), sizeof(double) * ne);
         if (stats->level) memcpy(stats->level, sc.r<uint8_t>(o_lout), ne);
     }
-    g_last_ba_waits = waits;
+    g_last_ba_waits = sc.waits;
     return ORBX_OK;
 }
 

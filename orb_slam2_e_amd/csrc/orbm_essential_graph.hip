@@ -66,8 +66,8 @@ struct EgDev {
     double *b, *x, *sterm;              // [n]
     double *S;                          // [n][n]
     double *part_chi;                   // [nblocks]
-    double *sc;                         // 0 chi2 at the iteration's start, 5 tempChi, 6 scale
-    int *isc;                           // 1 ok2
+    double *sc;                         // the block a trial reads back (LM_SC_*, LM_ISC_*: orbm_internal.h)
+    int *isc;
     float *poses_out, *points_out;
     double *est_out, *chi2_out;
 };
@@ -81,12 +81,6 @@ __device__ __forceinline__ void store_sim3(double *a, int k, const Sim3 &S)
 {
     double *o = a + 8 * (size_t)k;
     o[0] = S.q[0]; o[1] = S.q[1]; o[2] = S.q[2]; o[3] = S.q[3]; o[4] = S.t[0]; o[5] = S.t[1]; o[6] = S.t[2]; o[7] = S.s;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // vScw[v] (:1202-1216)
@@ -370,7 +364,7 @@ __global__ __launch_bounds__(PT) void k_eg_update(EgDev D, double lambda)
     double x[7];
     ORBM_UNROLL for (int j = 0; j < 7; ++j) x[j] = D.x[7 * r + j];
     if (D.fix_scale) { x[6] = 0; D.x[7 * r + 6] = 0; }
-    const bool ok = D.isc[1] != 0;
+    const bool ok = D.isc[LM_ISC_OK2] != 0;
     if (ok) {
         Sim3 up, o;
         sim3_exp(x, up);
@@ -396,11 +390,11 @@ __global__ __launch_bounds__(RT) void k_eg_reduce(EgDev D, int mode)
     for (int b = threadIdx.x; b < D.nblocks; b += RT) v[0] += D.part_chi[b];
     block_sum<1, RT / 64>(v, s_red);
     if (threadIdx.x == 0) {
-        if (!mode) D.sc[0] = v[0];
+        if (!mode) D.sc[LM_SC_CHI2] = v[0];
         else {
             double s = 0.0;
             for (int i = 0; i < D.n; ++i) s += D.sterm[i];
-            D.sc[5] = v[0]; D.sc[6] = s;
+            D.sc[LM_SC_TEMPCHI] = v[0]; D.sc[LM_SC_SCALE] = s;
         }
     }
 }
@@ -603,7 +597,7 @@ int orbm_essential_graph(const orbm_eg_graph *gp, const orbm_eg_options *op, orb
     const size_t o_cb = sc.scratch(solve ? sizeof(double) * NC * ne : 0), o_Hd = sc.scratch(sizeof(double) * 49 * na);
     const size_t o_b = sc.scratch(sizeof(double) * n), o_x = sc.scratch(sizeof(double) * n), o_st = sc.scratch(sizeof(double) * n);
     const size_t o_S = sc.scratch(solve ? sizeof(double) * n * n : 0), o_pchi = sc.scratch(sizeof(double) * nblk);
-    const size_t o_sc = sc.out(128);                                            // what a trial reads back: 8 doubles, 16 ints
+    const size_t o_sc = sc.out(LM_BLOCK_BYTES);                                 // what a trial reads back
     const size_t o_pout = sc.out(sizeof(float) * 16 * nv), o_xout = sc.out(sizeof(float) * 3 * np);
     const size_t o_eout = sc.out(sizeof(double) * 8 * nv), o_chi = sc.out(sizeof(double) * ne);
     if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
@@ -622,78 +616,32 @@ int orbm_essential_graph(const orbm_eg_graph *gp, const orbm_eg_options *op, orb
     const size_t nall = std::max(std::max(nv, np), ne);
     const dim3 g_all((unsigned)((nall + PT - 1) / PT)), g_init((unsigned)((std::max(nv, ne) + PT - 1) / PT)), g_edges((unsigned)nblk), b_pt(PT);
     const dim3 g_act((unsigned)((na + PT - 1) / PT)), g_lin((unsigned)((ne + EPW - 1) / EPW));
-    int waits = 0;
-    // the first 128 bytes of the result block: the scalars of a trial
-    auto read_scalars = [&]() -> int {
-        if (orbx::stage_out(sc.w.pin, sc.w.dev + sc.res_off, 128, st) != hipSuccess) return -1;
-        ++waits;
-        return hipStreamSynchronize(st) == hipSuccess ? 0 : -1;
-    };
-    const double *h_sc = reinterpret_cast<const double *>(sc.w.pin);
-    const int *h_isc = reinterpret_cast<const int *>(sc.w.pin + 64);
+    LmHostLoop L{sc, stats ? stats->trial_log : nullptr, stats ? stats->trial_capacity : 0};
 
     hipLaunchKernelGGL(k_eg_init, g_init, b_pt, 0, st, D);
-    int nt = 0, nr = 0, n_iter = 0, n_trials = 0;
+    int nr = 0, n_iter = 0, n_trials = 0;
     if (solve) {
-        double lambda = opt.lambda_init, ni = 2., currentChi = 0.;
-        int lmBad = 0;
         bool ok = true;
         for (int it = 0; it < opt.iterations && ok; ++it) {                     // SparseOptimizer::optimize
             hipLaunchKernelGGL(k_eg_errors, g_edges, b_pt, 0, st, D);
             hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(RT), 0, st, D, 0);
             hipLaunchKernelGGL(k_eg_linearize, g_lin, b_pt, 0, st, D);
             hipLaunchKernelGGL(k_eg_gather, dim3((unsigned)na), b_pt, 0, st, D);
-            if (it == 0) { lambda = opt.lambda_init; ni = 2; lmBad = 0; }       // levenberg.cpp:110-115, computeLambdaInit :245-246
-            double iniChi = currentChi, tempChi = currentChi, rho = 0;
-            int qmax = 0;
-            do {
+            if (it == 0) L.lm.start(opt.lambda_init);                           // levenberg.cpp:110-115, computeLambdaInit :245-246
+            auto trial = [&](double lambda) -> int {
                 hipLaunchKernelGGL(k_eg_assemble, dim3((unsigned)na), dim3(RT), 0, st, D, lambda);
-                if ((rc = orbm_llt_solve_dev((int)n, D.S, D.b, D.x, D.isc + 1, st)) != ORBX_OK) return rc;
+                if (const int e = orbm_llt_solve_dev((int)n, D.S, D.b, D.x, D.isc + LM_ISC_OK2, st)) return e;
                 hipLaunchKernelGGL(k_eg_update, g_act, b_pt, 0, st, D, lambda);
                 hipLaunchKernelGGL(k_eg_errors, g_edges, b_pt, 0, st, D);
                 hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(RT), 0, st, D, 1);
-                ORBX_HIP(hipGetLastError());
-                if (read_scalars()) ORBX_FAIL(ORBX_ERR_HIP, "a trial's read-back failed");
-                if (qmax == 0) {                                                // levenberg.cpp:97-99
-                    currentChi = h_sc[0];
-                    iniChi = currentChi;
-                }
-                const bool ok2 = h_isc[1] != 0;
-                tempChi = ok2 ? h_sc[5] : DBL_MAX;
-                rho = currentChi - tempChi;
-                double scale = ok2 ? h_sc[6] : 0.0;
-                scale += 1e-3;
-                rho /= scale;
-                const bool good = rho > 0 && std::isfinite(tempChi);
-                if (good) {
-                    double alpha = 1. - pow((2 * rho - 1), 3.0);
-                    alpha = (alpha < 2. / 3.) ? alpha : 2. / 3.;
-                    const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;
-                    lambda *= scaleFactor;
-                    ni = 2;
-                    currentChi = tempChi;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                    hipLaunchKernelGGL(k_eg_pop, g_act, b_pt, 0, st, D);
-                }
-                if (stats && nt < stats->trial_capacity) {
-                    orbm_ba_trial &t = stats->trial_log[nt];
-                    t.tempChi = tempChi; t.currentChi = currentChi; t.rho = rho; t.lambda = lambda; t.scale = scale;
-                    t.round = 0; t.qmax = qmax; t.accepted = good ? 1 : 0; t.ok2 = ok2 ? 1 : 0;
-                }
-                ++nt;
-                qmax++;
-            } while (rho < 0 && qmax < 10);
+                return ORBX_OK;
+            };
+            auto after_read = [&]() { if (L.qmax == 0) L.currentChi = L.iniChi = L.scalar(LM_SC_CHI2); };      // levenberg.cpp:97-99
+            auto pop = [&]() { hipLaunchKernelGGL(k_eg_pop, g_act, b_pt, 0, st, D); };
+            if ((rc = L.trials(0, trial, after_read, pop)) != ORBX_OK) return rc;
             ++n_iter;
-            n_trials += qmax;
-            int result;
-            if (qmax == 10 || rho == 0) result = 2;
-            else {
-                if ((iniChi - currentChi) * 1e3 < iniChi) lmBad++;
-                else lmBad = 0;
-                result = lmBad >= 3 ? 2 : 1;
-            }
+            n_trials += L.qmax;
+            const int result = L.lm.end_iteration(L.qmax, L.rho, L.iniChi, L.currentChi);
             if (stats && nr < 64) stats->results[nr] = result;
             ++nr;
             ok = result == 1;
@@ -702,15 +650,14 @@ int orbm_essential_graph(const orbm_eg_graph *gp, const orbm_eg_options *op, orb
     hipLaunchKernelGGL(k_eg_final, g_all, b_pt, 0, st, D);
     ORBX_HIP(hipGetLastError());
     if (sc.download()) ORBX_FAIL(ORBX_ERR_HIP, "download failed");
-    ++waits;
     memcpy(out.poses, sc.r<float>(o_pout), sizeof(float) * 16 * nv);
     if (np) memcpy(out.points, sc.r<float>(o_xout), sizeof(float) * 3 * np);
     if (stats) {
         stats->iterations = n_iter; stats->trials = n_trials; stats->nresults = nr;
-        stats->ntrials = nt; stats->trial_overflow = nt > stats->trial_capacity ? 1 : 0;
+        stats->ntrials = L.nt; stats->trial_overflow = L.nt > stats->trial_capacity ? 1 : 0;
         if (stats->estimates) memcpy(stats->estimates, sc.r<double>(o_eout), sizeof(double) * 8 * nv);
         if (stats->chi2 && ne) memcpy(stats->chi2, sc.r<double>(o_chi), sizeof(double) * ne);
     }
-    g_last_eg_waits = waits;
+    g_last_eg_waits = sc.waits;
     return ORBX_OK;
 }

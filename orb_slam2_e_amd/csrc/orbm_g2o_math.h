@@ -1,10 +1,14 @@
 // orbm_g2o_math.h -- the slice of Eigen and g2o that the double-precision solvers share (orbm_pose.hip: PoseOptimization,
-// orbm_sim3opt.hip: OptimizeSim3), in the restatements' operation order (tests/g2o_restated.h): Eigen's quaternion constructor and
-// rotation, g2o's Huber kernel, Eigen's pivoting LDLT and the fixed-order block reductions.  What belongs to one problem (Se3 /
-// Sim3, the exp maps, the edges) stays in its file.  Everything here is inline: two translation units include it.
+// orbm_sim3opt.hip: OptimizeSim3, orbm_pose_nr.hip: PoseOptimizationNR, orbm_ba.hip: the bundle adjustments,
+// orbm_essential_graph.hip: OptimizeEssentialGraph), in the restatements' operation order (tests/g2o_restated.h): Eigen's
+// quaternion constructor and rotation, its fixed 3 x 3 inverse and pivoting LDLT, g2o's Huber kernel and Levenberg step rule
+// (orbm_levenberg.h, which comes with this file) and the fixed-order wave and block reductions.  What belongs to one problem
+// (Se3 / Sim3, the exp maps, the edges) stays in its file.  Everything here is inline: each of the five solvers' translation units includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include "orbm_levenberg.h"
 
 #define ORBM_UNROLL _Pragma("unroll")
 
@@ -56,6 +60,24 @@ __device__ __forceinline__ void q_rotate(const double q[4], const double v[3], d
     uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
     const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
     ORBM_UNROLL for (int i = 0; i < 3; ++i) o[i] = v[i] + q[3] * uv[i] + c[i];
+}
+
+// ------------------------------------------------------------------ Eigen's fixed-size inverse
+
+// LU/InverseImpl.h, compute_inverse<Matrix3d>: the cofactors, the determinant from the first column, every entry a cofactor times
+// 1 / det.  A singular block gives non-finite entries, as there.
+__device__ __forceinline__ void inverse3(const double m[9], double o[9])
+{
+#define M(i, j) m[3 * (i) + (j)]
+#define COF(i, j) (M(((i) + 1) % 3, ((j) + 1) % 3) * M(((i) + 2) % 3, ((j) + 2) % 3) - M(((i) + 1) % 3, ((j) + 2) % 3) * M(((i) + 2) % 3, ((j) + 1) % 3))
+    const double c0 = COF(0, 0), c1 = COF(1, 0), c2 = COF(2, 0);
+    const double det = (c0 * M(0, 0) + c1 * M(1, 0)) + c2 * M(2, 0);
+    const double invdet = 1.0 / det;
+    o[0] = c0 * invdet; o[1] = c1 * invdet; o[2] = c2 * invdet;
+    o[3] = COF(0, 1) * invdet; o[4] = COF(1, 1) * invdet; o[5] = COF(2, 1) * invdet;
+    o[6] = COF(0, 2) * invdet; o[7] = COF(1, 2) * invdet; o[8] = COF(2, 2) * invdet;
+#undef COF
+#undef M
 }
 
 // ------------------------------------------------------------------ g2o's Huber kernel
@@ -150,15 +172,25 @@ __device__ inline bool ldlt_solve(double (&m)[N * N], const double (&b)[N], doub
     return true;
 }
 
-// ------------------------------------------------------------------ fixed-order block reductions
+// ------------------------------------------------------------------ fixed-order wave and block reductions
+
+__device__ __forceinline__ double wave_sum(double v)    // the butterfly: every lane ends with the wave's sum
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v)
+{
+    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
 
 // Sum of every v[j] over the block's NW waves: wave butterfly, then the waves in order.  red: NW rows of NS >= NV doubles in LDS.
 template <int NV, int NW, int NS>
 __device__ __forceinline__ void block_sum(double (&v)[NV], double (*red)[NS])
 {
     static_assert(NV <= NS, "a row of red holds every value");
-    for (int j = 0; j < NV; ++j)
-        for (int o = 32; o >= 1; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
+    for (int j = 0; j < NV; ++j) v[j] = wave_sum(v[j]);
     if (NW == 1) return;
     __syncthreads();                                        // the previous reduction's readers are done with red
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;

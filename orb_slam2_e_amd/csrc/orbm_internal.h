@@ -5,6 +5,7 @@
 // orbm_search.hip share among themselves is in orbm_search_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -14,6 +15,7 @@
 
 #include "../../include/orbslam_hip.h"
 #include "common.h"
+#include "orbm_levenberg.h"
 #include "orbx_math.h"
 
 namespace orbm_detail {
@@ -223,11 +225,70 @@ struct StagedCall {
         for (const In &i : ins) memcpy(w.pin + i.off, i.src, i.bytes);
         return orbx::stage_in(w.dev, w.pin, staged, stream()) != hipSuccess ? -1 : 0;
     }
-    int download()
+    int download() { return download_head(res_bytes); }
+    int download_head(size_t bytes) // the first bytes of the result block, in the middle of a call
     {
-        if (orbx::stage_out(w.pin, w.dev + res_off, res_bytes, stream()) != hipSuccess) return -1;
+        if (orbx::stage_out(w.pin, w.dev + res_off, bytes, stream()) != hipSuccess) return -1;
         ++waits;
         return hipStreamSynchronize(stream()) == hipSuccess ? 0 : -1;
+    }
+};
+
+// ---- OptimizationAlgorithmLevenberg::solve with the decisions on the host and the passes in kernels (orbm_ba.hip,
+// orbm_essential_graph.hip).  Such a call's result block begins with the 128 bytes a trial reads back: 8 doubles, then 16 ints.
+constexpr size_t LM_BLOCK_BYTES = 128;
+enum { LM_SC_CHI2 = 0,              // chi2 at the iteration's start
+       LM_SC_MAXDIAG = 3,           // the largest diagonal entry, and tau * that: computeLambdaInit (the bundle adjustments alone
+       LM_SC_LAMBDA_INIT = 4,       // write these two and the two counts below; the essential graph leaves them untouched)
+       LM_SC_TEMPCHI = 5,           // a trial's chi2
+       LM_SC_SCALE = 6 };           // computeScale's sum
+enum { LM_ISC_NACT = 0,             // the vertex poses of the round (the bundle adjustments)
+       LM_ISC_OK2 = 1,              // the solve's verdict
+       LM_ISC_NEDGES = 2 };         // the active edges of the round (the bundle adjustments)
+
+struct LmNever { bool operator()() const { return false; } };
+
+struct LmHostLoop {
+    StagedCall &sc;
+    orbm_ba_trial *log;             // [log_cap], or nullptr with log_cap 0
+    int log_cap;
+    LmStep lm;
+    double currentChi = 0., iniChi = 0., rho = 0.;
+    int qmax = 0, nt = 0;           // nt: trials of the call so far
+
+    int read_block() { return sc.download_head(LM_BLOCK_BYTES); }
+    double scalar(int k) const { return sc.r<double>(sc.res_off)[k]; }
+    int flag(int k) const { return reinterpret_cast<const int *>(sc.r<double>(sc.res_off) + 8)[k]; }
+
+    // The trial loop of one iteration (levenberg.cpp:129-226).  trial(lambda) enqueues a trial with its reductions and returns an
+    // ORBX code; after_read() runs behind every read-back, in front of the verdict (a caller sets currentChi / iniChi, or lambda
+    // itself, from the block there); pop() enqueues the copy back; terminate() is g2o's stop flag.  Every trial is appended to the
+    // log.  Leaves rho and qmax for lm.end_iteration.
+    template <class Trial, class AfterRead, class Pop, class Terminate = LmNever>
+    int trials(int round, Trial &&trial, AfterRead &&after_read, Pop &&pop, Terminate &&terminate = Terminate())
+    {
+        iniChi = currentChi;
+        rho = 0;
+        qmax = 0;
+        do {
+            const int rc = trial(lm.lambda);
+            if (rc != ORBX_OK) return rc;
+            ORBX_HIP(hipGetLastError());
+            if (read_block()) ORBX_FAIL(ORBX_ERR_HIP, "a trial's read-back failed");
+            after_read();
+            const bool ok2 = flag(LM_ISC_OK2) != 0;
+            const double tempChi = ok2 ? scalar(LM_SC_TEMPCHI) : DBL_MAX;
+            const LmVerdict vd = lm.verdict(currentChi, tempChi, ok2 ? scalar(LM_SC_SCALE) : 0.0, LmNothing(), pop);
+            rho = vd.rho;
+            if (nt < log_cap) {
+                orbm_ba_trial &t = log[nt];
+                t.tempChi = tempChi; t.currentChi = currentChi; t.rho = rho; t.lambda = lm.lambda; t.scale = vd.scale;
+                t.round = round; t.qmax = qmax; t.accepted = vd.accepted ? 1 : 0; t.ok2 = ok2 ? 1 : 0;
+            }
+            ++nt;
+            qmax++;
+        } while (rho < 0 && qmax < 10 && !terminate());
+        return ORBX_OK;
     }
 };
 

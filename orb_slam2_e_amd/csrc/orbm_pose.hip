@@ -307,8 +307,7 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
         };
 
         if (nactive > 0) {
-            double lambda = 0.0;
-            int ni = 2, lmBad = 0;
+            LmStep lm;
             for (int iteration = 0; iteration < 10; ++iteration) {      // SparseOptimizer::optimize
                 ++iters;
                 double v[NSYS];
@@ -323,16 +322,14 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
                 if (iteration == 0) {                                   // computeLambdaInit, tau = 1e-5
                     double maxDiagonal = 0.;
                     for (int j = 0; j < 6; ++j) { const double f = fabs(H[7 * j]); maxDiagonal = (f < maxDiagonal) ? maxDiagonal : f; }
-                    lambda = 1e-5 * maxDiagonal;
-                    ni = 2;
-                    lmBad = 0;
+                    lm.start(1e-5 * maxDiagonal);
                 }
                 double rho = 0;
                 int qmax = 0;
                 do {
                     double Hl[36], x[6] = {0, 0, 0, 0, 0, 0};
                     for (int j = 0; j < 36; ++j) Hl[j] = H[j];
-                    for (int j = 0; j < 6; ++j) Hl[7 * j] += lambda;
+                    for (int j = 0; j < 6; ++j) Hl[7 * j] += lm.lambda;
                     const bool ok2 = ldlt_solve<6, LdltZeroDiagonal::ReturnZero>(Hl, bb, x);
                     Se3 up, trial;
                     se3_exp(x, up);
@@ -342,31 +339,14 @@ __global__ __launch_bounds__(PT) void k_pose_optimization(PoseSrc src, PoseCam c
                     eval = trial;
                     double tempChi = cv[27];
                     if (!ok2) tempChi = 1.7976931348623157e308;
-                    rho = (currentChi - tempChi);
                     double scale = 0.;
-                    for (int j = 0; j < 6; ++j) scale += x[j] * (lambda * x[j] + bb[j]);
-                    scale += 1e-3;
-                    rho /= scale;
-                    if (rho > 0 && isfinite(tempChi)) {
-                        double alpha = 1. - pow((2 * rho - 1), 3.0);
-                        alpha = (alpha < 2. / 3.) ? alpha : 2. / 3.;
-                        const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;
-                        lambda *= scaleFactor;
-                        ni = 2;
-                        currentChi = tempChi;
-                        est = trial;
-                    } else {
-                        lambda *= ni;
-                        ni *= 2;
-                    }
+                    for (int j = 0; j < 6; ++j) scale += x[j] * (lm.lambda * x[j] + bb[j]);
+                    rho = lm.verdict(currentChi, tempChi, scale, [&]() { est = trial; }).rho;
                     qmax++;
                 } while (rho < 0 && qmax < 10);
                 trials += qmax;
                 currentChiOut = currentChi;
-                if (qmax == 10 || rho == 0) break;                      // Terminate
-                if ((iniChi - currentChi) * 1e3 < iniChi) lmBad++;      // Raul's stop criterion
-                else lmBad = 0;
-                if (lmBad >= 3) break;
+                if (lm.end_iteration(qmax, rho, iniChi, currentChi) != 1) break;
             }
         }
         st.rounds = it + 1; st.iterations[it] = iters; st.trials[it] = trials; st.chi2 = currentChiOut;

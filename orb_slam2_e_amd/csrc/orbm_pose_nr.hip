@@ -71,22 +71,6 @@ struct NrProblem {
     int log_cap;
 };
 
-// Eigen's fixed-size inverse (LU/InverseImpl.h, compute_inverse<Matrix3d>): the cofactors, the determinant from the first column,
-// every entry a cofactor times 1 / det.  A singular block gives non-finite entries, as there.
-__device__ __forceinline__ void inverse3(const double m[9], double o[9])
-{
-#define M(i, j) m[3 * (i) + (j)]
-#define COF(i, j) (M(((i) + 1) % 3, ((j) + 1) % 3) * M(((i) + 2) % 3, ((j) + 2) % 3) - M(((i) + 1) % 3, ((j) + 2) % 3) * M(((i) + 2) % 3, ((j) + 1) % 3))
-    const double c0 = COF(0, 0), c1 = COF(1, 0), c2 = COF(2, 0);
-    const double det = (c0 * M(0, 0) + c1 * M(1, 0)) + c2 * M(2, 0);
-    const double invdet = 1.0 / det;
-    o[0] = c0 * invdet; o[1] = c1 * invdet; o[2] = c2 * invdet;
-    o[3] = COF(0, 1) * invdet; o[4] = COF(1, 1) * invdet; o[5] = COF(2, 1) * invdet;
-    o[6] = COF(0, 2) * invdet; o[7] = COF(1, 2) * invdet; o[8] = COF(2, 2) * invdet;
-#undef COF
-#undef M
-}
-
 // EdgeSE3ProjectXYZ::computeError: obs - cam_project(T.map(X)); c = the mapped point
 __device__ __forceinline__ void edge_error(const Se3 &T, const double X[3], const float *obs, const float *K, double c[3], double err[2])
 {
@@ -111,7 +95,7 @@ __device__ __forceinline__ void edge_jacobians(const double c[3], const double R
 
 __device__ __forceinline__ double block_max(double v, double (*red)[NRED])
 {
-    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    v = wave_max(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = v;
     __syncthreads();
@@ -158,8 +142,7 @@ __global__ __launch_bounds__(NT) void k_pose_nr(const NrProblem *__restrict__ pr
     const float chi2Th = 5.991;                         // chi2[it]
     uint32_t m_out = 0, m_reloc = 0xffffffffu, m_act = 0;   // bit k, the k-th owned point: mvbOutlier, bRelocCheck, active vertex
     int nBad = 0;
-    double lambda = -1., ni = 2.;                       // OptimizationAlgorithmLevenberg's members (levenberg.cpp:46-57)
-    int lmBad = 0;
+    LmStep lm;                                          // OptimizationAlgorithmLevenberg's members
     int nt = 0, nr = 0;
     int st_iter[4] = {0, 0, 0, 0}, st_trials[4] = {0, 0, 0, 0};
 
@@ -233,9 +216,7 @@ __global__ __launch_bounds__(NT) void k_pose_nr(const NrProblem *__restrict__ pr
             if (iteration == 0) {                                               // computeLambdaInit over the pose AND the active points, tau = 1e-5
                 maxd = block_max(maxd, s_red);
                 ORBM_UNROLL for (int j = 0; j < 6; ++j) maxd = fmax(fabs(v[j * (j + 1) / 2 + j]), maxd);
-                lambda = 1e-5 * maxd;
-                ni = 2;
-                lmBad = 0;
+                lm.start(1e-5 * maxd);
             }
             double rho = 0;
             int qmax = 0;
@@ -253,7 +234,7 @@ __global__ __launch_bounds__(NT) void k_pose_nr(const NrProblem *__restrict__ pr
                         const double *blk = P.blocks + 30 * (size_t)n;
                         double D[9], inv[9], W[18];
                         for (int j = 0; j < 9; ++j) D[j] = blk[j];
-                        for (int j = 0; j < 3; ++j) D[4 * j] += lambda;
+                        for (int j = 0; j < 3; ++j) D[4 * j] += lm.lambda;
                         inverse3(D, inv);
                         const double *bl = blk + 9, *H = blk + 12;
                         ORBM_UNROLL for (int i = 0; i < 6; ++i)
@@ -268,7 +249,7 @@ __global__ __launch_bounds__(NT) void k_pose_nr(const NrProblem *__restrict__ pr
                 double S[36], bs[6], xp[6] = {0, 0, 0, 0, 0, 0};
                 for (int j = 0; j < 36; ++j) S[j] = 0.0;                        // (the LDLT reads the lower triangle)
                 ORBM_UNROLL for (int r = 0, h = 0; r < 6; ++r)
-                    ORBM_UNROLL for (int c = 0; c <= r; ++c, ++h) S[6 * r + c] = (r == c ? v[h] + lambda : v[h]) - sv[h];
+                    ORBM_UNROLL for (int c = 0; c <= r; ++c, ++h) S[6 * r + c] = (r == c ? v[h] + lm.lambda : v[h]) - sv[h];
                 ORBM_UNROLL for (int r = 0; r < 6; ++r) bs[r] = bp[r] - sv[21 + r];
                 const bool ok2 = ldlt_solve<6, LdltZeroDiagonal::ReturnZero>(S, bs, xp);
                 if (!ok2) for (int j = 0; j < 6; ++j) xp[j] = 0.0;              // x = 0: nothing moves
@@ -288,7 +269,7 @@ __global__ __launch_bounds__(NT) void k_pose_nr(const NrProblem *__restrict__ pr
                             const double *blk = P.blocks + 30 * (size_t)n;
                             double D[9], inv[9], r[3];
                             for (int j = 0; j < 9; ++j) D[j] = blk[j];
-                            for (int j = 0; j < 3; ++j) D[4 * j] += lambda;
+                            for (int j = 0; j < 3; ++j) D[4 * j] += lm.lambda;
                             inverse3(D, inv);
                             const double *bl = blk + 9, *H = blk + 12;
                             ORBM_UNROLL for (int j = 0; j < 3; ++j) {
@@ -299,7 +280,7 @@ __global__ __launch_bounds__(NT) void k_pose_nr(const NrProblem *__restrict__ pr
                             ORBM_UNROLL for (int j = 0; j < 3; ++j) {
                                 const double dx = inv[3 * j] * r[0] + inv[3 * j + 1] * r[1] + inv[3 * j + 2] * r[2];
                                 X[j] += dx;
-                                tv[1] += dx * (lambda * dx + bl[j]);
+                                tv[1] += dx * (lm.lambda * dx + bl[j]);
                             }
                             sX[3 * n] = X[0]; sX[3 * n + 1] = X[1]; sX[3 * n + 2] = X[2];
                         }
@@ -352,29 +333,18 @@ __global__ __launch_bounds__(NT) void k_pose_nr(const NrProblem *__restrict__ pr
                     currentChi += nsE;
                 }
                 tempChi = w_rE * tempChi + w_sE * nsE;                          // :198 (float * double + float * float)
-                rho = (currentChi - tempChi);                                   // :201
                 double scale = 0.;
-                for (int j = 0; j < 6; ++j) scale += xp[j] * (lambda * xp[j] + bp[j]);
+                for (int j = 0; j < 6; ++j) scale += xp[j] * (lm.lambda * xp[j] + bp[j]);
                 scale += tv[1];
-                scale += 1e-3;
-                rho /= scale;
-                const bool good = rho > 0 && isfinite(tempChi);
-                if (good) {                                                     // :207-217, discardTop
-                    double alpha = 1. - pow((2 * rho - 1), 3.0);
-                    alpha = (alpha < 2. / 3.) ? alpha : 2. / 3.;
-                    const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;
-                    lambda *= scaleFactor;
-                    ni = 2;
-                    currentChi = tempChi;
-                } else {                                                        // :218-223, pop
-                    lambda *= ni;
-                    ni *= 2;
-                    est = pushed;
+                const LmVerdict vd = lm.verdict(currentChi, tempChi, scale, LmNothing(), [&]() {     // :201-223; an accepted trial: discardTop
+                    est = pushed;                                               // pop
                     for (int n = tid; n < np; n += NT) { sX[3 * n] = sXp[3 * n]; sX[3 * n + 1] = sXp[3 * n + 1]; sX[3 * n + 2] = sXp[3 * n + 2]; }
-                }
+                });
+                rho = vd.rho;
+                const bool good = vd.accepted;
                 if (tid == 0 && nt < P.log_cap) {
                     orbm_pose_nr_trial &t = P.log[nt];
-                    t.sE = sE; t.nsE = nsE; t.tempChi = tempChi; t.currentChi = currentChi; t.rho = rho; t.lambda = lambda;
+                    t.sE = sE; t.nsE = nsE; t.tempChi = tempChi; t.currentChi = currentChi; t.rho = rho; t.lambda = lm.lambda;
                     t.qmax = qmax; t.accepted = good ? 1 : 0;
                 }
                 ++nt;
@@ -382,13 +352,7 @@ __global__ __launch_bounds__(NT) void k_pose_nr(const NrProblem *__restrict__ pr
             } while (rho < 0 && qmax < 10);                                     // :226 (nothing sets terminate() on this path)
             st_iter[it]++;
             st_trials[it] += qmax;
-            int result;
-            if (qmax == 10 || rho == 0) result = 2;                             // :228-229 Terminate
-            else {
-                if ((iniChi - currentChi) * 1e3 < iniChi) lmBad++;              // :232-235
-                else lmBad = 0;
-                result = lmBad >= 3 ? 2 : 1;
-            }
+            const int result = lm.end_iteration(qmax, rho, iniChi, currentChi);  // :228-239
             if (tid == 0 && P.stats && nr < 40) P.stats->results[nr] = result;
             ++nr;
             if (result != 1) break;                                             // sparse_optimizer.cpp:470

@@ -164,8 +164,7 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
 
     // SparseOptimizer::optimize(maxit) over the kept pairs
     auto run_round = [&](int maxit, int &iters, int &trials, double &chi_out) {
-        double lambda = 0.0;
-        int ni = 2, lmBad = 0;
+        LmStep lm;
         iters = 0; trials = 0;
         for (int iteration = 0; iteration < maxit; ++iteration) {
             ++iters;
@@ -203,9 +202,7 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
             if (iteration == 0) {                                       // computeLambdaInit, tau = 1e-5
                 double maxDiagonal = 0.;
                 ORBM_UNROLL for (int j = 0; j < 7; ++j) { const double f = fabs(v[j * (j + 1) / 2 + j]); maxDiagonal = (f < maxDiagonal) ? maxDiagonal : f; }
-                lambda = 1e-5 * maxDiagonal;
-                ni = 2;
-                lmBad = 0;
+                lm.start(1e-5 * maxDiagonal);
             }
             double rho = 0;
             int qmax = 0;
@@ -213,7 +210,7 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
                 double Hl[49], x[7] = {0, 0, 0, 0, 0, 0, 0};
                 ORBM_UNROLL for (int r = 0; r < 7; ++r)
                     ORBM_UNROLL for (int c = 0; c < 7; ++c) Hl[7 * r + c] = c <= r ? v[r * (r + 1) / 2 + c] : 0.0;
-                ORBM_UNROLL for (int j = 0; j < 7; ++j) Hl[8 * j] += lambda;
+                ORBM_UNROLL for (int j = 0; j < 7; ++j) Hl[8 * j] += lm.lambda;
                 const bool ok2 = ldlt_solve<7, LdltZeroDiagonal::AsEigen>(Hl, bb, x);
                 if (d.fix_scale) x[6] = 0;                              // oplusImpl writes into the solver's x
                 Sim3 up, trial;
@@ -222,31 +219,14 @@ __global__ __launch_bounds__(NT) void k_sim3_optimize(const Sim3OptDev *__restri
                 double tempChi = pass_chi(trial);
                 eval = trial;
                 if (!ok2) tempChi = 1.7976931348623157e308;
-                rho = (currentChi - tempChi);
                 double scale = 0.;
-                ORBM_UNROLL for (int j = 0; j < 7; ++j) scale += x[j] * (lambda * x[j] + bb[j]);
-                scale += 1e-3;
-                rho /= scale;
-                if (rho > 0 && isfinite(tempChi)) {
-                    double alpha = 1. - pow((2 * rho - 1), 3.0);
-                    alpha = (alpha < 2. / 3.) ? alpha : 2. / 3.;
-                    const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;
-                    lambda *= scaleFactor;
-                    ni = 2;
-                    currentChi = tempChi;
-                    est = trial;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                }
+                ORBM_UNROLL for (int j = 0; j < 7; ++j) scale += x[j] * (lm.lambda * x[j] + bb[j]);
+                rho = lm.verdict(currentChi, tempChi, scale, [&]() { est = trial; }).rho;
                 qmax++;
             } while (rho < 0 && qmax < 10);
             trials += qmax;
             chi_out = currentChi;
-            if (qmax == 10 || rho == 0) break;                          // Terminate
-            if ((iniChi - currentChi) * 1e3 < iniChi) lmBad++;          // Raul's stop criterion
-            else lmBad = 0;
-            if (lmBad >= 3) break;
+            if (lm.end_iteration(qmax, rho, iniChi, currentChi) != 1) break;
         }
     };
 
