@@ -39,7 +39,8 @@ const char *orbx_last_error(void);
  * orbm_fuse_keyframes, orbm_debug_last_fuse_keyframes_waits; orbm_pnp_hypotheses, orbm_debug_last_pnp_waits, orbm_debug_pnp_pose;
  * orbm_debug_fill_workspaces, orbm_debug_last_search_waits; orbm_bundle_adjustment, orbm_ba_plan, orbm_debug_last_ba_waits;
  * orbm_global_bundle_adjustment, orbm_global_ba_plan, orbm_llt_tile, orbm_llt_solve_dev, orbm_debug_last_llt_launches;
- * orbm_essential_graph, orbm_eg_plan, orbm_debug_last_eg_waits; orbm_refine_sim3_candidates, orbm_debug_last_refine_sim3_waits. */
+ * orbm_essential_graph, orbm_eg_plan, orbm_debug_last_eg_waits; orbm_refine_sim3_candidates, orbm_debug_last_refine_sim3_waits;
+ * orbm_llt_env_plan, orbm_llt_env_solve_dev, orbm_essential_graph_env, orbm_eg_env_plan. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -1154,8 +1155,46 @@ int orbm_global_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *po
  * n outside 1 .. 3,072 or a NULL pointer: ORBX_ERR_ARG before any device work.  4 ceil(n / T) - 1 launches. */
 int orbm_llt_tile(void);
 int orbm_llt_solve_dev(int n, double *S_dev, const double *b_dev, double *x_dev, int32_t *ok_dev, void *stream);
-/* Kernel launches of the last orbm_llt_solve_dev of this process. */
+/* Kernel launches of the last orbm_llt_solve_dev or orbm_llt_env_solve_dev of this process. */
 int orbm_debug_last_llt_launches(void);
+
+/* ------------------------------------------------------------------ tiled Cholesky solve over a tile envelope
+ * The same solve for a sparse S of 1 <= n <= 28,672 rows whose non-zeros lie inside a TILE ENVELOPE.  With
+ * T = orbm_llt_tile() and nt = ceil(n / T), first[R] (0 <= first[R] <= R, host memory, need not be monotone) is the first live column
+ * tile of row tile R: the tiles (R, C), first[R] <= C <= R, are LIVE, every other tile is structurally zero and is neither stored
+ * nor touched.  Cholesky fill stays inside such an envelope.  At most 8,192 live tiles (2 x 256 MiB of tiles): every envelope up to
+ * nt = 127, the full one included, fits.
+ *   A_dev    the live tiles, packed: tile (R, C) is tile number off[R] + C - first[R], off[R] = sum over r < R of r - first[r] + 1,
+ *            each tile T x T doubles COLUMN-major (entry (R T + i, C T + j) at j * T + i).  EVERY entry of a live tile with a row
+ *            below n is input, the zeros too; of a diagonal tile only i >= j is read.  On return the tiles hold L.  Rows at or
+ *            beyond n of the last row tile, and the strict upper part of a diagonal tile, are never read or written
+ *   W_dev    as many doubles as A_dev: the running dots, the call's scratch (written before read, unspecified afterwards).  The
+ *            dense solver keeps them in the mirrored triangle and in x; a packed triangle has no mirror, so the caller lends the
+ *            room.  The diagonal's dots are on W's diagonal (no further array)
+ *   b_dev, x_dev, ok_dev   as orbm_llt_solve_dev
+ *   plan_dev int32, device: first[nt], off[nt + 1], row_start[nt + 1], rows[row_start[nt]] of orbm_llt_env_plan, one after the other.
+ *            The caller uploads it (once per call, or once for many calls with the same envelope); the solver reads `first` on the
+ *            host for its grids and never waits
+ * The arithmetic is orbm_llt_solve_dev's, entry by entry, restricted to live tiles: the dot of an entry of tile (R, C) STARTS as its
+ * first product of panel max(first[R], first[C]) and adds the later panels' products in ascending k; a tile whose row and column
+ * start at itself has no dot; y_i takes the panels first[R] .. R - 1 ascending, x_i the rows R' with first[R'] <= R descending.  On a
+ * matrix that is zero outside the envelope, L's live tiles and x equal the dense solver's as numbers (the products it skips are
+ * +-0.0, so the sign of a zero may differ and nothing else); ok is the same.  Failure as there: ok = 0, x = 0.0 everywhere.
+ * Launches: 1 + 2 nt + per panel K < nt - 1 one (two when a row tile has first[R] <= K < R), at most 4 nt - 1; never an empty grid.
+ * ORBX_ERR_ARG: n outside 1 .. 28,672, a first[R] outside 0 .. R, a NULL pointer; ORBX_ERR_UNSUPPORTED: more than 8,192 live tiles;
+ * both before any device work, nothing written.
+ *
+ * orbm_llt_env_plan: host only, no device; what the solver will do for n and first[].  Any output may be NULL.
+ *   off[nt + 1]           tile number of (R, first[R]); off[nt] = the live tiles
+ *   row_start[nt + 1], rows[]     panel K's row tiles: R > K with first[R] <= K, ascending (the tiles that solve against diagonal
+ *                         tile K, subtract y_K in the forward pass and give x_K its terms in the backward pass)
+ *   trail_start[nt + 1], trail[][2]   panel K's trailing tiles (R, C), K < C <= R, first[R] <= K and first[C] <= K, by R then C: the
+ *                         pairs of panel K's row tiles
+ *   counts[4]             live tiles, entries of rows, trailing tiles, launches (call once with NULL lists to size them) */
+int orbm_llt_env_plan(int n, const int32_t *first, int32_t *off, int32_t *row_start, int32_t *rows, int32_t *trail_start, int32_t *trail,
+                      int32_t *counts);
+int orbm_llt_env_solve_dev(int n, const int32_t *first, const int32_t *plan_dev, double *A_dev, double *W_dev, const double *b_dev,
+                           double *x_dev, int32_t *ok_dev, void *stream);
 
 /* ------------------------------------------------------------------ essential graph
  * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1165-1428): the Sim3 pose graph LoopClosing::CorrectLoop
@@ -1221,8 +1260,29 @@ int orbm_essential_graph(const orbm_eg_graph *g, const orbm_eg_options *opt, orb
  *   counts[3]                entries of vert_edges, pairs, entries of pair_edges (call once with NULL lists to size them) */
 int orbm_eg_plan(const orbm_eg_graph *g, int32_t *vertex_class, int32_t *row, int32_t *vert_edge_start, int32_t *vert_edges,
                  int32_t *pair_start, int32_t *pair_v, int32_t *pair_edges, int32_t *counts);
-/* Host waits of the last orbm_essential_graph of this process: trials + 1; 0 when nothing was launched. */
+/* Host waits of the last orbm_essential_graph or orbm_essential_graph_env of this process: trials + 1; 0 when nothing was launched. */
 int orbm_debug_last_eg_waits(void);
+/* The same call for the essential graph of a long session: structs, options, statistics, waits and every documented
+ * deviation as orbm_essential_graph.  What differs: the system is assembled into the live tiles of a TILE ENVELOPE and solved by
+ * orbm_llt_env_solve_dev, so the limits are nact <= 4,096 (a system 28,672 wide), nvert <= 8,192, nedges <= 131,072, npoints <=
+ * 1,048,576 and at most 8,192 live tiles (ORBX_ERR_UNSUPPORTED before any device work, nothing written; the tile cap is checked
+ * behind every ORBX_ERR_ARG of the graph, the options and the result, and also when iterations = 0 or nothing would be solved: the call
+ * refuses what orbm_eg_env_plan refuses).  Rows are the caller's
+ * vertex order, and that order decides the envelope: row tile R of the system (7 rows per class-0 vertex, T = orbm_llt_tile() rows
+ * per tile) starts at the smallest column tile any of its vertices' pairs reaches.  LIST THE KEYFRAMES BY ASCENDING mnId: spanning-
+ * tree and covisibility edges then join neighbours in the list and form a band a few tiles wide, and a loop edge widens only the
+ * rows of its later keyframe; a shuffled list gives a wide envelope, more work, and past the tile cap a refusal.  Every entry of the
+ * system has the value orbm_essential_graph gives it (same sums in the same order), and the solver skips only products with exact
+ * zeros: a graph both entries admit gives the same numbers through either (the sign of a zero inside the solve aside).  The leased
+ * workspace holds two copies of the live tiles (up to 2 x 256 MiB) and stays leased to the process like every arena.
+ *
+ * orbm_eg_env_plan: host only, no device; what orbm_eg_plan returns under the limits above, plus
+ *   first[counts[3]]         the envelope: first live column tile of every row tile (orbm_llt_env_plan takes it from there)
+ *   counts[6]                the three of orbm_eg_plan, then row tiles, live tiles, kernel launches of one solve
+ * so a caller can see what an ordering costs before it calls.  Refuses what the call refuses. */
+int orbm_essential_graph_env(const orbm_eg_graph *g, const orbm_eg_options *opt, orbm_eg_result *out, orbm_eg_stats *stats);
+int orbm_eg_env_plan(const orbm_eg_graph *g, int32_t *vertex_class, int32_t *row, int32_t *vert_edge_start, int32_t *vert_edges,
+                     int32_t *pair_start, int32_t *pair_v, int32_t *pair_edges, int32_t *first, int32_t *counts);
 
 /* KeyFrameDatabase on the device (src/KeyFrameDatabase.cc:40-309, src/LoopClosing.cc:120-141): the BowVectors of the
  * added keyframes live in HBM, one row of (word id, value) per keyframe under a SLOT number.  Slots are handed out in ascending

@@ -1582,7 +1582,9 @@ private:
 // addLoopConnection for the LoopConnections loop (:1236-1264), addEdge for a spanning-tree, old-loop or covisibility edge
 // (:1284-1366), vertex 0 = nIDi first; addPoint with the index of the keyframe :1404-1413 choose.  Optimize() replaces poses by what
 // SetPose receives and points by what SetWorldPos receives.  false on a library error (status(): ORBX_ERR_UNSUPPORTED beyond 438
-// free keyframes with an edge, where g2o remains the path).
+// free keyframes with an edge).  OptimizeEnv() is the same call through orbm_essential_graph_env, for up to 4,096 free keyframes: add
+// the keyframes by ascending mnId, since their order decides the tile envelope (ORBX_ERR_UNSUPPORTED beyond its limits, where g2o
+// remains the path).
 class EssentialGraph {
 public:
     std::vector<float> poses, points;               // [nvert][16], [npoints][3]
@@ -1606,7 +1608,12 @@ public:
         return (int)pRef.size() - 1;
     }
 
-    bool Optimize(int nIterations = ORBM_EG_ITERATIONS, orbm_eg_stats *stats = nullptr)
+    bool Optimize(int nIterations = ORBM_EG_ITERATIONS, orbm_eg_stats *stats = nullptr) { return run(orbm_essential_graph, nIterations, stats); }
+    bool OptimizeEnv(int nIterations = ORBM_EG_ITERATIONS, orbm_eg_stats *stats = nullptr) { return run(orbm_essential_graph_env, nIterations, stats); }
+    int status() const { return mStatus; }
+
+private:
+    bool run(int (*call)(const orbm_eg_graph *, const orbm_eg_options *, orbm_eg_result *, orbm_eg_stats *), int nIterations, orbm_eg_stats *stats)
     {
         orbm_eg_graph g;
         std::memset(&g, 0, sizeof(g));
@@ -1620,15 +1627,12 @@ public:
         std::vector<float> posesOut(poses.size() + 1), pointsOut(points.size() + 1);
         orbm_eg_result r;
         r.poses = posesOut.data(); r.points = pointsOut.data();
-        mStatus = orbm_essential_graph(&g, &o, &r, stats);
+        mStatus = call(&g, &o, &r, stats);
         if (mStatus != ORBX_OK) return false;
         std::copy(posesOut.begin(), posesOut.begin() + poses.size(), poses.begin());
         std::copy(pointsOut.begin(), pointsOut.begin() + points.size(), points.begin());
         return true;
     }
-    int status() const { return mStatus; }
-
-private:
     static int32_t entry(std::vector<double> &table, const double *e)
     {
         if (!e) return -1;

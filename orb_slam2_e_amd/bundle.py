@@ -163,3 +163,40 @@ def llt_solve_device(S_dev, b_dev, x_dev, ok_dev, stream=None):
             raise ValueError("llt_solve_device: contiguous device tensors float64 [n][n], [n], [n] and int32 [1]")
     st = (stream if stream is not None else torch.cuda.current_stream(S_dev.device)).cuda_stream
     check(lib().orbm_llt_solve_dev(n, S_dev.data_ptr(), b_dev.data_ptr(), x_dev.data_ptr(), ok_dev.data_ptr(), st))
+
+
+def llt_env_plan(n, first):
+    """orbm_llt_env_plan (host only): what the envelope solve does for n rows and first[] (the first live column tile of every row
+    tile).  A dict: off [nt + 1], row_start [nt + 1], rows, trail_start [nt + 1], trail [][2], live_tiles, launches, and `device`,
+    the int32 image orbm_llt_env_solve_dev reads on the device (first, off, row_start, rows)."""
+    first = np.ascontiguousarray(first, np.int32)
+    nt = len(first)
+    counts = np.zeros(4, np.int32)
+    check(lib().orbm_llt_env_plan(n, ptr(first), None, None, None, None, None, ptr(counts)))
+    off, row_start, trail_start = (np.zeros(nt + 1, np.int32) for _ in range(3))
+    rows, trail = np.zeros(max(int(counts[1]), 1), np.int32), np.zeros((max(int(counts[2]), 1), 2), np.int32)
+    check(lib().orbm_llt_env_plan(n, ptr(first), ptr(off), ptr(row_start), ptr(rows), ptr(trail_start), ptr(trail), ptr(counts)))
+    rows, trail = rows[:counts[1]], trail[:counts[2]]
+    return {"first": first, "off": off, "row_start": row_start, "rows": rows, "trail_start": trail_start, "trail": trail,
+            "live_tiles": int(counts[0]), "launches": int(counts[3]), "device": np.concatenate([first, off, row_start, rows])}
+
+
+def llt_env_solve_device(first, plan_dev, A_dev, W_dev, b_dev, x_dev, ok_dev, stream=None):
+    """orbm_llt_env_solve_dev on torch device tensors, asynchronous on `stream` (None: the current one).  first: host int32 [nt];
+    plan_dev: llt_env_plan(...)["device"] as a device int32 tensor; A_dev: the live tiles, float64 [live][T][T] with element
+    [tile][j][i] = entry (i, j) of the tile -- it comes back with L; W_dev: as many float64, scratch; b_dev, x_dev: float64 [n];
+    ok_dev: int32 [1].  Nothing is waited for."""
+    import torch
+    first = np.ascontiguousarray(first, np.int32)
+    n, T = int(b_dev.numel()), llt_tile()
+    nt = (n + T - 1) // T
+    if len(first) != nt:
+        raise ValueError("llt_env_solve_device: first holds one entry per row tile")
+    live = int(np.sum(np.arange(nt) - first + 1))
+    for t, dt, numel in ((A_dev, torch.float64, live * T * T), (W_dev, torch.float64, live * T * T), (b_dev, torch.float64, n),
+                         (x_dev, torch.float64, n), (ok_dev, torch.int32, 1), (plan_dev, torch.int32, None)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and (numel is None or t.numel() == numel)):
+            raise ValueError("llt_env_solve_device: contiguous device tensors float64 [live][T][T] twice, [n], [n], int32 [1] and the plan")
+    st = (stream if stream is not None else torch.cuda.current_stream(A_dev.device)).cuda_stream
+    check(lib().orbm_llt_env_solve_dev(n, ptr(first), plan_dev.data_ptr(), A_dev.data_ptr(), W_dev.data_ptr(), b_dev.data_ptr(),
+                                       x_dev.data_ptr(), ok_dev.data_ptr(), st))

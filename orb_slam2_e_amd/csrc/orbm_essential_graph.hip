@@ -16,6 +16,8 @@
 //   k_eg_assemble    S = H + lambda I: the WHOLE lower triangle of the column-major n x n square (the factorisation overwrites it),
 //                    zeros, the diagonal blocks, every off-diagonal block summed over its pair's edges in edge order
 //   orbm_llt_solve_dev   the solve (orbm_llt.hip), as it is, at every size
+//   k_eg_assemble_env, orbm_llt_env_solve_dev   orbm_essential_graph_env: the same entries into the live tiles of the
+//                    tile envelope the pair list gives, and the solve over those tiles; every other pass is shared
 //   k_eg_update      push; x[6] = 0 in place when the scale is fixed (oplusImpl writes into the solver's vector); Sim3(x) * estimate;
 //                    the terms of computeScale
 //   k_eg_reduce      chi2's block partials in the fixed tree of orbm_ba.hip; computeScale's terms in index order by one thread
@@ -49,6 +51,18 @@ constexpr int EPW = 4;                  // edges per wave of k_eg_linearize: 16 
 constexpr int NC = 161;                 // an edge's store: A^T A [49], A^T B [49], B^T B [49], -A^T e [7], -B^T e [7]
 constexpr int EG_MAXACT = 438, EG_MAXVERT = 1024, EG_MAXEDGES = 32768, EG_MAXPOINTS = 1048576, EG_MAXITER = 64;
 static_assert(7 * EG_MAXACT <= 3072 && 7 * (EG_MAXACT + 1) > 3072, "the system fits orbm_llt_solve_dev");
+constexpr int EGE_MAXACT = 4096, EGE_MAXVERT = 8192, EGE_MAXEDGES = 131072;    // orbm_essential_graph_env
+static_assert(7 * EGE_MAXACT == 28672, "the system fits orbm_llt_env_solve_dev");
+
+// what the two entries differ in before the device is touched
+struct EgLimits {
+    int maxact, maxvert, maxedges;
+    const char *act_msg, *vert_msg, *edges_msg;
+};
+constexpr EgLimits EG_DENSE = {EG_MAXACT, EG_MAXVERT, EG_MAXEDGES, "more than 438 free keyframes with an edge", "more than 1,024 keyframes",
+                               "more than 32,768 edges"};
+constexpr EgLimits EG_ENV = {EGE_MAXACT, EGE_MAXVERT, EGE_MAXEDGES, "more than 4,096 free keyframes with an edge", "more than 8,192 keyframes",
+                             "more than 131,072 edges"};
 
 // the call's arrays on the device
 struct EgDev {
@@ -65,6 +79,10 @@ struct EgDev {
     double *Hd;                         // [nact][49]
     double *b, *x, *sterm;              // [n]
     double *S;                          // [n][n]
+    double *A, *W;                      // the envelope entry: the live tiles and the solver's running dots in place of S
+    const int *env;                     // its device plan (first, off, row_start, rows: orbm_llt_env_solve_dev)
+    const int *tile_row;                // [live tiles]: the row tile of a packed tile
+    int T, nt;                          // orbm_llt_tile(), ceil(n / T)
     double *part_chi;                   // [nblocks]
     double *sc;                         // the block a trial reads back (LM_SC_*, LM_ISC_*: orbm_internal.h)
     int *isc;
@@ -321,6 +339,33 @@ __global__ __launch_bounds__(PT) void k_eg_gather(EgDev D)
     else D.b[7 * r + (l - 49)] = s;
 }
 
+// Entry (row r of block row rb, column c of block column cb), rb >= cb, of S = H + lambda I as k_eg_assemble below forms it, value
+// and summation order: the diagonal block plus lambda, or 0.0 + the pair's edges in edge order.  For k_eg_assemble_env, which has
+// no block column of its own to hoist the pair range for; k_eg_assemble stays as it is.
+__device__ __forceinline__ double system_entry(const EgDev &D, int rb, int r, int cb, int c, double lambda)
+{
+    double v = 0.0;
+    if (rb == cb) {
+        v = D.Hd[49 * cb + 7 * r + c];
+        if (r == c) v += lambda;
+        return v;
+    }
+    const int p1 = D.col_start[cb + 1];
+    int lo = D.col_start[cb], hi = p1;                              // the pair (cb, rb), if an edge joins the two
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (D.pair_hi[mid] < rb) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < p1 && D.pair_hi[lo] == rb)
+        for (int k = D.pe_start[lo]; k < D.pe_start[lo + 1]; ++k) {
+            const int code = D.pe_list[k], e = code >> 1;
+            // A^T B is (vertex 0) x (vertex 1): entry (row r of rb, column c of cb) is its transpose unless vertex 0 is rb
+            v += D.contrib[NC * (size_t)e + 49 + ((code & 1) ? 7 * r + c : 7 * c + r)];
+        }
+    return v;
+}
+
 // S = H + lambda I, block column blockIdx.x: every entry on and below the diagonal; consecutive threads run down a column
 __global__ __launch_bounds__(RT) void k_eg_assemble(EgDev D, double lambda)
 {
@@ -349,6 +394,22 @@ __global__ __launch_bounds__(RT) void k_eg_assemble(EgDev D, double lambda)
                 }
         }
         D.S[(size_t)col * n + row] = v;
+    }
+}
+
+// The same entries into live tile blockIdx.x of the envelope (orbm_llt_env_solve_dev's packing): EVERY entry on and below the
+// diagonal with a row below n, the zeros too (the factorisation has overwritten the tile with fill-in)
+__global__ __launch_bounds__(RT) void k_eg_assemble_env(EgDev D, double lambda)
+{
+    const int T = D.T, t = blockIdx.x, R = D.tile_row[t];
+    const int *first = D.env, *off = D.env + D.nt;
+    const int C = t - off[R] + first[R];
+    double *tile = D.A + (size_t)t * T * T;
+    for (int idx = threadIdx.x; idx < T * T; idx += RT) {
+        const int row = R * T + idx % T, col = C * T + idx / T;
+        if (row >= D.n || row < col) continue;
+        const int rb = row / 7, cb = col / 7;
+        tile[idx] = system_entry(D, rb, row - 7 * rb, cb, col - 7 * cb, lambda);
     }
 }
 
@@ -444,11 +505,11 @@ struct EgPlan {
 };
 
 // arguments, limits, indices; the vertex classes, the vertex -> edge lists and the pair -> edge lists
-int eg_plan(const orbm_eg_graph &g, EgPlan &P)
+int eg_plan(const orbm_eg_graph &g, EgPlan &P, const EgLimits &lim)
 {
     if (g.nvert < 0 || g.ncorr < 0 || g.nnc < 0 || g.nedges < 0 || g.npoints < 0) ORBX_FAIL(ORBX_ERR_ARG, "negative size");
-    if (g.nvert > EG_MAXVERT) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 1,024 keyframes");
-    if (g.nedges > EG_MAXEDGES) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 32,768 edges");
+    if (g.nvert > lim.maxvert) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, lim.vert_msg);
+    if (g.nedges > lim.maxedges) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, lim.edges_msg);
     if (g.npoints > EG_MAXPOINTS) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 1,048,576 points");
     if ((g.nvert && (!g.poses || !g.corrected || !g.noncorrected || !g.fixed)) || (g.ncorr && !g.corrected_sim3) || (g.nnc && !g.noncorrected_sim3) ||
         (g.nedges && (!g.e_v0 || !g.e_v1 || !g.e_kind)) || (g.npoints && (!g.points || !g.p_ref)))
@@ -476,7 +537,7 @@ int eg_plan(const orbm_eg_graph &g, EgPlan &P)
     for (int v = 0; v < nv; ++v)
         if (P.vclass[v] == 0) { P.row[v] = (int32_t)P.act_vert.size(); P.act_vert.push_back(v); }
     P.nact = (int)P.act_vert.size();
-    if (P.nact > EG_MAXACT) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 438 free keyframes with an edge");
+    if (P.nact > lim.maxact) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, lim.act_msg);
     auto finite = [](const auto *a, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite((double)a[i])) return false; return true; };
     if (!finite(g.poses, 16 * (size_t)nv) || !finite(g.corrected_sim3, 8 * (size_t)g.ncorr) || !finite(g.noncorrected_sim3, 8 * (size_t)g.nnc) ||
         !finite(g.points, 3 * (size_t)g.npoints))
@@ -526,6 +587,43 @@ int eg_plan(const orbm_eg_graph &g, EgPlan &P)
     return ORBX_OK;
 }
 
+// The tile envelope of the system in the caller's vertex order, and what orbm_llt_env_solve_dev reads on the device: first[R] = the
+// smallest column tile over the pairs (and the diagonal blocks) of the block rows that reach into row tile R.  Refuses as
+// orbm_llt_env_plan does (more than 8,192 live tiles).
+struct EgEnvPlan {
+    int nt = 0, live = 0, launches = 0;
+    std::vector<int32_t> first, image, tile_row;            // image: first, off, row_start, rows
+};
+
+int eg_env_plan(const EgPlan &P, EgEnvPlan &E)
+{
+    const int T = orbm_llt_tile(), n = 7 * P.nact;
+    E = EgEnvPlan();
+    if (n == 0) return ORBX_OK;
+    const int nt = E.nt = (n + T - 1) / T;
+    E.first.resize((size_t)nt);
+    for (int R = 0; R < nt; ++R) E.first[(size_t)R] = R;
+    auto reach = [&](int rb, int cb) {                              // block (rb, cb), rb >= cb: rows 7 rb .. 7 rb + 6, columns from 7 cb
+        const int32_t c = 7 * cb / T;
+        for (int R = 7 * rb / T; R <= (7 * rb + 6) / T; ++R) E.first[(size_t)R] = std::min(E.first[(size_t)R], c);
+    };
+    for (int r = 0; r < P.nact; ++r) {
+        reach(r, r);
+        for (int k = P.col_start[(size_t)r]; k < P.col_start[(size_t)r + 1]; ++k) reach(P.pair_hi[(size_t)k], r);
+    }
+    int32_t counts[4];
+    if (const int e = orbm_llt_env_plan(n, E.first.data(), nullptr, nullptr, nullptr, nullptr, nullptr, counts)) return e;
+    E.live = counts[0]; E.launches = counts[3];
+    E.image.assign((size_t)nt + 2 * ((size_t)nt + 1) + (size_t)counts[1], 0);
+    memcpy(E.image.data(), E.first.data(), sizeof(int32_t) * (size_t)nt);
+    int32_t *off = E.image.data() + nt, *row_start = off + nt + 1, *rows = row_start + nt + 1;
+    if (const int e = orbm_llt_env_plan(n, E.first.data(), off, row_start, rows, nullptr, nullptr, counts)) return e;
+    E.tile_row.resize((size_t)E.live);
+    for (int R = 0; R < nt; ++R)
+        for (int t = off[R]; t < off[R + 1]; ++t) E.tile_row[(size_t)t] = R;
+    return ORBX_OK;
+}
+
 std::atomic<int> g_last_eg_waits{0};    // host waits of the last orbm_essential_graph of this process
 
 void reset_stats(orbm_eg_stats *st)
@@ -543,7 +641,7 @@ int orbm_eg_plan(const orbm_eg_graph *g, int32_t *vertex_class, int32_t *row, in
 {
     if (!g) ORBX_FAIL(ORBX_ERR_ARG, "null graph");
     EgPlan P;
-    const int rc = eg_plan(*g, P);
+    const int rc = eg_plan(*g, P, EG_DENSE);
     if (rc != ORBX_OK) return rc;
     auto copy = [](int32_t *dst, const std::vector<int32_t> &v) { if (dst && !v.empty()) memcpy(dst, v.data(), sizeof(int32_t) * v.size()); };
     copy(vertex_class, P.vclass); copy(row, P.row); copy(vert_edge_start, P.ve_start); copy(vert_edges, P.ve_list);
@@ -552,22 +650,47 @@ int orbm_eg_plan(const orbm_eg_graph *g, int32_t *vertex_class, int32_t *row, in
     return ORBX_OK;
 }
 
+int orbm_eg_env_plan(const orbm_eg_graph *g, int32_t *vertex_class, int32_t *row, int32_t *vert_edge_start, int32_t *vert_edges,
+                     int32_t *pair_start, int32_t *pair_v, int32_t *pair_edges, int32_t *first, int32_t *counts)
+{
+    if (!g) ORBX_FAIL(ORBX_ERR_ARG, "null graph");
+    EgPlan P;
+    EgEnvPlan E;
+    int rc = eg_plan(*g, P, EG_ENV);
+    if (rc == ORBX_OK) rc = eg_env_plan(P, E);
+    if (rc != ORBX_OK) return rc;
+    auto copy = [](int32_t *dst, const std::vector<int32_t> &v) { if (dst && !v.empty()) memcpy(dst, v.data(), sizeof(int32_t) * v.size()); };
+    copy(vertex_class, P.vclass); copy(row, P.row); copy(vert_edge_start, P.ve_start); copy(vert_edges, P.ve_list);
+    copy(pair_start, P.pair_start); copy(pair_v, P.pair_v); copy(pair_edges, P.pe_list); copy(first, E.first);
+    if (counts) {
+        counts[0] = (int32_t)P.ve_list.size(); counts[1] = (int32_t)P.pair_hi.size(); counts[2] = (int32_t)P.pe_list.size();
+        counts[3] = E.nt; counts[4] = E.live; counts[5] = E.launches;
+    }
+    return ORBX_OK;
+}
+
 int orbm_debug_last_eg_waits(void) { return g_last_eg_waits.load(); }
 
-int orbm_essential_graph(const orbm_eg_graph *gp, const orbm_eg_options *op, orbm_eg_result *outp, orbm_eg_stats *stats)
+namespace {
+
+// The body of both public entries.  env: the limits of orbm_essential_graph_env, its assembly into the live tiles of the envelope and
+// the solve over them; everything else is one code.
+int eg_run(const orbm_eg_graph *gp, const orbm_eg_options *op, orbm_eg_result *outp, orbm_eg_stats *stats, bool env)
 {
     if (!gp || !op || !outp) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     const orbm_eg_graph &g = *gp;
     const orbm_eg_options &opt = *op;
     orbm_eg_result &out = *outp;
     EgPlan P;
-    int rc = eg_plan(g, P);
+    EgEnvPlan E;
+    int rc = eg_plan(g, P, env ? EG_ENV : EG_DENSE);
     if (rc != ORBX_OK) return rc;
     if (opt.iterations < 0 || opt.iterations > EG_MAXITER) ORBX_FAIL(ORBX_ERR_ARG, "iterations outside 0 .. 64");
     if (!(opt.lambda_init > 0) || !std::isfinite(opt.lambda_init)) ORBX_FAIL(ORBX_ERR_ARG, "lambda_init must be positive and finite");
     if ((g.nvert && !out.poses) || (g.npoints && !out.points)) ORBX_FAIL(ORBX_ERR_ARG, "null result array");
     if (stats && stats->trial_capacity < 0) ORBX_FAIL(ORBX_ERR_ARG, "negative trial capacity");
     if (stats && stats->trial_capacity > 0 && !stats->trial_log) ORBX_FAIL(ORBX_ERR_ARG, "trial capacity without a trial log");
+    if (env && (rc = eg_env_plan(P, E)) != ORBX_OK) return rc;                  // the tile cap, behind every argument check (also when no solve will run)
     g_last_eg_waits = 0;
     reset_stats(stats);
     if (g.nvert == 0) return ORBX_OK;                                           // (no vertex: no edge and no point either)
@@ -592,11 +715,14 @@ int orbm_essential_graph(const orbm_eg_graph *gp, const orbm_eg_options *op, orb
     const size_t o_vl = sc.in(P.ve_list.data(), sizeof(int32_t) * P.ve_list.size()), o_cs = sc.in(P.col_start.data(), sizeof(int32_t) * (na + 1));
     const size_t o_ph = sc.in(P.pair_hi.data(), sizeof(int32_t) * npairs), o_ps = sc.in(P.pair_start.data(), sizeof(int32_t) * P.pair_start.size());
     const size_t o_pl = sc.in(P.pe_list.data(), sizeof(int32_t) * P.pe_list.size());
+    const size_t o_env = sc.in(E.image.data(), sizeof(int32_t) * E.image.size()), o_tr = sc.in(E.tile_row.data(), sizeof(int32_t) * E.tile_row.size());
     const size_t o_vscw = sc.scratch(sizeof(double) * 8 * nv), o_est = sc.scratch(sizeof(double) * 8 * nv), o_estb = sc.scratch(sizeof(double) * 8 * nv);
     const size_t o_meas = sc.scratch(sizeof(double) * 8 * ne), o_err = sc.scratch(sizeof(double) * 7 * ne);
     const size_t o_cb = sc.scratch(solve ? sizeof(double) * NC * ne : 0), o_Hd = sc.scratch(sizeof(double) * 49 * na);
     const size_t o_b = sc.scratch(sizeof(double) * n), o_x = sc.scratch(sizeof(double) * n), o_st = sc.scratch(sizeof(double) * n);
-    const size_t o_S = sc.scratch(solve ? sizeof(double) * n * n : 0), o_pchi = sc.scratch(sizeof(double) * nblk);
+    const size_t tile_bytes = sizeof(double) * (size_t)E.live * (size_t)orbm_llt_tile() * (size_t)orbm_llt_tile();
+    const size_t o_S = sc.scratch(solve && !env ? sizeof(double) * n * n : 0), o_pchi = sc.scratch(sizeof(double) * nblk);
+    const size_t o_A = sc.scratch(solve && env ? tile_bytes : 0), o_W = sc.scratch(solve && env ? tile_bytes : 0);
     const size_t o_sc = sc.out(LM_BLOCK_BYTES);                                 // what a trial reads back
     const size_t o_pout = sc.out(sizeof(float) * 16 * nv), o_xout = sc.out(sizeof(float) * 3 * np);
     const size_t o_eout = sc.out(sizeof(double) * 8 * nv), o_chi = sc.out(sizeof(double) * ne);
@@ -609,6 +735,7 @@ int orbm_essential_graph(const orbm_eg_graph *gp, const orbm_eg_options *op, orb
     D.vscw = sc.d<double>(o_vscw); D.est = sc.d<double>(o_est); D.est_bak = sc.d<double>(o_estb); D.meas = sc.d<double>(o_meas);
     D.e_err = sc.d<double>(o_err); D.contrib = sc.d<double>(o_cb); D.Hd = sc.d<double>(o_Hd); D.b = sc.d<double>(o_b); D.x = sc.d<double>(o_x);
     D.sterm = sc.d<double>(o_st); D.S = sc.d<double>(o_S); D.part_chi = sc.d<double>(o_pchi);
+    D.A = sc.d<double>(o_A); D.W = sc.d<double>(o_W); D.env = sc.d<int>(o_env); D.tile_row = sc.d<int>(o_tr); D.T = orbm_llt_tile(); D.nt = E.nt;
     D.sc = sc.d<double>(o_sc); D.isc = reinterpret_cast<int *>(sc.d<double>(o_sc) + 8);
     D.poses_out = sc.d<float>(o_pout); D.points_out = sc.d<float>(o_xout); D.est_out = sc.d<double>(o_eout); D.chi2_out = sc.d<double>(o_chi);
 
@@ -629,8 +756,13 @@ int orbm_essential_graph(const orbm_eg_graph *gp, const orbm_eg_options *op, orb
             hipLaunchKernelGGL(k_eg_gather, dim3((unsigned)na), b_pt, 0, st, D);
             if (it == 0) L.lm.start(opt.lambda_init);                           // levenberg.cpp:110-115, computeLambdaInit :245-246
             auto trial = [&](double lambda) -> int {
-                hipLaunchKernelGGL(k_eg_assemble, dim3((unsigned)na), dim3(RT), 0, st, D, lambda);
-                if (const int e = orbm_llt_solve_dev((int)n, D.S, D.b, D.x, D.isc + LM_ISC_OK2, st)) return e;
+                if (env) {
+                    hipLaunchKernelGGL(k_eg_assemble_env, dim3((unsigned)E.live), dim3(RT), 0, st, D, lambda);
+                    if (const int e = orbm_llt_env_solve_dev((int)n, E.first.data(), D.env, D.A, D.W, D.b, D.x, D.isc + LM_ISC_OK2, st)) return e;
+                } else {
+                    hipLaunchKernelGGL(k_eg_assemble, dim3((unsigned)na), dim3(RT), 0, st, D, lambda);
+                    if (const int e = orbm_llt_solve_dev((int)n, D.S, D.b, D.x, D.isc + LM_ISC_OK2, st)) return e;
+                }
                 hipLaunchKernelGGL(k_eg_update, g_act, b_pt, 0, st, D, lambda);
                 hipLaunchKernelGGL(k_eg_errors, g_edges, b_pt, 0, st, D);
                 hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(RT), 0, st, D, 1);
@@ -660,4 +792,16 @@ int orbm_essential_graph(const orbm_eg_graph *gp, const orbm_eg_options *op, orb
     }
     g_last_eg_waits = sc.waits;
     return ORBX_OK;
+}
+
+} // namespace
+
+int orbm_essential_graph(const orbm_eg_graph *g, const orbm_eg_options *opt, orbm_eg_result *out, orbm_eg_stats *stats)
+{
+    return eg_run(g, opt, out, stats, false);
+}
+
+int orbm_essential_graph_env(const orbm_eg_graph *g, const orbm_eg_options *opt, orbm_eg_result *out, orbm_eg_stats *stats)
+{
+    return eg_run(g, opt, out, stats, true);
 }

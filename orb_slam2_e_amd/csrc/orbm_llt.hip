@@ -15,6 +15,7 @@
 // workgroups solve against it): no workgroup waits for another, ordering is the stream's, every loop is bounded by n or T.  4 nt - 1
 // launches for nt = ceil(n / T) tiles.  A pivot that is not > 0 clears *ok; every later launch reads it first and does nothing,
 // the substitutions write x = 0 instead.  Plain double multiplies and adds (-ffp-contract=off), no MFMA, no floating-point atomics.
+// The second half of the file is the same solve over the live tiles of a tile envelope (orbm_llt_env_solve_dev, k_env_*).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -50,20 +51,22 @@ __device__ __forceinline__ int flag_read(int *ok) { return __hip_atomic_load(ok,
 __device__ __forceinline__ void flag_write(int *ok, int v) { __hip_atomic_store(ok, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __device__ __forceinline__ int tile_rows(const Llt &P, int R) { const int r = P.n - R * T; return r < T ? r : T; }
+__device__ __forceinline__ double *diag_tile(const Llt &P, int c0) { return P.S + (size_t)c0 * P.n + c0; }
 
-// D[x][y] (x >= y) = entry (c0 + x, c0 + y) of the lower triangle, all threads; the upper part of D is left alone
-__device__ __forceinline__ void load_diag_lower(const Llt &P, int c0, int tw, double *D)
+// D[x][y] (x >= y) = entry (x, y) of the diagonal tile at `tile` (column-major, ld doubles from a column to the next: n in the dense
+// matrix, T in a packed tile), all threads; the upper part of D is left alone
+__device__ __forceinline__ void load_diag_lower(const double *tile, size_t ld, int tw, double *D)
 {
     for (int idx = threadIdx.x; idx < T * T; idx += NT) {
         const int x = idx % T, y = idx / T;
-        if (x >= y && x < tw) D[x * LD + y] = P.S[(size_t)(c0 + y) * P.n + c0 + x];
+        if (x >= y && x < tw) D[x * LD + y] = tile[y * ld + x];
     }
 }
 
-// The diagonal tile at c0, tw wide, in D: the lower part holds a, and with has_dots D[j][r] (r > j) the running dot of entry (r, j)
-// and dd[r] the diagonal's.  Thread t owns row t.  Leaves L in the lower part of D and writes it to S; 0 (in every thread) at a
-// pivot that is not > 0, with nothing written.
-__device__ int factor_diag(const Llt &P, int c0, int tw, double *D, const double *dd, bool has_dots, int *s_fail, double *s_piv)
+// The diagonal tile, tw wide, in D: the lower part holds a, and with has_dots D[j][r] (r > j) the running dot of entry (r, j)
+// and dd[r] the diagonal's.  Thread t owns row t.  Leaves L in the lower part of D and writes it to the tile (as load_diag_lower
+// reads it); 0 (in every thread) at a pivot that is not > 0, with nothing written.
+__device__ int factor_diag(double *tile, size_t ld, int tw, double *D, const double *dd, bool has_dots, int *s_fail, double *s_piv)
 {
     const int t = threadIdx.x;
     if (t == 0) *s_fail = 0;
@@ -95,7 +98,7 @@ __device__ int factor_diag(const Llt &P, int c0, int tw, double *D, const double
     }
     for (int idx = t; idx < T * T; idx += NT) {
         const int x = idx % T, y = idx / T;
-        if (x >= y && x < tw) P.S[(size_t)(c0 + y) * P.n + c0 + x] = D[x * LD + y];
+        if (x >= y && x < tw) tile[y * ld + x] = D[x * LD + y];
     }
     return 1;
 }
@@ -106,9 +109,9 @@ __global__ __launch_bounds__(NT) void k_llt_diag0(Llt P)
     __shared__ double s_piv;
     __shared__ int s_fail;
     const int tw = tile_rows(P, 0);
-    load_diag_lower(P, 0, tw, D);
+    load_diag_lower(P.S, P.n, tw, D);
     __syncthreads();
-    const int ok = factor_diag(P, 0, tw, D, nullptr, false, &s_fail, &s_piv);
+    const int ok = factor_diag(P.S, P.n, tw, D, nullptr, false, &s_fail, &s_piv);
     if (threadIdx.x == 0) flag_write(P.ok, ok);                 // written on either path: the word is stale
 }
 
@@ -216,9 +219,9 @@ __global__ __launch_bounds__(NT) void k_llt_update(Llt P, int K)
             if (i > j) D[j * LD + i] = acc[a][b];
             else if (i == j) dd[i] = acc[a][b];
         }
-    load_diag_lower(P, r0, tw, D);
+    load_diag_lower(diag_tile(P, r0), P.n, tw, D);
     __syncthreads();
-    if (!factor_diag(P, r0, tw, D, dd, true, &s_fail, &s_piv) && t == 0) flag_write(P.ok, 0);
+    if (!factor_diag(diag_tile(P, r0), P.n, tw, D, dd, true, &s_fail, &s_piv) && t == 0) flag_write(P.ok, 0);
 }
 
 // L y = b.  K = -1: tile 0 alone (y = b through its diagonal tile).  K >= 0: row tile R = K + 1 + blockIdx.x subtracts L[i][j] y_j
@@ -251,7 +254,7 @@ __global__ __launch_bounds__(NT) void k_llt_fwd(Llt P, int K)
         }
         __syncthreads();
     }
-    load_diag_lower(P, r0, rows, Ls);
+    load_diag_lower(diag_tile(P, r0), P.n, rows, Ls);
     __syncthreads();
     for (int j = 0; j < rows; ++j) {
         if (t == j) { y = y / Ls[j * LD + j]; sh[j & 1] = y; }
@@ -290,7 +293,7 @@ __global__ __launch_bounds__(NT) void k_llt_bwd(Llt P, int K)
         }
         __syncthreads();
     }
-    load_diag_lower(P, r0, rows, Ls);
+    load_diag_lower(diag_tile(P, r0), P.n, rows, Ls);
     __syncthreads();
     for (int j = rows - 1; j >= 0; --j) {
         if (t == j) { y = y / Ls[j * LD + j]; sh[j & 1] = y; }
@@ -300,9 +303,349 @@ __global__ __launch_bounds__(NT) void k_llt_bwd(Llt P, int K)
     if (t < rows) P.x[r0 + t] = y;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- tile envelope
+// The same factorisation over the LIVE tiles of a tile envelope (orbm_llt_env_solve_dev): row tile R holds the tiles
+// (R, first[R]) .. (R, R), packed one after the other, and every kernel above has a copy below that addresses packed tiles and takes
+// its tiles from the plan's lists.  The arithmetic of an entry is the dense solver's restricted to live tiles: the running dot of
+// tile (R, C) is ASSIGNED by its first live panel max(first[R], first[C]), as panel 0 assigns it above; a tile no panel reaches has
+// no dot.  Running dots live in W at the tile's own index, ROW-major (the update's lanes run along j), the diagonal's on the diagonal.
+constexpr int ENV_MAXN = 28672;
+constexpr int ENV_MAXTILES = 8192;
+
+struct Env {
+    int n, nt;
+    double *A, *W;
+    const double *b;
+    double *x;
+    int *ok;
+    const int *first, *off, *row_start, *rows;                  // the device image of the plan (include/orbslam_hip.h)
+};
+
+__device__ __forceinline__ int env_rows(const Env &P, int R) { const int r = P.n - R * T; return r < T ? r : T; }
+__device__ __forceinline__ size_t env_tile(const Env &P, int R, int C) { return (size_t)(P.off[R] + C - P.first[R]) * (T * T); }
+__device__ __forceinline__ int env_first_panel(const Env &P, int R, int C) { const int a = P.first[R], b = P.first[C]; return a > b ? a : b; }
+
+// Diagonal tile Kd from a alone: tile 0 (which writes the flag on either path: the word is stale), or a tile whose row starts at
+// itself (first[Kd] = Kd), which only ever clears it.
+__device__ void env_diag_alone(const Env &P, int Kd, double *D, int *s_fail, double *s_piv)
+{
+    double *tile = P.A + env_tile(P, Kd, Kd);
+    const int tw = env_rows(P, Kd);
+    load_diag_lower(tile, T, tw, D);
+    __syncthreads();
+    const int ok = factor_diag(tile, T, tw, D, nullptr, false, s_fail, s_piv);
+    if (threadIdx.x == 0 && (Kd == 0 || !ok)) flag_write(P.ok, ok);
+}
+
+__global__ __launch_bounds__(NT) void k_env_diag0(Env P)
+{
+    __shared__ double D[T * LD];
+    __shared__ double s_piv;
+    __shared__ int s_fail;
+    env_diag_alone(P, 0, D, &s_fail, &s_piv);
+}
+
+// Panel K: row tile R = the blockIdx.x-th of the panel's list (first[R] <= K < R) against the final diagonal tile, as k_llt_rows.
+__global__ __launch_bounds__(NT) void k_env_rows(Env P, int K)
+{
+    __shared__ double Dp[T * (T + 1) / 2];
+    __shared__ double O[T * LD];
+    if (!flag_read(P.ok)) return;
+    const int R = P.rows[P.row_start[K] + blockIdx.x], rows = env_rows(P, R), t = threadIdx.x;
+    const bool dots = K > env_first_panel(P, R, K);
+    const double *Dt = P.A + env_tile(P, K, K), *Wt = P.W + env_tile(P, R, K);
+    double *At = P.A + env_tile(P, R, K);
+    for (int idx = t; idx < T * T; idx += NT) {
+        const int x = idx % T, y = idx / T;
+        if (x >= y) Dp[x * (x + 1) / 2 + y] = Dt[y * T + x];
+        const int j = idx % T, i = idx / T;
+        if (dots && i < rows) O[i * LD + j] = Wt[i * T + j];
+    }
+    __syncthreads();
+    if (t >= rows) return;
+    double *o = O + t * LD;
+    double a_next = At[t];
+    for (int j = 0; j < T; ++j) {
+        const double a = a_next;
+        if (j + 1 < T) a_next = At[(j + 1) * T + t];
+        const double *dj = Dp + j * (j + 1) / 2;
+        double s = a;
+        if (dots) {
+            double dot = o[j];
+            LLT_UNROLL_K
+            for (int k = 0; k < j; ++k) dot = dot + o[k] * dj[k];
+            s = a - dot;
+        } else if (j > 0) {
+            double dot = o[0] * dj[0];
+            LLT_UNROLL_K
+            for (int k = 1; k < j; ++k) dot = dot + o[k] * dj[k];
+            s = a - dot;
+        }
+        const double l = s / dj[j];
+        o[j] = l;
+        At[j * T + t] = l;
+    }
+}
+
+// Panel K: the trailing tiles are the pairs (R, C), C <= R, of the panel's row list (m entries): grid (max(m, 1), m + alone), as
+// k_llt_update.  The next diagonal tile (K + 1, K + 1) is the list's first pair when the panel reaches it; when it does not
+// (first[K + 1] = K + 1) the grid has one more row, whose first workgroup factorises that tile from a alone.
+__global__ __launch_bounds__(NT) void k_env_update(Env P, int K)
+{
+    __shared__ double sm[T * LD + T];
+    __shared__ double s_piv;
+    __shared__ int s_fail;
+    const int *rl = P.rows + P.row_start[K];
+    const int m = P.row_start[K + 1] - P.row_start[K];
+    if ((int)blockIdx.y == m) {
+        if (blockIdx.x == 0 && flag_read(P.ok)) env_diag_alone(P, K + 1, sm, &s_fail, &s_piv);
+        return;
+    }
+    if ((int)blockIdx.x >= m) return;
+    const int R = rl[blockIdx.y], C = rl[blockIdx.x];
+    if (C > R) return;
+    if (!flag_read(P.ok)) return;
+    const int r0 = R * T, c0 = C * T, rr = env_rows(P, R), rc = env_rows(P, C), t = threadIdx.x;
+    const int lj = 4 * (t % (T / 4)), li = 4 * (t / (T / 4));
+    const bool next_diag = R == K + 1 && C == K + 1, assign = K == env_first_panel(P, R, C);
+    const double *Ar = P.A + env_tile(P, R, K), *Ac = P.A + env_tile(P, C, K);
+    double *Wt = P.W + env_tile(P, R, C);
+    double *As = sm, *Bs = sm + KH * T;
+    double acc[4][4];
+    if (!assign)
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                const int i = li + a, j = lj + b;
+                acc[a][b] = i < rr && r0 + i >= c0 + j ? Wt[i * T + j] : 0.0;
+            }
+    for (int h = 0; h < T / KH; ++h) {
+        __syncthreads();
+        for (int idx = t; idx < KH * T; idx += NT) {
+            const int i = idx % T, k = idx / T;
+            const int col = (h * KH + k) * T;
+            As[k * T + i] = i < rr ? Ar[col + i] : 0.0;
+            Bs[k * T + i] = i < rc ? Ac[col + i] : 0.0;
+        }
+        __syncthreads();
+        int k = 0;
+        if (assign && h == 0) {                                 // the dot STARTS as the product for the panel's first column
+            for (int a = 0; a < 4; ++a)
+                for (int b = 0; b < 4; ++b) acc[a][b] = As[li + a] * Bs[lj + b];
+            k = 1;
+        }
+        for (; k < KH; ++k) {
+            double av[4], bv[4];
+            for (int a = 0; a < 4; ++a) { av[a] = As[k * T + li + a]; bv[a] = Bs[k * T + lj + a]; }
+            for (int a = 0; a < 4; ++a)
+                for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] + av[a] * bv[b];
+        }
+    }
+    if (!next_diag) {
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                const int i = li + a, j = lj + b;
+                if (i < rr && r0 + i >= c0 + j) Wt[i * T + j] = acc[a][b];
+            }
+        return;
+    }
+    __syncthreads();
+    double *D = sm, *dd = sm + T * LD;
+    for (int a = 0; a < 4; ++a)
+        for (int b = 0; b < 4; ++b) {
+            const int i = li + a, j = lj + b;
+            if (i > j) D[j * LD + i] = acc[a][b];
+            else if (i == j) dd[i] = acc[a][b];
+        }
+    double *tile = P.A + env_tile(P, R, R);
+    load_diag_lower(tile, T, rr, D);
+    __syncthreads();
+    if (!factor_diag(tile, T, rr, D, dd, true, &s_fail, &s_piv) && t == 0) flag_write(P.ok, 0);
+}
+
+// L y = b.  K = -1: tile 0 alone.  K >= 0: the panel's row tiles subtract its final y_j; one more workgroup stands for tile K + 1 when
+// the list does not hold it.  Tile K + 1 is complete either way and divides through its own diagonal tile.  A row tile starts from b
+// at its first panel.
+__global__ __launch_bounds__(NT) void k_env_fwd(Env P, int K)
+{
+    __shared__ double Ls[T * LD];
+    __shared__ double yk[T];
+    __shared__ double sh[2];
+    const int m = K < 0 ? 0 : P.row_start[K + 1] - P.row_start[K];
+    const bool panel = (int)blockIdx.x < m;
+    const int R = panel ? P.rows[P.row_start[K] + blockIdx.x] : K + 1;
+    const int r0 = R * T, rows = env_rows(P, R), t = threadIdx.x;
+    if (!flag_read(P.ok)) {
+        if (t < rows) P.x[r0 + t] = 0.0;
+        return;
+    }
+    double y = 0.0;
+    if (t < rows) y = !panel || K == P.first[R] ? P.b[r0 + t] : P.x[r0 + t];
+    if (panel) {
+        const int k0 = K * T;
+        const double *Lt = P.A + env_tile(P, R, K);
+        for (int idx = t; idx < T * T; idx += NT) {
+            const int i = idx % T, j = idx / T;
+            if (i < rows) Ls[j * LD + i] = Lt[j * T + i];
+        }
+        if (t < T) yk[t] = P.x[k0 + t];
+        __syncthreads();
+        if (t < rows)
+            for (int j = 0; j < T; ++j) y -= Ls[j * LD + t] * yk[j];
+        if (R != K + 1) {
+            if (t < rows) P.x[r0 + t] = y;
+            return;
+        }
+        __syncthreads();
+    }
+    load_diag_lower(P.A + env_tile(P, R, R), T, rows, Ls);
+    __syncthreads();
+    for (int j = 0; j < rows; ++j) {
+        if (t == j) { y = y / Ls[j * LD + j]; sh[j & 1] = y; }
+        __syncthreads();
+        if (t > j && t < rows) y -= Ls[t * LD + j] * sh[j & 1];
+    }
+    if (t < rows) P.x[r0 + t] = y;
+}
+
+// L^T x = y.  K = nt: the last tile alone.  K < nt: tile R = first[K] + blockIdx.x < K subtracts L[j][i] x_j through the live tile
+// (K, R); when row K has no such tile (first[K] = K) the one workgroup stands for tile K - 1, which is complete either way.
+__global__ __launch_bounds__(NT) void k_env_bwd(Env P, int K)
+{
+    __shared__ double Ls[T * LD];
+    __shared__ double xk[T];
+    __shared__ double sh[2];
+    const bool panel = K < P.nt && P.first[K] < K;
+    const int R = K == P.nt ? P.nt - 1 : panel ? P.first[K] + (int)blockIdx.x : K - 1;
+    const int r0 = R * T, rows = env_rows(P, R), t = threadIdx.x;
+    if (!flag_read(P.ok)) {
+        if (t < rows) P.x[r0 + t] = 0.0;
+        return;
+    }
+    double y = t < rows ? P.x[r0 + t] : 0.0;
+    if (panel) {
+        const int k0 = K * T, kw = env_rows(P, K);
+        const double *Lt = P.A + env_tile(P, K, R);
+        for (int idx = t; idx < T * T; idx += NT) {
+            const int j = idx % T, i = idx / T;                 // entry (k0 + j, r0 + i) of L: lanes run along its column
+            if (j < kw) Ls[j * LD + i] = Lt[i * T + j];
+        }
+        if (t < kw) xk[t] = P.x[k0 + t];
+        __syncthreads();
+        if (t < rows)
+            for (int j = kw - 1; j >= 0; --j) y -= Ls[j * LD + t] * xk[j];
+        if (R != K - 1) {
+            if (t < rows) P.x[r0 + t] = y;
+            return;
+        }
+        __syncthreads();
+    }
+    load_diag_lower(P.A + env_tile(P, R, R), T, rows, Ls);
+    __syncthreads();
+    for (int j = rows - 1; j >= 0; --j) {
+        if (t == j) { y = y / Ls[j * LD + j]; sh[j & 1] = y; }
+        __syncthreads();
+        if (t < j) y -= Ls[j * LD + t] * sh[j & 1];
+    }
+    if (t < rows) P.x[r0 + t] = y;
+}
+
+// n and first[] as both entries check them; *live = the live tiles
+int env_check(int n, const int32_t *first, int *live)
+{
+    if (n < 1 || n > ENV_MAXN) ORBX_FAIL(ORBX_ERR_ARG, "n outside 1 .. 28,672");
+    if (!first) ORBX_FAIL(ORBX_ERR_ARG, "null pointer");
+    const int nt = (n + T - 1) / T;
+    long long tiles = 0;
+    for (int R = 0; R < nt; ++R) {
+        if (first[R] < 0 || first[R] > R) ORBX_FAIL(ORBX_ERR_ARG, "first[R] outside 0 .. R");
+        tiles += R - first[R] + 1;
+    }
+    if (tiles > ENV_MAXTILES) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 8,192 live tiles");
+    *live = (int)tiles;
+    return ORBX_OK;
+}
+
+// rows_of[K] = row tiles R > K with first[R] <= K (nt entries, the last one 0)
+void env_row_counts(int nt, const int32_t *first, int *rows_of)
+{
+    for (int K = 0; K < nt; ++K) rows_of[K] = 0;
+    for (int R = 1; R < nt; ++R)
+        for (int K = first[R]; K < R; ++K) ++rows_of[K];        // one step per live off-diagonal tile
+}
+
 std::atomic<int> g_last_llt_launches{0};
 
 } // namespace
+
+int orbm_llt_env_plan(int n, const int32_t *first, int32_t *off, int32_t *row_start, int32_t *rows, int32_t *trail_start, int32_t *trail,
+                      int32_t *counts)
+{
+    int live = 0;
+    if (const int e = env_check(n, first, &live)) return e;
+    const int nt = (n + T - 1) / T;
+    int nrows = 0, ntrail = 0, launches = 1 + 2 * nt;           // the first diagonal tile, and a launch per tile in either substitution
+    if (off) off[0] = 0;
+    for (int R = 0; R < nt; ++R)
+        if (off) off[R + 1] = off[R] + R - first[R] + 1;
+    for (int K = 0; K < nt; ++K) {
+        if (row_start) row_start[K] = nrows;
+        if (trail_start) trail_start[K] = ntrail;
+        const int r_begin = nrows;
+        for (int R = K + 1; R < nt; ++R)
+            if (first[R] <= K) {
+                if (rows) rows[nrows] = R;
+                ++nrows;
+                int c = 0;
+                for (int C = K + 1; C <= R; ++C)
+                    if (first[C] <= K) {
+                        if (trail) { trail[2 * (ntrail + c)] = R; trail[2 * (ntrail + c) + 1] = C; }
+                        ++c;
+                    }
+                ntrail += c;
+            }
+        if (K + 1 < nt) launches += nrows > r_begin ? 2 : 1;    // the row tiles if there are any; the trailing tiles and the next diagonal tile
+    }
+    if (row_start) row_start[nt] = nrows;
+    if (trail_start) trail_start[nt] = ntrail;
+    if (counts) { counts[0] = live; counts[1] = nrows; counts[2] = ntrail; counts[3] = launches; }
+    return ORBX_OK;
+}
+
+int orbm_llt_env_solve_dev(int n, const int32_t *first, const int32_t *plan_dev, double *A_dev, double *W_dev, const double *b_dev,
+                           double *x_dev, int32_t *ok_dev, void *stream)
+{
+    int live = 0;
+    if (const int e = env_check(n, first, &live)) return e;
+    if (!plan_dev || !A_dev || !W_dev || !b_dev || !x_dev || !ok_dev) ORBX_FAIL(ORBX_ERR_ARG, "null pointer");
+    ORBX_NEED_DEVICE();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nt = (n + T - 1) / T;
+    int rows_of[(ENV_MAXN + T - 1) / T];
+    env_row_counts(nt, first, rows_of);
+    Env P;
+    P.n = n; P.nt = nt; P.A = A_dev; P.W = W_dev; P.b = b_dev; P.x = x_dev; P.ok = ok_dev;
+    P.first = plan_dev; P.off = plan_dev + nt; P.row_start = P.off + nt + 1; P.rows = P.row_start + nt + 1;
+    int launches = 0;
+    hipLaunchKernelGGL(k_env_diag0, dim3(1), dim3(NT), 0, st, P); ++launches;
+    for (int K = 0; K + 1 < nt; ++K) {
+        const unsigned m = (unsigned)rows_of[K], alone = first[K + 1] == K + 1;
+        if (m) { hipLaunchKernelGGL(k_env_rows, dim3(m), dim3(NT), 0, st, P, K); ++launches; }
+        hipLaunchKernelGGL(k_env_update, dim3(m ? m : 1, m + alone), dim3(NT), 0, st, P, K); ++launches;
+    }
+    hipLaunchKernelGGL(k_env_fwd, dim3(1), dim3(NT), 0, st, P, -1); ++launches;
+    for (int K = 0; K + 1 < nt; ++K) {
+        const unsigned m = (unsigned)rows_of[K] + (first[K + 1] == K + 1);
+        hipLaunchKernelGGL(k_env_fwd, dim3(m), dim3(NT), 0, st, P, K); ++launches;
+    }
+    hipLaunchKernelGGL(k_env_bwd, dim3(1), dim3(NT), 0, st, P, nt); ++launches;
+    for (int K = nt - 1; K >= 1; --K) {
+        const unsigned m = (unsigned)(K - first[K]);
+        hipLaunchKernelGGL(k_env_bwd, dim3(m ? m : 1), dim3(NT), 0, st, P, K); ++launches;
+    }
+    ORBX_HIP(hipGetLastError());
+    g_last_llt_launches = launches;
+    return ORBX_OK;
+}
 
 int orbm_llt_tile(void) { return T; }
 

@@ -1,5 +1,6 @@
 """Optimizer::OptimizeEssentialGraph on the device (include/orbslam_hip.h, orbm_essential_graph): the struct mirrors of
-the C ABI, the flat graph from numpy arrays, the call and its host-only plan."""
+the C ABI, the flat graph from numpy arrays, the call and its host-only plan; and the same two for the essential graph of a long
+session on the tile-envelope solver (orbm_essential_graph_env)."""
 import ctypes as C
 
 import numpy as np
@@ -66,26 +67,43 @@ def c_graph(g):
                    p(g["e_v0"]), p(g["e_v1"]), p(g["e_kind"]), p(g["points"]), p(g["p_ref"]))
 
 
-def plan(g):
-    """orbm_eg_plan: the vertex classes, the rows and the index lists the call would use (host only)."""
-    entry = lib().orbm_eg_plan
+def plan(g, env=False):
+    """orbm_eg_plan: the vertex classes, the rows and the index lists the call would use (host only).  env: orbm_eg_env_plan, which
+    adds first (the tile envelope), row_tiles, live_tiles and launches (of one solve)."""
+    entry = lib().orbm_eg_env_plan if env else lib().orbm_eg_plan
     cg = c_graph(g)
     nv = len(g["poses"])
-    counts = np.zeros(3, np.int32)
-    check(entry(C.byref(cg), None, None, None, None, None, None, None, ptr(counts)))
-    nve, npairs, npe = (int(c) for c in counts)
+    counts = np.zeros(6 if env else 3, np.int32)
+    first = [np.zeros(1, np.int32)] if env else []
+    check(entry(C.byref(cg), None, None, None, None, None, None, None, *([None] if env else []), ptr(counts)))
+    nve, npairs, npe = (int(c) for c in counts[:3])
+    if env:
+        first = [np.zeros(max(int(counts[3]), 1), np.int32)]
     out = {"vertex_class": np.zeros(max(nv, 1), np.int32), "row": np.zeros(max(nv, 1), np.int32), "vert_edge_start": np.zeros(nv + 1, np.int32),
            "vert_edges": np.zeros(max(nve, 1), np.int32), "pair_start": np.zeros(npairs + 1, np.int32),
            "pair_v": np.zeros((max(npairs, 1), 2), np.int32), "pair_edges": np.zeros(max(npe, 1), np.int32)}
     check(entry(C.byref(cg), *(ptr(out[k]) for k in ("vertex_class", "row", "vert_edge_start", "vert_edges", "pair_start", "pair_v", "pair_edges")),
-                ptr(counts)))
+                *(ptr(a) for a in first), ptr(counts)))
+    if env:
+        out.update(first=first[0][:counts[3]], row_tiles=int(counts[3]), live_tiles=int(counts[4]), launches=int(counts[5]))
     out["vertex_class"] = out["vertex_class"][:nv]; out["row"] = out["row"][:nv]
     out["vert_edges"] = out["vert_edges"][:nve]; out["pair_v"] = out["pair_v"][:npairs]; out["pair_edges"] = out["pair_edges"][:npe]
     return out
 
 
-def optimize(g, iterations=ITERATIONS, lambda_init=LAMBDA_INIT, want_stats=False):
-    """orbm_essential_graph.  Returns a dict: poses [nvert][16], points [npoints][3], waits, and with want_stats the fields of
+def plan_env(g):
+    """orbm_eg_env_plan: plan(g) under the envelope entry's limits, plus first, row_tiles, live_tiles and launches."""
+    return plan(g, env=True)
+
+
+def optimize_env(g, iterations=ITERATIONS, lambda_init=LAMBDA_INIT, want_stats=False):
+    """orbm_essential_graph_env: optimize() for up to 4,096 free keyframes, on the tile-envelope solver.  List the keyframes by
+    ascending mnId: the order decides the envelope (plan_env shows what it costs)."""
+    return optimize(g, iterations, lambda_init, want_stats, env=True)
+
+
+def optimize(g, iterations=ITERATIONS, lambda_init=LAMBDA_INIT, want_stats=False, env=False):
+    """orbm_essential_graph (env: orbm_essential_graph_env).  Returns a dict: poses [nvert][16], points [npoints][3], waits, and with want_stats the fields of
     orbm_eg_stats (iterations, trials, results, ntrials, trial_overflow, trial_log, estimates [nvert][8], chi2 [nedges])."""
     L = lib()
     cg = c_graph(g)
@@ -100,7 +118,7 @@ def optimize(g, iterations=ITERATIONS, lambda_init=LAMBDA_INIT, want_stats=False
         st = EgStats()
         st.trial_capacity = TRIAL_CAPACITY
         st.trial_log, st.estimates, st.chi2 = (ptr(a).value for a in (log, est, chi2))
-    check(L.orbm_essential_graph(C.byref(cg), C.byref(opt), C.byref(res), C.byref(st) if st is not None else None))
+    check((L.orbm_essential_graph_env if env else L.orbm_essential_graph)(C.byref(cg), C.byref(opt), C.byref(res), C.byref(st) if st is not None else None))
     out = {"poses": poses[:nv], "points": points[:npts], "waits": L.orbm_debug_last_eg_waits()}
     if want_stats:
         out.update(iterations=st.iterations, trials=st.trials, results=list(st.results[:min(st.nresults, 64)]), ntrials=st.ntrials,
