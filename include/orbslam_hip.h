@@ -40,7 +40,8 @@ const char *orbx_last_error(void);
  * orbm_debug_fill_workspaces, orbm_debug_last_search_waits; orbm_bundle_adjustment, orbm_ba_plan, orbm_debug_last_ba_waits;
  * orbm_global_bundle_adjustment, orbm_global_ba_plan, orbm_llt_tile, orbm_llt_solve_dev, orbm_debug_last_llt_launches;
  * orbm_essential_graph, orbm_eg_plan, orbm_debug_last_eg_waits; orbm_refine_sim3_candidates, orbm_debug_last_refine_sim3_waits;
- * orbm_llt_env_plan, orbm_llt_env_solve_dev, orbm_essential_graph_env, orbm_eg_env_plan. */
+ * orbm_llt_env_plan, orbm_llt_env_solve_dev, orbm_essential_graph_env, orbm_eg_env_plan; orbm_global_bundle_adjustment_env,
+ * orbm_global_ba_env_plan. */
 int orbx_abi_version(void);
 
 /* ------------------------------------------------------------------ extractor
@@ -1135,6 +1136,38 @@ int orbm_global_bundle_adjustment(const orbm_ba_graph *g, const orbm_ba_options 
                                   orbm_ba_stats *stats);
 int orbm_global_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
                         int32_t *block_start, int32_t *block_entries, int32_t *counts);
+/* The same call for the map of a long session, up to 4,096 keyframes: structs, options (either ORBM_BA_OPTIONS_* form),
+ * stop flag, waits (trials + rounds) and every documented deviation as orbm_global_bundle_adjustment.  What differs: the reduced
+ * system is assembled into the live tiles of its TILE ENVELOPE and solved by orbm_llt_env_solve_dev (below), at every size; the
+ * n x n square is never allocated.  Limits (ORBX_ERR_UNSUPPORTED before any device work, nothing written; the call refuses what
+ * orbm_global_ba_env_plan refuses): nfree <= 4,096, nfixed <= 1,024, npoints <= 1,048,576, nedges <= 4,194,304, block_entries <= 2^26 =
+ * 67,108,864, and at most 8,192 live tiles in round 0 (checked behind every ORBX_ERR_ARG of the graph, the options and the result).
+ * Rows are the caller's order of the free keyframes, and that order decides the envelope: block (i1 <= i2) of two keyframes that share a
+ * map point covers rows 6 r2 .. 6 r2 + 5 from column 6 r1 (r = the keyframe's rank among the vertices of the round), and row tile R
+ * (T = orbm_llt_tile() rows) starts at the smallest column tile a block reaching it has.  LIST THEM BY ASCENDING mnId: covisibility is
+ * local in time, so the blocks then form a band, and the points re-observed at a loop widen only the rows of the later keyframes; a
+ * shuffled list gives a wide envelope, more work, and past the tile cap a refusal.  Every entry of the system has the value
+ * orbm_global_bundle_adjustment gives it (the same operations in the same order; an empty block between two vertices is +0.0 in
+ * both), and the solver skips only products with exact zeros: a graph both entries admit gives the same numbers through either.
+ * THE SECOND ROUND (nrounds = 2): keyframes that left the system compact the rows, so round 1 has an envelope of its own.  The
+ * read-back between the rounds brings the rows, the envelope is planned again on the host and its image uploaded: no further wait.
+ * A two-round call reserves min(2 live + nt, the full triangle, 8,192) tiles (live, nt: round 0's live tiles and row tiles), which
+ * holds every second round but for the solver's cap: if round 1's envelope has more than 8,192 live tiles the call returns
+ * ORBX_ERR_UNSUPPORTED behind round 0, with the result arrays untouched (the statistics are reset).  The leased workspace holds two copies of the live tiles (up
+ * to 2 x 256 MiB) and stays leased to the process like every arena.
+ *
+ * orbm_global_ba_env_plan: host only, no device; pose_class, point_class, pose_edge_start, pose_edges as orbm_ba_plan, then the COMPACT
+ * block list -- the non-empty upper blocks alone, sorted by (i1, i2) -- and round 0's envelope.  Any output may be NULL.
+ *   blk_i1[counts[2]], blk_i2[counts[2]]   the listed blocks; the diagonal block of every free, connected keyframe is among them
+ *   blk_start[counts[2] + 1], block_entries[counts[1]][3]   a block's entries (point, edge of i1, edge of i2), points ascending: the
+ *                            concatenation is orbm_global_ba_plan's block_entries with the empty blocks left out
+ *   first[counts[3]]         round 0's envelope: first live column tile of every row tile (orbm_llt_env_plan takes it from there)
+ *   counts[6]                entries of pose_edges, of block_entries, listed blocks, row tiles, live tiles, kernel launches of one solve
+ * so a caller can see what an ordering costs before it calls. */
+int orbm_global_bundle_adjustment_env(const orbm_ba_graph *g, const orbm_ba_options *opt, const volatile uint8_t *stop_flag,
+                                      orbm_ba_result *out, orbm_ba_stats *stats);
+int orbm_global_ba_env_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
+                            int32_t *blk_i1, int32_t *blk_i2, int32_t *blk_start, int32_t *block_entries, int32_t *first, int32_t *counts);
 
 /* ------------------------------------------------------------------ tiled dense Cholesky solve
  * S x = b for a symmetric positive definite S of 1 <= n <= 3,072 rows, over many workgroups, in T x T tiles (T = orbm_llt_tile()).

@@ -1500,6 +1500,9 @@ private:
 // false on a library error (status(): ORBX_ERR_UNSUPPORTED beyond 64 free keyframes, where g2o remains the path).  GlobalMap() is
 // Global() over orbm_global_bundle_adjustment: a whole map of up to 512 keyframes (Optimizer::GlobalBundleAdjustemnt behind a loop
 // closure), the reduced system solved by the tiled multi-workgroup Cholesky; the same bytes as Global() where both accept the graph.
+// GlobalMapEnv() is the same call through orbm_global_bundle_adjustment_env, for the map of a long session of up to 4,096 keyframes:
+// add the keyframes by ascending mnId, since their order decides the tile envelope of the reduced system (ORBX_ERR_UNSUPPORTED beyond
+// its limits, where g2o remains the path); the same numbers as GlobalMap() where both accept the graph.
 class BundleAdjustment {
 public:
     std::vector<float> poses, points;               // [nfree + nfixed][16], [npoints][3]
@@ -1547,13 +1550,18 @@ public:
     bool GlobalMap(int nIterations, bool bRobust, const volatile uint8_t *pbStopFlag = nullptr, orbm_ba_stats *stats = nullptr)
     {
         const orbm_ba_options o = ORBM_BA_OPTIONS_GLOBAL(nIterations, bRobust);
-        return run(o, pbStopFlag, stats, true);
+        return run(o, pbStopFlag, stats, 1);
+    }
+    bool GlobalMapEnv(int nIterations, bool bRobust, const volatile uint8_t *pbStopFlag = nullptr, orbm_ba_stats *stats = nullptr)
+    {
+        const orbm_ba_options o = ORBM_BA_OPTIONS_GLOBAL(nIterations, bRobust);
+        return run(o, pbStopFlag, stats, 2);
     }
     int status() const { return mStatus; }
     int nFreeKeyFrames() const { return nFree; }
 
 private:
-    bool run(const orbm_ba_options &o, const volatile uint8_t *pbStopFlag, orbm_ba_stats *stats, bool wholeMap = false)
+    bool run(const orbm_ba_options &o, const volatile uint8_t *pbStopFlag, orbm_ba_stats *stats, int entry = 0)
     {
         orbm_ba_graph g;
         std::memset(&g, 0, sizeof(g));
@@ -1565,7 +1573,9 @@ private:
         orbm_ba_result r;
         std::memset(&r, 0, sizeof(r));
         r.poses = posesOut.data(); r.points = pointsOut.data(); r.erase = erase.data(); r.not_included = notIncluded.data();
-        mStatus = wholeMap ? orbm_global_bundle_adjustment(&g, &o, pbStopFlag, &r, stats) : orbm_bundle_adjustment(&g, &o, pbStopFlag, &r, stats);
+        mStatus = entry == 2   ? orbm_global_bundle_adjustment_env(&g, &o, pbStopFlag, &r, stats)
+                  : entry == 1 ? orbm_global_bundle_adjustment(&g, &o, pbStopFlag, &r, stats)
+                               : orbm_bundle_adjustment(&g, &o, pbStopFlag, &r, stats);
         if (mStatus != ORBX_OK) return false;
         std::copy(posesOut.begin(), posesOut.begin() + 16 * (size_t)nFree, poses.begin());
         std::copy(pointsOut.begin(), pointsOut.begin() + points.size(), points.begin());

@@ -15,7 +15,7 @@ from .initializer import Initializer, check_rt, find_models, last_init_waits, re
 from .keyframe_database import KeyFrameDatabase  # noqa: F401
 from .pnp import PnPsolver, PnpProblem, pnp_hypotheses  # noqa: F401
 from .bundle import (BaGraph, BaOptions, BaResult, BaStats, bundle_adjustment, global_bundle_adjustment,  # noqa: F401
-                     llt_env_plan, llt_env_solve_device, llt_solve_device, local_bundle_adjustment)
+                     global_bundle_adjustment_env, llt_env_plan, llt_env_solve_device, llt_solve_device, local_bundle_adjustment)
 from .essential_graph import EgGraph, EgOptions, EgResult, EgStats  # noqa: F401
 from .essential_graph import optimize as optimize_essential_graph  # noqa: F401
 from .essential_graph import optimize_env as optimize_essential_graph_env  # noqa: F401

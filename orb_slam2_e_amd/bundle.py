@@ -1,6 +1,7 @@
 """Optimizer::LocalBundleAdjustment / Optimizer::BundleAdjustment on the device (include/orbslam_hip.h, orbm_bundle_adjustment;
 DESIGN.md 24): the struct mirrors of the C ABI, the flat graph from numpy arrays, and the two calls.  The same for a whole map of up
-to 512 keyframes (orbm_global_bundle_adjustment) and the tiled Cholesky solve under it on torch device tensors."""
+to 512 keyframes (orbm_global_bundle_adjustment), of up to 4,096 keyframes on the tile envelope
+(orbm_global_bundle_adjustment_env), and the tiled Cholesky solves under them on torch device tensors."""
 import ctypes as C
 
 import numpy as np
@@ -92,6 +93,29 @@ def _plan(g, entry):
     return out
 
 
+def plan_global_env(g):
+    """orbm_global_ba_env_plan (host only): the vertex classes and pose -> edge lists of plan(), the COMPACT block list -- blk_i1,
+    blk_i2, block_start [listed + 1], block_entries, the non-empty upper blocks sorted by (i1, i2) -- and round 0's tile envelope:
+    first [row tiles], live_tiles, launches (of one solve).  Limits: 4,096 free keyframes, 8,192 live tiles."""
+    cg = c_graph(g)
+    nfree, npose, npts = g["nfree"], len(g["poses"]), len(g["points"])
+    counts = np.zeros(6, np.int32)
+    entry = lib().orbm_global_ba_env_plan
+    check(entry(C.byref(cg), *([None] * 9), ptr(counts)))
+    out = {"pose_class": np.zeros(npose, np.int32), "point_class": np.zeros(npts, np.int32), "pose_edge_start": np.zeros(nfree + 1, np.int32),
+           "pose_edges": np.zeros(max(int(counts[0]), 1), np.int32), "blk_i1": np.zeros(max(int(counts[2]), 1), np.int32),
+           "blk_i2": np.zeros(max(int(counts[2]), 1), np.int32), "block_start": np.zeros(int(counts[2]) + 1, np.int32),
+           "block_entries": np.zeros((max(int(counts[1]), 1), 3), np.int32), "first": np.zeros(max(int(counts[3]), 1), np.int32)}
+    check(entry(C.byref(cg), *(ptr(out[k]) if out[k].size else None for k in
+                               ("pose_class", "point_class", "pose_edge_start", "pose_edges", "blk_i1", "blk_i2", "block_start",
+                                "block_entries", "first")), ptr(counts)))
+    out["pose_edges"] = out["pose_edges"][:counts[0]]
+    out["block_entries"] = out["block_entries"][:counts[1]]
+    out["blk_i1"], out["blk_i2"], out["first"] = out["blk_i1"][:counts[2]], out["blk_i2"][:counts[2]], out["first"][:counts[3]]
+    out.update(live_tiles=int(counts[4]), launches=int(counts[5]))
+    return out
+
+
 def run(g, options, stop_flag=None, want_stats=False):
     """orbm_bundle_adjustment (up to 64 free keyframes).  See _run for the arguments and the result."""
     return _run(g, options, stop_flag, want_stats, lib().orbm_bundle_adjustment)
@@ -101,6 +125,13 @@ def run_global(g, options, stop_flag=None, want_stats=False):
     """orbm_global_bundle_adjustment: the same call for up to 512 free keyframes; its reduced system is always solved by the tiled
     multi-workgroup Cholesky (llt_solve_device), which gives run()'s bytes wherever both accept the graph."""
     return _run(g, options, stop_flag, want_stats, lib().orbm_global_bundle_adjustment)
+
+
+def run_global_env(g, options, stop_flag=None, want_stats=False):
+    """orbm_global_bundle_adjustment_env: the same call for up to 4,096 free keyframes, LISTED BY ASCENDING mnId; its reduced system
+    lives in the live tiles of its tile envelope and is solved by the envelope Cholesky (llt_env_solve_device), which gives
+    run_global()'s numbers wherever both accept the graph."""
+    return _run(g, options, stop_flag, want_stats, lib().orbm_global_bundle_adjustment_env)
 
 
 def _run(g, options, stop_flag, want_stats, entry):
@@ -145,6 +176,12 @@ def global_bundle_adjustment(g, iterations=10, robust=False, stop_flag=None, wan
     """Optimizer::GlobalBundleAdjustemnt on the flattened graph of a whole map, up to 512 keyframes (LoopClosing runs it with 10
     iterations and bRobust = false): bundle_adjustment through orbm_global_bundle_adjustment."""
     return run_global(g, global_options(iterations, robust), stop_flag, want_stats)
+
+
+def global_bundle_adjustment_env(g, iterations=10, robust=False, stop_flag=None, want_stats=False):
+    """Optimizer::GlobalBundleAdjustemnt on the flattened graph of the map of a long session, up to 4,096 keyframes listed by
+    ascending mnId: global_bundle_adjustment through orbm_global_bundle_adjustment_env."""
+    return run_global_env(g, global_options(iterations, robust), stop_flag, want_stats)
 
 
 def llt_tile():

@@ -16,6 +16,9 @@
 //                     workgroup; the matrix lives in the workspace, a row at a time goes through LDS.  orbm_global_bundle_adjustment
 //                     (up to 512 free keyframes, a system up to 3,072 wide) calls orbm_llt_solve_dev (orbm_llt.hip) in its place:
 //                     the same operations in the same order over many workgroups, hence the same bytes
+//   k_ba_schur_env    orbm_global_bundle_adjustment_env (up to 4,096 free keyframes): the same entries, a wave per
+//                     block of the COMPACT list of non-empty blocks, into the live tiles of the system's tile envelope, which a fill
+//                     on the stream has set to +0.0; orbm_llt_env_solve_dev solves there.  The square S does not exist on that path
 //   k_ba_update(_pose) push; xl = Dinv (bl - B^T xp); oplus on points and poses; computeScale's terms
 //   k_ba_reduce       the block partials of chi2 / scale / the largest diagonal entry joined in a fixed tree
 //   k_ba_pop, k_ba_classify, k_ba_activate, k_ba_final   the copies, the level pass, initializeOptimization(0)'s vertex set, write-back
@@ -28,6 +31,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <vector>
 
@@ -50,12 +54,23 @@ static_assert(ST == 6 * BA_MAXFREE, "a thread per row");
 constexpr int BA_MAXFREE_GLOBAL = 512;
 constexpr int64_t BA_MAXBLOCKENT_GLOBAL = (int64_t)1 << 25;
 static_assert(BA_MAXFREE_GLOBAL * (BA_MAXFREE_GLOBAL + 1) / 2 < (1 << 30), "block indices are ints");
+// orbm_global_bundle_adjustment_env: the envelope solve takes 28,672 rows; the block list holds the non-empty blocks only (805 MB at its cap)
+constexpr int BA_MAXFREE_ENV = 4096, BA_MAXPOINTS_ENV = 1 << 20, BA_MAXEDGES_ENV = 1 << 22;
+constexpr int64_t BA_MAXBLOCKENT_ENV = (int64_t)1 << 26;
+constexpr int BA_ENV_MAXTILES = 8192;   // orbm_llt_env_solve_dev's cap on live tiles
+static_assert(6 * BA_MAXFREE_ENV <= 28672, "the system fits orbm_llt_env_solve_dev");
+static_assert(BA_MAXBLOCKENT_ENV < 0x7fffffff, "block_start holds ints (3 k, the index into the entries, is formed as size_t)");
+enum { BA_LOCAL = 0, BA_GLOBAL = 1, BA_ENV = 2 };      // the three public entries of the one body
 
 // the call's arrays on the device
 struct BaDev {
     int nfree, npose, npoints, nedges, nblocks;     // nblocks: blocks of the per-point passes
     const float *poses_in, *points_in, *e_obs, *e_info, *e_K;
     const int *e_cam, *e_start, *pose_class, *pe_start, *pe_list, *blk_start, *blk_ent;
+    const int *blk_i1, *blk_i2;         // [listed blocks]: the env entry's compact list, sorted by (i1, i2)
+    const int *env;                     // the envelope's device plan (first, off, row_start, rows: orbm_llt_env_solve_dev)
+    double *A, *W;                      // the live tiles and the solver's running dots
+    int T, nt;                          // tile edge; row tiles of the round's system
     double *est, *est_bak;              // [npose][7], [nfree][7]: q, t
     double *X, *X_bak;                  // [npoints][3]
     double *e_err;                      // [nedges][3]: _error as the last computeError that had the edge active left it
@@ -154,7 +169,7 @@ __global__ __launch_bounds__(PT) void k_ba_init(BaDev D)
 // initializeOptimization(level 0): a vertex is in the system iff one of its edges is on level 0.  One block.
 __global__ __launch_bounds__(RT) void k_ba_activate(BaDev D)
 {
-    __shared__ int s_act[BA_MAXFREE_GLOBAL];
+    __shared__ int s_act[BA_MAXFREE_ENV];
     __shared__ int s_edges;
     if (threadIdx.x == 0) s_edges = 0;
     __syncthreads();
@@ -322,8 +337,44 @@ __global__ __launch_bounds__(PT) void k_ba_dinv(BaDev D, double lambda, int lamb
     ORBM_UNROLL for (int j = 0; j < 3; ++j) o[9 + j] = inv[3 * j] * blk[9] + inv[3 * j + 1] * blk[10] + inv[3 * j + 2] * blk[11];
 }
 
-// One wave per upper block (i1 <= i2) of the free poses.  Lane 6 r + c owns entry (r, c) of the block: Hpp (+ lambda on the
-// diagonal) minus (B_i1 Dinv) B_i2^T, point after point.  Lanes 36 .. 41 of a diagonal block: bschur = bp - sum B_i (Dinv bl).
+// Entry (r, c) of block b = (i1 <= i2) of the free poses: Hpp (+ lambda on the diagonal) minus (B_i1 Dinv) B_i2^T, point after point
+// over the block's entry list, edges off level 0 skipped.
+__device__ __forceinline__ double ba_schur_entry(const BaDev &D, int b, int i1, int i2, int r, int c, double lam)
+{
+    double v = 0.0;
+    if (i1 == i2) {
+        const int hi = r > c ? r : c, lo = r > c ? c : r;
+        v = D.Hpp[27 * i1 + hi * (hi + 1) / 2 + lo];
+        if (r == c) v += lam;
+    }
+    for (int k = D.blk_start[b]; k < D.blk_start[b + 1]; ++k) {
+        const int pt = D.blk_ent[3 * (size_t)k], e1 = D.blk_ent[3 * (size_t)k + 1], e2 = D.blk_ent[3 * (size_t)k + 2];
+        if (D.e_level[e1] || D.e_level[e2]) continue;
+        const double *h1 = D.Hpl + 18 * (size_t)e1 + 3 * r, *h2 = D.Hpl + 18 * (size_t)e2 + 3 * c, *inv = D.Dinv + 12 * (size_t)pt;
+        const double w0 = h1[0] * inv[0] + h1[1] * inv[3] + h1[2] * inv[6];
+        const double w1 = h1[0] * inv[1] + h1[1] * inv[4] + h1[2] * inv[7];
+        const double w2 = h1[0] * inv[2] + h1[1] * inv[5] + h1[2] * inv[8];
+        v -= w0 * h2[0] + w1 * h2[1] + w2 * h2[2];
+    }
+    return v;
+}
+
+// Row r of bschur of free pose i1, whose diagonal block is b: bp - sum B_i (Dinv bl) over the pose's edges (the diagonal block's
+// entries are the pose's edge list, one for one)
+__device__ __forceinline__ double ba_schur_rhs(const BaDev &D, int b, int i1, int r)
+{
+    double co = 0.0;
+    for (int k = D.pe_start[i1]; k < D.pe_start[i1 + 1]; ++k) {
+        const int e = D.pe_list[k];
+        if (D.e_level[e]) continue;
+        const double *h = D.Hpl + 18 * (size_t)e + 3 * r, *db = D.Dinv + 12 * (size_t)D.blk_ent[3 * ((size_t)D.blk_start[b] + (size_t)(k - D.pe_start[i1]))] + 9;
+        co += h[0] * db[0] + h[1] * db[1] + h[2] * db[2];
+    }
+    return D.Hpp[27 * i1 + 21 + r] - co;
+}
+
+// One wave per upper block (i1 <= i2) of the free poses.  Lane 6 r + c owns entry (r, c) of the block; lanes 36 .. 41 of a diagonal
+// block form bschur.
 // The block's (i1, i2) is found by walking the rows: at most nfree steps (512, for the 131,328 blocks of the largest graph of
 // orbm_global_bundle_adjustment), which is short beside the entry list of any block that has work.
 __global__ __launch_bounds__(PT) void k_ba_schur(BaDev D, double lambda, int lambda_on_device)
@@ -337,34 +388,33 @@ __global__ __launch_bounds__(PT) void k_ba_schur(BaDev D, double lambda, int lam
     const int n = 6 * D.isc[LM_ISC_NACT], l = threadIdx.x;
     if (l < 36) {
         const int r = l / 6, c = l % 6;
-        double v = 0.0;
-        if (i1 == i2) {
-            const int hi = r > c ? r : c, lo = r > c ? c : r;
-            v = D.Hpp[27 * i1 + hi * (hi + 1) / 2 + lo];
-            if (r == c) v += lam;
-        }
-        for (int k = D.blk_start[blockIdx.x]; k < D.blk_start[blockIdx.x + 1]; ++k) {
-            const int pt = D.blk_ent[3 * (size_t)k], e1 = D.blk_ent[3 * (size_t)k + 1], e2 = D.blk_ent[3 * (size_t)k + 2];
-            if (D.e_level[e1] || D.e_level[e2]) continue;
-            const double *h1 = D.Hpl + 18 * (size_t)e1 + 3 * r, *h2 = D.Hpl + 18 * (size_t)e2 + 3 * c, *inv = D.Dinv + 12 * (size_t)pt;
-            const double w0 = h1[0] * inv[0] + h1[1] * inv[3] + h1[2] * inv[6];
-            const double w1 = h1[0] * inv[1] + h1[1] * inv[4] + h1[2] * inv[7];
-            const double w2 = h1[0] * inv[2] + h1[1] * inv[5] + h1[2] * inv[8];
-            v -= w0 * h2[0] + w1 * h2[1] + w2 * h2[2];
-        }
+        const double v = ba_schur_entry(D, (int)blockIdx.x, i1, i2, r, c, lam);
         const int row = 6 * r2 + c, col = 6 * r1 + r;                   // the transposed entry: the lower triangle is what the LLT reads
         if (row >= col) D.S[(size_t)col * n + row] = v;
-    } else if (l < 42 && i1 == i2) {
-        const int r = l - 36;
-        double co = 0.0;
-        for (int k = D.pe_start[i1]; k < D.pe_start[i1 + 1]; ++k) {
-            const int e = D.pe_list[k];
-            if (D.e_level[e]) continue;
-            const double *h = D.Hpl + 18 * (size_t)e + 3 * r, *db = D.Dinv + 12 * (size_t)D.blk_ent[3 * (size_t)(D.blk_start[blockIdx.x] + (k - D.pe_start[i1]))] + 9;
-            co += h[0] * db[0] + h[1] * db[1] + h[2] * db[2];
-        }
-        D.bsch[6 * r1 + r] = D.Hpp[27 * i1 + 21 + r] - co;
-    }
+    } else if (l < 42 && i1 == i2)
+        D.bsch[6 * r1 + l - 36] = ba_schur_rhs(D, (int)blockIdx.x, i1, l - 36);
+}
+
+// The same entries for LISTED block blockIdx.x of the compact list (orbm_global_bundle_adjustment_env): (i1, i2) come from the list,
+// and the transposed entry with row >= col goes into packed tile off[R] + C - first[R] of the envelope, column-major.  T is no
+// multiple of 6, so a block may reach into two row tiles and two column tiles.  The host took first[] from the same list and the
+// same ridx, so C >= first[R] holds for every entry; the test keeps a write inside its own row tile's span whatever happens.
+__global__ __launch_bounds__(PT) void k_ba_schur_env(BaDev D, double lambda, int lambda_on_device)
+{
+    const int b = blockIdx.x, i1 = D.blk_i1[b], i2 = D.blk_i2[b];
+    const int r1 = D.ridx[i1], r2 = D.ridx[i2];
+    if (r1 < 0 || r2 < 0) return;
+    const double lam = lambda_on_device ? D.sc[LM_SC_LAMBDA_INIT] : lambda;
+    const int l = threadIdx.x;
+    if (l < 36) {
+        const int r = l / 6, c = l % 6;
+        const double v = ba_schur_entry(D, b, i1, i2, r, c, lam);
+        const int row = 6 * r2 + c, col = 6 * r1 + r, T = D.T;
+        const int R = row / T, C = col / T;
+        const int *first = D.env, *off = D.env + D.nt;
+        if (row >= col && R < D.nt && C >= first[R]) D.A[((size_t)(off[R] + C - first[R]) * T + (size_t)(col - C * T)) * T + (size_t)(row - R * T)] = v;
+    } else if (l < 42 && i1 == i2)
+        D.bsch[6 * r1 + l - 36] = ba_schur_rhs(D, b, i1, l - 36);
 }
 
 // Dense LLT of the reduced system and the two triangular solves.  Thread i owns row i.  L[i][j] = (a[i][j] - sum_{k < j} L[i][k]
@@ -541,19 +591,24 @@ __global__ __launch_bounds__(PT) void k_ba_final(BaDev D)
 
 struct BaPlan {
     std::vector<int32_t> e_start, pose_class, point_class, pe_start, pe_list, blk_start, blk_ent;
+    std::vector<int32_t> blk_i1, blk_i2;        // BA_ENV: the listed blocks; blk_start then has one entry per listed block, and one more
 };
 
 inline int block_index(int nfree, int i1, int i2) { return i1 * nfree - i1 * (i1 - 1) / 2 + (i2 - i1); }
 
 // limits, indices, grouping; the vertex classes, the pose -> edge lists and the block -> (point, edge, edge) lists
-int ba_plan(const orbm_ba_graph &g, BaPlan &P, bool global)
+int ba_plan(const orbm_ba_graph &g, BaPlan &P, int mode)
 {
+    const bool env = mode == BA_ENV;
     if (g.nfree < 0 || g.nfixed < 0 || g.npoints < 0 || g.nedges < 0) ORBX_FAIL(ORBX_ERR_ARG, "negative size");
-    if (!global && g.nfree > BA_MAXFREE) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 64 free keyframes");
-    if (global && g.nfree > BA_MAXFREE_GLOBAL) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 512 free keyframes");
+    if (mode == BA_LOCAL && g.nfree > BA_MAXFREE) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 64 free keyframes");
+    if (mode == BA_GLOBAL && g.nfree > BA_MAXFREE_GLOBAL) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 512 free keyframes");
+    if (env && g.nfree > BA_MAXFREE_ENV) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 4,096 free keyframes");
     if (g.nfixed > BA_MAXFIXED) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 1,024 fixed keyframes");
-    if (g.npoints > BA_MAXPOINTS) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 65,536 points");
-    if (g.nedges > BA_MAXEDGES) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 524,288 edges");
+    if (!env && g.npoints > BA_MAXPOINTS) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 65,536 points");
+    if (!env && g.nedges > BA_MAXEDGES) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 524,288 edges");
+    if (env && g.npoints > BA_MAXPOINTS_ENV) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 1,048,576 points");
+    if (env && g.nedges > BA_MAXEDGES_ENV) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "more than 4,194,304 edges");
     const int npose = g.nfree + g.nfixed;
     if ((npose && !g.poses) || (g.npoints && !g.points) || (g.nedges && (!g.e_point || !g.e_cam || !g.e_obs || !g.e_inv_sigma2 || !g.e_cam_k)))
         ORBX_FAIL(ORBX_ERR_ARG, "null pointer in the graph");
@@ -584,24 +639,27 @@ int ba_plan(const orbm_ba_graph &g, BaPlan &P, bool global)
         }
     }
     auto is_free = [&](int c) { return c < g.nfree && P.pose_class[c] == 0; };
-    if (global) {                                                       // the block lists' size, before they are counted block by block
+    int64_t nentries = 0;
+    if (mode != BA_LOCAL) {                                             // the block lists' size, before they are counted block by block
         int64_t entries = 0;
         for (int n = 0; n < g.npoints; ++n) {
             int64_t d = 0;
             for (int a = P.e_start[n]; a < P.e_start[n + 1]; ++a) d += is_free(g.e_cam[a]);
             entries += d * (d + 1) / 2;
         }
-        if (entries > BA_MAXBLOCKENT_GLOBAL) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "the block lists exceed 2^25 entries");
+        if (!env && entries > BA_MAXBLOCKENT_GLOBAL) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "the block lists exceed 2^25 entries");
+        if (env && entries > BA_MAXBLOCKENT_ENV) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "the block lists exceed 2^26 entries");
+        nentries = entries;
     }
-    const int nblk = g.nfree * (g.nfree + 1) / 2;
+    const int nblk = env ? 0 : g.nfree * (g.nfree + 1) / 2;                 // (the env entry has no dense block index)
     P.pe_start.assign((size_t)g.nfree + 1, 0);
-    P.blk_start.assign((size_t)nblk + 1, 0);
+    P.blk_start.assign(env ? 0 : (size_t)nblk + 1, 0);
     for (int n = 0; n < g.npoints; ++n)
         for (int a = P.e_start[n]; a < P.e_start[n + 1]; ++a) {
             const int ca = g.e_cam[a];
             if (!is_free(ca)) continue;
             P.pe_start[(size_t)ca + 1]++;
-            for (int b = P.e_start[n]; b < P.e_start[n + 1]; ++b) {
+            for (int b = P.e_start[n]; b < P.e_start[n + 1] && !env; ++b) {
                 const int cb = g.e_cam[b];
                 if (!is_free(cb) || cb < ca) continue;
                 P.blk_start[(size_t)block_index(g.nfree, ca, cb) + 1]++;
@@ -613,21 +671,87 @@ int ba_plan(const orbm_ba_graph &g, BaPlan &P, bool global)
         P.blk_start[(size_t)b + 1] += P.blk_start[b];
     }
     P.pe_list.assign((size_t)P.pe_start[g.nfree], 0);
-    P.blk_ent.assign(3 * (size_t)P.blk_start[nblk], 0);
-    std::vector<int32_t> pe_fill(P.pe_start.begin(), P.pe_start.end() - 1), blk_fill(P.blk_start.begin(), P.blk_start.end() - 1);
+    P.blk_ent.assign(env ? 0 : 3 * (size_t)P.blk_start[nblk], 0);
+    std::vector<int32_t> pe_fill(P.pe_start.begin(), P.pe_start.end() - 1), blk_fill(P.blk_start.begin(), P.blk_start.end() - (env ? 0 : 1));
     for (int n = 0; n < g.npoints; ++n)
         for (int a = P.e_start[n]; a < P.e_start[n + 1]; ++a) {
             const int ca = g.e_cam[a];
             if (!is_free(ca)) continue;
             P.pe_list[(size_t)pe_fill[ca]++] = a;
-            for (int b = P.e_start[n]; b < P.e_start[n + 1]; ++b) {
+            for (int b = P.e_start[n]; b < P.e_start[n + 1] && !env; ++b) {
                 const int cb = g.e_cam[b];
                 if (!is_free(cb) || cb < ca) continue;
                 int32_t *o = &P.blk_ent[3 * (size_t)blk_fill[block_index(g.nfree, ca, cb)]++];
                 o[0] = n; o[1] = a; o[2] = b;
             }
         }
+    if (!env) return ORBX_OK;
+    // The compact list: the non-empty blocks alone, sorted by (i1, i2).  Row i1's entries are found from the pose's edge list (edges
+    // ascending, so points ascending) and sorted by i2 in a stable sort: a block's entries keep the dense lists' order.
+    struct Ent { int32_t i2, n, a, b; };
+    std::vector<Ent> row;
+    P.blk_ent.reserve(3 * (size_t)nentries);
+    for (int i1 = 0; i1 < g.nfree; ++i1) {
+        row.clear();
+        for (int k = P.pe_start[i1]; k < P.pe_start[i1 + 1]; ++k) {
+            const int a = P.pe_list[k], n = g.e_point[a];
+            for (int b = P.e_start[n]; b < P.e_start[n + 1]; ++b)
+                if (is_free(g.e_cam[b]) && g.e_cam[b] >= i1) row.push_back({g.e_cam[b], n, a, b});
+        }
+        std::stable_sort(row.begin(), row.end(), [](const Ent &x, const Ent &y) { return x.i2 < y.i2; });
+        for (size_t k = 0; k < row.size(); ++k) {
+            if (k == 0 || row[k].i2 != row[k - 1].i2) {
+                P.blk_i1.push_back(i1); P.blk_i2.push_back(row[k].i2);
+                P.blk_start.push_back((int32_t)(P.blk_ent.size() / 3));
+            }
+            P.blk_ent.push_back(row[k].n); P.blk_ent.push_back(row[k].a); P.blk_ent.push_back(row[k].b);
+        }
+    }
+    P.blk_start.push_back((int32_t)(P.blk_ent.size() / 3));
     return ORBX_OK;
+}
+
+// The tile envelope of the reduced system of one round, and what orbm_llt_env_solve_dev reads on the device.  ridx[nfree]: a pose's
+// row block in the round's system, or -1.  Listed block (i1 <= i2) covers rows 6 r2 .. 6 r2 + 5 from column 6 r1: first[R] is the
+// smallest column tile over the blocks that reach row tile R, and R where none does.  The block STRUCTURE decides, not the edge
+// levels: a superset, exactly zero where the levels mask.  Refuses as orbm_llt_env_plan does (more than 8,192 live tiles).
+struct BaEnvPlan {
+    int n = 0, nt = 0, live = 0, launches = 0;
+    std::vector<int32_t> first, image;                      // image: first, off, row_start, rows
+};
+
+int ba_env_plan(const BaPlan &P, const int32_t *ridx, int nact, BaEnvPlan &E)
+{
+    const int T = orbm_llt_tile(), n = 6 * nact;
+    E = BaEnvPlan();
+    if (n == 0) return ORBX_OK;
+    const int nt = (n + T - 1) / T;
+    E.n = n; E.nt = nt;
+    E.first.resize((size_t)nt);
+    for (int R = 0; R < nt; ++R) E.first[(size_t)R] = R;
+    for (size_t b = 0; b < P.blk_i1.size(); ++b) {
+        const int r1 = ridx[P.blk_i1[b]], r2 = ridx[P.blk_i2[b]];
+        if (r1 < 0 || r2 < 0) continue;
+        const int32_t c = 6 * r1 / T;
+        for (int R = 6 * r2 / T; R <= (6 * r2 + 5) / T; ++R) E.first[(size_t)R] = std::min(E.first[(size_t)R], c);
+    }
+    int32_t counts[4];
+    if (const int e = orbm_llt_env_plan(n, E.first.data(), nullptr, nullptr, nullptr, nullptr, nullptr, counts)) return e;
+    E.live = counts[0]; E.launches = counts[3];
+    E.image.assign((size_t)nt + 2 * ((size_t)nt + 1) + (size_t)counts[1], 0);
+    memcpy(E.image.data(), E.first.data(), sizeof(int32_t) * (size_t)nt);
+    int32_t *off = E.image.data() + nt, *row_start = off + nt + 1, *rows = row_start + nt + 1;
+    return orbm_llt_env_plan(n, E.first.data(), off, row_start, rows, nullptr, nullptr, counts);
+}
+
+// round 0's system: every free, connected keyframe, in the caller's order (what k_ba_activate finds with every edge on level 0)
+int round0_rows(const orbm_ba_graph &g, const BaPlan &P, std::vector<int32_t> &ridx)
+{
+    int r = 0;
+    ridx.assign((size_t)g.nfree, -1);
+    for (int p = 0; p < g.nfree; ++p)
+        if (P.pose_class[p] == 0) ridx[(size_t)p] = r++;
+    return r;
 }
 
 int check_options(const orbm_ba_options &o)
@@ -665,12 +789,12 @@ void answer_unchanged(const orbm_ba_graph &g, const orbm_ba_options &opt, const 
     reset_stats(st);
 }
 
-int plan_out(const orbm_ba_graph *g, bool global, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
+int plan_out(const orbm_ba_graph *g, int mode, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
              int32_t *block_start, int32_t *block_entries, int32_t *counts)
 {
     if (!g) ORBX_FAIL(ORBX_ERR_ARG, "null graph");
     BaPlan P;
-    const int rc = ba_plan(*g, P, global);
+    const int rc = ba_plan(*g, P, mode);
     if (rc != ORBX_OK) return rc;
     auto copy = [](int32_t *dst, const std::vector<int32_t> &v) { if (dst && !v.empty()) memcpy(dst, v.data(), sizeof(int32_t) * v.size()); };
     copy(pose_class, P.pose_class); copy(point_class, P.point_class); copy(pose_edge_start, P.pe_start); copy(pose_edges, P.pe_list);
@@ -679,23 +803,32 @@ int plan_out(const orbm_ba_graph *g, bool global, int32_t *pose_class, int32_t *
     return ORBX_OK;
 }
 
-// The body of both public entries.  global: the limits of orbm_global_bundle_adjustment and the tiled solve (orbm_llt_solve_dev over
-// the arena's S, bschur, xp and the trial block's ok2 word) in k_ba_solve's place, at every size.  results[128] holds for both: an
-// iteration writes one, and two rounds of at most 64 make 128.
+// The body of the three public entries.  BA_GLOBAL: the limits of orbm_global_bundle_adjustment and the tiled solve (orbm_llt_solve_dev over
+// the arena's S, bschur, xp and the trial block's ok2 word) in k_ba_solve's place, at every size.  BA_ENV: the limits of
+// orbm_global_bundle_adjustment_env, the compact block list, the live tiles A (zeroed, then k_ba_schur_env) with the solver's W in
+// S's place, orbm_llt_env_solve_dev at every size, and between the rounds ridx[] in the read-back, the envelope planned again on the
+// host and its image uploaded.  results[128] holds for all: an iteration writes one, and two rounds of at most 64 make 128.
 int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile uint8_t *stop_flag, orbm_ba_result *outp, orbm_ba_stats *stats,
-           bool global)
+           int mode)
 {
     if (!gp || !op || !outp) ORBX_FAIL(ORBX_ERR_ARG, "bad arguments");
     const orbm_ba_graph &g = *gp;
     const orbm_ba_options &opt = *op;
     orbm_ba_result &out = *outp;
+    const bool env = mode == BA_ENV;
     BaPlan P;
-    int rc = ba_plan(g, P, global);
+    BaEnvPlan E;
+    int rc = ba_plan(g, P, mode);
     if (rc != ORBX_OK) return rc;
     if ((rc = check_options(opt)) != ORBX_OK) return rc;
     if ((g.nfree && !out.poses) || (g.npoints && !out.points) || (opt.classify && g.nedges && !out.erase)) ORBX_FAIL(ORBX_ERR_ARG, "null result array");
     if (stats && stats->trial_capacity < 0) ORBX_FAIL(ORBX_ERR_ARG, "negative trial capacity");
     if (stats && stats->trial_capacity > 0 && !stats->trial_log) ORBX_FAIL(ORBX_ERR_ARG, "trial capacity without a trial log");
+    if (env) {                                                                  // round 0's tile cap, behind every argument check
+        std::vector<int32_t> ridx0;
+        const int nact0 = round0_rows(g, P, ridx0);
+        if ((rc = ba_env_plan(P, ridx0.data(), nact0, E)) != ORBX_OK) return rc;
+    }
     bool stop_seen = false;
     auto terminate = [&]() { if (stop_flag && *stop_flag) stop_seen = true; return stop_seen && stop_flag && *stop_flag; };
     g_last_ba_waits = 0;
@@ -729,15 +862,29 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
     const size_t o_pc = sc.in(P.pose_class.data(), sizeof(int32_t) * npose), o_ps = sc.in(P.pe_start.data(), sizeof(int32_t) * (nf + 1));
     const size_t o_pl = sc.in(P.pe_list.data(), sizeof(int32_t) * P.pe_list.size()), o_bs = sc.in(P.blk_start.data(), sizeof(int32_t) * P.blk_start.size());
     const size_t o_be = sc.in(P.blk_ent.data(), sizeof(int32_t) * P.blk_ent.size());
+    // BA_ENV: the block list's (i1, i2); room for the largest plan image a round of this call can have; the live tiles twice.  A
+    // second round's rows are the first's with some keyframes left out: an old row tile's rows land in at most two new ones and no
+    // entry moves further from the diagonal, so 2 live + nt tiles hold any second round (the solver's own cap aside).
+    const size_t Tt = (size_t)orbm_llt_tile(), nlisted = P.blk_i1.size();
+    const size_t tile_cap = !env ? 0 : opt.nrounds == 1 ? (size_t)E.live : std::min(std::min(2 * (size_t)E.live + (size_t)E.nt, (size_t)E.nt * ((size_t)E.nt + 1) / 2), (size_t)BA_ENV_MAXTILES);
+    const size_t image_cap = sizeof(int32_t) * (3 * (size_t)E.nt + 2 + tile_cap);
+    const size_t o_bi1 = env ? sc.in(P.blk_i1.data(), sizeof(int32_t) * nlisted) : 0, o_bi2 = env ? sc.in(P.blk_i2.data(), sizeof(int32_t) * nlisted) : 0;
+    const size_t o_env = env ? sc.in(nullptr, image_cap) : 0;
+    if (env) sc.in_at(o_env, E.image.data(), sizeof(int32_t) * E.image.size());
     const size_t o_est = sc.scratch(sizeof(double) * 7 * npose), o_estb = sc.scratch(sizeof(double) * 7 * nf);
     const size_t o_X = sc.scratch(sizeof(double) * 3 * np), o_Xb = sc.scratch(sizeof(double) * 3 * np), o_err = sc.scratch(sizeof(double) * 3 * ne);
     const size_t o_Hll = sc.scratch(sizeof(double) * 12 * np), o_Dinv = sc.scratch(sizeof(double) * 12 * np);
     const size_t o_Hpl = sc.scratch(sizeof(double) * 18 * ne), o_cb = sc.scratch(sizeof(double) * 27 * ne), o_Hpp = sc.scratch(sizeof(double) * 27 * nf);
     const size_t o_pm = sc.scratch(sizeof(double) * nf), o_psc = sc.scratch(sizeof(double) * nf);
-    const size_t o_S = sc.scratch(sizeof(double) * nmax * nmax), o_bsch = sc.scratch(sizeof(double) * nmax), o_xp = sc.scratch(sizeof(double) * nmax);
+    const size_t o_S = sc.scratch(env ? 0 : sizeof(double) * nmax * nmax), o_bsch = sc.scratch(sizeof(double) * nmax), o_xp = sc.scratch(sizeof(double) * nmax);
     const size_t o_pchi = sc.scratch(sizeof(double) * nblk), o_pmax = sc.scratch(sizeof(double) * nblk), o_pscale = sc.scratch(sizeof(double) * nblk);
-    const size_t o_lvl = sc.scratch(ne), o_pact = sc.scratch(np), o_ridx = sc.scratch(sizeof(int) * nf);
+    const size_t o_lvl = sc.scratch(ne), o_pact = sc.scratch(np);
+    const size_t o_A = env ? sc.scratch(sizeof(double) * tile_cap * Tt * Tt) : 0, o_W = env ? sc.scratch(sizeof(double) * tile_cap * Tt * Tt) : 0;
+    size_t o_ridx = env ? 0 : sc.scratch(sizeof(int) * nf);
     const size_t o_sc = sc.out(LM_BLOCK_BYTES);                                 // what a trial reads back
+    if (env) o_ridx = sc.out(sizeof(int) * nf);                                 // BA_ENV: behind it, so that a round's read-back brings the rows too
+    const size_t round_head = env ? o_ridx + sizeof(int) * nf - o_sc : LM_BLOCK_BYTES;
+    if (env && o_env < round_head) ORBX_FAIL(ORBX_ERR_ARG, "internal: the plan image overlaps the round's read-back");   // (the inputs in front of it are longer)
     const size_t o_pout = sc.out(sizeof(float) * 16 * nf), o_xout = sc.out(sizeof(float) * 3 * np), o_erase = sc.out(ne), o_lout = sc.out(ne);
     const size_t o_chi = sc.out(sizeof(double) * ne), o_pd = sc.out(sizeof(double) * 7 * nf), o_xd = sc.out(sizeof(double) * 3 * np);
     if (sc.upload()) ORBX_FAIL(ORBX_ERR_HIP, "workspace allocation / upload failed");
@@ -753,6 +900,10 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
     D.sc = sc.d<double>(o_sc); D.isc = reinterpret_cast<int *>(sc.d<double>(o_sc) + 8);
     D.poses_out = sc.d<float>(o_pout); D.points_out = sc.d<float>(o_xout); D.erase = sc.d<uint8_t>(o_erase); D.level_out = sc.d<uint8_t>(o_lout);
     D.chi2_out = sc.d<double>(o_chi); D.poses_d = sc.d<double>(o_pd); D.points_d = sc.d<double>(o_xd);
+    if (env) {
+        D.blk_i1 = sc.d<int>(o_bi1); D.blk_i2 = sc.d<int>(o_bi2); D.env = sc.d<int>(o_env); D.A = sc.d<double>(o_A); D.W = sc.d<double>(o_W);
+        D.T = (int)Tt; D.nt = E.nt;
+    }
 
     hipStream_t st = sc.stream();
     const size_t nall = std::max(std::max(npose, np), ne);
@@ -782,9 +933,15 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
                 auto trial = [&](double lambda) -> int {
                     const int od = on_dev();
                     hipLaunchKernelGGL(k_ba_dinv, g_pts, b_pt, 0, st, D, lambda, od);
-                    hipLaunchKernelGGL(k_ba_schur, dim3(nblocks_schur), b_pt, 0, st, D, lambda, od);
-                    if (!global) hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(ST), 0, st, D);
-                    else if (const int e = orbm_llt_solve_dev(6 * nact, D.S, D.bsch, D.xp, D.isc + LM_ISC_OK2, st)) return e;   // nact: what k_ba_activate left in isc[LM_ISC_NACT]
+                    if (env) {                                                  // the factorisation has overwritten the live tiles, and the solver reads every entry of one
+                        ORBX_HIP(hipMemsetAsync(D.A, 0, sizeof(double) * (size_t)E.live * Tt * Tt, st));
+                        hipLaunchKernelGGL(k_ba_schur_env, dim3((unsigned)nlisted), b_pt, 0, st, D, lambda, od);
+                        if (const int e = orbm_llt_env_solve_dev(6 * nact, E.first.data(), D.env, D.A, D.W, D.bsch, D.xp, D.isc + LM_ISC_OK2, st)) return e;
+                    } else {
+                        hipLaunchKernelGGL(k_ba_schur, dim3(nblocks_schur), b_pt, 0, st, D, lambda, od);
+                        if (mode == BA_LOCAL) hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(ST), 0, st, D);
+                        else if (const int e = orbm_llt_solve_dev(6 * nact, D.S, D.bsch, D.xp, D.isc + LM_ISC_OK2, st)) return e;   // nact: what k_ba_activate left in isc[LM_ISC_NACT]
+                    }
                     hipLaunchKernelGGL(k_ba_update, g_pts, b_pt, 0, st, D, lambda, od);
                     hipLaunchKernelGGL(k_ba_update_pose, dim3((unsigned)((g.nfree + PT - 1) / PT)), b_pt, 0, st, D, lambda, od);
                     hipLaunchKernelGGL(k_ba_errors, g_pts, b_pt, 0, st, D, robust, dm, ds);
@@ -814,9 +971,17 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
             if (opt.classify) hipLaunchKernelGGL(k_ba_classify, g_pts, b_pt, 0, st, D, opt.chi2_mono, opt.chi2_stereo, 0);
             hipLaunchKernelGGL(k_ba_activate, dim3(1), dim3(RT), 0, st, D);
             ORBX_HIP(hipGetLastError());
-            if (L.read_block()) ORBX_FAIL(ORBX_ERR_HIP, "a round's read-back failed");
+            if (sc.download_head(round_head)) ORBX_FAIL(ORBX_ERR_HIP, "a round's read-back failed");
             nact = L.flag(LM_ISC_NACT);
             nactive_edges = L.flag(LM_ISC_NEDGES);
+            if (env && nact > 0 && nactive_edges > 0) {                         // the next round's rows: its envelope, planned here, and the image the solver reads
+                if ((rc = ba_env_plan(P, sc.r<int32_t>(o_ridx), nact, E)) != ORBX_OK) return rc;
+                if ((size_t)E.live > tile_cap) ORBX_FAIL(ORBX_ERR_UNSUPPORTED, "the second round's envelope has more live tiles than the call reserved");
+                const size_t bytes = (sizeof(int32_t) * E.image.size() + 15) & ~(size_t)15;
+                memcpy(sc.w.pin + o_env, E.image.data(), sizeof(int32_t) * E.image.size());
+                ORBX_HIP(orbx::stage_in(sc.w.dev + o_env, sc.w.pin + o_env, bytes, st));
+                D.nt = E.nt;
+            }
         }
     }
     if (opt.classify) hipLaunchKernelGGL(k_ba_classify, g_pts, b_pt, 0, st, D, opt.chi2_mono, opt.chi2_stereo, 1);
@@ -847,13 +1012,36 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
 int orbm_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
                  int32_t *block_start, int32_t *block_entries, int32_t *counts)
 {
-    return plan_out(g, false, pose_class, point_class, pose_edge_start, pose_edges, block_start, block_entries, counts);
+    return plan_out(g, BA_LOCAL, pose_class, point_class, pose_edge_start, pose_edges, block_start, block_entries, counts);
 }
 
 int orbm_global_ba_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
                         int32_t *block_start, int32_t *block_entries, int32_t *counts)
 {
-    return plan_out(g, true, pose_class, point_class, pose_edge_start, pose_edges, block_start, block_entries, counts);
+    return plan_out(g, BA_GLOBAL, pose_class, point_class, pose_edge_start, pose_edges, block_start, block_entries, counts);
+}
+
+int orbm_global_ba_env_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t *point_class, int32_t *pose_edge_start, int32_t *pose_edges,
+                            int32_t *blk_i1, int32_t *blk_i2, int32_t *blk_start, int32_t *block_entries, int32_t *first, int32_t *counts)
+{
+    if (!g) ORBX_FAIL(ORBX_ERR_ARG, "null graph");
+    BaPlan P;
+    BaEnvPlan E;
+    std::vector<int32_t> ridx0;
+    int rc = ba_plan(*g, P, BA_ENV);
+    if (rc == ORBX_OK) {
+        const int nact0 = round0_rows(*g, P, ridx0);
+        rc = ba_env_plan(P, ridx0.data(), nact0, E);
+    }
+    if (rc != ORBX_OK) return rc;
+    auto copy = [](int32_t *dst, const std::vector<int32_t> &v) { if (dst && !v.empty()) memcpy(dst, v.data(), sizeof(int32_t) * v.size()); };
+    copy(pose_class, P.pose_class); copy(point_class, P.point_class); copy(pose_edge_start, P.pe_start); copy(pose_edges, P.pe_list);
+    copy(blk_i1, P.blk_i1); copy(blk_i2, P.blk_i2); copy(blk_start, P.blk_start); copy(block_entries, P.blk_ent); copy(first, E.first);
+    if (counts) {
+        counts[0] = (int32_t)P.pe_list.size(); counts[1] = (int32_t)(P.blk_ent.size() / 3); counts[2] = (int32_t)P.blk_i1.size();
+        counts[3] = E.nt; counts[4] = E.live; counts[5] = E.launches;
+    }
+    return ORBX_OK;
 }
 
 int orbm_debug_last_ba_waits(void) { return g_last_ba_waits.load(); }
@@ -861,11 +1049,17 @@ int orbm_debug_last_ba_waits(void) { return g_last_ba_waits.load(); }
 int orbm_bundle_adjustment(const orbm_ba_graph *g, const orbm_ba_options *opt, const volatile uint8_t *stop_flag, orbm_ba_result *out,
                            orbm_ba_stats *stats)
 {
-    return ba_run(g, opt, stop_flag, out, stats, false);
+    return ba_run(g, opt, stop_flag, out, stats, BA_LOCAL);
 }
 
 int orbm_global_bundle_adjustment(const orbm_ba_graph *g, const orbm_ba_options *opt, const volatile uint8_t *stop_flag, orbm_ba_result *out,
                                   orbm_ba_stats *stats)
 {
-    return ba_run(g, opt, stop_flag, out, stats, true);
+    return ba_run(g, opt, stop_flag, out, stats, BA_GLOBAL);
+}
+
+int orbm_global_bundle_adjustment_env(const orbm_ba_graph *g, const orbm_ba_options *opt, const volatile uint8_t *stop_flag, orbm_ba_result *out,
+                                      orbm_ba_stats *stats)
+{
+    return ba_run(g, opt, stop_flag, out, stats, BA_ENV);
 }
