@@ -39,6 +39,7 @@
 #include "common.h"
 #include "orbm_g2o_math.h"
 #include "orbm_internal.h"
+#include "orbm_llt_env.h"
 #include "orbm_se3.h"
 
 using namespace orbm_detail;
@@ -68,7 +69,7 @@ struct BaDev {
     const float *poses_in, *points_in, *e_obs, *e_info, *e_K;
     const int *e_cam, *e_start, *pose_class, *pe_start, *pe_list, *blk_start, *blk_ent;
     const int *blk_i1, *blk_i2;         // [listed blocks]: the env entry's compact list, sorted by (i1, i2)
-    const int *env;                     // the envelope's device plan (first, off, row_start, rows: orbm_llt_env_solve_dev)
+    const int *env;                     // the envelope's device plan image (orbm_llt_env.h)
     double *A, *W;                      // the live tiles and the solver's running dots
     int T, nt;                          // tile edge; row tiles of the round's system
     double *est, *est_bak;              // [npose][7], [nfree][7]: q, t
@@ -411,8 +412,8 @@ __global__ __launch_bounds__(PT) void k_ba_schur_env(BaDev D, double lambda, int
         const double v = ba_schur_entry(D, b, i1, i2, r, c, lam);
         const int row = 6 * r2 + c, col = 6 * r1 + r, T = D.T;
         const int R = row / T, C = col / T;
-        const int *first = D.env, *off = D.env + D.nt;
-        if (row >= col && R < D.nt && C >= first[R]) D.A[((size_t)(off[R] + C - first[R]) * T + (size_t)(col - C * T)) * T + (size_t)(row - R * T)] = v;
+        const LltEnvView env(D.env, D.nt);
+        if (row >= col && R < D.nt && C >= env.first[R]) D.A[((size_t)env.tile_index(R, C) * T + (size_t)(col - C * T)) * T + (size_t)(row - R * T)] = v;
     } else if (l < 42 && i1 == i2)
         D.bsch[6 * r1 + l - 36] = ba_schur_rhs(D, b, i1, l - 36);
 }
@@ -715,33 +716,16 @@ int ba_plan(const orbm_ba_graph &g, BaPlan &P, int mode)
 // row block in the round's system, or -1.  Listed block (i1 <= i2) covers rows 6 r2 .. 6 r2 + 5 from column 6 r1: first[R] is the
 // smallest column tile over the blocks that reach row tile R, and R where none does.  The block STRUCTURE decides, not the edge
 // levels: a superset, exactly zero where the levels mask.  Refuses as orbm_llt_env_plan does (more than 8,192 live tiles).
-struct BaEnvPlan {
-    int n = 0, nt = 0, live = 0, launches = 0;
-    std::vector<int32_t> first, image;                      // image: first, off, row_start, rows
-};
-
-int ba_env_plan(const BaPlan &P, const int32_t *ridx, int nact, BaEnvPlan &E)
+int ba_env_plan(const BaPlan &P, const int32_t *ridx, int nact, LltEnvPlan &E)
 {
-    const int T = orbm_llt_tile(), n = 6 * nact;
-    E = BaEnvPlan();
-    if (n == 0) return ORBX_OK;
-    const int nt = (n + T - 1) / T;
-    E.n = n; E.nt = nt;
-    E.first.resize((size_t)nt);
-    for (int R = 0; R < nt; ++R) E.first[(size_t)R] = R;
+    const int T = orbm_llt_tile();
+    llt_env_start(E, 6 * nact);
+    if (nact == 0) return ORBX_OK;                                  // no row tile: first[] is empty and nothing may reach into it
     for (size_t b = 0; b < P.blk_i1.size(); ++b) {
         const int r1 = ridx[P.blk_i1[b]], r2 = ridx[P.blk_i2[b]];
-        if (r1 < 0 || r2 < 0) continue;
-        const int32_t c = 6 * r1 / T;
-        for (int R = 6 * r2 / T; R <= (6 * r2 + 5) / T; ++R) E.first[(size_t)R] = std::min(E.first[(size_t)R], c);
+        if (r1 >= 0 && r2 >= 0) llt_env_reach(E.first, T, 6 * r2, 6 * r2 + 5, 6 * r1);
     }
-    int32_t counts[4];
-    if (const int e = orbm_llt_env_plan(n, E.first.data(), nullptr, nullptr, nullptr, nullptr, nullptr, counts)) return e;
-    E.live = counts[0]; E.launches = counts[3];
-    E.image.assign((size_t)nt + 2 * ((size_t)nt + 1) + (size_t)counts[1], 0);
-    memcpy(E.image.data(), E.first.data(), sizeof(int32_t) * (size_t)nt);
-    int32_t *off = E.image.data() + nt, *row_start = off + nt + 1, *rows = row_start + nt + 1;
-    return orbm_llt_env_plan(n, E.first.data(), off, row_start, rows, nullptr, nullptr, counts);
+    return llt_env_finish(E);
 }
 
 // round 0's system: every free, connected keyframe, in the caller's order (what k_ba_activate finds with every edge on level 0)
@@ -817,7 +801,7 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
     orbm_ba_result &out = *outp;
     const bool env = mode == BA_ENV;
     BaPlan P;
-    BaEnvPlan E;
+    LltEnvPlan E;
     int rc = ba_plan(g, P, mode);
     if (rc != ORBX_OK) return rc;
     if ((rc = check_options(opt)) != ORBX_OK) return rc;
@@ -867,7 +851,7 @@ int ba_run(const orbm_ba_graph *gp, const orbm_ba_options *op, const volatile ui
     // entry moves further from the diagonal, so 2 live + nt tiles hold any second round (the solver's own cap aside).
     const size_t Tt = (size_t)orbm_llt_tile(), nlisted = P.blk_i1.size();
     const size_t tile_cap = !env ? 0 : opt.nrounds == 1 ? (size_t)E.live : std::min(std::min(2 * (size_t)E.live + (size_t)E.nt, (size_t)E.nt * ((size_t)E.nt + 1) / 2), (size_t)BA_ENV_MAXTILES);
-    const size_t image_cap = sizeof(int32_t) * (3 * (size_t)E.nt + 2 + tile_cap);
+    const size_t image_cap = sizeof(int32_t) * LltEnvView::words((size_t)E.nt, tile_cap);
     const size_t o_bi1 = env ? sc.in(P.blk_i1.data(), sizeof(int32_t) * nlisted) : 0, o_bi2 = env ? sc.in(P.blk_i2.data(), sizeof(int32_t) * nlisted) : 0;
     const size_t o_env = env ? sc.in(nullptr, image_cap) : 0;
     if (env) sc.in_at(o_env, E.image.data(), sizeof(int32_t) * E.image.size());
@@ -1026,7 +1010,7 @@ int orbm_global_ba_env_plan(const orbm_ba_graph *g, int32_t *pose_class, int32_t
 {
     if (!g) ORBX_FAIL(ORBX_ERR_ARG, "null graph");
     BaPlan P;
-    BaEnvPlan E;
+    LltEnvPlan E;
     std::vector<int32_t> ridx0;
     int rc = ba_plan(*g, P, BA_ENV);
     if (rc == ORBX_OK) {

@@ -38,6 +38,7 @@
 #include "common.h"
 #include "orbm_g2o_math.h"
 #include "orbm_internal.h"
+#include "orbm_llt_env.h"
 #include "orbm_se3.h"
 #include "orbm_sim3_math.h"
 
@@ -80,7 +81,7 @@ struct EgDev {
     double *b, *x, *sterm;              // [n]
     double *S;                          // [n][n]
     double *A, *W;                      // the envelope entry: the live tiles and the solver's running dots in place of S
-    const int *env;                     // its device plan (first, off, row_start, rows: orbm_llt_env_solve_dev)
+    const int *env;                     // its device plan image (orbm_llt_env.h)
     const int *tile_row;                // [live tiles]: the row tile of a packed tile
     int T, nt;                          // orbm_llt_tile(), ceil(n / T)
     double *part_chi;                   // [nblocks]
@@ -402,8 +403,7 @@ __global__ __launch_bounds__(RT) void k_eg_assemble(EgDev D, double lambda)
 __global__ __launch_bounds__(RT) void k_eg_assemble_env(EgDev D, double lambda)
 {
     const int T = D.T, t = blockIdx.x, R = D.tile_row[t];
-    const int *first = D.env, *off = D.env + D.nt;
-    const int C = t - off[R] + first[R];
+    const int C = LltEnvView(D.env, D.nt).col_of(R, t);
     double *tile = D.A + (size_t)t * T * T;
     for (int idx = threadIdx.x; idx < T * T; idx += RT) {
         const int row = R * T + idx % T, col = C * T + idx / T;
@@ -588,39 +588,23 @@ int eg_plan(const orbm_eg_graph &g, EgPlan &P, const EgLimits &lim)
 }
 
 // The tile envelope of the system in the caller's vertex order, and what orbm_llt_env_solve_dev reads on the device: first[R] = the
-// smallest column tile over the pairs (and the diagonal blocks) of the block rows that reach into row tile R.  Refuses as
-// orbm_llt_env_plan does (more than 8,192 live tiles).
-struct EgEnvPlan {
-    int nt = 0, live = 0, launches = 0;
-    std::vector<int32_t> first, image, tile_row;            // image: first, off, row_start, rows
+// smallest column tile over the pairs (and the diagonal blocks) of the block rows that reach into row tile R.  tile_row[t]: the row
+// tile of live tile t.  Refuses as orbm_llt_env_plan does (more than 8,192 live tiles).
+struct EgEnvPlan : LltEnvPlan {
+    std::vector<int32_t> tile_row;
 };
 
 int eg_env_plan(const EgPlan &P, EgEnvPlan &E)
 {
-    const int T = orbm_llt_tile(), n = 7 * P.nact;
-    E = EgEnvPlan();
-    if (n == 0) return ORBX_OK;
-    const int nt = E.nt = (n + T - 1) / T;
-    E.first.resize((size_t)nt);
-    for (int R = 0; R < nt; ++R) E.first[(size_t)R] = R;
-    auto reach = [&](int rb, int cb) {                              // block (rb, cb), rb >= cb: rows 7 rb .. 7 rb + 6, columns from 7 cb
-        const int32_t c = 7 * cb / T;
-        for (int R = 7 * rb / T; R <= (7 * rb + 6) / T; ++R) E.first[(size_t)R] = std::min(E.first[(size_t)R], c);
-    };
-    for (int r = 0; r < P.nact; ++r) {
-        reach(r, r);
-        for (int k = P.col_start[(size_t)r]; k < P.col_start[(size_t)r + 1]; ++k) reach(P.pair_hi[(size_t)k], r);
+    const int T = orbm_llt_tile();
+    E.tile_row.clear();
+    llt_env_start(E, 7 * P.nact);
+    for (int r = 0; r < P.nact; ++r) {                              // block (rb, r), rb >= r: rows 7 rb .. 7 rb + 6, columns from 7 r
+        llt_env_reach(E.first, T, 7 * r, 7 * r + 6, 7 * r);
+        for (int k = P.col_start[(size_t)r]; k < P.col_start[(size_t)r + 1]; ++k) llt_env_reach(E.first, T, 7 * P.pair_hi[(size_t)k], 7 * P.pair_hi[(size_t)k] + 6, 7 * r);
     }
-    int32_t counts[4];
-    if (const int e = orbm_llt_env_plan(n, E.first.data(), nullptr, nullptr, nullptr, nullptr, nullptr, counts)) return e;
-    E.live = counts[0]; E.launches = counts[3];
-    E.image.assign((size_t)nt + 2 * ((size_t)nt + 1) + (size_t)counts[1], 0);
-    memcpy(E.image.data(), E.first.data(), sizeof(int32_t) * (size_t)nt);
-    int32_t *off = E.image.data() + nt, *row_start = off + nt + 1, *rows = row_start + nt + 1;
-    if (const int e = orbm_llt_env_plan(n, E.first.data(), off, row_start, rows, nullptr, nullptr, counts)) return e;
-    E.tile_row.resize((size_t)E.live);
-    for (int R = 0; R < nt; ++R)
-        for (int t = off[R]; t < off[R + 1]; ++t) E.tile_row[(size_t)t] = R;
+    if (const int e = llt_env_finish(E)) return e;
+    for (int R = 0; R < E.nt; ++R) E.tile_row.insert(E.tile_row.end(), (size_t)(R - E.first[(size_t)R] + 1), R);     // off[R + 1] - off[R] tiles
     return ORBX_OK;
 }
 

@@ -1,21 +1,24 @@
 // orbm_llt.hip -- dense Cholesky solve of a system wider than one workgroup can factorise (include/orbslam_hip.h,
-// orbm_llt_solve_dev).  S = L L^T in place on the lower triangle, L y = b, L^T x = y, in T x T tiles over many
-// workgroups, and every number by the operations of k_ba_solve (orbm_ba.hip) in k_ba_solve's order:
+// orbm_llt_solve_dev), and the same solve over the live tiles of a tile envelope (orbm_llt_env_solve_dev).
+// S = L L^T in place on the lower triangle, L y = b, L^T x = y, in T x T tiles over many workgroups, and every number by the
+// operations of k_ba_solve (orbm_ba.hip) in k_ba_solve's order:
 //   L[i][j] = (a[i][j] - dot) / L[j][j],  dot = L[i][0] L[j][0], then dot = dot + L[i][k] L[j][k] for k = 1 .. j - 1 ascending
 // The order is per ENTRY, so a tiled, right-looking factorisation keeps it: every lower entry (i, j) that is not final yet owns ONE
-// running dot, held at the mirrored place S[i * n + j] of the strict upper triangle (the diagonal's in x, which is free until the
-// substitutions); when panel K's columns are final every trailing entry adds the panel's T products in ascending k.
+// running dot; when panel K's columns are final every trailing entry adds the panel's T products in ascending k.  Row tile R holds
+// the tiles (R, first[R]) .. (R, R); the running dot of tile (R, C) is ASSIGNED by its first live panel max(first[R], first[C]), and a
+// tile no panel reaches has no dot.  The dense solver is the envelope solver with first[R] = 0.
 //   k_llt_diag0    the first diagonal tile, one workgroup
-//   k_llt_rows     panel K: a workgroup per row tile below the diagonal tile solves its rows against the FINAL diagonal tile
+//   k_llt_rows     panel K: a workgroup per row tile of the panel solves its rows against the FINAL diagonal tile
 //   k_llt_update   panel K: a workgroup per trailing tile adds the panel's products to its running dots; the workgroup of the NEXT
 //                  diagonal tile then holds that tile's complete dots and factorises it on the spot
 //   k_llt_fwd / k_llt_bwd   the substitutions, a launch per panel: every row tile subtracts the panel's T final unknowns in order;
 //                  the tile that is complete with that divides through its own diagonal tile
+// ONE body per kernel, a template over where a tile and its running dot live (Dense, Env below); the arithmetic is written once.
 // A diagonal tile is written by ONE workgroup, in a launch in which no other workgroup reads it (the launch BEFORE the one whose
-// workgroups solve against it): no workgroup waits for another, ordering is the stream's, every loop is bounded by n or T.  4 nt - 1
-// launches for nt = ceil(n / T) tiles.  A pivot that is not > 0 clears *ok; every later launch reads it first and does nothing,
-// the substitutions write x = 0 instead.  Plain double multiplies and adds (-ffp-contract=off), no MFMA, no floating-point atomics.
-// The second half of the file is the same solve over the live tiles of a tile envelope (orbm_llt_env_solve_dev, k_env_*).
+// workgroups solve against it): no workgroup waits for another, ordering is the stream's, every loop is bounded by n, T or a count of
+// the plan.  4 nt - 1 launches for nt = ceil(n / T) tiles, fewer where a panel of the envelope has no row tile.  A pivot that is not
+// > 0 clears *ok; every later launch reads it first and does nothing, the substitutions write x = 0 instead.  Plain double multiplies
+// and adds (-ffp-contract=off), no MFMA, no floating-point atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -24,6 +27,7 @@
 
 #include "../../include/orbslam_hip.h"
 #include "common.h"
+#include "orbm_llt_env.h"
 
 namespace {
 
@@ -32,17 +36,60 @@ constexpr int NT = 256;                 // threads per workgroup; thread t < T o
 constexpr int LD = T + 1;               // row stride of a tile in LDS: rows read by lanes fall on distinct banks
 constexpr int KH = 32;                  // the update's strips go through LDS in two halves of the panel
 constexpr int LLT_MAXN = 3072;
+constexpr int ENV_MAXN = 28672;
+constexpr int ENV_MAXTILES = 8192;
 // the k loops of the serial parts: the two LDS reads of a step do not depend on the running sum, so eight steps' reads are issued
 // together and only the adds stay a chain (the order of the adds is the source's: nothing is reassociated)
 #define LLT_UNROLL_K _Pragma("unroll 8")
 static_assert(T % KH == 0 && NT == (T / 4) * (T / 4), "4 x 4 entries per thread");
 
-struct Llt {
+// Where a tile and its running dot live, and which row tiles a panel has.  tile(R, C): entry (0, 0) of tile (R, C), column-major,
+// ld() doubles from a column to the next.  dots(R, C)(i, j): the running dot of the tile's entry (i, j) (the tile's part of the
+// address is taken once per workgroup, not once per entry).  rows_in(K), row(K, idx): panel K's row tiles (R > K with
+// first(R) <= K), ascending.  ALONE: the update's grid may carry one more row (below).
+
+// The n x n column-major square: the dot of entry (gi, gj), gi > gj, at the mirrored place S[gi * n + gj] of the strict upper
+// triangle, the diagonal's in x, which is free until the substitutions.  Every tile is live.
+struct Dense {
+    static constexpr bool ALONE = false;
     int n, nt;
     double *S;
     const double *b;
     double *x;
     int *ok;
+    __device__ size_t ld() const { return (size_t)n; }
+    __device__ double *tile(int R, int C) const { return S + (size_t)C * T * n + (size_t)R * T; }
+    struct Dots {
+        double *s, *xd;                 // the dot of the tile's entry (0, 0); x at the tile's first row on the diagonal, or null
+        size_t n;
+        __device__ double *operator()(int i, int j) const { return xd && i == j ? xd + i : s + (size_t)i * n + j; }
+    };
+    __device__ Dots dots(int R, int C) const { return Dots{S + (size_t)R * T * n + (size_t)C * T, R == C ? x + R * T : nullptr, (size_t)n}; }
+    __device__ int first(int) const { return 0; }
+    __device__ int rows_in(int K) const { return nt - K - 1; }
+    __device__ int row(int K, int idx) const { return K + 1 + idx; }
+};
+
+// Packed tiles of T x T doubles in A at the plan's tile numbers; the dots in W at the tile's own number, ROW-major (the update's
+// lanes run along j), the diagonal's on the diagonal.
+struct Env {
+    static constexpr bool ALONE = true;
+    int n, nt;
+    double *A, *W;
+    const double *b;
+    double *x;
+    int *ok;
+    LltEnvView v;
+    __device__ size_t ld() const { return T; }
+    __device__ double *tile(int R, int C) const { return A + (size_t)v.tile_index(R, C) * (T * T); }
+    struct Dots {
+        double *w;
+        __device__ double *operator()(int i, int j) const { return w + (i * T + j); }
+    };
+    __device__ Dots dots(int R, int C) const { return Dots{W + (size_t)v.tile_index(R, C) * (T * T)}; }
+    __device__ int first(int R) const { return v.first[R]; }
+    __device__ int rows_in(int K) const { return v.row_start[K + 1] - v.row_start[K]; }
+    __device__ int row(int K, int idx) const { return v.rows[v.row_start[K] + idx]; }
 };
 
 // the flag: one workgroup may clear it while others of the same launch read it (either value makes them do what they should: the
@@ -50,11 +97,12 @@ struct Llt {
 __device__ __forceinline__ int flag_read(int *ok) { return __hip_atomic_load(ok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void flag_write(int *ok, int v) { __hip_atomic_store(ok, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ __forceinline__ int tile_rows(const Llt &P, int R) { const int r = P.n - R * T; return r < T ? r : T; }
-__device__ __forceinline__ double *diag_tile(const Llt &P, int c0) { return P.S + (size_t)c0 * P.n + c0; }
+template <class P> __device__ __forceinline__ int tile_rows(const P &p, int R) { const int r = p.n - R * T; return r < T ? r : T; }
+// the panel that assigns the dots of tile (R, C)
+template <class P> __device__ __forceinline__ int first_panel(const P &p, int R, int C) { const int a = p.first(R), b = p.first(C); return a > b ? a : b; }
 
-// D[x][y] (x >= y) = entry (x, y) of the diagonal tile at `tile` (column-major, ld doubles from a column to the next: n in the dense
-// matrix, T in a packed tile), all threads; the upper part of D is left alone
+// D[x][y] (x >= y) = entry (x, y) of the diagonal tile at `tile` (column-major, ld doubles from a column to the next), all threads;
+// the upper part of D is left alone
 __device__ __forceinline__ void load_diag_lower(const double *tile, size_t ld, int tw, double *D)
 {
     for (int idx = threadIdx.x; idx < T * T; idx += NT) {
@@ -103,263 +151,44 @@ __device__ int factor_diag(double *tile, size_t ld, int tw, double *D, const dou
     return 1;
 }
 
-__global__ __launch_bounds__(NT) void k_llt_diag0(Llt P)
+// Diagonal tile Kd from a alone: tile 0 (which writes the flag on either path: the word is stale), or a tile whose row starts at
+// itself (first(Kd) = Kd), which only ever clears it.
+template <class P> __device__ void diag_alone(const P &p, int Kd, double *D, int *s_fail, double *s_piv)
+{
+    double *tile = p.tile(Kd, Kd);
+    const int tw = tile_rows(p, Kd);
+    load_diag_lower(tile, p.ld(), tw, D);
+    __syncthreads();
+    const int ok = factor_diag(tile, p.ld(), tw, D, nullptr, false, s_fail, s_piv);
+    if (threadIdx.x == 0 && (Kd == 0 || !ok)) flag_write(p.ok, ok);
+}
+
+template <class P> __global__ __launch_bounds__(NT) void k_llt_diag0(P p)
 {
     __shared__ double D[T * LD];
     __shared__ double s_piv;
     __shared__ int s_fail;
-    const int tw = tile_rows(P, 0);
-    load_diag_lower(P.S, P.n, tw, D);
-    __syncthreads();
-    const int ok = factor_diag(P.S, P.n, tw, D, nullptr, false, &s_fail, &s_piv);
-    if (threadIdx.x == 0) flag_write(P.ok, ok);                 // written on either path: the word is stale
+    diag_alone(p, 0, D, &s_fail, &s_piv);
 }
 
-// Panel K (not the last): row tile R = K + 1 + blockIdx.x against the final diagonal tile.  Thread i owns row r0 + i: its T
-// entries one after the other, each dot continued over the tile's columns in ascending k.
-__global__ __launch_bounds__(NT) void k_llt_rows(Llt P, int K)
+// Panel K (not the last): row tile R = the blockIdx.x-th of the panel's against the final diagonal tile.  Thread i owns row i of the
+// tile: its T entries one after the other, each dot continued over the tile's columns in ascending k.
+template <class P> __global__ __launch_bounds__(NT) void k_llt_rows(P p, int K)
 {
     __shared__ double Dp[T * (T + 1) / 2];      // L of the diagonal tile, packed rows: read at uniform addresses only
     __shared__ double O[T * LD];                // row i: the running dots, then L as the columns become final
-    if (!flag_read(P.ok)) return;
-    const int n = P.n, R = K + 1 + blockIdx.x, c0 = K * T, r0 = R * T, rows = tile_rows(P, R), t = threadIdx.x;
+    if (!flag_read(p.ok)) return;
+    const int R = p.row(K, blockIdx.x), rows = tile_rows(p, R), t = threadIdx.x;
+    const bool dots = K > first_panel(p, R, K);
+    const size_t ld = p.ld();
+    const double *Dt = p.tile(K, K);
+    double *At = p.tile(R, K);
+    const auto dot = p.dots(R, K);
     for (int idx = t; idx < T * T; idx += NT) {
         const int x = idx % T, y = idx / T;
-        if (x >= y) Dp[x * (x + 1) / 2 + y] = P.S[(size_t)(c0 + y) * n + c0 + x];
+        if (x >= y) Dp[x * (x + 1) / 2 + y] = Dt[y * ld + x];
         const int j = idx % T, i = idx / T;
-        if (K > 0 && i < rows) O[i * LD + j] = P.S[(size_t)(r0 + i) * n + c0 + j];
-    }
-    __syncthreads();
-    if (t >= rows) return;
-    double *o = O + t * LD;
-    double a_next = P.S[(size_t)c0 * n + r0 + t];
-    for (int j = 0; j < T; ++j) {
-        const double a = a_next;
-        if (j + 1 < T) a_next = P.S[(size_t)(c0 + j + 1) * n + r0 + t];
-        const double *dj = Dp + j * (j + 1) / 2;
-        double s = a;
-        if (K > 0) {
-            double dot = o[j];
-            LLT_UNROLL_K
-            for (int k = 0; k < j; ++k) dot = dot + o[k] * dj[k];
-            s = a - dot;
-        } else if (j > 0) {
-            double dot = o[0] * dj[0];
-            LLT_UNROLL_K
-            for (int k = 1; k < j; ++k) dot = dot + o[k] * dj[k];
-            s = a - dot;
-        }
-        const double l = s / dj[j];
-        o[j] = l;
-        P.S[(size_t)(c0 + j) * n + r0 + t] = l;
-    }
-}
-
-// Panel K (not the last): trailing tile (R, C), K < C <= R, adds the panel's T products to its running dots, 4 x 4 entries per
-// thread with k innermost.  Entry (i, j), i > j, keeps its dot at S[i * n + j]; the diagonal's is x[i].  The workgroup of tile
-// (K + 1, K + 1) keeps its dots in LDS instead and factorises the tile.
-__global__ __launch_bounds__(NT) void k_llt_update(Llt P, int K)
-{
-    __shared__ double sm[T * LD + T];
-    __shared__ double s_piv;
-    __shared__ int s_fail;
-    const int R = K + 1 + blockIdx.y, C = K + 1 + blockIdx.x;
-    if (C > R) return;
-    if (!flag_read(P.ok)) return;
-    const int n = P.n, p0 = K * T, r0 = R * T, c0 = C * T, t = threadIdx.x;
-    const int lj = 4 * (t % (T / 4)), li = 4 * (t / (T / 4));      // lanes run along j: a dot row is contiguous in S
-    const bool next_diag = R == K + 1 && C == K + 1;
-    double *As = sm, *Bs = sm + KH * T;
-    double acc[4][4];
-    if (K > 0)
-        for (int a = 0; a < 4; ++a)
-            for (int b = 0; b < 4; ++b) {
-                const int gi = r0 + li + a, gj = c0 + lj + b;
-                acc[a][b] = 0.0;
-                if (gi < n && gi > gj) acc[a][b] = P.S[(size_t)gi * n + gj];
-                else if (gi < n && gi == gj) acc[a][b] = P.x[gi];
-            }
-    for (int h = 0; h < T / KH; ++h) {
-        __syncthreads();
-        for (int idx = t; idx < KH * T; idx += NT) {
-            const int i = idx % T, k = idx / T;
-            const size_t col = (size_t)(p0 + h * KH + k) * n;
-            As[k * T + i] = r0 + i < n ? P.S[col + r0 + i] : 0.0;
-            Bs[k * T + i] = c0 + i < n ? P.S[col + c0 + i] : 0.0;
-        }
-        __syncthreads();
-        int k = 0;
-        if (K == 0 && h == 0) {                                 // the dot STARTS as the product for k = 0
-            for (int a = 0; a < 4; ++a)
-                for (int b = 0; b < 4; ++b) acc[a][b] = As[li + a] * Bs[lj + b];
-            k = 1;
-        }
-        for (; k < KH; ++k) {
-            double av[4], bv[4];
-            for (int a = 0; a < 4; ++a) { av[a] = As[k * T + li + a]; bv[a] = Bs[k * T + lj + a]; }
-            for (int a = 0; a < 4; ++a)
-                for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] + av[a] * bv[b];
-        }
-    }
-    if (!next_diag) {
-        for (int a = 0; a < 4; ++a)
-            for (int b = 0; b < 4; ++b) {
-                const int gi = r0 + li + a, gj = c0 + lj + b;
-                if (gi < n && gi > gj) P.S[(size_t)gi * n + gj] = acc[a][b];
-                else if (gi < n && gi == gj) P.x[gi] = acc[a][b];
-            }
-        return;
-    }
-    __syncthreads();                                            // the strips are done with: the tile takes their place
-    double *D = sm, *dd = sm + T * LD;
-    const int tw = tile_rows(P, R);
-    for (int a = 0; a < 4; ++a)
-        for (int b = 0; b < 4; ++b) {
-            const int i = li + a, j = lj + b;
-            if (i > j) D[j * LD + i] = acc[a][b];
-            else if (i == j) dd[i] = acc[a][b];
-        }
-    load_diag_lower(diag_tile(P, r0), P.n, tw, D);
-    __syncthreads();
-    if (!factor_diag(diag_tile(P, r0), P.n, tw, D, dd, true, &s_fail, &s_piv) && t == 0) flag_write(P.ok, 0);
-}
-
-// L y = b.  K = -1: tile 0 alone (y = b through its diagonal tile).  K >= 0: row tile R = K + 1 + blockIdx.x subtracts L[i][j] y_j
-// for the panel's final y_j in ascending j; tile K + 1 is complete with that and divides through its own diagonal tile.
-__global__ __launch_bounds__(NT) void k_llt_fwd(Llt P, int K)
-{
-    __shared__ double Ls[T * LD];
-    __shared__ double yk[T];
-    __shared__ double sh[2];
-    const int n = P.n, R = K + 1 + blockIdx.x, r0 = R * T, rows = tile_rows(P, R), t = threadIdx.x;
-    if (!flag_read(P.ok)) {
-        if (t < rows) P.x[r0 + t] = 0.0;
-        return;
-    }
-    double y = 0.0;
-    if (t < rows) y = K <= 0 ? P.b[r0 + t] : P.x[r0 + t];
-    if (K >= 0) {
-        const int k0 = K * T;
-        for (int idx = t; idx < T * T; idx += NT) {
-            const int i = idx % T, j = idx / T;
-            if (i < rows) Ls[j * LD + i] = P.S[(size_t)(k0 + j) * n + r0 + i];
-        }
-        if (t < T) yk[t] = P.x[k0 + t];
-        __syncthreads();
-        if (t < rows)
-            for (int j = 0; j < T; ++j) y -= Ls[j * LD + t] * yk[j];
-        if (R != K + 1) {
-            if (t < rows) P.x[r0 + t] = y;
-            return;
-        }
-        __syncthreads();
-    }
-    load_diag_lower(diag_tile(P, r0), P.n, rows, Ls);
-    __syncthreads();
-    for (int j = 0; j < rows; ++j) {
-        if (t == j) { y = y / Ls[j * LD + j]; sh[j & 1] = y; }
-        __syncthreads();
-        if (t > j && t < rows) y -= Ls[t * LD + j] * sh[j & 1];
-    }
-    if (t < rows) P.x[r0 + t] = y;
-}
-
-// L^T x = y.  K = nt: the last tile alone.  K < nt: row tile R = blockIdx.x < K subtracts L[j][i] x_j for the panel's final x_j in
-// descending j; tile K - 1 is complete with that.
-__global__ __launch_bounds__(NT) void k_llt_bwd(Llt P, int K)
-{
-    __shared__ double Ls[T * LD];
-    __shared__ double xk[T];
-    __shared__ double sh[2];
-    const int n = P.n, R = K == P.nt ? P.nt - 1 : (int)blockIdx.x, r0 = R * T, rows = tile_rows(P, R), t = threadIdx.x;
-    if (!flag_read(P.ok)) {
-        if (t < rows) P.x[r0 + t] = 0.0;
-        return;
-    }
-    double y = t < rows ? P.x[r0 + t] : 0.0;
-    if (K < P.nt) {
-        const int k0 = K * T, kw = tile_rows(P, K);
-        for (int idx = t; idx < T * T; idx += NT) {
-            const int j = idx % T, i = idx / T;                 // entry (k0 + j, r0 + i) of L: lanes run along its column
-            if (j < kw) Ls[j * LD + i] = P.S[(size_t)(r0 + i) * n + k0 + j];
-        }
-        if (t < kw) xk[t] = P.x[k0 + t];
-        __syncthreads();
-        if (t < rows)
-            for (int j = kw - 1; j >= 0; --j) y -= Ls[j * LD + t] * xk[j];
-        if (R != K - 1) {
-            if (t < rows) P.x[r0 + t] = y;
-            return;
-        }
-        __syncthreads();
-    }
-    load_diag_lower(diag_tile(P, r0), P.n, rows, Ls);
-    __syncthreads();
-    for (int j = rows - 1; j >= 0; --j) {
-        if (t == j) { y = y / Ls[j * LD + j]; sh[j & 1] = y; }
-        __syncthreads();
-        if (t < j) y -= Ls[j * LD + t] * sh[j & 1];
-    }
-    if (t < rows) P.x[r0 + t] = y;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- tile envelope
-// The same factorisation over the LIVE tiles of a tile envelope (orbm_llt_env_solve_dev): row tile R holds the tiles
-// (R, first[R]) .. (R, R), packed one after the other, and every kernel above has a copy below that addresses packed tiles and takes
-// its tiles from the plan's lists.  The arithmetic of an entry is the dense solver's restricted to live tiles: the running dot of
-// tile (R, C) is ASSIGNED by its first live panel max(first[R], first[C]), as panel 0 assigns it above; a tile no panel reaches has
-// no dot.  Running dots live in W at the tile's own index, ROW-major (the update's lanes run along j), the diagonal's on the diagonal.
-constexpr int ENV_MAXN = 28672;
-constexpr int ENV_MAXTILES = 8192;
-
-struct Env {
-    int n, nt;
-    double *A, *W;
-    const double *b;
-    double *x;
-    int *ok;
-    const int *first, *off, *row_start, *rows;                  // the device image of the plan (include/orbslam_hip.h)
-};
-
-__device__ __forceinline__ int env_rows(const Env &P, int R) { const int r = P.n - R * T; return r < T ? r : T; }
-__device__ __forceinline__ size_t env_tile(const Env &P, int R, int C) { return (size_t)(P.off[R] + C - P.first[R]) * (T * T); }
-__device__ __forceinline__ int env_first_panel(const Env &P, int R, int C) { const int a = P.first[R], b = P.first[C]; return a > b ? a : b; }
-
-// Diagonal tile Kd from a alone: tile 0 (which writes the flag on either path: the word is stale), or a tile whose row starts at
-// itself (first[Kd] = Kd), which only ever clears it.
-__device__ void env_diag_alone(const Env &P, int Kd, double *D, int *s_fail, double *s_piv)
-{
-    double *tile = P.A + env_tile(P, Kd, Kd);
-    const int tw = env_rows(P, Kd);
-    load_diag_lower(tile, T, tw, D);
-    __syncthreads();
-    const int ok = factor_diag(tile, T, tw, D, nullptr, false, s_fail, s_piv);
-    if (threadIdx.x == 0 && (Kd == 0 || !ok)) flag_write(P.ok, ok);
-}
-
-__global__ __launch_bounds__(NT) void k_env_diag0(Env P)
-{
-    __shared__ double D[T * LD];
-    __shared__ double s_piv;
-    __shared__ int s_fail;
-    env_diag_alone(P, 0, D, &s_fail, &s_piv);
-}
-
-// Panel K: row tile R = the blockIdx.x-th of the panel's list (first[R] <= K < R) against the final diagonal tile, as k_llt_rows.
-__global__ __launch_bounds__(NT) void k_env_rows(Env P, int K)
-{
-    __shared__ double Dp[T * (T + 1) / 2];
-    __shared__ double O[T * LD];
-    if (!flag_read(P.ok)) return;
-    const int R = P.rows[P.row_start[K] + blockIdx.x], rows = env_rows(P, R), t = threadIdx.x;
-    const bool dots = K > env_first_panel(P, R, K);
-    const double *Dt = P.A + env_tile(P, K, K), *Wt = P.W + env_tile(P, R, K);
-    double *At = P.A + env_tile(P, R, K);
-    for (int idx = t; idx < T * T; idx += NT) {
-        const int x = idx % T, y = idx / T;
-        if (x >= y) Dp[x * (x + 1) / 2 + y] = Dt[y * T + x];
-        const int j = idx % T, i = idx / T;
-        if (dots && i < rows) O[i * LD + j] = Wt[i * T + j];
+        if (dots && i < rows) O[i * LD + j] = *dot(i, j);
     }
     __syncthreads();
     if (t >= rows) return;
@@ -367,7 +196,7 @@ __global__ __launch_bounds__(NT) void k_env_rows(Env P, int K)
     double a_next = At[t];
     for (int j = 0; j < T; ++j) {
         const double a = a_next;
-        if (j + 1 < T) a_next = At[(j + 1) * T + t];
+        if (j + 1 < T) a_next = At[(j + 1) * ld + t];
         const double *dj = Dp + j * (j + 1) / 2;
         double s = a;
         if (dots) {
@@ -383,46 +212,48 @@ __global__ __launch_bounds__(NT) void k_env_rows(Env P, int K)
         }
         const double l = s / dj[j];
         o[j] = l;
-        At[j * T + t] = l;
+        At[j * ld + t] = l;
     }
 }
 
-// Panel K: the trailing tiles are the pairs (R, C), C <= R, of the panel's row list (m entries): grid (max(m, 1), m + alone), as
-// k_llt_update.  The next diagonal tile (K + 1, K + 1) is the list's first pair when the panel reaches it; when it does not
-// (first[K + 1] = K + 1) the grid has one more row, whose first workgroup factorises that tile from a alone.
-__global__ __launch_bounds__(NT) void k_env_update(Env P, int K)
+// Panel K (not the last): the trailing tiles are the pairs (R, C), C <= R, of the panel's m row tiles: grid (max(m, 1), m + alone),
+// the upper half exits.  A tile adds the panel's T products to its running dots, 4 x 4 entries per thread with k innermost.  The next
+// diagonal tile (K + 1, K + 1) is the list's first pair when the panel reaches it: its workgroup keeps the dots in LDS instead and
+// factorises the tile.  When the panel does not reach it (first(K + 1) = K + 1, ALONE policies only) the grid has one more row, whose
+// first workgroup factorises that tile from a alone.
+template <class P> __global__ __launch_bounds__(NT) void k_llt_update(P p, int K)
 {
     __shared__ double sm[T * LD + T];
     __shared__ double s_piv;
     __shared__ int s_fail;
-    const int *rl = P.rows + P.row_start[K];
-    const int m = P.row_start[K + 1] - P.row_start[K];
-    if ((int)blockIdx.y == m) {
-        if (blockIdx.x == 0 && flag_read(P.ok)) env_diag_alone(P, K + 1, sm, &s_fail, &s_piv);
+    const int m = p.rows_in(K);
+    if (P::ALONE && (int)blockIdx.y == m) {
+        if (blockIdx.x == 0 && flag_read(p.ok)) diag_alone(p, K + 1, sm, &s_fail, &s_piv);
         return;
     }
     if ((int)blockIdx.x >= m) return;
-    const int R = rl[blockIdx.y], C = rl[blockIdx.x];
+    const int R = p.row(K, blockIdx.y), C = p.row(K, blockIdx.x);
     if (C > R) return;
-    if (!flag_read(P.ok)) return;
-    const int r0 = R * T, c0 = C * T, rr = env_rows(P, R), rc = env_rows(P, C), t = threadIdx.x;
-    const int lj = 4 * (t % (T / 4)), li = 4 * (t / (T / 4));
-    const bool next_diag = R == K + 1 && C == K + 1, assign = K == env_first_panel(P, R, C);
-    const double *Ar = P.A + env_tile(P, R, K), *Ac = P.A + env_tile(P, C, K);
-    double *Wt = P.W + env_tile(P, R, C);
+    if (!flag_read(p.ok)) return;
+    const int r0 = R * T, c0 = C * T, rr = tile_rows(p, R), rc = tile_rows(p, C), t = threadIdx.x;
+    const int lj = 4 * (t % (T / 4)), li = 4 * (t / (T / 4));      // lanes run along j: a dot row is contiguous
+    const bool next_diag = R == K + 1 && C == K + 1, assign = K == first_panel(p, R, C);
+    const size_t ld = p.ld();
+    const double *Ar = p.tile(R, K), *Ac = p.tile(C, K);
+    const auto dot = p.dots(R, C);
     double *As = sm, *Bs = sm + KH * T;
     double acc[4][4];
     if (!assign)
         for (int a = 0; a < 4; ++a)
             for (int b = 0; b < 4; ++b) {
                 const int i = li + a, j = lj + b;
-                acc[a][b] = i < rr && r0 + i >= c0 + j ? Wt[i * T + j] : 0.0;
+                acc[a][b] = i < rr && r0 + i >= c0 + j ? *dot(i, j) : 0.0;
             }
     for (int h = 0; h < T / KH; ++h) {
         __syncthreads();
         for (int idx = t; idx < KH * T; idx += NT) {
             const int i = idx % T, k = idx / T;
-            const int col = (h * KH + k) * T;
+            const size_t col = (size_t)(h * KH + k) * ld;
             As[k * T + i] = i < rr ? Ar[col + i] : 0.0;
             Bs[k * T + i] = i < rc ? Ac[col + i] : 0.0;
         }
@@ -444,11 +275,11 @@ __global__ __launch_bounds__(NT) void k_env_update(Env P, int K)
         for (int a = 0; a < 4; ++a)
             for (int b = 0; b < 4; ++b) {
                 const int i = li + a, j = lj + b;
-                if (i < rr && r0 + i >= c0 + j) Wt[i * T + j] = acc[a][b];
+                if (i < rr && r0 + i >= c0 + j) *dot(i, j) = acc[a][b];
             }
         return;
     }
-    __syncthreads();
+    __syncthreads();                                            // the strips are done with: the tile takes their place
     double *D = sm, *dd = sm + T * LD;
     for (int a = 0; a < 4; ++a)
         for (int b = 0; b < 4; ++b) {
@@ -456,97 +287,124 @@ __global__ __launch_bounds__(NT) void k_env_update(Env P, int K)
             if (i > j) D[j * LD + i] = acc[a][b];
             else if (i == j) dd[i] = acc[a][b];
         }
-    double *tile = P.A + env_tile(P, R, R);
-    load_diag_lower(tile, T, rr, D);
+    double *tile = p.tile(R, R);
+    load_diag_lower(tile, ld, rr, D);
     __syncthreads();
-    if (!factor_diag(tile, T, rr, D, dd, true, &s_fail, &s_piv) && t == 0) flag_write(P.ok, 0);
+    if (!factor_diag(tile, ld, rr, D, dd, true, &s_fail, &s_piv) && t == 0) flag_write(p.ok, 0);
 }
 
-// L y = b.  K = -1: tile 0 alone.  K >= 0: the panel's row tiles subtract its final y_j; one more workgroup stands for tile K + 1 when
-// the list does not hold it.  Tile K + 1 is complete either way and divides through its own diagonal tile.  A row tile starts from b
-// at its first panel.
-__global__ __launch_bounds__(NT) void k_env_fwd(Env P, int K)
+// L y = b.  K = -1: tile 0 alone (y = b through its diagonal tile).  K >= 0: the panel's row tiles subtract L[i][j] y_j for its final
+// y_j in ascending j; one more workgroup stands for tile K + 1 when the list does not hold it.  Tile K + 1 is complete either way and
+// divides through its own diagonal tile.  A row tile starts from b at its first panel.
+template <class P> __global__ __launch_bounds__(NT) void k_llt_fwd(P p, int K)
 {
     __shared__ double Ls[T * LD];
     __shared__ double yk[T];
     __shared__ double sh[2];
-    const int m = K < 0 ? 0 : P.row_start[K + 1] - P.row_start[K];
-    const bool panel = (int)blockIdx.x < m;
-    const int R = panel ? P.rows[P.row_start[K] + blockIdx.x] : K + 1;
-    const int r0 = R * T, rows = env_rows(P, R), t = threadIdx.x;
-    if (!flag_read(P.ok)) {
-        if (t < rows) P.x[r0 + t] = 0.0;
+    const bool panel = K >= 0 && (int)blockIdx.x < p.rows_in(K);
+    const int R = panel ? p.row(K, blockIdx.x) : K + 1;
+    const int r0 = R * T, rows = tile_rows(p, R), t = threadIdx.x;
+    const size_t ld = p.ld();
+    if (!flag_read(p.ok)) {
+        if (t < rows) p.x[r0 + t] = 0.0;
         return;
     }
     double y = 0.0;
-    if (t < rows) y = !panel || K == P.first[R] ? P.b[r0 + t] : P.x[r0 + t];
+    if (t < rows) y = !panel || K == p.first(R) ? p.b[r0 + t] : p.x[r0 + t];
     if (panel) {
         const int k0 = K * T;
-        const double *Lt = P.A + env_tile(P, R, K);
+        const double *Lt = p.tile(R, K);
         for (int idx = t; idx < T * T; idx += NT) {
             const int i = idx % T, j = idx / T;
-            if (i < rows) Ls[j * LD + i] = Lt[j * T + i];
+            if (i < rows) Ls[j * LD + i] = Lt[j * ld + i];
         }
-        if (t < T) yk[t] = P.x[k0 + t];
+        if (t < T) yk[t] = p.x[k0 + t];
         __syncthreads();
         if (t < rows)
             for (int j = 0; j < T; ++j) y -= Ls[j * LD + t] * yk[j];
         if (R != K + 1) {
-            if (t < rows) P.x[r0 + t] = y;
+            if (t < rows) p.x[r0 + t] = y;
             return;
         }
         __syncthreads();
     }
-    load_diag_lower(P.A + env_tile(P, R, R), T, rows, Ls);
+    load_diag_lower(p.tile(R, R), ld, rows, Ls);
     __syncthreads();
     for (int j = 0; j < rows; ++j) {
         if (t == j) { y = y / Ls[j * LD + j]; sh[j & 1] = y; }
         __syncthreads();
         if (t > j && t < rows) y -= Ls[t * LD + j] * sh[j & 1];
     }
-    if (t < rows) P.x[r0 + t] = y;
+    if (t < rows) p.x[r0 + t] = y;
 }
 
-// L^T x = y.  K = nt: the last tile alone.  K < nt: tile R = first[K] + blockIdx.x < K subtracts L[j][i] x_j through the live tile
-// (K, R); when row K has no such tile (first[K] = K) the one workgroup stands for tile K - 1, which is complete either way.
-__global__ __launch_bounds__(NT) void k_env_bwd(Env P, int K)
+// L^T x = y.  K = nt: the last tile alone.  K < nt: tile R = first(K) + blockIdx.x < K subtracts L[j][i] x_j for the panel's final x_j
+// in descending j through the live tile (K, R); when row K has no such tile (first(K) = K) the one workgroup stands for tile K - 1,
+// which is complete either way.
+template <class P> __global__ __launch_bounds__(NT) void k_llt_bwd(P p, int K)
 {
     __shared__ double Ls[T * LD];
     __shared__ double xk[T];
     __shared__ double sh[2];
-    const bool panel = K < P.nt && P.first[K] < K;
-    const int R = K == P.nt ? P.nt - 1 : panel ? P.first[K] + (int)blockIdx.x : K - 1;
-    const int r0 = R * T, rows = env_rows(P, R), t = threadIdx.x;
-    if (!flag_read(P.ok)) {
-        if (t < rows) P.x[r0 + t] = 0.0;
+    const bool panel = K < p.nt && p.first(K) < K;
+    const int R = K == p.nt ? p.nt - 1 : panel ? p.first(K) + (int)blockIdx.x : K - 1;
+    const int r0 = R * T, rows = tile_rows(p, R), t = threadIdx.x;
+    const size_t ld = p.ld();
+    if (!flag_read(p.ok)) {
+        if (t < rows) p.x[r0 + t] = 0.0;
         return;
     }
-    double y = t < rows ? P.x[r0 + t] : 0.0;
+    double y = t < rows ? p.x[r0 + t] : 0.0;
     if (panel) {
-        const int k0 = K * T, kw = env_rows(P, K);
-        const double *Lt = P.A + env_tile(P, K, R);
+        const int k0 = K * T, kw = tile_rows(p, K);
+        const double *Lt = p.tile(K, R);
         for (int idx = t; idx < T * T; idx += NT) {
             const int j = idx % T, i = idx / T;                 // entry (k0 + j, r0 + i) of L: lanes run along its column
-            if (j < kw) Ls[j * LD + i] = Lt[i * T + j];
+            if (j < kw) Ls[j * LD + i] = Lt[i * ld + j];
         }
-        if (t < kw) xk[t] = P.x[k0 + t];
+        if (t < kw) xk[t] = p.x[k0 + t];
         __syncthreads();
         if (t < rows)
             for (int j = kw - 1; j >= 0; --j) y -= Ls[j * LD + t] * xk[j];
         if (R != K - 1) {
-            if (t < rows) P.x[r0 + t] = y;
+            if (t < rows) p.x[r0 + t] = y;
             return;
         }
         __syncthreads();
     }
-    load_diag_lower(P.A + env_tile(P, R, R), T, rows, Ls);
+    load_diag_lower(p.tile(R, R), ld, rows, Ls);
     __syncthreads();
     for (int j = rows - 1; j >= 0; --j) {
         if (t == j) { y = y / Ls[j * LD + j]; sh[j & 1] = y; }
         __syncthreads();
         if (t < j) y -= Ls[j * LD + t] * sh[j & 1];
     }
-    if (t < rows) P.x[r0 + t] = y;
+    if (t < rows) p.x[r0 + t] = y;
+}
+
+// The launch chain of either solver.  rows_of(K): the row tiles of panel K; first(R) as in the policy.  Returns the launches.
+template <class P, class RowsOf, class First> int llt_launch(const P &p, hipStream_t st, RowsOf rows_of, First first)
+{
+    const int nt = p.nt;
+    const dim3 wg(NT);
+    int launches = 0;
+    hipLaunchKernelGGL(k_llt_diag0<P>, dim3(1), wg, 0, st, p); ++launches;
+    for (int K = 0; K + 1 < nt; ++K) {
+        const unsigned m = (unsigned)rows_of(K), alone = first(K + 1) == K + 1;
+        if (m) { hipLaunchKernelGGL(k_llt_rows<P>, dim3(m), wg, 0, st, p, K); ++launches; }   // skipped when empty, never an empty grid
+        hipLaunchKernelGGL(k_llt_update<P>, dim3(m ? m : 1, m + alone), wg, 0, st, p, K); ++launches;
+    }
+    hipLaunchKernelGGL(k_llt_fwd<P>, dim3(1), wg, 0, st, p, -1); ++launches;
+    for (int K = 0; K + 1 < nt; ++K) {
+        const unsigned m = (unsigned)rows_of(K) + (first(K + 1) == K + 1);
+        hipLaunchKernelGGL(k_llt_fwd<P>, dim3(m), wg, 0, st, p, K); ++launches;
+    }
+    hipLaunchKernelGGL(k_llt_bwd<P>, dim3(1), wg, 0, st, p, nt); ++launches;
+    for (int K = nt - 1; K >= 1; --K) {
+        const unsigned m = (unsigned)(K - first(K));
+        hipLaunchKernelGGL(k_llt_bwd<P>, dim3(m ? m : 1), wg, 0, st, p, K); ++launches;
+    }
+    return launches;
 }
 
 // n and first[] as both entries check them; *live = the live tiles
@@ -576,6 +434,19 @@ void env_row_counts(int nt, const int32_t *first, int *rows_of)
 std::atomic<int> g_last_llt_launches{0};
 
 } // namespace
+
+int orbm_llt_solve_dev(int n, double *S_dev, const double *b_dev, double *x_dev, int32_t *ok_dev, void *stream)
+{
+    if (n < 1 || n > LLT_MAXN) ORBX_FAIL(ORBX_ERR_ARG, "n outside 1 .. 3,072");
+    if (!S_dev || !b_dev || !x_dev || !ok_dev) ORBX_FAIL(ORBX_ERR_ARG, "null pointer");
+    ORBX_NEED_DEVICE();
+    const int nt = (n + T - 1) / T;
+    const Dense p{n, nt, S_dev, b_dev, x_dev, ok_dev};
+    const int launches = llt_launch(p, static_cast<hipStream_t>(stream), [&](int K) { return nt - K - 1; }, [](int) { return 0; });
+    ORBX_HIP(hipGetLastError());
+    g_last_llt_launches = launches;
+    return ORBX_OK;
+}
 
 int orbm_llt_env_plan(int n, const int32_t *first, int32_t *off, int32_t *row_start, int32_t *rows, int32_t *trail_start, int32_t *trail,
                       int32_t *counts)
@@ -618,30 +489,11 @@ int orbm_llt_env_solve_dev(int n, const int32_t *first, const int32_t *plan_dev,
     if (const int e = env_check(n, first, &live)) return e;
     if (!plan_dev || !A_dev || !W_dev || !b_dev || !x_dev || !ok_dev) ORBX_FAIL(ORBX_ERR_ARG, "null pointer");
     ORBX_NEED_DEVICE();
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const int nt = (n + T - 1) / T;
     int rows_of[(ENV_MAXN + T - 1) / T];
     env_row_counts(nt, first, rows_of);
-    Env P;
-    P.n = n; P.nt = nt; P.A = A_dev; P.W = W_dev; P.b = b_dev; P.x = x_dev; P.ok = ok_dev;
-    P.first = plan_dev; P.off = plan_dev + nt; P.row_start = P.off + nt + 1; P.rows = P.row_start + nt + 1;
-    int launches = 0;
-    hipLaunchKernelGGL(k_env_diag0, dim3(1), dim3(NT), 0, st, P); ++launches;
-    for (int K = 0; K + 1 < nt; ++K) {
-        const unsigned m = (unsigned)rows_of[K], alone = first[K + 1] == K + 1;
-        if (m) { hipLaunchKernelGGL(k_env_rows, dim3(m), dim3(NT), 0, st, P, K); ++launches; }
-        hipLaunchKernelGGL(k_env_update, dim3(m ? m : 1, m + alone), dim3(NT), 0, st, P, K); ++launches;
-    }
-    hipLaunchKernelGGL(k_env_fwd, dim3(1), dim3(NT), 0, st, P, -1); ++launches;
-    for (int K = 0; K + 1 < nt; ++K) {
-        const unsigned m = (unsigned)rows_of[K] + (first[K + 1] == K + 1);
-        hipLaunchKernelGGL(k_env_fwd, dim3(m), dim3(NT), 0, st, P, K); ++launches;
-    }
-    hipLaunchKernelGGL(k_env_bwd, dim3(1), dim3(NT), 0, st, P, nt); ++launches;
-    for (int K = nt - 1; K >= 1; --K) {
-        const unsigned m = (unsigned)(K - first[K]);
-        hipLaunchKernelGGL(k_env_bwd, dim3(m ? m : 1), dim3(NT), 0, st, P, K); ++launches;
-    }
+    const Env p{n, nt, A_dev, W_dev, b_dev, x_dev, ok_dev, LltEnvView(plan_dev, nt)};
+    const int launches = llt_launch(p, static_cast<hipStream_t>(stream), [&](int K) { return rows_of[K]; }, [&](int R) { return first[R]; });
     ORBX_HIP(hipGetLastError());
     g_last_llt_launches = launches;
     return ORBX_OK;
@@ -650,28 +502,3 @@ int orbm_llt_env_solve_dev(int n, const int32_t *first, const int32_t *plan_dev,
 int orbm_llt_tile(void) { return T; }
 
 int orbm_debug_last_llt_launches(void) { return g_last_llt_launches.load(); }
-
-int orbm_llt_solve_dev(int n, double *S_dev, const double *b_dev, double *x_dev, int32_t *ok_dev, void *stream)
-{
-    if (n < 1 || n > LLT_MAXN) ORBX_FAIL(ORBX_ERR_ARG, "n outside 1 .. 3,072");
-    if (!S_dev || !b_dev || !x_dev || !ok_dev) ORBX_FAIL(ORBX_ERR_ARG, "null pointer");
-    ORBX_NEED_DEVICE();
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Llt P;
-    P.n = n; P.nt = (n + T - 1) / T; P.S = S_dev; P.b = b_dev; P.x = x_dev; P.ok = ok_dev;
-    const int nt = P.nt;
-    int launches = 0;
-    hipLaunchKernelGGL(k_llt_diag0, dim3(1), dim3(NT), 0, st, P); ++launches;
-    for (int K = 0; K + 1 < nt; ++K) {
-        const unsigned m = (unsigned)(nt - K - 1);
-        hipLaunchKernelGGL(k_llt_rows, dim3(m), dim3(NT), 0, st, P, K); ++launches;
-        hipLaunchKernelGGL(k_llt_update, dim3(m, m), dim3(NT), 0, st, P, K); ++launches;
-    }
-    hipLaunchKernelGGL(k_llt_fwd, dim3(1), dim3(NT), 0, st, P, -1); ++launches;
-    for (int K = 0; K + 1 < nt; ++K) { hipLaunchKernelGGL(k_llt_fwd, dim3((unsigned)(nt - K - 1)), dim3(NT), 0, st, P, K); ++launches; }
-    hipLaunchKernelGGL(k_llt_bwd, dim3(1), dim3(NT), 0, st, P, nt); ++launches;
-    for (int K = nt - 1; K >= 1; --K) { hipLaunchKernelGGL(k_llt_bwd, dim3((unsigned)K), dim3(NT), 0, st, P, K); ++launches; }
-    ORBX_HIP(hipGetLastError());
-    g_last_llt_launches = launches;
-    return ORBX_OK;
-}

@@ -15,7 +15,7 @@ these sizes.  The launch chain (about 43 us per launch, up to 4 nt - 1 launches 
 line per size.
 
 --profile: kernel times from a `rocprofv3 --kernel-trace --stats` pass of its own per size (a fresh child process runs the device
-part under the profiler): every k_ba_* and k_env_* kernel and the fill with its calls, mean and share; per trial the fill,
+part under the profiler): every k_ba_* and k_llt_* kernel and the fill with its calls, mean and share; per trial the fill,
 k_ba_schur_env and the solve; per round k_ba_activate."""
 import argparse
 import csv
@@ -66,13 +66,13 @@ def profile(names):
             by = {}
             for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
                 for row in csv.DictReader(open(path)):
-                    k = re.search(r"k_ba_\w+|k_env_\w+|k_llt_\w+|k_stage_copy|fill\w*", row.get("Name", ""), re.I)
+                    k = re.search(r"k_ba_\w+|k_llt_\w+|k_stage_copy|fill\w*", row.get("Name", ""), re.I)
                     if k:
                         e = by.setdefault(k.group(0), [0, 0.0]); e[0] += int(row["Calls"]); e[1] += float(row["TotalDurationNs"])
             total = sum(t for _, t in by.values()) or 1.0
             calls = 2 + 2                                                           # the timed calls and the child's warm-up
             trials = run["trials"] * calls
-            solve = sum(t for k, (c, t) in by.items() if k.startswith(("k_env_", "k_llt_")))
+            solve = sum(t for k, (c, t) in by.items() if k.startswith("k_llt_"))
             fill = sum(t for k, (c, t) in by.items() if k.lower().startswith("fill"))
             print(json.dumps({"scene": name, "trials": run["trials"], "kernel_ms_per_call": round(total / 1e6 / calls, 3),
                               "per_trial_us": {"fill": round(fill / 1e3 / max(trials, 1), 2),

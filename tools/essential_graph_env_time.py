@@ -11,7 +11,7 @@
 No CPU figure: the dense restatement is no baseline at these sizes, and g2o's sparse solver does not run here.  One JSON line per size.
 
 --profile: kernel times from a `rocprofv3 --kernel-trace --stats` pass of its own per size (a fresh child process runs the device
-part under the profiler): every k_eg_* and k_env_* kernel with its calls, mean and share, and per trial k_eg_assemble_env and the
+part under the profiler): every k_eg_* and k_llt_* kernel with its calls, mean and share, and per trial k_eg_assemble_env and the
 solve."""
 import argparse
 import csv
@@ -54,12 +54,12 @@ def profile(sizes, large):
             by = {}
             for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
                 for row in csv.DictReader(open(path)):
-                    k = re.search(r"k_eg_\w+|k_env_\w+|k_stage_copy", row.get("Name", ""))
+                    k = re.search(r"k_eg_\w+|k_llt_\w+|k_stage_copy", row.get("Name", ""))
                     if k:
                         e = by.setdefault(k.group(0), [0, 0.0]); e[0] += int(row["Calls"]); e[1] += float(row["TotalDurationNs"])
             total = sum(t for _, t in by.values()) or 1.0
             trials = run["trials"] * (2 + 2)                                        # the timed calls and the child's warm-up
-            solve = sum(t for k, (c, t) in by.items() if k.startswith("k_env_"))
+            solve = sum(t for k, (c, t) in by.items() if k.startswith("k_llt_"))
             print(json.dumps({"nact": nact, "trials": run["trials"],
                               "per_trial_us": {"k_eg_assemble_env": round(by.get("k_eg_assemble_env", [0, 0.0])[1] / 1e3 / max(trials, 1), 2),
                                                "solve": round(solve / 1e3 / max(trials, 1), 2)},
